@@ -11,6 +11,11 @@ ITS shard of the database rows for all 128*N queries, and the [B,k] partial resu
 and merged keyed on (distance, id) (weak scaling: per-GPU encoder work is fixed and every rank streams
 one full database's worth of bytes per step).  Inputs are resident in HBM before the
 timed region.  Rank 0 prints ONE JSON line.
+
+A plain run sets up, warms up, times --steps steps, writes the last step's outputs (--dump-outputs DIR) and
+prints the headline line.  --full adds everything else this file measures and checks: per-kernel-class
+hipEvents in the timed steps (roofline figures), the self-verification against the oracle, the legs of the
+other BASELINE configurations and operating points, the measured Recall@k parity and the CPU baseline.
 """
 import argparse
 import json
@@ -586,6 +591,84 @@ def recall_leg(keds_amd, dev, precisions=("bf16", "fp32x3")):
     return out
 
 
+def headline(args, dual, world, B, N, D, k, elapsed, shared_gpu, dry):
+    """The head of the result line, the same in a plain run and in --full: the measured figure, its unit and its setting."""
+    fp8, f32, x3 = args.precision == "fp8", args.precision == "fp32", args.precision == "fp32x3"
+    steps = args.steps
+    if dual:
+        metric = "composed dual-stream queries/sec (ViT-L/14 encode + 2 x top-16 with rows + knowledge streams + 2 text passes)"
+        workload = ("dual-stream composed query, BASELINE config 4: ViT-L/14 encode_image (224x224 synthetic, random-init "
+                    "weights) + exact top-16 with row gather over TWO synthetic unit-norm %.1fM x 768 databases + 2 knowledge "
+                    "streams (IM2TEXT + 2 x CrossFormer) + 2 text-tower passes with pseudo-token splice + normalise / "
+                    "mixture" % (N / 1e6))
+        par = f"dp{world} encoders + knowledge path, {world}-way row-sharded scans, rows shipped with the partial lists"
+    else:
+        metric = "query-images/sec (encode+0.5M top-10) ViT-L/14"
+        workload = ("ViT-L/14 encode_image (224x224 synthetic, random-init weights) + exact top-%d over a synthetic "
+                    "unit-norm %.1fM x 768 database" % (k, N / 1e6))
+        par = f"dp{world} encoders + {world}-way row-sharded scan"
+    return {
+        "metric": metric,
+        "value": world * B * steps / elapsed,
+        "unit": "queries/sec" if dual else "query-images/sec",
+        "n_gpus": world, "steps": steps, "warmup": args.warmup,
+        "ms_per_step": elapsed / steps * 1e3,
+        "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
+        "dtype": ("fp8 (MXFP8 e4m3 operands, fp32 accumulate; config 5)" if fp8 else
+                  "f32 (f32-input MFMA, no operand rounding: the accuracy operating point)" if f32 else
+                  "fp32x3 (fp32 flow, block GEMMs on split fp16 operands: 3 fp16 MFMA products per product, fp32 accumulate)" if x3 else
+                  "bf16/fp16 operands, fp32 accumulate"), "data": "synthetic",
+        **({"diagnostic": "KEDS_BENCH_SHARED_GPU=1: all ranks share ONE GPU over a host-staged gloo transport -- a test of the "
+                          "N > 1 flow, not a scaling measurement"} if shared_gpu else {}),
+        **({"diagnostic": "KEDS_BENCH_CPU_DRYRUN=1: CPU tensors over gloo with stand-ins for the encoder and the shard scan -- "
+                          "a test of this file's N-rank flow; NOTHING here is a measurement"} if dry else {}),
+        "config": {"workload": workload,
+                   "batch_per_gpu": B, "global_batch": B * world, "db_rows": N, "dim": D, "k": k,
+                   "db_shards": world, "parallelism": par},
+    }
+
+
+def search_overlap_note(dual, xchg, on):
+    return ("n/a (dual: the knowledge path consumes the neighbours at once)" if dual else
+            "none (one GPU: no collective to hide)" if xchg is None else
+            ("search of batch i on a second stream beside the encoder pass of batch i+1" if on
+             else "serial: search on the encoder's stream"))
+
+
+def emit(out):
+    try:                                   # RCCL writes its version banner through C stdio, which flushes at exit:
+        import ctypes                      # push it out now so that the JSON line is the last line on stdout
+        ctypes.CDLL(None).fflush(None)
+    except Exception:
+        pass
+    print(json.dumps(out), flush=True)
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(directory, arrays, seed=0):
+    """--dump-outputs: each array the timed path returned in its last step as <directory>/<name>.npy, floating outputs in float32,
+    integer ones in float64 (exact below 2**53).  Beyond DUMP_LIMIT_BYTES in all, every array keeps the same fixed, seeded sample of
+    its rows, and <name>.rows.npy holds the row numbers kept."""
+    import numpy as np
+    host = {}
+    for name, t in arrays.items():
+        if isinstance(t, torch.Tensor):
+            t = t.detach().cpu()
+            host[name] = (t.float() if t.is_floating_point() else t.double()).numpy()
+    total = sum(a.nbytes for a in host.values())
+    os.makedirs(directory, exist_ok=True)
+    for name, a in host.items():
+        if total > DUMP_LIMIT_BYTES and a.ndim and a.shape[0] > 1:
+            keep = max(1, int(a.shape[0] * (DUMP_LIMIT_BYTES // 2) / total))
+            rows = np.sort(np.random.RandomState(seed).permutation(a.shape[0])[:keep])
+            a = a[rows]
+            np.save(os.path.join(directory, name + ".rows.npy"), rows.astype(np.float64))
+        np.save(os.path.join(directory, name + ".npy"), a)
+    print(f"bench: wrote {len(host)} output arrays to {directory}", file=sys.stderr, flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -615,8 +698,15 @@ def main():
     ap.add_argument("--prof-every", type=int, default=4, help="record the per-launch hipEvents on every N-th timed step")
     ap.add_argument("--prof-all", action="store_true", help="hipEvent pairs around every kernel class (default: only the "
                     "dominant GEMM class and the scan; the full breakdown costs ~1-2 %% of the step)")
+    ap.add_argument("--full", action="store_true", help="everything beyond the headline: per-kernel-class hipEvents in the timed "
+                    "steps (roofline, stage times), the self-verification, the legs of the other configurations, the measured "
+                    "Recall@k parity and the CPU baseline (--no-verify / --no-legs / --no-cpu-baseline / --prof-* apply here)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write what the timed path returned in its last step "
+                    "as DIR/<name>.npy (float32 / float64; at most 64 MB in all)")
     args = ap.parse_args()
     args.prof_every = max(1, args.prof_every)
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     rank = int(os.environ.get("RANK", "0"))
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -717,9 +807,11 @@ def main():
     search_events = []                                          # hipEvent pairs around the whole local search of profiled steps
 
     cur = {"index": index}                                   # (a leg behind the timed region swaps the database: fp8_point)
+    last = {}                                                # what the latest step returned to its caller (--dump-outputs)
 
     def step_encode_search(timed=False):
         q = model.encode_image(images, normalize=True)          # [B,768] on device
+        last["query_embeddings"] = q
         ovl = overlap["on"] and not dry
         search_stream = side_stream if ovl else main_stream
         if ovl:
@@ -751,6 +843,7 @@ def main():
 
     def step_dual(timed=False):
         out = keds_amd.compose_query_features(model, s_img, s_txt, images, tokens, database, id_split=265, verify=False)
+        last.update(out)
         return out["mixture"], None
 
     step = step_dual if dual else step_encode_search
@@ -801,8 +894,9 @@ def main():
     # hipEvent pair around every launch of the dominant kernel class (GEMM) and of the scan, on the launch stream, inside
     # the timed region -- on every `--prof-every`-th timed step (default 4: steps 0, 4, 8, ...).  An event pair costs ~3.5 us
     # of stream time; around all 100 launches of every step that is 2.7 % of the step, sampled it is 0.7 %.
+    # A plain run carries no event pairs: they feed the per-kernel figures of --full only.
     classes = None if args.prof_all else (_lib.PROF_GEMM, _lib.PROF_SCAN)
-    events = os.environ.get("KEDS_BENCH_NO_EVENTS") != "1"      # A/B of the event overhead only
+    events = args.full and os.environ.get("KEDS_BENCH_NO_EVENTS") != "1"      # (the latter: A/B of the event overhead only)
     prof_steps = 0
     t0 = time.perf_counter()
     for i in range(args.steps):
@@ -819,6 +913,25 @@ def main():
     if fault == "2" and Ik is not None:                          # 2: a search that returns two neighbours in the wrong order
         Ik = Ik.clone()
         Ik[0, [0, 1]] = Ik[0, [1, 0]]
+    t = torch.tensor([elapsed], device=red_dev, dtype=torch.float64)
+    if use_dist:
+        dist.all_reduce(t, op=dist.ReduceOp.MAX)
+    elapsed = float(t.item())
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, dict(last) if dual else
+                     {"query_embeddings": last["query_embeddings"], "topk_distances": Dk, "topk_ids": Ik})
+
+    if not args.full:
+        if rank == 0:
+            out = headline(args, dual, world, B, N, D, k, elapsed, shared_gpu, dry)
+            out["numerics_guard"] = {"mode": model.numerics, "tripped": guard_tripped}
+            out["search_overlap"] = search_overlap_note(dual, xchg, overlap["on"])
+            out["search_overlap_pilot"] = pilot
+            emit(out)
+        if use_dist:
+            dist.barrier()
+            dist.destroy_process_group()
+        return
 
     # ---- self-verification, OUTSIDE the timed region: the line must not be able to report a speed for wrong results
     # (round 4, finding 1: a "10 % gain" was a kernel writing garbage).  (a) the LAST timed step's top-k of rank 0's first 8
@@ -853,10 +966,6 @@ def main():
                           "what": "the same step with set_precision('fp32'): f32-input MFMA, no operand rounding -- the operating "
                                   "point whose Recall@k equals the reference's (tests/test_gpu_fp32.py)",
                           "headline_vs_fp32_embeddings": {"min_cosine": c32, "rel_l2": r32, "images": 8}}
-    t = torch.tensor([elapsed], device=red_dev, dtype=torch.float64)
-    if use_dist:
-        dist.all_reduce(t, op=dist.ReduceOp.MAX)
-    elapsed = float(t.item())
 
     failed = False
     per_rank = None
@@ -979,7 +1088,6 @@ def main():
         legs_failed |= legs["recall_parity_measured"]["ok"] is False
 
     if rank == 0:
-        steps = args.steps
         psteps = max(prof_steps, 1)                              # timed steps whose launches carried event pairs
         fp8, f32, x3 = args.precision == "fp8", args.precision == "fp32", args.precision == "fp32x3"
         side_rows = 0 if (f32 or x3 or dry) else _lib.load().keds_tower_side_rows(VITL["vision_width"], 257, B, int(fp8))
@@ -1012,40 +1120,12 @@ def main():
             whole_ms = sum(a.elapsed_time(b2) for a, b2 in search_events) / len(search_events)
             whole_ach = (hi - lo) * D * 2.0 * world / (whole_ms * 1e-3) / 1e9 if whole_ms > 0 else 0.0
             whole = {"ms": whole_ms, "query_blocks": world, "achieved": whole_ach, "frac": whole_ach / PEAK_HBM_GBPS}
-        if dual:
-            metric = "composed dual-stream queries/sec (ViT-L/14 encode + 2 x top-16 with rows + knowledge streams + 2 text passes)"
-            workload = ("dual-stream composed query, BASELINE config 4: ViT-L/14 encode_image (224x224 synthetic, random-init "
-                        "weights) + exact top-16 with row gather over TWO synthetic unit-norm %.1fM x 768 databases + 2 knowledge "
-                        "streams (IM2TEXT + 2 x CrossFormer) + 2 text-tower passes with pseudo-token splice + normalise / "
-                        "mixture" % (N / 1e6))
-            par = f"dp{world} encoders + knowledge path, {world}-way row-sharded scans, rows shipped with the partial lists"
-        else:
-            metric = "query-images/sec (encode+0.5M top-10) ViT-L/14"
-            workload = ("ViT-L/14 encode_image (224x224 synthetic, random-init weights) + exact top-%d over a synthetic "
-                        "unit-norm %.1fM x 768 database" % (k, N / 1e6))
-            par = f"dp{world} encoders + {world}-way row-sharded scan"
         gemm_traffic, gemm_traffic_note = (None, "PMC passes are of the bf16 encode_search workload only") if (fp8 or f32 or x3 or dual) \
             else pmc_traffic("gemm_256x256_all", B, N, world)
         scan_traffic, scan_traffic_note = (None, "n/a") if dual else pmc_traffic("scan_topk_kernel<768, 16", B, N, world)
         parity, parity_note = recall_parity()
         out = {
-            "metric": metric,
-            "value": world * B * steps / elapsed,
-            "unit": "queries/sec" if dual else "query-images/sec",
-            "n_gpus": world, "steps": steps, "warmup": args.warmup,
-            "ms_per_step": elapsed / steps * 1e3,
-            "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
-            "dtype": ("fp8 (MXFP8 e4m3 operands, fp32 accumulate; config 5)" if fp8 else
-                      "f32 (f32-input MFMA, no operand rounding: the accuracy operating point)" if f32 else
-                      "fp32x3 (fp32 flow, block GEMMs on split fp16 operands: 3 fp16 MFMA products per product, fp32 accumulate)" if x3 else
-                      "bf16/fp16 operands, fp32 accumulate"), "data": "synthetic",
-            **({"diagnostic": "KEDS_BENCH_SHARED_GPU=1: all ranks share ONE GPU over a host-staged gloo transport -- a test of the "
-                              "N > 1 flow, not a scaling measurement"} if shared_gpu else {}),
-            **({"diagnostic": "KEDS_BENCH_CPU_DRYRUN=1: CPU tensors over gloo with stand-ins for the encoder and the shard scan -- "
-                              "a test of this file's N-rank flow; NOTHING here is a measurement"} if dry else {}),
-            "config": {"workload": workload,
-                       "batch_per_gpu": B, "global_batch": B * world, "db_rows": N, "dim": D, "k": k,
-                       "db_shards": world, "parallelism": par},
+            **headline(args, dual, world, B, N, D, k, elapsed, shared_gpu, dry),
             "roofline": {"kernel": ("gemm_f32_kernel (128x128 tiles, v_mfma_f32_32x32x2_f32)" if f32 else
                                     "gemm_bt_pair_kernel<KEDS_EPI_X3_*> (256x256 tiles, three K segments over split fp16 planes; achieved = algorithmic 2MNK flops, peak = fp16 MFMA / 3)" if x3 else
                                     ("gemm_mxfp8_kernel" if fp8 else "gemm_bt_quad_kernel / gemm_bt_quad3_kernel / gemm_bt_pair_kernel") + " (256x256 tiles; all main-lane GEMM launches of the step incl. the few 128x128-tile ones)"), "bound": "mfma",
@@ -1070,10 +1150,7 @@ def main():
             "numerics_guard": {"mode": model.numerics, "tripped": guard_tripped,
                                "checked": "eagerly on the first passes, then lazily (flag copied to pinned memory behind every pass, "
                                           "verified after the timed region)"},
-            "search_overlap": ("n/a (dual: the knowledge path consumes the neighbours at once)" if dual else
-                               "none (one GPU: no collective to hide)" if xchg is None else
-                               ("search of batch i on a second stream beside the encoder pass of batch i+1" if overlap["on"]
-                                else "serial: search on the encoder's stream")),
+            "search_overlap": search_overlap_note(dual, xchg, overlap["on"]),
             "search_overlap_pilot": pilot,
             "per_rank_search": per_rank,
             # (classes whose launches carried no event pairs -- everything but GEMM and scan unless --prof-all -- read null)
@@ -1126,12 +1203,7 @@ def main():
                                       and not guard_tripped)
             verification["rows_searched"] = N
             out["verification"] = verification
-        try:                                   # RCCL writes its version banner through C stdio, which flushes at exit:
-            import ctypes                      # push it out now so that the JSON line is the last line on stdout
-            ctypes.CDLL(None).fflush(None)
-        except Exception:
-            pass
-        print(json.dumps(out), flush=True)
+        emit(out)
         if (verification is not None and not verification["ok"]) or failed_dual or legs_failed:
             failed = True
     if use_dist:

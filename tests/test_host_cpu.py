@@ -466,13 +466,14 @@ def test_extract_feature_database_streams_its_inputs_and_reencodes_a_late_trippe
     assert m.calls == 2 * n + retrieval.VERIFY_CHUNK                     # one chunk encoded twice
 
 
-def _run_bench_dry(gpus, extra_env=None, timeout=600):
+def _run_bench_dry(gpus, extra_env=None, timeout=600, extra_args=(), steps=3):
     import subprocess
     env = dict(os.environ)
     env.update({"KEDS_BENCH_CPU_DRYRUN": "1", "OMP_NUM_THREADS": "1"})
     env.update(extra_env or {})
-    return subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(gpus), "--steps", "3", "--warmup", "1",
-                           "--db-rows", "4096", "--batch", "4"], env=env, capture_output=True, text=True, timeout=timeout, cwd=ROOT)
+    return subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(gpus), "--steps", str(steps), "--warmup", "1",
+                           "--db-rows", "4096", "--batch", "4", *extra_args], env=env, capture_output=True, text=True, timeout=timeout,
+                          cwd=ROOT)
 
 
 def test_bench_eight_rank_flow_on_cpu():
@@ -481,7 +482,7 @@ def test_bench_eight_rank_flow_on_cpu():
     placements, packed query all-gather, shard search, packed all-to-all + merge, per-rank report, the self-verification against
     the oracle over all shards) on CPU tensors over gloo with stand-ins for the encoder and the shard scan, and rank 0's JSON
     line is the last line on stdout."""
-    res = _run_bench_dry(8)
+    res = _run_bench_dry(8, extra_args=("--full",))
     assert res.returncode == 0, res.stdout[-2000:] + res.stderr[-3000:]
     line = res.stdout.strip().splitlines()[-1]
     out = json.loads(line)
@@ -508,7 +509,31 @@ def test_bench_rank_failure_exits_nonzero_with_the_failing_ranks_message():
 def test_bench_self_verification_flags_a_wrong_neighbour_list():
     """KEDS_BENCH_INJECT_FAULT=2 swaps two neighbours of one query in the last timed step's result: the line still prints, says
     verification.ok = false with the mismatch count, and the process exits 3 -- a speed for wrong results is not a result."""
-    res = _run_bench_dry(2, {"KEDS_BENCH_INJECT_FAULT": "2"})
+    res = _run_bench_dry(2, {"KEDS_BENCH_INJECT_FAULT": "2"}, extra_args=("--full",))
     assert res.returncode != 0, res.stdout[-1500:]
     out = json.loads([l for l in res.stdout.strip().splitlines() if l.startswith("{") and '"metric"' in l][-1])
     assert out["verification"]["ok"] is False and out["verification"]["id_mismatches"] == 2
+
+
+def test_bench_plain_run_prints_the_headline_only_and_dumps_the_last_steps_outputs(tmp_path):
+    """A plain run (no --full) times exactly --steps steps and prints the headline line without the checks and legs of --full;
+    --dump-outputs writes what the last timed step returned (the query embeddings and the merged top-k of rank 0), float32 /
+    float64, and the same arguments give the same inputs, hence the same outputs of the deterministic stand-ins."""
+    dirs = [tmp_path / "a", tmp_path / "b"]
+    for d in dirs:
+        res = _run_bench_dry(2, extra_args=("--dump-outputs", str(d)), steps=5)
+        assert res.returncode == 0, res.stdout[-2000:] + res.stderr[-3000:]
+        out = json.loads(res.stdout.strip().splitlines()[-1])
+        assert out["steps"] == 5 and out["ms_per_step"] > 0 and out["higher_is_better"] is True
+        assert abs(out["value"] - 8 * 1e3 / out["ms_per_step"]) <= 1e-6 * out["value"]
+        for key in ("metric", "unit", "dtype"):
+            assert isinstance(out[key], str) and out[key]
+        for key in ("verification", "roofline", "cpu_baseline", "fp32_point", "per_rank_search", "stage_ms_per_step"):
+            assert key not in out, key
+    want = {"query_embeddings": (np.float32, (4, 768)), "topk_distances": (np.float32, (4, 10)), "topk_ids": (np.float64, (4, 10))}
+    assert sorted(p.name for p in dirs[0].iterdir()) == sorted(f"{n}.npy" for n in want)
+    for name, (dtype, shape) in want.items():
+        a, b = np.load(dirs[0] / f"{name}.npy"), np.load(dirs[1] / f"{name}.npy")
+        assert a.dtype == dtype and a.shape == shape and np.array_equal(a, b), name
+    ids = np.load(dirs[0] / "topk_ids.npy")
+    assert ((ids >= 0) & (ids < 4096)).all() and (ids == np.round(ids)).all()

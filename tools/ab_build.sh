@@ -1,7 +1,7 @@
 #!/bin/bash
 # Same-box A/B of compile-time variants: bench, rebuild the library ON THE GPU BOX with extra flags, bench, ..., base again.
 # Usage (on the box, from the repo root): [BENCH_ARGS='--precision fp8'] [RUNS=2] bash tools/ab_build.sh "-DA=1" "-DA=1 -DB=2" ...
-B="python bench.py --steps 40 --warmup 4 --no-cpu-baseline $BENCH_ARGS"
+B="python bench.py --full --steps 40 --warmup 4 --no-cpu-baseline $BENCH_ARGS"
 run() { for i in $(seq ${RUNS:-2}); do $B 2>/dev/null | tail -1 | python3 tools/ab_line.py; done
   # a variant that computes garbage can be FASTER (fewer toggling bits at the power cap): every variant must also reproduce the embeddings
   python - <<'PY'

@@ -1,7 +1,7 @@
 #!/bin/bash
 # kernel-time table of the bench command (rocprofv3 --kernel-trace --stats), top rows
 export TMPDIR=/tmp; W=/tmp/kp; rm -rf $W; mkdir -p $W
-rocprofv3 --kernel-trace --stats --output-format csv -d $W/stats -o bench -- python3 bench.py --steps 5 --warmup 2 --no-cpu-baseline > $W/bench.log 2>&1
+rocprofv3 --kernel-trace --stats --output-format csv -d $W/stats -o bench -- python3 bench.py --full --steps 5 --warmup 2 --no-cpu-baseline > $W/bench.log 2>&1
 f=$(find $W/stats -name "*kernel_stats.csv" | head -1)
 python3 - "$f" <<'PY'
 import csv, sys, re

@@ -5,7 +5,7 @@
 tag=${1:-r03_final}
 export TMPDIR=/tmp
 W=/tmp/keds_prof_$tag; rm -rf $W; mkdir -p $W gpurun_out
-rocprofv3 --kernel-trace --stats --output-format csv -d $W/stats -o bench -- python3 bench.py --steps 5 --warmup 2 --no-cpu-baseline --no-verify > $W/bench.log 2>&1
+rocprofv3 --kernel-trace --stats --output-format csv -d $W/stats -o bench -- python3 bench.py --full --steps 5 --warmup 2 --no-cpu-baseline --no-verify > $W/bench.log 2>&1
 echo "stats rc=$?"; tail -2 $W/bench.log | cut -c1-400
 rocprofv3 --pmc FETCH_SIZE --output-format csv -d $W/pmc/a -o p -- python3 tools/pmc_step.py > $W/pmc_a.log 2>&1
 echo "pmc fetch rc=$?"; tail -2 $W/pmc_a.log | cut -c1-300
