@@ -30,7 +30,9 @@ extern "C" {
 #define KEDS_E_LAUNCH (-2)   /* HIP launch or runtime error */
 #define KEDS_E_WORKSPACE (-3)/* workspace too small */
 
-#define KEDS_ABI_VERSION 8        /* 8 (round 6): keds_gemm_x3 takes w_exp, keds_split_f16_weight, keds_block_params.x3_exp, keds_text_run_packed / keds_attention_packed; keds_gemm_duo_enable left the product */
+#define KEDS_ABI_VERSION 9        /* 9: the "fp16" operating point -- keds_tower_params.f16, KEDS_EPI_*_F16_H / *_F32_H epilogues, keds_attention_h /
+                                     keds_attention_packed_h, keds_im2col_ex, keds_layernorm_ex, keds_cast_f16;
+                                     8 (round 6): keds_gemm_x3 takes w_exp, keds_split_f16_weight, keds_block_params.x3_exp, keds_text_run_packed / keds_attention_packed; keds_gemm_duo_enable left the product */
 
 int keds_abi_version(void);
 /* compiler flags of this build beyond the Makefile's defaults ("" for the product build; `make EXTRA="-D..."` variants of the
@@ -204,6 +206,17 @@ int keds_label_hits(const int32_t* order, int nq, int ng, const int32_t* gallery
 #define KEDS_EPI_X3_RESID_F32 14    /* out f32 += acc + bias (in place) */
 #define KEDS_EPI_X3_QGELU_PAIR 15   /* out = fp16 planes [2][rows][N] of qgelu(acc + bias) (full-precision expf / division): the
                                        next split-operand GEMM's A operand; aux_i = elements between the two planes */
+/* The "fp16" operating point (keds_tower_params.f16; the reference's --precision fp16, convert_weights model.py:927-948): BOTH
+ * operands fp16 (v_mfma_f32_16x16x32_f16, fp32 accumulate, the bf16 rate), and every 16-bit output fp16.  Epilogues that STORE fp16
+ * values (qkv, the MLP hidden layer) raise the numerics-guard flag (keds_numerics_guard_set) on any |v| > 65504 or non-finite v
+ * instead of letting inf through; the host then re-runs the pass on another operating point. */
+#define KEDS_EPI_LN_BIAS_F16_H 16     /* KEDS_EPI_LN_BIAS_BF16_H with an fp16 output (+ range guard) */
+#define KEDS_EPI_LN_QGELU_F16_H 17    /* KEDS_EPI_LN_QGELU_BF16_H with an fp16 output (+ range guard) */
+#define KEDS_EPI_RESID_STATS_F16_H 18 /* KEDS_EPI_RESID_STATS_F16 with an fp16 A operand and fp16 W */
+#define KEDS_EPI_BIAS_RESID_F32_H 19  /* KEDS_EPI_BIAS_RESID_F32 on fp16 operands */
+#define KEDS_EPI_BIAS_QGELU_F16_H 20  /* out fp16 = qgelu(acc + bias) on fp16 operands (+ range guard) */
+#define KEDS_EPI_PATCH_F32_H 21       /* KEDS_EPI_PATCH_F32 on fp16 operands */
+#define KEDS_EPI_BIAS_F32_H 22        /* KEDS_EPI_BIAS_F32 on fp16 operands (the read-out projections) */
 
 /* out[M,N] = epilogue(A[M,K] . W[N,K]^T + bias[N]).  A, W bf16 row-major (W is the nn.Linear
  * weight as stored).  N % 128 == 0, K % 64 == 0; rows of A / out up to the next multiple of
@@ -292,6 +305,9 @@ int keds_gemm_force_small(int on);
  * dense [rows, dim].  dim % 256 == 0 or dim == 128; dim <= 2048. */
 int keds_layernorm(const float* x, int64_t x_stride, const float* gamma, const float* beta,
                    void* out, int out_f32, int rows, int dim, void* stream);
+/* out_type: 0 bf16, 1 fp32, 2 fp16 */
+int keds_layernorm_ex(const float* x, int64_t x_stride, const float* gamma, const float* beta,
+                      void* out, int out_type, int rows, int dim, void* stream);
 
 /* timing-only ablation hook of the S > 96 attention kernel (0 = product path) */
 int keds_attention_debug(int variant);
@@ -313,10 +329,15 @@ int keds_attention_mx(const void* qkv, void* out, int B, int S, int heads, int c
 /* PACKED rows (round 6): sample b is rows [seq_off[b], seq_off[b + 1]) of qkv / out (device int32 [B + 1]; lengths 1 .. s_max
  * <= 288) instead of [b S, (b + 1) S): sequences of different lengths without padding rows (the text tower, keds_text_run_packed) */
 int keds_attention_packed(const void* qkv, void* out, int B, int s_max, const int32_t* seq_off, int heads, int causal, void* stream);
+/* fp16 forms of keds_attention_ex / keds_attention_packed (keds_tower_params.f16): qkv and out fp16, both products on the fp16
+ * matrix instruction, the probabilities rounded to fp16.  The output is a convex combination of V and cannot overflow. */
+int keds_attention_h(const void* qkv, void* out, int B, int S, int heads, int causal, int q_limit, void* stream);
+int keds_attention_packed_h(const void* qkv, void* out, int B, int s_max, const int32_t* seq_off, int heads, int causal, void* stream);
 
 /* patch im2col for conv1 (model.py:381,394-396): image fp32 [B,3,R,R] -> bf16 [B*G, Kpad],
  * column c*P*P + ky*P + kx, zero padded to Kpad (a multiple of 64). */
 int keds_im2col(const float* image, void* out, int B, int R, int P, int Kpad, void* stream);
+int keds_im2col_ex(const float* image, void* out, int out_f16, int B, int R, int P, int Kpad, void* stream);   /* out fp16 */
 
 /* token embedding + optional pseudo-token splice + positional embedding
  * (model.py:579-581, 817-837): x fp32 [B, L, d].
@@ -342,6 +363,7 @@ int keds_mix_normalize(const float* a, const float* b, float wa, float wb,
                        float* a_n, float* b_n, float* mix, int rows, int dim, void* stream);
 /* fp32 -> bf16 cast (weight packing, model.py:927-948 stand-in) */
 int keds_cast_bf16(const float* x, void* out, int64_t count, void* stream);
+int keds_cast_f16(const float* x, void* out, int64_t count, void* stream);    /* fp32 -> fp16 (round to nearest even) */
 
 /* =====================================================================================
  * 3. Whole towers
@@ -380,6 +402,11 @@ typedef struct {
                                                        every block -- and conv_w / proj_t of the enclosing vit / text struct --
                                                        point to FP32 arrays of the same shapes; the folded / MXFP8 fields are
                                                        unused; fp8 must be 0 */
+    int f16;                                        /* 1: the "fp16" operating point -- EVERY 16-bit operand of the tower is fp16:
+                                                       qkv_w / out_w / fc_w / proj_w (and the folded qkv_wf / fc_wf) of every
+                                                       block, conv_w / proj_t of the enclosing vit / text struct; qkv, the
+                                                       attention output and the MLP hidden layer are fp16 too (KEDS_EPI_*_F16_H,
+                                                       keds_attention_h).  Folded flow only; fp8 and f32 must be 0 */
 } keds_tower_params;
 
 typedef struct {

@@ -17,13 +17,16 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "csrc", "libkeds_hip.so")
 
 # ---- constants mirrored from keds_hip.h ------------------------------------------------------
-ABI_VERSION = 8
+ABI_VERSION = 9
 METRIC_L2, METRIC_IP = 0, 1
 EPI_BIAS_BF16, EPI_BIAS_QGELU_BF16, EPI_BIAS_RELU_BF16, EPI_BIAS_RESID_F32, EPI_BIAS_F32, EPI_PATCH_F32 = range(6)
 EPI_LN_BIAS_BF16, EPI_LN_QGELU_BF16, EPI_RESID_STATS_F32, EPI_RESID_STATS_F16 = 6, 7, 8, 9
 EPI_LN_BIAS_BF16_H, EPI_LN_QGELU_BF16_H = 10, 11
 EPI_BIAS_BF16_HEADF32 = 12
 EPI_X3_BIAS_F32, EPI_X3_RESID_F32, EPI_X3_QGELU_PAIR = 13, 14, 15
+# the "fp16" operating point: fp16 A and W (ABI 9)
+EPI_LN_BIAS_F16_H, EPI_LN_QGELU_F16_H, EPI_RESID_STATS_F16_H, EPI_BIAS_RESID_F32_H = 16, 17, 18, 19
+EPI_BIAS_QGELU_F16_H, EPI_PATCH_F32_H, EPI_BIAS_F32_H = 20, 21, 22
 F32_EPI_BIAS, F32_EPI_QGELU, F32_EPI_RESID, F32_EPI_RELU, F32_EPI_PATCH = range(5)
 FP8_EPI_BIAS_BF16, FP8_EPI_LN_BIAS_BF16, FP8_EPI_LN_QGELU_MX, FP8_EPI_RESID_STATS_MX, FP8_EPI_RESID_STATS_MX_H = range(5)
 PROF_GEMM, PROF_ATTN, PROF_SCAN, PROF_LN, PROF_OTHER = range(5)
@@ -41,7 +44,8 @@ class BlockParams(C.Structure):
 
 class TowerParams(C.Structure):
     _fields_ = [("width", i32), ("layers", i32), ("heads", i32), ("seq", i32), ("causal", i32),
-                ("blocks", C.POINTER(BlockParams)), ("fp8", i32), ("last_cls_only", i32), ("f32", i32)]
+                ("blocks", C.POINTER(BlockParams)), ("fp8", i32), ("last_cls_only", i32), ("f32", i32),
+                ("f16", i32)]      # (f16 = 1: the "fp16" operating point -- every 16-bit operand of the tower fp16)
 
 
 class VitParams(C.Structure):
@@ -219,6 +223,12 @@ SIGNATURES = {
     "keds_text_trim_mode": (i32, []),
     "keds_text_run_packed": (i32, [C.POINTER(TextParams), vp, vp, vp, i32, i32, vp, i32, i32, i32, vp, i32, vp, sz, vp]),
     "keds_attention_packed": (i32, [vp, vp, i32, i32, vp, i32, i32, vp]),
+    # the "fp16" operating point (ABI 9)
+    "keds_attention_h": (i32, [vp, vp, i32, i32, i32, i32, i32, vp]),
+    "keds_attention_packed_h": (i32, [vp, vp, i32, i32, vp, i32, i32, vp]),
+    "keds_im2col_ex": (i32, [vp, vp, i32, i32, i32, i32, i32, vp]),
+    "keds_layernorm_ex": (i32, [vp, i64, vp, vp, vp, i32, i32, i32, vp]),
+    "keds_cast_f16": (i32, [vp, vp, i64, vp]),
     "keds_im2text_workspace_bytes": (sz, [C.POINTER(Im2TextParams), i32]),
     "keds_im2text_forward": (i32, [C.POINTER(Im2TextParams), vp, i32, vp, vp, sz, vp]),
     "keds_crossformer_workspace_bytes": (sz, [C.POINTER(CrossFormerParams), i32, i32]),

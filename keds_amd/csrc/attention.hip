@@ -36,9 +36,28 @@ __device__ __forceinline__ f32x2 pk_fma(f32x2 a, f32x2 b, f32x2 c) {
     return d;
 }
 
+// element type of the kernels below: bf16 (default flow) or fp16 (the "fp16" operating point, keds_attention_h) -- the
+// same code; only the matrix instructions, the dot products and the roundings of P / the output follow the type
+template <typename T> struct Ev;
+template <> struct Ev<bf16_t> { using v8 = bf16x8; using v4 = bf16x4; };
+template <> struct Ev<f16_t> { using v8 = f16x8; using v4 = __attribute__((ext_vector_type(4))) _Float16; };
+__device__ __forceinline__ f32x4 mfma16(bf16x8 a, bf16x8 b, f32x4 c, int, int, int) {
+    return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0);
+}
+__device__ __forceinline__ f32x4 mfma16(f16x8 a, f16x8 b, f32x4 c, int, int, int) {
+    return __builtin_amdgcn_mfma_f32_16x16x32_f16(a, b, c, 0, 0, 0);
+}
+__device__ __forceinline__ f32x16 mfma32(bf16x8 a, bf16x8 b, f32x16 c, int, int, int) {
+    return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, c, 0, 0, 0);
+}
+__device__ __forceinline__ f32x16 mfma32(f16x8 a, f16x8 b, f32x16 c, int, int, int) {
+    return __builtin_amdgcn_mfma_f32_32x32x16_f16(a, b, c, 0, 0, 0);
+}
+
+template <typename T>
 struct AttnCtx {
-    const bf16_t* base;   // qkv of (b, h): row stride ld
-    bf16_t* out;          // out of (b, h): row stride d
+    const T* base;   // qkv of (b, h): row stride ld
+    T* out;          // out of (b, h): row stride d
     const char* k_lds;
     const char* vt_lds;
     int S, q_limit, ld, d, g, c;
@@ -53,20 +72,22 @@ struct AttnCtx {
 // TAIL: the sequence is 16*NKT + 1 keys; the MFMA tiles cover the first 16*NKT and the last key is a rank-1 VALU update
 // (its score from the lane's 16 query dims + a reduction over the four lanes of the query, its P.V term 16 FMAs per tile)
 // instead of two more key tiles of which 31 of 32 columns would be padding.
-template <int NKT, bool CAUSAL, int NFULL, int DBG, int NQ, bool TAIL = false>
-__device__ __forceinline__ void attn_tiles(const AttnCtx& cx, int qt0) {
+template <typename T, int NKT, bool CAUSAL, int NFULL, int DBG, int NQ, bool TAIL = false>
+__device__ __forceinline__ void attn_tiles(const AttnCtx<T>& cx, int qt0) {
     using C = AttnCfg<NKT>;
+    using V8 = typename Ev<T>::v8;
+    using V4 = typename Ev<T>::v4;
     const int g = cx.g, c = cx.c, S = cx.S;
     const float sl2 = 0.125f * 1.4426950408889634f;  // 1/sqrt(64) * log2(e)
     int qidx[NQ];
-    bf16x8 qf[NQ][2];
+    V8 qf[NQ][2];
 #pragma unroll
     for (int t = 0; t < NQ; ++t) {
         qidx[t] = (qt0 + t) * 16 + c;
         const int qrow = qidx[t] < S ? qidx[t] : S - 1;
-        const bf16_t* qp = cx.base + (size_t)qrow * cx.ld + 8 * g;
-        qf[t][0] = *reinterpret_cast<const bf16x8*>(qp);
-        qf[t][1] = *reinterpret_cast<const bf16x8*>(qp + 32);
+        const T* qp = cx.base + (size_t)qrow * cx.ld + 8 * g;
+        qf[t][0] = *reinterpret_cast<const V8*>(qp);
+        qf[t][1] = *reinterpret_cast<const V8*>(qp + 32);
     }
     // ---- S^T tiles
     f32x4 sc[NQ][NKT];
@@ -75,14 +96,14 @@ __device__ __forceinline__ void attn_tiles(const AttnCtx& cx, int qt0) {
         const int key = kt * 16 + c;
         const char* kr = cx.k_lds + key * 128;
         const int f = (key >> 1) & 7;
-        const bf16x8 a0 = *reinterpret_cast<const bf16x8*>(kr + ((g ^ f) << 4));
-        const bf16x8 a1 = *reinterpret_cast<const bf16x8*>(kr + (((4 + g) ^ f) << 4));
+        const V8 a0 = *reinterpret_cast<const V8*>(kr + ((g ^ f) << 4));
+        const V8 a1 = *reinterpret_cast<const V8*>(kr + (((4 + g) ^ f) << 4));
 #pragma unroll
         for (int t = 0; t < NQ; ++t) {
             f32x4 acc = f32x4{0.f, 0.f, 0.f, 0.f};
             if constexpr (DBG != 2) {
-                acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a0, qf[t][0], acc, 0, 0, 0);
-                acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a1, qf[t][1], acc, 0, 0, 0);
+                acc = mfma16(a0, qf[t][0], acc, 0, 0, 0);
+                acc = mfma16(a1, qf[t][1], acc, 0, 0, 0);
             } else {
                 acc[0] = (float)qf[t][0][kt & 7];
             }
@@ -93,8 +114,8 @@ __device__ __forceinline__ void attn_tiles(const AttnCtx& cx, int qt0) {
     // ---- TAIL: score of the last key for the lane's query (replicated over the four g lanes after the reduction)
     [[maybe_unused]] float tsc[NQ];
     if constexpr (TAIL) {
-        const bf16x8 k0 = *reinterpret_cast<const bf16x8*>(cx.tail + g * 16);
-        const bf16x8 k1 = *reinterpret_cast<const bf16x8*>(cx.tail + (4 + g) * 16);
+        const V8 k0 = *reinterpret_cast<const V8*>(cx.tail + g * 16);
+        const V8 k1 = *reinterpret_cast<const V8*>(cx.tail + (4 + g) * 16);
 #pragma unroll
         for (int t = 0; t < NQ; ++t) {
             float a = 0.f;
@@ -148,7 +169,7 @@ __device__ __forceinline__ void attn_tiles(const AttnCtx& cx, int qt0) {
         if constexpr (TAIL) {
             const float e = __builtin_amdgcn_exp2f(tsc[t] * sl2 + nmx);
             sum += e;
-            tp[t] = (float)(bf16_t)e;             // rounded like the probabilities the MFMA path multiplies
+            tp[t] = (float)(T)e;             // rounded to T like the probabilities the MFMA path multiplies
         }
         inv[t] = 1.0f / sum;
     }
@@ -160,20 +181,20 @@ __device__ __forceinline__ void attn_tiles(const AttnCtx& cx, int qt0) {
         for (int dt = 0; dt < 4; ++dt) o[t][dt] = f32x4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
     for (int u = 0; u < NKT / 2; ++u) {
-        bf16x8 pf[NQ];
+        V8 pf[NQ];
 #pragma unroll
         for (int t = 0; t < NQ; ++t) {
             const f32x4 p0 = sc[t][2 * u], p1 = sc[t][2 * u + 1];
-            pf[t] = bf16x8{(bf16_t)p0[0], (bf16_t)p0[1], (bf16_t)p0[2], (bf16_t)p0[3],
-                           (bf16_t)p1[0], (bf16_t)p1[1], (bf16_t)p1[2], (bf16_t)p1[3]};
+            pf[t] = V8{(T)p0[0], (T)p0[1], (T)p0[2], (T)p0[3],
+                           (T)p1[0], (T)p1[1], (T)p1[2], (T)p1[3]};
         }
 #pragma unroll
         for (int dt = 0; dt < 4; ++dt) {
             if constexpr (DBG != 4) {
-                const bf16x8 a =
-                    *reinterpret_cast<const bf16x8*>(cx.vt_lds + (dt * 16 + c) * C::VT_ROW + (4 * u + g) * 16);
+                const V8 a =
+                    *reinterpret_cast<const V8*>(cx.vt_lds + (dt * 16 + c) * C::VT_ROW + (4 * u + g) * 16);
 #pragma unroll
-                for (int t = 0; t < NQ; ++t) o[t][dt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, pf[t], o[t][dt], 0, 0, 0);
+                for (int t = 0; t < NQ; ++t) o[t][dt] = mfma16(a, pf[t], o[t][dt], 0, 0, 0);
             } else {
 #pragma unroll
                 for (int t = 0; t < NQ; ++t) o[t][dt][0] += (float)pf[t][dt];
@@ -184,7 +205,7 @@ __device__ __forceinline__ void attn_tiles(const AttnCtx& cx, int qt0) {
     if constexpr (TAIL) {      // + p_last * V[last key][16 dt + 4 g + r]
 #pragma unroll
         for (int dt = 0; dt < 4; ++dt) {
-            const bf16x4 v = *reinterpret_cast<const bf16x4*>(cx.tail + 128 + (16 * dt + 4 * g) * 2);
+            const V4 v = *reinterpret_cast<const V4*>(cx.tail + 128 + (16 * dt + 4 * g) * 2);
 #pragma unroll
             for (int t = 0; t < NQ; ++t)
 #pragma unroll
@@ -213,11 +234,11 @@ __device__ __forceinline__ void attn_tiles(const AttnCtx& cx, int qt0) {
                     if (g == 0) cx.s8[mx_scale_index((cx.col0 >> 5) + b2, row, cx.q8_rows)] = (unsigned char)(e + 127);
                 }
             } else {
-                bf16_t* op = cx.out + (size_t)qidx[t] * cx.d + 4 * g;
+                T* op = cx.out + (size_t)qidx[t] * cx.d + 4 * g;
 #pragma unroll
                 for (int dt = 0; dt < 4; ++dt) {
                     const f32x4 v = o[t][dt] * inv[t];
-                    *reinterpret_cast<bf16x4*>(op + dt * 16) = bf16x4{(bf16_t)v[0], (bf16_t)v[1], (bf16_t)v[2], (bf16_t)v[3]};
+                    *reinterpret_cast<V4*>(op + dt * 16) = V4{(T)v[0], (T)v[1], (T)v[2], (T)v[3]};
                 }
             }
         }
@@ -227,12 +248,14 @@ __device__ __forceinline__ void attn_tiles(const AttnCtx& cx, int qt0) {
 // DBG (timing-only ablations): 1 = no K/V staging, 2 = no QK^T MFMA/reads, 3 = no softmax math, 4 = no PV, 5 = no q loop
 // CAUSAL: text tower mask.  NFULL: key tiles [0, NFULL) are known at compile time to lie entirely below S and
 // need no mask (non-causal only) -- evaluating the mask for all 72 score registers cost half the loop's instructions.
-template <int NKT, bool CAUSAL, int NFULL, int DBG = 0, bool NQ2 = (NKT == 18 && !CAUSAL)>
-__global__ __launch_bounds__(256, 2) void attention_kernel(const bf16_t* __restrict__ qkv, bf16_t* __restrict__ out, int S,
+template <int NKT, bool CAUSAL, int NFULL, int DBG = 0, bool NQ2 = (NKT == 18 && !CAUSAL), typename T = bf16_t>
+__global__ __launch_bounds__(256, 2) void attention_kernel(const T* __restrict__ qkv, T* __restrict__ out, int S,
                                                         int heads, int q_limit, unsigned char* __restrict__ q8,
                                                         unsigned char* __restrict__ s8, int q8_rows,
                                                         const int* __restrict__ seq_off) {
     using C = AttnCfg<NKT>;
+    using V8 = typename Ev<T>::v8;
+    using V4 = typename Ev<T>::v4;
     extern __shared__ __attribute__((aligned(16))) char smem[];
     char* k_lds = smem;
     char* vt_lds = smem + C::K_BYTES;
@@ -249,7 +272,7 @@ __global__ __launch_bounds__(256, 2) void attention_kernel(const bf16_t* __restr
         S = seq_off[b + 1] - row0;
         q_limit = q_limit < S ? q_limit : S;
     }
-    const bf16_t* base = qkv + (size_t)row0 * ld + h * DH;
+    const T* base = qkv + (size_t)row0 * ld + h * DH;
 
     // ---- stage K (swizzled rows) and V^T (permuted key order); keys >= S are zero.
     // Work item = (4 consecutive keys, one 8-wide dh chunk): all global loads of a thread are issued before the
@@ -258,7 +281,7 @@ __global__ __launch_bounds__(256, 2) void attention_kernel(const bf16_t* __restr
     if constexpr (DBG != 1) {
         constexpr int ITEMS = (C::KEYS / 4) * 8;
         constexpr int PER = (ITEMS + 255) / 256;
-        bf16x8 kreg[PER][4], vreg[PER][4];
+        V8 kreg[PER][4], vreg[PER][4];
 #pragma unroll
         for (int it = 0; it < PER; ++it) {
             const int id = tid + it * 256;
@@ -266,12 +289,12 @@ __global__ __launch_bounds__(256, 2) void attention_kernel(const bf16_t* __restr
 #pragma unroll
             for (int e = 0; e < 4; ++e) {
                 const int key = quad * 4 + e;
-                kreg[it][e] = bf16x8{0, 0, 0, 0, 0, 0, 0, 0};
+                kreg[it][e] = V8{0, 0, 0, 0, 0, 0, 0, 0};
                 vreg[it][e] = kreg[it][e];
                 if (id < ITEMS && key < S) {
-                    const bf16_t* row = base + (size_t)key * ld + ch * 8;
-                    kreg[it][e] = *reinterpret_cast<const bf16x8*>(row + d);
-                    vreg[it][e] = *reinterpret_cast<const bf16x8*>(row + 2 * d);
+                    const T* row = base + (size_t)key * ld + ch * 8;
+                    kreg[it][e] = *reinterpret_cast<const V8*>(row + d);
+                    vreg[it][e] = *reinterpret_cast<const V8*>(row + 2 * d);
                 }
             }
         }
@@ -283,7 +306,7 @@ __global__ __launch_bounds__(256, 2) void attention_kernel(const bf16_t* __restr
 #pragma unroll
             for (int e = 0; e < 4; ++e) {
                 const int key = quad * 4 + e;
-                *reinterpret_cast<bf16x8*>(k_lds + key * 128 + ((ch ^ ((key >> 1) & 7)) << 4)) = kreg[it][e];
+                *reinterpret_cast<V8*>(k_lds + key * 128 + ((ch ^ ((key >> 1) & 7)) << 4)) = kreg[it][e];
             }
             // keys 4*quad .. 4*quad+3: u = key>>5, w = key&31, chunk (4u + ((w&15)>>2)), element 4*(w>>4) + (w&3)
             const int k0 = quad * 4;
@@ -291,8 +314,8 @@ __global__ __launch_bounds__(256, 2) void attention_kernel(const bf16_t* __restr
             const int pos = (4 * u + ((w & 15) >> 2)) * 16 + ((w >> 4) << 2) * 2;
 #pragma unroll
             for (int j = 0; j < 8; ++j)
-                *reinterpret_cast<bf16x4*>(vt_lds + (ch * 8 + j) * C::VT_ROW + pos) =
-                    bf16x4{vreg[it][0][j], vreg[it][1][j], vreg[it][2][j], vreg[it][3][j]};
+                *reinterpret_cast<V4*>(vt_lds + (ch * 8 + j) * C::VT_ROW + pos) =
+                    V4{vreg[it][0][j], vreg[it][1][j], vreg[it][2][j], vreg[it][3][j]};
         }
     }
     __syncthreads();
@@ -300,13 +323,13 @@ __global__ __launch_bounds__(256, 2) void attention_kernel(const bf16_t* __restr
     // ---- queries: NQ = 2 tiles (32 queries) per step share every K / V^T fragment read from LDS (the loop is
     // LDS-bandwidth bound: 72 ds_read_b128 per 16-query tile); an odd last tile runs alone on a rotating wave.
     const int nqt = DBG == 5 ? 0 : (q_limit + 15) >> 4;      // only the first q_limit query rows are computed and stored
-    AttnCtx cx{base, out + (size_t)row0 * d + h * DH, k_lds, vt_lds, S, q_limit, ld, d, g, c, q8, s8, q8_rows, row0, h * DH};
+    AttnCtx<T> cx{base, out + (size_t)row0 * d + h * DH, k_lds, vt_lds, S, q_limit, ld, d, g, c, q8, s8, q8_rows, row0, h * DH};
     if constexpr (NQ2) {
         const int npair = nqt >> 1;
-        for (int qp = wave; qp < npair; qp += 4) attn_tiles<NKT, CAUSAL, NFULL, DBG, 2>(cx, 2 * qp);
-        if ((nqt & 1) && wave == ((blockIdx.x + npair) & 3)) attn_tiles<NKT, CAUSAL, NFULL, DBG, 1>(cx, nqt - 1);
+        for (int qp = wave; qp < npair; qp += 4) attn_tiles<T, NKT, CAUSAL, NFULL, DBG, 2>(cx, 2 * qp);
+        if ((nqt & 1) && wave == ((blockIdx.x + npair) & 3)) attn_tiles<T, NKT, CAUSAL, NFULL, DBG, 1>(cx, nqt - 1);
     } else {
-        for (int qt = wave; qt < nqt; qt += 4) attn_tiles<NKT, CAUSAL, NFULL, DBG, 1>(cx, qt);
+        for (int qt = wave; qt < nqt; qt += 4) attn_tiles<T, NKT, CAUSAL, NFULL, DBG, 1>(cx, qt);
     }
 }
 
@@ -319,10 +342,12 @@ __global__ __launch_bounds__(256, 2) void attention_kernel(const bf16_t* __restr
 // accumulates output dims [16 w, 16 w + 16) (lane = dim x key quarter, reduced over the quarters with permlane swaps).
 constexpr int TAIL_LDS = 256 + 2 * 1056;      // last key's K and V rows | scores [257+] | probabilities [257+]
 
-template <int NKT, int DBG = 0>
-__global__ __launch_bounds__(256, 2) void attention_tail1_kernel(const bf16_t* __restrict__ qkv, bf16_t* __restrict__ out,
+template <int NKT, int DBG = 0, typename T = bf16_t>
+__global__ __launch_bounds__(256, 2) void attention_tail1_kernel(const T* __restrict__ qkv, T* __restrict__ out,
                                                                  int heads, int q_limit) {
     using C = AttnCfg<NKT>;
+    using V8 = typename Ev<T>::v8;
+    using V4 = typename Ev<T>::v4;
     constexpr int S = 16 * NKT + 1, LAST = 16 * NKT;
     extern __shared__ __attribute__((aligned(16))) char smem[];
     char* k_lds = smem;
@@ -335,27 +360,27 @@ __global__ __launch_bounds__(256, 2) void attention_tail1_kernel(const bf16_t* _
     const int ld = 3 * d;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int g = lane >> 4, c = lane & 15;
-    const bf16_t* base = qkv + (size_t)b * S * ld + h * DH;
+    const T* base = qkv + (size_t)b * S * ld + h * DH;
 
     // ---- stage K (swizzled rows), V^T (permuted key order) of the 16 * NKT leading keys, and the last key's two rows
     {
         constexpr int ITEMS = (C::KEYS / 4) * 8;
         constexpr int PER = ITEMS / 256;
         static_assert(ITEMS % 256 == 0, "staging items must divide over the workgroup");
-        bf16x8 kreg[PER][4], vreg[PER][4];
-        bf16x8 treg = bf16x8{0, 0, 0, 0, 0, 0, 0, 0};
+        V8 kreg[PER][4], vreg[PER][4];
+        V8 treg = V8{0, 0, 0, 0, 0, 0, 0, 0};
 #pragma unroll
         for (int it = 0; it < PER; ++it) {
             const int id = tid + it * 256;
             const int quad = id >> 3, ch = id & 7;
 #pragma unroll
             for (int e = 0; e < 4; ++e) {
-                const bf16_t* row = base + (size_t)(quad * 4 + e) * ld + ch * 8;
-                kreg[it][e] = *reinterpret_cast<const bf16x8*>(row + d);
-                vreg[it][e] = *reinterpret_cast<const bf16x8*>(row + 2 * d);
+                const T* row = base + (size_t)(quad * 4 + e) * ld + ch * 8;
+                kreg[it][e] = *reinterpret_cast<const V8*>(row + d);
+                vreg[it][e] = *reinterpret_cast<const V8*>(row + 2 * d);
             }
         }
-        if (tid < 16) treg = *reinterpret_cast<const bf16x8*>(base + (size_t)LAST * ld + (tid < 8 ? d : 2 * d) + (tid & 7) * 8);
+        if (tid < 16) treg = *reinterpret_cast<const V8*>(base + (size_t)LAST * ld + (tid < 8 ? d : 2 * d) + (tid & 7) * 8);
 #pragma unroll
         for (int it = 0; it < PER; ++it) {
             const int id = tid + it * 256;
@@ -363,31 +388,31 @@ __global__ __launch_bounds__(256, 2) void attention_tail1_kernel(const bf16_t* _
 #pragma unroll
             for (int e = 0; e < 4; ++e) {
                 const int key = quad * 4 + e;
-                *reinterpret_cast<bf16x8*>(k_lds + key * 128 + ((ch ^ ((key >> 1) & 7)) << 4)) = kreg[it][e];
+                *reinterpret_cast<V8*>(k_lds + key * 128 + ((ch ^ ((key >> 1) & 7)) << 4)) = kreg[it][e];
             }
             const int k0 = quad * 4;
             const int u = k0 >> 5, w = k0 & 31;
             const int pos = (4 * u + ((w & 15) >> 2)) * 16 + ((w >> 4) << 2) * 2;
 #pragma unroll
             for (int j = 0; j < 8; ++j)
-                *reinterpret_cast<bf16x4*>(vt_lds + (ch * 8 + j) * C::VT_ROW + pos) =
-                    bf16x4{vreg[it][0][j], vreg[it][1][j], vreg[it][2][j], vreg[it][3][j]};
+                *reinterpret_cast<V4*>(vt_lds + (ch * 8 + j) * C::VT_ROW + pos) =
+                    V4{vreg[it][0][j], vreg[it][1][j], vreg[it][2][j], vreg[it][3][j]};
         }
-        if (tid < 16) *reinterpret_cast<bf16x8*>(tail + tid * 16) = treg;
+        if (tid < 16) *reinterpret_cast<V8*>(tail + tid * 16) = treg;
     }
     __syncthreads();
 
     const int ql = q_limit < LAST ? q_limit : LAST;               // query rows covered by the MFMA tiles
     const int nqt = DBG == 5 ? 0 : (ql + 15) >> 4;
-    AttnCtx cx{base, out + (size_t)b * S * d + h * DH, k_lds, vt_lds, S, q_limit, ld, d, g, c, nullptr, nullptr, 0, b * S, h * DH, tail};
+    AttnCtx<T> cx{base, out + (size_t)b * S * d + h * DH, k_lds, vt_lds, S, q_limit, ld, d, g, c, nullptr, nullptr, 0, b * S, h * DH, tail};
     const int npair = nqt >> 1;
-    for (int qp = wave; qp < npair; qp += 4) attn_tiles<NKT, false, NKT, DBG, 2, true>(cx, 2 * qp);
-    if ((nqt & 1) && wave == ((blockIdx.x + npair) & 3)) attn_tiles<NKT, false, NKT, DBG, 1, true>(cx, nqt - 1);
+    for (int qp = wave; qp < npair; qp += 4) attn_tiles<T, NKT, false, NKT, DBG, 2, true>(cx, 2 * qp);
+    if ((nqt & 1) && wave == ((blockIdx.x + npair) & 3)) attn_tiles<T, NKT, false, NKT, DBG, 1, true>(cx, nqt - 1);
     if (q_limit <= LAST) return;                                   // kernel-uniform: nobody waits at the barriers below
 
     // ---- the last query row: scores of this wave's 64 keys (lane = key)
     const float sl2 = 0.125f * 1.4426950408889634f;
-    const bf16_t* qrow = base + (size_t)LAST * ld;
+    const T* qrow = base + (size_t)LAST * ld;
     float s = 0.f;
     {
         const int key = 64 * wave + lane;
@@ -395,15 +420,15 @@ __global__ __launch_bounds__(256, 2) void attention_tail1_kernel(const bf16_t* _
         const int f = (key >> 1) & 7;
 #pragma unroll
         for (int ch = 0; ch < 8; ++ch) {
-            const bf16x8 qv = *reinterpret_cast<const bf16x8*>(qrow + 8 * ch);       // same address in every lane: one fetch
-            const bf16x8 kv = *reinterpret_cast<const bf16x8*>(kr + ((ch ^ f) << 4));
+            const V8 qv = *reinterpret_cast<const V8*>(qrow + 8 * ch);       // same address in every lane: one fetch
+            const V8 kv = *reinterpret_cast<const V8*>(kr + ((ch ^ f) << 4));
 #pragma unroll
             for (int j = 0; j < 8; ++j) s += (float)qv[j] * (float)kv[j];
         }
         sc_lds[key] = s;
     }
     const float q_own = (float)qrow[lane];                                            // lane = head dim
-    const float s_last = wave_sum(q_own * (float)reinterpret_cast<const bf16_t*>(tail)[lane]);
+    const float s_last = wave_sum(q_own * (float)reinterpret_cast<const T*>(tail)[lane]);
     __syncthreads();
     // every wave: softmax statistics over all 16 * NKT + 1 scores (lane reads keys lane, lane + 64, ...)
     float mx = s_last;
@@ -417,7 +442,7 @@ __global__ __launch_bounds__(256, 2) void attention_tail1_kernel(const bf16_t* _
     sum = wave_sum(sum);
     const float e_last = __builtin_amdgcn_exp2f(s_last * sl2 + nmx);
     sum += e_last;
-    p_lds[64 * wave + lane] = (float)(bf16_t)__builtin_amdgcn_exp2f(s * sl2 + nmx);   // bf16-rounded like the MFMA path's P
+    p_lds[64 * wave + lane] = (float)(T)__builtin_amdgcn_exp2f(s * sl2 + nmx);   // rounded to T like the MFMA path's P
     __syncthreads();
     // P.V: lane = (dim 16 wave + c, key quarter g); chunk 4u + gg of a V^T row holds keys 32u + 4gg + {0..3}, 32u + 16 + 4gg + {0..3}
     {
@@ -429,7 +454,7 @@ __global__ __launch_bounds__(256, 2) void attention_tail1_kernel(const bf16_t* _
             const int u = g * (NKT / 8) + uu;                       // this quarter's 32-key steps
 #pragma unroll
             for (int gg = 0; gg < 4; ++gg) {
-                const bf16x8 v = *reinterpret_cast<const bf16x8*>(vrow + (4 * u + gg) * 16);
+                const V8 v = *reinterpret_cast<const V8*>(vrow + (4 * u + gg) * 16);
                 const f32x4 pa = *reinterpret_cast<const f32x4*>(p_lds + 32 * u + 4 * gg);
                 const f32x4 pb = *reinterpret_cast<const f32x4*>(p_lds + 32 * u + 16 + 4 * gg);
 #pragma unroll
@@ -437,8 +462,8 @@ __global__ __launch_bounds__(256, 2) void attention_tail1_kernel(const bf16_t* _
             }
         }
         acc = rows_sum(acc);
-        acc += (float)(bf16_t)e_last * (float)reinterpret_cast<const bf16_t*>(tail + 128)[dim];
-        if (g == 0) cx.out[(size_t)LAST * d + dim] = (bf16_t)(acc / sum);
+        acc += (float)(T)e_last * (float)reinterpret_cast<const T*>(tail + 128)[dim];
+        if (g == 0) cx.out[(size_t)LAST * d + dim] = (T)(acc / sum);
     }
 }
 
@@ -456,7 +481,8 @@ __global__ __launch_bounds__(256, 2) void attention_tail1_kernel(const bf16_t* _
 //     fp32 keep their relative precision at any exponent, so exp2(s - m0) is as good as exp2(s - max) as long as it cannot
 //     overflow.  The lane tracks the true maximum on the side (v_max3, 1 cycle per score); if it exceeds m0 by more than 64
 //     (log2 units) for any query of the block -- it never does on real activations -- the block is recomputed once with the now
-//     known maximum.  Exact, branch-free in the common case.
+//     known maximum.  Exact, branch-free in the common case.  The fp16 form (keds_attention_h) packs P to fp16, whose range ends
+//     at 2^16: there the bound is 15 (and a row sum of 2^15), which peaked attention does exceed -- a recompute, not an inf.
 //   * K and V go to LDS by LDS-DMA (global_load_lds_dwordx4, 8 per wave, no staging registers, no LDS-write issue): both
 //     row-major [key][64] with a chunk swizzle applied on the SOURCE side; V^T fragments are read with ds_read_b64_tr_b16
 //     (hardware transpose), so no V^T image is built (the 8-byte V^T writes of the 4-wave kernels were 8-way bank conflicted).
@@ -478,20 +504,27 @@ __device__ __forceinline__ float halves_sum(float x) {
     auto b = __builtin_amdgcn_permlane32_swap(__float_as_uint(x), __float_as_uint(x), false, false);
     return __uint_as_float(b[0]) + __uint_as_float(b[1]);
 }
-// c + sum_j a[j] b[j] with v_dot2c_f32_bf16 (two products per instruction, fp32 accumulate)
+// c + sum_j a[j] b[j] with v_dot2c_f32_bf16 / v_dot2c_f32_f16 (two products per instruction, fp32 accumulate)
 __device__ __forceinline__ float dot8(bf16x8 a, bf16x8 b, float c) {
     c = __builtin_amdgcn_fdot2_f32_bf16(__builtin_shufflevector(a, a, 0, 1), __builtin_shufflevector(b, b, 0, 1), c, false);
     c = __builtin_amdgcn_fdot2_f32_bf16(__builtin_shufflevector(a, a, 2, 3), __builtin_shufflevector(b, b, 2, 3), c, false);
     c = __builtin_amdgcn_fdot2_f32_bf16(__builtin_shufflevector(a, a, 4, 5), __builtin_shufflevector(b, b, 4, 5), c, false);
     return __builtin_amdgcn_fdot2_f32_bf16(__builtin_shufflevector(a, a, 6, 7), __builtin_shufflevector(b, b, 6, 7), c, false);
 }
+__device__ __forceinline__ float dot8(f16x8 a, f16x8 b, float c) {
+    c = __builtin_amdgcn_fdot2(__builtin_shufflevector(a, a, 0, 1), __builtin_shufflevector(b, b, 0, 1), c, false);
+    c = __builtin_amdgcn_fdot2(__builtin_shufflevector(a, a, 2, 3), __builtin_shufflevector(b, b, 2, 3), c, false);
+    c = __builtin_amdgcn_fdot2(__builtin_shufflevector(a, a, 4, 5), __builtin_shufflevector(b, b, 4, 5), c, false);
+    return __builtin_amdgcn_fdot2(__builtin_shufflevector(a, a, 6, 7), __builtin_shufflevector(b, b, 6, 7), c, false);
+}
 typedef __attribute__((ext_vector_type(4))) short s16x4;
-__device__ __forceinline__ bf16x8 tr_pair(const char* lo, const char* hi) {
+template <typename V8>
+__device__ __forceinline__ V8 tr_pair(const char* lo, const char* hi) {
     const s16x4 a = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)lo);
     const s16x4 b = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)hi);
     typedef __attribute__((ext_vector_type(8))) short s16x8;
     const s16x8 v = s16x8{a[0], a[1], a[2], a[3], b[0], b[1], b[2], b[3]};
-    return __builtin_bit_cast(bf16x8, v);
+    return __builtin_bit_cast(V8, v);
 }
 
 // all-VALU wave reductions (DPP within the 16-lane rows, permlane swaps across them); __shfl_xor is six LDS round trips
@@ -513,13 +546,15 @@ __device__ __forceinline__ float wave_max_v(float x) {
 
 // Q8 (fp8 towers): rows < q8_rows of the [B*S, d] output go out as MXFP8 (e4m3 + one e8m0 scale per 32 columns: q8 / s8
 // as in attention_kernel) INSTEAD of bf16; a 32-dim output tile of a query is exactly one MX block, held by two lanes.
-template <int DBG = 0, bool Q8 = false>
-__global__ __launch_bounds__(512, 4) void attention_s257_kernel(const bf16_t* __restrict__ qkv, bf16_t* __restrict__ out,
+template <int DBG = 0, bool Q8 = false, typename T = bf16_t>
+__global__ __launch_bounds__(512, 4) void attention_s257_kernel(const T* __restrict__ qkv, T* __restrict__ out,
                                                                 int heads, int q_limit,
                                                                 unsigned long long* __restrict__ stamp,
                                                                 unsigned char* __restrict__ q8 = nullptr,
                                                                 unsigned char* __restrict__ s8 = nullptr, int q8_rows = 0) {
     using namespace s257;
+    using V8 = typename Ev<T>::v8;
+    using V4 = typename Ev<T>::v4;
     constexpr int S = 257, LAST = 256;
     extern __shared__ __attribute__((aligned(16))) char smem[];
     [[maybe_unused]] unsigned long long t_in = 0, t_staged = 0, t_lastq = 0, t_loop = 0;
@@ -537,20 +572,20 @@ __global__ __launch_bounds__(512, 4) void attention_s257_kernel(const bf16_t* __
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int r = lane & 31, hh = lane >> 5;
-    const bf16_t* base = qkv + (size_t)b * S * ld + h * DH;
-    bf16_t* obase = out + (size_t)b * S * d + h * DH;
+    const T* base = qkv + (size_t)b * S * ld + h * DH;
+    T* obase = out + (size_t)b * S * d + h * DH;
     const float sl2 = 0.125f * 1.4426950408889634f;
 
     // ---- row 256 (q, k, v: 3 x 128 B) through registers, this wave's 32 queries as B operands (k = head dims), then the
     // 256 leading K and V rows by LDS-DMA: piece = 8 rows = 1 KiB = one wave-instruction; LDS slot (row, c) holds source
     // chunk c ^ f(row).  Keys 0-127 are issued first and waited for alone: the first four key tiles run while 128-255 land.
-    bf16x8 trow = bf16x8{0, 0, 0, 0, 0, 0, 0, 0};
-    if (tid < 24) trow = *reinterpret_cast<const bf16x8*>(base + (size_t)LAST * ld + (tid >> 3) * d + (tid & 7) * 8);
-    bf16x8 qf[4];
+    V8 trow = V8{0, 0, 0, 0, 0, 0, 0, 0};
+    if (tid < 24) trow = *reinterpret_cast<const V8*>(base + (size_t)LAST * ld + (tid >> 3) * d + (tid & 7) * 8);
+    V8 qf[4];
     {
-        const bf16_t* qp = base + (size_t)(32 * wave + r) * ld + 8 * hh;
+        const T* qp = base + (size_t)(32 * wave + r) * ld + 8 * hh;
 #pragma unroll
-        for (int ks = 0; ks < 4; ++ks) qf[ks] = *reinterpret_cast<const bf16x8*>(qp + 16 * ks);
+        for (int ks = 0; ks < 4; ++ks) qf[ks] = *reinterpret_cast<const V8*>(qp + 16 * ks);
     }
     if constexpr (DBG != 1) {
         const int prow = lane >> 3, slot = lane & 7;
@@ -559,7 +594,7 @@ __global__ __launch_bounds__(512, 4) void attention_s257_kernel(const bf16_t* __
             const int piece = wave + 8 * i;
             const int row = 8 * piece + prow;
             const int fk = (row >> 1) & 7, fv = ((row >> 1) & 1) << 2;
-            const bf16_t* src = base + (size_t)row * ld;
+            const T* src = base + (size_t)row * ld;
             __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(src + d + ((slot ^ fk) << 3)),
                                              (__attribute__((address_space(3))) void*)(smem + K_OFF + piece * 1024), 16, 0, KEDS_LD_ATTN_AUX);
             __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(src + 2 * d + ((slot ^ fv) << 3)),
@@ -567,7 +602,7 @@ __global__ __launch_bounds__(512, 4) void attention_s257_kernel(const bf16_t* __
         }
     }
     // tail image: [q row 256 | k row 256 | v row 256], 128 B each, unswizzled; the last-query arrival counter
-    if (tid < 24) *reinterpret_cast<bf16x8*>(smem + TAIL_OFF + tid * 16) = trow;
+    if (tid < 24) *reinterpret_cast<V8*>(smem + TAIL_OFF + tid * 16) = trow;
     if (tid == 24) *reinterpret_cast<int*>(smem + CNT_OFF) = 0;
     if constexpr (DBG != 1) asm volatile("s_waitcnt vmcnt(4)" ::: "memory");   // everything older than the last four DMA pieces
     __syncthreads();
@@ -587,19 +622,19 @@ __global__ __launch_bounds__(512, 4) void attention_s257_kernel(const bf16_t* __
 #pragma unroll
         for (int c4 = 0; c4 < 4; ++c4) {
             const int ch = 4 * hh + c4;
-            sq = dot8(*reinterpret_cast<const bf16x8*>(tq + ch * 16),
-                      *reinterpret_cast<const bf16x8*>(smem + K_OFF + key * 128 + ((ch ^ fk) << 4)), sq);
+            sq = dot8(*reinterpret_cast<const V8*>(tq + ch * 16),
+                      *reinterpret_cast<const V8*>(smem + K_OFF + key * 128 + ((ch ^ fk) << 4)), sq);
         }
         sq = halves_sum(sq);                                        // lanes r and r + 32: score of key 32 w + r
         float s256 = -INFINITY;
         if (wave == 0) {                                            // key 256: lanes 0-7 take one chunk each
-            const float t = lane < 8 ? dot8(*reinterpret_cast<const bf16x8*>(tq + (lane & 7) * 16),
-                                            *reinterpret_cast<const bf16x8*>(tk + (lane & 7) * 16), 0.f) : 0.f;
+            const float t = lane < 8 ? dot8(*reinterpret_cast<const V8*>(tq + (lane & 7) * 16),
+                                            *reinterpret_cast<const V8*>(tk + (lane & 7) * 16), 0.f) : 0.f;
             s256 = wave_sum_v(t);
         }
         const float mw = fmaxf(wave_max_v(sq), s256);
         const float nmw = -mw * sl2;
-        const float pk = (float)(bf16_t)__builtin_amdgcn_exp2f(__builtin_fmaf(sq, sl2, nmw));   // bf16-rounded like the MFMA path's P
+        const float pk = (float)(T)__builtin_amdgcn_exp2f(__builtin_fmaf(sq, sl2, nmw));   // rounded to T like the MFMA path's P
         const float e256 = wave == 0 ? __builtin_amdgcn_exp2f(__builtin_fmaf(s256, sl2, nmw)) : 0.f;
         const float lw = wave_sum_v(hh == 0 ? __builtin_amdgcn_exp2f(__builtin_fmaf(sq, sl2, nmw)) : 0.f) + e256;
         // P.V over the wave's 32 keys: lane = (8-dim chunk ch, key subset sub): keys 32 w + sub + 8 i
@@ -613,7 +648,7 @@ __global__ __launch_bounds__(512, 4) void attention_s257_kernel(const bf16_t* __
             const float p = __uint_as_float(__builtin_amdgcn_ds_bpermute(kk << 2, __float_as_uint(pk)));
             const int key2 = 32 * wave + kk;
             const int fv = ((key2 >> 1) & 1) << 2;
-            const bf16x8 v = *reinterpret_cast<const bf16x8*>(smem + V_OFF + key2 * 128 + ((ch ^ fv) << 4));
+            const V8 v = *reinterpret_cast<const V8*>(smem + V_OFF + key2 * 128 + ((ch ^ fv) << 4));
 #pragma unroll
             for (int j = 0; j < 8; ++j) acc[j] += p * (float)v[j];
         }
@@ -625,8 +660,8 @@ __global__ __launch_bounds__(512, 4) void attention_s257_kernel(const bf16_t* __
         }
         if (lane < 8) {
             if (wave == 0) {
-                const bf16x8 v = *reinterpret_cast<const bf16x8*>(tv + ch * 16);
-                const float p = (float)(bf16_t)e256;
+                const V8 v = *reinterpret_cast<const V8*>(tv + ch * 16);
+                const float p = (float)(T)e256;
 #pragma unroll
                 for (int j = 0; j < 8; ++j) acc[j] += p * (float)v[j];
             }
@@ -669,7 +704,7 @@ __global__ __launch_bounds__(512, 4) void attention_s257_kernel(const bf16_t* __
                 q8[(size_t)row * d + h * DH + lane] = (unsigned char)(pk & 0xFFu);
                 if ((lane & 31) == 0) s8[mx_scale_index((h * DH + lane) >> 5, row, q8_rows)] = (unsigned char)(e + 127);
             } else {
-                obase[(size_t)LAST * d + lane] = (bf16_t)val;
+                obase[(size_t)LAST * d + lane] = (T)val;
             }
         }
     };
@@ -704,7 +739,7 @@ __global__ __launch_bounds__(512, 4) void attention_s257_kernel(const bf16_t* __
                     for (int i = 0; i < 16; ++i) sc[i] = 0.f;
 #pragma unroll
                     for (int ks = 0; ks < 4; ++ks)
-                        sc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(*reinterpret_cast<const bf16x8*>(smem + ka[ks] + kt * 4096), qf[ks], sc, 0, 0, 0);
+                        sc = mfma32(*reinterpret_cast<const V8*>(smem + ka[ks] + kt * 4096), qf[ks], sc, 0, 0, 0);
 #pragma unroll
                     for (int i = 0; i < 16; ++i) mrun = fmaxf(mrun, sc[i]);
                 }
@@ -725,7 +760,7 @@ __global__ __launch_bounds__(512, 4) void attention_s257_kernel(const bf16_t* __
                         const int nb = (int)blockIdx.x + KEDS_ATTN_PREFETCH;
                         if (nb < (int)gridDim.x) {
                             const int b2 = nb / heads, h2 = nb - b2 * heads;
-                            const bf16_t* base2 = qkv + (size_t)b2 * S * ld + h2 * DH;
+                            const T* base2 = qkv + (size_t)b2 * S * ld + h2 * DH;
 #pragma unroll
                             for (int i = 0; i < 2; ++i) {
                                 const int line = 64 * (2 * wave + i) + lane;
@@ -741,9 +776,9 @@ __global__ __launch_bounds__(512, 4) void attention_s257_kernel(const bf16_t* __
                     if (do_last) last_query_partial();
                 }
                 const char* kb = smem + half * 16384;
-                bf16x8 a[4];                                               // K fragments of the NEXT tile: read under the P.V MFMAs
+                V8 a[4];                                               // K fragments of the NEXT tile: read under the P.V MFMAs
 #pragma unroll
-                for (int ks = 0; ks < 4; ++ks) a[ks] = *reinterpret_cast<const bf16x8*>(kb + ka[ks]);
+                for (int ks = 0; ks < 4; ++ks) a[ks] = *reinterpret_cast<const V8*>(kb + ka[ks]);
                 // four tiles unrolled: every LDS address is a lane constant + an immediate
 #pragma unroll
                 for (int k4 = 0; k4 < 4; ++k4) {
@@ -752,7 +787,7 @@ __global__ __launch_bounds__(512, 4) void attention_s257_kernel(const bf16_t* __
                     for (int i = 0; i < 16; ++i) sc[i] = 0.f;
                     if constexpr (DBG != 2) {
 #pragma unroll
-                        for (int ks = 0; ks < 4; ++ks) sc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[ks], qf[ks], sc, 0, 0, 0);
+                        for (int ks = 0; ks < 4; ++ks) sc = mfma32(a[ks], qf[ks], sc, 0, 0, 0);
                     } else {
                         sc[0] = (float)qf[k4][0] + (float)a[k4][0];
                     }
@@ -772,21 +807,21 @@ __global__ __launch_bounds__(512, 4) void attention_s257_kernel(const bf16_t* __
                             sc[i] = e;
                         }
                     }
-                    const bf16x8 p0 = bf16x8{(bf16_t)sc[0], (bf16_t)sc[1], (bf16_t)sc[2], (bf16_t)sc[3],
-                                             (bf16_t)sc[4], (bf16_t)sc[5], (bf16_t)sc[6], (bf16_t)sc[7]};
-                    const bf16x8 p1 = bf16x8{(bf16_t)sc[8], (bf16_t)sc[9], (bf16_t)sc[10], (bf16_t)sc[11],
-                                             (bf16_t)sc[12], (bf16_t)sc[13], (bf16_t)sc[14], (bf16_t)sc[15]};
+                    const V8 p0 = V8{(T)sc[0], (T)sc[1], (T)sc[2], (T)sc[3],
+                                             (T)sc[4], (T)sc[5], (T)sc[6], (T)sc[7]};
+                    const V8 p1 = V8{(T)sc[8], (T)sc[9], (T)sc[10], (T)sc[11],
+                                             (T)sc[12], (T)sc[13], (T)sc[14], (T)sc[15]};
                     if (k4 < 3) {
 #pragma unroll
-                        for (int ks = 0; ks < 4; ++ks) a[ks] = *reinterpret_cast<const bf16x8*>(kb + ka[ks] + (k4 + 1) * 4096);
+                        for (int ks = 0; ks < 4; ++ks) a[ks] = *reinterpret_cast<const V8*>(kb + ka[ks] + (k4 + 1) * 4096);
                     }
                     if constexpr (DBG != 4) {
                         const char* v0 = kb + vb0 + k4 * 4096;
                         const char* v1 = kb + vb1 + k4 * 4096;
-                        o0 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(tr_pair(v0, v0 + 1024), p0, o0, 0, 0, 0);
-                        o1 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(tr_pair(v1, v1 + 1024), p0, o1, 0, 0, 0);
-                        o0 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(tr_pair(v0 + 2048, v0 + 3072), p1, o0, 0, 0, 0);
-                        o1 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(tr_pair(v1 + 2048, v1 + 3072), p1, o1, 0, 0, 0);
+                        o0 = mfma32(tr_pair<V8>(v0, v0 + 1024), p0, o0, 0, 0, 0);
+                        o1 = mfma32(tr_pair<V8>(v1, v1 + 1024), p0, o1, 0, 0, 0);
+                        o0 = mfma32(tr_pair<V8>(v0 + 2048, v0 + 3072), p1, o0, 0, 0, 0);
+                        o1 = mfma32(tr_pair<V8>(v1 + 2048, v1 + 3072), p1, o1, 0, 0, 0);
                     } else {
                         o0[0] += (float)p0[0] + (float)p1[0];
                     }
@@ -797,12 +832,15 @@ __global__ __launch_bounds__(512, 4) void attention_s257_kernel(const bf16_t* __
             // ---- the last key: score from this lane's 32 query dims, combined over the two halves
             float ts = 0.f;
 #pragma unroll
-            for (int ks = 0; ks < 4; ++ks) ts = dot8(qf[ks], *reinterpret_cast<const bf16x8*>(tk + (2 * ks + hh) * 16), ts);
+            for (int ks = 0; ks < 4; ++ks) ts = dot8(qf[ks], *reinterpret_cast<const V8*>(tk + (2 * ks + hh) * 16), ts);
             ts = halves_sum(ts);
             // Overflow check of the reference: every e <= the row sum, so a bounded sum bounds every probability and every
             // P.V term; (ts - mref) covers the rank-1 key.  A NaN row fails the test too (recomputed once, stays NaN).
             const float ltot = halves_sum(lsum);
-            const bool bad = !(ltot <= 0x1p80f) || !((ts - mref) * sl2 <= 64.0f);
+            // (fp16 P: every probability is packed to fp16 before the P.V product, so the bound is the fp16 range -- the row sum, and
+            // with it every e, at most 2^15 -- where bf16 P has the fp32 exponent range)
+            constexpr bool P16 = __is_same(T, f16_t);
+            const bool bad = !(ltot <= (P16 ? 0x1p15f : 0x1p80f)) || !((ts - mref) * sl2 <= (P16 ? 15.0f : 64.0f));
             if (!have && __builtin_amdgcn_ballot_w64(bad) != 0ull) {
                 mgiven = ts;
                 have = true;
@@ -810,11 +848,11 @@ __global__ __launch_bounds__(512, 4) void attention_s257_kernel(const bf16_t* __
             }
             const float et = __builtin_amdgcn_exp2f(__builtin_fmaf(ts, sl2, nm));
             const float inv = 1.0f / (ltot + et);
-            const float tp = (float)(bf16_t)et;                         // rounded like the probabilities the MFMA path multiplies
+            const float tp = (float)(T)et;                         // rounded to T like the probabilities the MFMA path multiplies
 #pragma unroll
             for (int g4 = 0; g4 < 4; ++g4) {
-                const bf16x4 va = *reinterpret_cast<const bf16x4*>(tv + (8 * g4 + 4 * hh) * 2);
-                const bf16x4 vb = *reinterpret_cast<const bf16x4*>(tv + (32 + 8 * g4 + 4 * hh) * 2);
+                const V4 va = *reinterpret_cast<const V4*>(tv + (8 * g4 + 4 * hh) * 2);
+                const V4 vb = *reinterpret_cast<const V4*>(tv + (32 + 8 * g4 + 4 * hh) * 2);
 #pragma unroll
                 for (int j = 0; j < 4; ++j) {
                     o0[4 * g4 + j] += tp * (float)va[j];
@@ -867,10 +905,10 @@ __global__ __launch_bounds__(512, 4) void attention_s257_kernel(const bf16_t* __
                 for (int pr2 = 0; pr2 < 2; ++pr2) {
                     const int ge = 2 * pr2, go = 2 * pr2 + 1;
                     const f32x16& o = tile ? o1 : o0;
-                    const bf16x4 pe = bf16x4{(bf16_t)(o[4 * ge] * inv), (bf16_t)(o[4 * ge + 1] * inv), (bf16_t)(o[4 * ge + 2] * inv),
-                                             (bf16_t)(o[4 * ge + 3] * inv)};
-                    const bf16x4 po = bf16x4{(bf16_t)(o[4 * go] * inv), (bf16_t)(o[4 * go + 1] * inv), (bf16_t)(o[4 * go + 2] * inv),
-                                             (bf16_t)(o[4 * go + 3] * inv)};
+                    const V4 pe = V4{(T)(o[4 * ge] * inv), (T)(o[4 * ge + 1] * inv), (T)(o[4 * ge + 2] * inv),
+                                             (T)(o[4 * ge + 3] * inv)};
+                    const V4 po = V4{(T)(o[4 * go] * inv), (T)(o[4 * go + 1] * inv), (T)(o[4 * go + 2] * inv),
+                                             (T)(o[4 * go + 3] * inv)};
                     const u32x2 ue = __builtin_bit_cast(u32x2, pe), uo = __builtin_bit_cast(u32x2, po);
                     const auto s0 = __builtin_amdgcn_permlane32_swap(ue[0], uo[0], false, false);
                     const auto s1 = __builtin_amdgcn_permlane32_swap(ue[1], uo[1], false, false);
@@ -956,12 +994,13 @@ __global__ __launch_bounds__(512, 4) void attention_s257_kernel(const bf16_t* __
 int g_attn_debug = 0;   // timing-only ablations (ViT kernel)
 int g_attn_tail = 1;    // A/B hook: 0 routes S = 257 through the generic (padded) kernel
 
+template <typename T = bf16_t>
 int launch_attn_tail1(const void* qkv, void* out, int B, int heads, int q_limit, hipStream_t st) {
     using C = AttnCfg<16>;
     constexpr int LDS = C::LDS + TAIL_LDS;
-    if (int rc = keds_func_lds_once((const void*)attention_tail1_kernel<16>, LDS, "attention_tail1_kernel")) return rc;
+    if (int rc = keds_func_lds_once((const void*)attention_tail1_kernel<16, 0, T>, LDS, "attention_tail1_kernel")) return rc;
     KedsProfScope prof(KEDS_PROF_ATTN, st);
-    attention_tail1_kernel<16><<<B * heads, 256, LDS, st>>>((const bf16_t*)qkv, (bf16_t*)out, heads, q_limit);
+    attention_tail1_kernel<16, 0, T><<<B * heads, 256, LDS, st>>>((const T*)qkv, (T*)out, heads, q_limit);
     return keds_check_launch("attention_tail1_kernel");
 }
 
@@ -1005,7 +1044,15 @@ int launch_attn_s257_q8(const void* qkv, void* out, int B, int heads, int q_limi
     return keds_check_launch("attention_s257_kernel<q8>");
 }
 
+template <typename T = bf16_t>
 int launch_attn_s257(const void* qkv, void* out, int B, int heads, int q_limit, hipStream_t st) {
+    if constexpr (__is_same(T, f16_t)) {                          // the fp16 form: product kernel only (no ablation builds)
+        if (int rc = keds_func_lds_once((const void*)attention_s257_kernel<0, false, f16_t>, s257::LDS, "attention_s257_kernel<f16>")) return rc;
+        KedsProfScope prof(KEDS_PROF_ATTN, st);
+        launch_s257(attention_s257_kernel<0, false, f16_t>, B * heads, st, (const f16_t*)qkv, (f16_t*)out, heads, q_limit,
+                    (unsigned long long*)nullptr, (unsigned char*)nullptr, (unsigned char*)nullptr, 0);
+        return keds_check_launch("attention_s257_kernel<f16>");
+    }
     switch (g_attn_s257_dbg) {
         case 1: return launch_attn_s257_dbg<1>(qkv, out, B, heads, q_limit, st);
         case 2: return launch_attn_s257_dbg<2>(qkv, out, B, heads, q_limit, st);
@@ -1025,10 +1072,19 @@ int launch_attn_s257(const void* qkv, void* out, int B, int heads, int q_limit, 
     return keds_check_launch("attention_s257_kernel");
 }
 
-template <int NKT, bool CAUSAL, int NFULL>
+template <int NKT, bool CAUSAL, int NFULL, typename T = bf16_t>
 int launch_attn(const void* qkv, void* out, int B, int S, int heads, int q_limit, void* q8, void* s8, int q8_rows,
                 hipStream_t st, const int* seq_off = nullptr) {
     using C = AttnCfg<NKT>;
+    if constexpr (__is_same(T, f16_t)) {                          // the fp16 form: product kernels only
+        constexpr bool NQ2 = NKT == 18 && !CAUSAL;
+        if (int rc = keds_func_lds_once((const void*)attention_kernel<NKT, CAUSAL, NFULL, 0, NQ2, f16_t>, C::LDS, "attention_kernel<f16>"))
+            return rc;
+        KedsProfScope prof(KEDS_PROF_ATTN, st);
+        attention_kernel<NKT, CAUSAL, NFULL, 0, NQ2, f16_t><<<B * heads, 256, C::LDS, st>>>((const f16_t*)qkv, (f16_t*)out, S, heads, q_limit,
+                                                                                             nullptr, nullptr, 0, seq_off);
+        return keds_check_launch("attention_kernel<f16>");
+    }
     if (int rc = keds_func_lds_once((const void*)attention_kernel<NKT, CAUSAL, NFULL>, C::LDS, "attention_kernel")) return rc;
     KedsProfScope prof(KEDS_PROF_ATTN, st);
     if constexpr (NKT == 18 && !CAUSAL && NFULL == 16) {
@@ -1105,6 +1161,40 @@ extern "C" int keds_attention_mx(const void* qkv, void* out, int B, int S, int h
     if (S == 257 && !q8 && g_attn_tail && !g_attn_debug) return launch_attn_tail1(qkv, out, B, heads, q_limit, st);
     if (S >= 256) return launch_attn<18, false, 16>(qkv, out, B, S, heads, q_limit, q8, s8, q8_rows, st);   // ViT-L/14: 257 tokens
     return launch_attn<18, false, 0>(qkv, out, B, S, heads, q_limit, q8, s8, q8_rows, st);
+}
+
+// fp16 forms (the "fp16" operating point): the same dispatch on fp16 qkv / out
+extern "C" int keds_attention_h(const void* qkv, void* out, int B, int S, int heads, int causal, int q_limit, void* stream) {
+    KEDS_REQUIRE(qkv && out && B > 0 && heads > 0, "keds_attention_h: bad argument");
+    KEDS_REQUIRE(S >= 1 && S <= 288, "keds_attention_h: S=%d unsupported (1..288)", S);
+    if (q_limit <= 0 || q_limit > S) q_limit = S;
+    hipStream_t st = (hipStream_t)stream;
+    if (causal) {
+        if (S <= 32) return launch_attn<2, true, 0, f16_t>(qkv, out, B, S, heads, q_limit, nullptr, nullptr, 0, st);
+        if (S <= 96) return launch_attn<6, true, 0, f16_t>(qkv, out, B, S, heads, q_limit, nullptr, nullptr, 0, st);
+        return launch_attn<18, true, 0, f16_t>(qkv, out, B, S, heads, q_limit, nullptr, nullptr, 0, st);
+    }
+    if (S <= 32) return launch_attn<2, false, 0, f16_t>(qkv, out, B, S, heads, q_limit, nullptr, nullptr, 0, st);
+    if (S <= 96) return launch_attn<6, false, 0, f16_t>(qkv, out, B, S, heads, q_limit, nullptr, nullptr, 0, st);
+    if (S == 257 && g_attn_tail && g_attn_s257) return launch_attn_s257<f16_t>(qkv, out, B, heads, q_limit, st);
+    if (S == 257 && g_attn_tail) return launch_attn_tail1<f16_t>(qkv, out, B, heads, q_limit, st);
+    if (S >= 256) return launch_attn<18, false, 16, f16_t>(qkv, out, B, S, heads, q_limit, nullptr, nullptr, 0, st);
+    return launch_attn<18, false, 0, f16_t>(qkv, out, B, S, heads, q_limit, nullptr, nullptr, 0, st);
+}
+
+extern "C" int keds_attention_packed_h(const void* qkv, void* out, int B, int s_max, const int32_t* seq_off, int heads, int causal,
+                                       void* stream) {
+    KEDS_REQUIRE(qkv && out && seq_off && B > 0 && heads > 0, "keds_attention_packed_h: bad argument");
+    KEDS_REQUIRE(s_max >= 1 && s_max <= 288, "keds_attention_packed_h: s_max=%d unsupported (1..288)", s_max);
+    hipStream_t st = (hipStream_t)stream;
+    if (causal) {
+        if (s_max <= 32) return launch_attn<2, true, 0, f16_t>(qkv, out, B, s_max, heads, s_max, nullptr, nullptr, 0, st, seq_off);
+        if (s_max <= 96) return launch_attn<6, true, 0, f16_t>(qkv, out, B, s_max, heads, s_max, nullptr, nullptr, 0, st, seq_off);
+        return launch_attn<18, true, 0, f16_t>(qkv, out, B, s_max, heads, s_max, nullptr, nullptr, 0, st, seq_off);
+    }
+    if (s_max <= 32) return launch_attn<2, false, 0, f16_t>(qkv, out, B, s_max, heads, s_max, nullptr, nullptr, 0, st, seq_off);
+    if (s_max <= 96) return launch_attn<6, false, 0, f16_t>(qkv, out, B, s_max, heads, s_max, nullptr, nullptr, 0, st, seq_off);
+    return launch_attn<18, false, 0, f16_t>(qkv, out, B, s_max, heads, s_max, nullptr, nullptr, 0, st, seq_off);
 }
 
 // Packed rows: sample b is rows [seq_off[b], seq_off[b + 1]) of qkv / out (device int32 [B + 1], lengths 1 .. s_max).  The text

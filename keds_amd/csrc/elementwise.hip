@@ -15,7 +15,7 @@ constexpr int LN_MAXV = 8;  // f32x4 chunks per lane: dim <= 2048
 // NV = dim/256 f32x4 chunks per lane, known at compile time so all row loads (and gamma/beta) are issued
 // back to back before the first reduction (predicated loads were being serialised: 2.6 TB/s -> see profiles/);
 // NV == 0 is the generic fallback (dim == 128 or any dim <= 2048 that is a multiple of 4).
-// OUT: 0 = bf16, 1 = fp32, 2 = a PAIR of fp16 planes (hi = out, lo = out + pair_plane elements: y = hi + lo to 22 bits, the A
+// OUT: 0 = bf16, 1 = fp32, 3 = fp16 (the "fp16" operating point), 2 = a PAIR of fp16 planes (hi = out, lo = out + pair_plane elements: y = hi + lo to 22 bits, the A
 // operand of a split-operand GEMM, keds_gemm_x3)
 template <int OUT, int NV>
 __global__ __launch_bounds__(256) void layernorm_kernel(const float* __restrict__ x, long long x_stride,
@@ -77,6 +77,10 @@ __global__ __launch_bounds__(256) void layernorm_kernel(const float* __restrict_
                 f16_t* o = reinterpret_cast<f16_t*>(out) + (size_t)r * dim + i;
                 *reinterpret_cast<f16x4*>(o) = hi;
                 *reinterpret_cast<f16x4*>(o + pair_plane) = lo;
+            } else if constexpr (OUT == 3) {
+                typedef __attribute__((ext_vector_type(4))) _Float16 f16x4;
+                *reinterpret_cast<f16x4*>(reinterpret_cast<f16_t*>(out) + (size_t)r * dim + i) =
+                    f16x4{(f16_t)y[0], (f16_t)y[1], (f16_t)y[2], (f16_t)y[3]};
             } else {
                 *reinterpret_cast<bf16x4*>(reinterpret_cast<bf16_t*>(out) + (size_t)r * dim + i) =
                     bf16x4{(bf16_t)y[0], (bf16_t)y[1], (bf16_t)y[2], (bf16_t)y[3]};
@@ -335,7 +339,8 @@ __global__ __launch_bounds__(256) void preprocess_pil_kernel(const unsigned char
 }
 
 // one block per output row (b, patch); columns c*P*P + ky*P + kx, zero padded to Kpad
-__global__ __launch_bounds__(256) void im2col_kernel(const float* __restrict__ img, bf16_t* __restrict__ out, int R,
+template <typename T>   // bf16_t, or f16_t (the "fp16" operating point)
+__global__ __launch_bounds__(256) void im2col_kernel(const float* __restrict__ img, T* __restrict__ out, int R,
                                                      int P, int Kpad) {
     const int g = R / P;
     const int row = blockIdx.x;
@@ -350,7 +355,7 @@ __global__ __launch_bounds__(256) void im2col_kernel(const float* __restrict__ i
             const int ky = rem / P, kx = rem % P;
             v = base[(size_t)ch * R * R + (size_t)(py * P + ky) * R + px * P + kx];
         }
-        out[(size_t)row * Kpad + k] = (bf16_t)v;
+        out[(size_t)row * Kpad + k] = (T)v;
     }
 }
 
@@ -434,15 +439,17 @@ __global__ __launch_bounds__(256) void mix_kernel(const float* __restrict__ a, c
     }
 }
 
-__global__ void cast_bf16_kernel(const float* __restrict__ x, bf16_t* __restrict__ out, long long n) {
+template <typename T>   // bf16_t (keds_cast_bf16) or f16_t (keds_cast_f16)
+__global__ void cast16_kernel(const float* __restrict__ x, T* __restrict__ out, long long n) {
+    typedef __attribute__((ext_vector_type(4))) T t4;
     long long i = (blockIdx.x * (long long)blockDim.x + threadIdx.x) * 4;
     const long long step = (long long)gridDim.x * blockDim.x * 4;
     for (; i + 3 < n; i += step) {
         const f32x4 v = *reinterpret_cast<const f32x4*>(x + i);
-        *reinterpret_cast<bf16x4*>(out + i) = bf16x4{(bf16_t)v[0], (bf16_t)v[1], (bf16_t)v[2], (bf16_t)v[3]};
+        *reinterpret_cast<t4*>(out + i) = t4{(T)v[0], (T)v[1], (T)v[2], (T)v[3]};
     }
     if (i < n && i + 3 >= n)
-        for (long long j = i; j < n; ++j) out[j] = (bf16_t)x[j];
+        for (long long j = i; j < n; ++j) out[j] = (T)x[j];
 }
 
 bool ln_dim_ok(int dim) { return dim > 0 && dim <= 2048 && dim % 4 == 0 && (dim % 256 == 0 || dim == 128); }
@@ -464,10 +471,12 @@ static void ln_launch(const float* x, long long x_stride, const int* row_map, in
 #undef KEDS_LN
 }
 
+// out_f32: 0 bf16, 1 fp32, 2 fp16 (the "fp16" operating point's tail rows and read-out)
 int keds_layernorm_impl(const float* x, long long x_stride, const int* row_map, int row_mul, const float* gamma,
                         const float* beta, void* out, int out_f32, int rows, int dim, hipStream_t st) {
     KedsProfScope prof(KEDS_PROF_LN, st);
-    if (out_f32) ln_launch<1>(x, x_stride, row_map, row_mul, gamma, beta, out, rows, dim, st);
+    if (out_f32 == 2) ln_launch<3>(x, x_stride, row_map, row_mul, gamma, beta, out, rows, dim, st);
+    else if (out_f32) ln_launch<1>(x, x_stride, row_map, row_mul, gamma, beta, out, rows, dim, st);
     else ln_launch<0>(x, x_stride, row_map, row_mul, gamma, beta, out, rows, dim, st);
     return keds_check_launch("layernorm_kernel");
 }
@@ -679,16 +688,31 @@ extern "C" int keds_layernorm(const float* x, int64_t x_stride, const float* gam
     KEDS_REQUIRE(x && gamma && beta && out && rows > 0, "keds_layernorm: bad argument");
     KEDS_REQUIRE(ln_dim_ok(dim), "keds_layernorm: dim %d unsupported", dim);
     KEDS_REQUIRE(x_stride % 4 == 0, "keds_layernorm: row stride must be a multiple of 4");
-    return keds_layernorm_impl(x, x_stride, nullptr, 1, gamma, beta, out, out_f32, rows, dim, (hipStream_t)stream);
+    // (out_f32 is a flag here: any nonzero value is fp32; fp16 output goes through keds_layernorm_ex)
+    return keds_layernorm_impl(x, x_stride, nullptr, 1, gamma, beta, out, out_f32 ? 1 : 0, rows, dim, (hipStream_t)stream);
 }
 
-extern "C" int keds_im2col(const float* image, void* out, int B, int R, int P, int Kpad, void* stream) {
+extern "C" int keds_layernorm_ex(const float* x, int64_t x_stride, const float* gamma, const float* beta, void* out,
+                                 int out_type, int rows, int dim, void* stream) {
+    KEDS_REQUIRE(out_type >= 0 && out_type <= 2, "keds_layernorm_ex: out_type %d (0 bf16, 1 fp32, 2 fp16)", out_type);
+    KEDS_REQUIRE(x && gamma && beta && out && rows > 0, "keds_layernorm: bad argument");
+    KEDS_REQUIRE(ln_dim_ok(dim), "keds_layernorm: dim %d unsupported", dim);
+    KEDS_REQUIRE(x_stride % 4 == 0, "keds_layernorm: row stride must be a multiple of 4");
+    return keds_layernorm_impl(x, x_stride, nullptr, 1, gamma, beta, out, out_type, rows, dim, (hipStream_t)stream);
+}
+
+extern "C" int keds_im2col_ex(const float* image, void* out, int out_f16, int B, int R, int P, int Kpad, void* stream) {
     KEDS_REQUIRE(image && out && B > 0 && P > 0 && R % P == 0, "keds_im2col: bad argument");
     KEDS_REQUIRE(Kpad >= 3 * P * P && Kpad % 64 == 0, "keds_im2col: Kpad must cover 3*P*P and be a multiple of 64");
     const int g = R / P;
     KedsProfScope prof(KEDS_PROF_OTHER, (hipStream_t)stream);
-    im2col_kernel<<<B * g * g, 256, 0, (hipStream_t)stream>>>(image, (bf16_t*)out, R, P, Kpad);
+    if (out_f16) im2col_kernel<f16_t><<<B * g * g, 256, 0, (hipStream_t)stream>>>(image, (f16_t*)out, R, P, Kpad);
+    else im2col_kernel<bf16_t><<<B * g * g, 256, 0, (hipStream_t)stream>>>(image, (bf16_t*)out, R, P, Kpad);
     return keds_check_launch("im2col_kernel");
+}
+
+extern "C" int keds_im2col(const float* image, void* out, int B, int R, int P, int Kpad, void* stream) {
+    return keds_im2col_ex(image, out, 0, B, R, P, Kpad, stream);
 }
 
 int keds_cls_rows_impl(float* x, const float* cls, const float* pos, int B, int S, int d, hipStream_t st) {
@@ -724,9 +748,10 @@ extern "C" size_t keds_readout_workspace_bytes(int B, int d) {
     return keds_align_up((size_t)B, 128) * d * 2;
 }
 
-extern "C" int keds_readout(const float* x, int S, const int32_t* row, const float* gamma, const float* beta,
-                            const void* proj_t, float* out, int B, int d, int E, int normalize, void* workspace,
-                            size_t workspace_bytes, void* stream) {
+// f16: the "fp16" operating point -- LayerNorm output and proj_t fp16
+int keds_readout_impl(const float* x, int S, const int32_t* row, const float* gamma, const float* beta,
+                      const void* proj_t, float* out, int B, int d, int E, int normalize, void* workspace,
+                      size_t workspace_bytes, void* stream, bool f16) {
     KEDS_REQUIRE(x && gamma && beta && proj_t && out && workspace && B > 0, "keds_readout: bad argument");
     KEDS_REQUIRE(ln_dim_ok(d), "keds_readout: d %d unsupported", d);
     if (workspace_bytes < keds_readout_workspace_bytes(B, d)) {
@@ -734,15 +759,21 @@ extern "C" int keds_readout(const float* x, int S, const int32_t* row, const flo
         return KEDS_E_WORKSPACE;
     }
     hipStream_t st = (hipStream_t)stream;
-    int rc = keds_layernorm_impl(x, d, row, S, gamma, beta, workspace, 0, B, d, st);
+    int rc = keds_layernorm_impl(x, d, row, S, gamma, beta, workspace, f16 ? 2 : 0, B, d, st);
     if (rc) return rc;
-    rc = keds_gemm_bt(workspace, proj_t, nullptr, out, B, E, d, KEDS_EPI_BIAS_F32, nullptr, 0, stream);
+    rc = keds_gemm_bt(workspace, proj_t, nullptr, out, B, E, d, f16 ? KEDS_EPI_BIAS_F32_H : KEDS_EPI_BIAS_F32, nullptr, 0, stream);
     if (rc) return rc;
     if (normalize) {
         l2norm_kernel<<<(B + 3) / 4, 256, 0, st>>>(out, out, B, E);
         rc = keds_check_launch("l2norm_kernel");
     }
     return rc;
+}
+
+extern "C" int keds_readout(const float* x, int S, const int32_t* row, const float* gamma, const float* beta,
+                            const void* proj_t, float* out, int B, int d, int E, int normalize, void* workspace,
+                            size_t workspace_bytes, void* stream) {
+    return keds_readout_impl(x, S, row, gamma, beta, proj_t, out, B, d, E, normalize, workspace, workspace_bytes, stream, false);
 }
 
 extern "C" int keds_l2_normalize(const float* x, float* out, int rows, int dim, void* stream) {
@@ -763,8 +794,17 @@ extern "C" int keds_cast_bf16(const float* x, void* out, int64_t count, void* st
     long long blocks = (count / 4 + 255) / 256;
     if (blocks > 4096) blocks = 4096;
     if (blocks < 1) blocks = 1;
-    cast_bf16_kernel<<<(unsigned)blocks, 256, 0, (hipStream_t)stream>>>(x, (bf16_t*)out, count);
-    return keds_check_launch("cast_bf16_kernel");
+    cast16_kernel<bf16_t><<<(unsigned)blocks, 256, 0, (hipStream_t)stream>>>(x, (bf16_t*)out, count);
+    return keds_check_launch("cast16_kernel<bf16>");
+}
+
+extern "C" int keds_cast_f16(const float* x, void* out, int64_t count, void* stream) {
+    KEDS_REQUIRE(x && out && count > 0, "keds_cast_f16: bad argument");
+    long long blocks = (count / 4 + 255) / 256;
+    if (blocks > 4096) blocks = 4096;
+    if (blocks < 1) blocks = 1;
+    cast16_kernel<f16_t><<<(unsigned)blocks, 256, 0, (hipStream_t)stream>>>(x, (f16_t*)out, count);
+    return keds_check_launch("cast16_kernel<f16>");
 }
 
 extern "C" int keds_rowstats_cast_ex(const float* x, void* xb, int out_f16, float* stats, int rows, int dim, void* stream) {

@@ -53,8 +53,9 @@ __device__ __forceinline__ float qgelu(float x) {
 // one lane's 8 consecutive output columns [n, n+8) of row m
 template <int EPI>
 __device__ __forceinline__ void epilogue_store(f32x4 v0, f32x4 v1, void* __restrict__ out, int m, int n, int N,
-                                               const float* __restrict__ aux, int aux_i, long long ldc) {
-    if constexpr (EPI == KEDS_EPI_BIAS_QGELU_BF16) {
+                                               const float* __restrict__ aux, int aux_i, long long ldc,
+                                               int* __restrict__ guard = nullptr) {
+    if constexpr (EPI == KEDS_EPI_BIAS_QGELU_BF16 || EPI == KEDS_EPI_BIAS_QGELU_F16_H) {
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
             v0[j] = qgelu(v0[j]);
@@ -80,6 +81,11 @@ __device__ __forceinline__ void epilogue_store(f32x4 v0, f32x4 v1, void* __restr
                 *reinterpret_cast<f32x4*>(t + 4) = v1;
             }
         }
+    } else if constexpr (EPI == EPI_INT_BIAS_F16 || EPI == KEDS_EPI_BIAS_QGELU_F16_H) {
+        // fp16 operating point: fp16 out, and the range guard (|v| > 65504 or non-finite raises the flag instead of passing inf on)
+        *reinterpret_cast<f16x8*>(reinterpret_cast<f16_t*>(out) + (size_t)m * ldc + n) =
+            f16x8{(f16_t)v0[0], (f16_t)v0[1], (f16_t)v0[2], (f16_t)v0[3], (f16_t)v1[0], (f16_t)v1[1], (f16_t)v1[2], (f16_t)v1[3]};
+        f16_range_flag(guard, f16_range_max(0u, v0, v1));
     } else if constexpr (EPI == KEDS_EPI_X3_QGELU_PAIR) {
         // QuickGELU in full precision (model.py:300-302; f32path.hip's form), then the value as two fp16 planes: hi = fp16(v),
         // lo = fp16(v - hi) -- the A operand of the next split-operand GEMM (aux_i = elements between the planes)
@@ -182,7 +188,8 @@ __device__ __forceinline__ void tile_epilogue(f32x4 (&acc)[4][MI], const float* 
                     continue;
                 }
                 epilogue_store<epi_base(EPI)>(acc[2 * p][mi] * rstd[mi] + (c0 * nmr[mi] + b0),
-                                              acc[2 * p + 1][mi] * rstd[mi] + (c1 * nmr[mi] + b1), out, m, n, N, nullptr, 0, ldc);
+                                              acc[2 * p + 1][mi] * rstd[mi] + (c1 * nmr[mi] + b1), out, m, n, N, nullptr, 0, ldc,
+                                              guard);
             }
         }
     } else if constexpr (EPI == KEDS_EPI_RESID_STATS_F32) {
@@ -226,7 +233,7 @@ __device__ __forceinline__ void tile_epilogue(f32x4 (&acc)[4][MI], const float* 
             ss = rows_sum(ss);
             if (valid && zero_lane) keds_stat_add(stats + 2 * (size_t)m, s, ss);
         }
-    } else if constexpr (EPI == KEDS_EPI_RESID_STATS_F16) {
+    } else if constexpr (epi_resid16(EPI)) {
         // the residual stream kept in fp16 (the reference's own storage type, model.py:531-548 convert_weights): one
         // copy is both the residual and the next GEMM's operand, 4 B per element of traffic instead of 10
         keds_stat_t* stats = reinterpret_cast<keds_stat_t*>(const_cast<float*>(aux));
@@ -277,7 +284,7 @@ __device__ __forceinline__ void tile_epilogue(f32x4 (&acc)[4][MI], const float* 
                 if constexpr (epi_x3(EPI))      // the weight planes hold W * 2^e: the product comes back to scale before the bias (exact)
                     epilogue_store<epi_base(EPI)>(acc[2 * p][mi] * x3_ws + b0, acc[2 * p + 1][mi] * x3_ws + b1, out, m, n, N, aux, aux_i, ldc);
                 else
-                    epilogue_store<epi_base(EPI)>(acc[2 * p][mi] + b0, acc[2 * p + 1][mi] + b1, out, m, n, N, aux, aux_i, ldc);
+                    epilogue_store<epi_base(EPI)>(acc[2 * p][mi] + b0, acc[2 * p + 1][mi] + b1, out, m, n, N, aux, aux_i, ldc, guard);
             }
         }
     }
@@ -296,8 +303,10 @@ constexpr int quad_nd() { return 18; }       // (measured on qkv, same-process A
 template <int EPI, int DBG, int ND = 0, int H = 0, int PSEL = -1>
 __device__ __forceinline__ void pair_ln_epilogue(f32x4 (&acc)[4][8], const char* __restrict__ side, void* __restrict__ out,
                                                  int m0, int n0, int N, int wm, int wn, int g, int c,
-                                                 void* __restrict__ aux2, u32x4* __restrict__ pend = nullptr, bool defer = false) {
+                                                 void* __restrict__ aux2, u32x4* __restrict__ pend = nullptr, bool defer = false,
+                                                 int* __restrict__ guard = nullptr) {
     float rstd[8], nmr[8];
+    [[maybe_unused]] unsigned rmax = 0;                                  // fp16 outputs: running max |v| (range guard)
     int r0 = 128 * wm + c;
     // opaque to the optimiser: inside the persistent kernel's tile loop the 16 lane-constant store offsets derived from r0
     // would otherwise be hoisted out of the loop and, with no register to spare, kept in scratch (measured: +48 % time)
@@ -324,7 +333,7 @@ __device__ __forceinline__ void pair_ln_epilogue(f32x4 (&acc)[4][8], const char*
         for (int mi = 0; mi < 8; ++mi) {
             f32x4 v0 = acc[2 * p][mi] * rstd[mi] + (c0 * nmr[mi] + b0);
             f32x4 v1 = acc[2 * p + 1][mi] * rstd[mi] + (c1 * nmr[mi] + b1);
-            if constexpr (epi_base(EPI) == KEDS_EPI_BIAS_QGELU_BF16) {
+            if constexpr (epi_qgelu(EPI)) {
                 // qgelu() on whole vectors: the same operations in the same order, but the scale, the + 1 and the final product are
                 // packed (v_pk_mul_f32 / v_pk_add_f32: two elements per issue slot) -- 6 of the 28 issue cycles per element
                 f32x4 z0 = v0 * -2.4554669595930157f, z1 = v1 * -2.4554669595930157f;
@@ -349,8 +358,15 @@ __device__ __forceinline__ void pair_ln_epilogue(f32x4 (&acc)[4][8], const char*
                 continue;
             }
             const unsigned off = ((unsigned)(r0 + 16 * mi) * (unsigned)N + (unsigned)nl) * 2u;
-            const bf16x8 ov = bf16x8{(bf16_t)v0[0], (bf16_t)v0[1], (bf16_t)v0[2], (bf16_t)v0[3],
-                                     (bf16_t)v1[0], (bf16_t)v1[1], (bf16_t)v1[2], (bf16_t)v1[3]};
+            u32x4 ov;
+            if constexpr (epi_out_f16(EPI)) {
+                rmax = f16_range_max(rmax, v0, v1);
+                ov = __builtin_bit_cast(u32x4, f16x8{(f16_t)v0[0], (f16_t)v0[1], (f16_t)v0[2], (f16_t)v0[3],
+                                                     (f16_t)v1[0], (f16_t)v1[1], (f16_t)v1[2], (f16_t)v1[3]});
+            } else {
+                ov = __builtin_bit_cast(u32x4, bf16x8{(bf16_t)v0[0], (bf16_t)v0[1], (bf16_t)v0[2], (bf16_t)v0[3],
+                                                      (bf16_t)v1[0], (bf16_t)v1[1], (bf16_t)v1[2], (bf16_t)v1[3]});
+            }
             // non-temporal: the tile is read next by another kernel, after 200+ MB of other traffic; keeping it out of the way
             // of the operand panels in L2 is worth 0.55 ms of the 21.7 ms step (same-box A/B, round 2, tools/ab_nt.sh).  The same
             // hint on the A-panel DMA costs 2.5 ms (the four tiles of an XCD that share a panel stop sharing it), on the
@@ -358,13 +374,14 @@ __device__ __forceinline__ void pair_ln_epilogue(f32x4 (&acc)[4][8], const char*
             // output of the MXFP8 kernel (gemm_fp8.hip) it costs 0.2 ms of that mode's 17.2 ms step.
             if constexpr (ND > 0) {
                 if (16 * H + p * 8 + mi >= 32 - ND && defer) {              // (wave-uniform)
-                    pend[16 * H + p * 8 + mi - (32 - ND)] = __builtin_bit_cast(u32x4, ov);
+                    pend[16 * H + p * 8 + mi - (32 - ND)] = ov;
                     continue;
                 }
             }
             keds_store16<KEDS_ST_LN>(ov, tile_out, off);
         }
     }
+    if constexpr (epi_out_f16(EPI)) f16_range_flag(guard, rmax);
 }
 // stores [i0, i1) of the ND deferred ones: the same addresses the epilogue would have used (tile base kept by the caller)
 template <int ND>
@@ -719,7 +736,7 @@ __global__ __launch_bounds__(256) void gemm_splitk_reduce_kernel(const float* __
         keds_stat_t* zero = reinterpret_cast<keds_stat_t*>(aux2);
         if (zero && n == 0) keds_stat_zero(zero + 2 * (size_t)m);
         const f32x4 c0 = *reinterpret_cast<const f32x4*>(bias + N + n), c1 = *reinterpret_cast<const f32x4*>(bias + N + n + 4);
-        epilogue_store<epi_base(EPI)>(v0 * rstd + (c0 * nmr + b0), v1 * rstd + (c1 * nmr + b1), out, m, n, N, nullptr, 0, ldc);
+        epilogue_store<epi_base(EPI)>(v0 * rstd + (c0 * nmr + b0), v1 * rstd + (c1 * nmr + b1), out, m, n, N, nullptr, 0, ldc, guard);
     } else if constexpr (EPI == KEDS_EPI_RESID_STATS_F32) {
         float* o = reinterpret_cast<float*>(out) + (size_t)m * ldc + n;
         v0 += *reinterpret_cast<const f32x4*>(o) + b0;
@@ -731,7 +748,7 @@ __global__ __launch_bounds__(256) void gemm_splitk_reduce_kernel(const float* __
                    (bf16_t)v1[0], (bf16_t)v1[1], (bf16_t)v1[2], (bf16_t)v1[3]};
         row_stats_add(reinterpret_cast<keds_stat_t*>(const_cast<float*>(aux)) + 2 * (size_t)m, sum8(v0, v1),
                       sum8(v0 * v0, v1 * v1), per_row);
-    } else if constexpr (EPI == KEDS_EPI_RESID_STATS_F16) {
+    } else if constexpr (epi_resid16(EPI)) {
         f16x8* o = reinterpret_cast<f16x8*>(reinterpret_cast<f16_t*>(out) + (size_t)m * ldc + n);
         const f16x8 r = *o;
         v0 += f32x4{(float)r[0], (float)r[1], (float)r[2], (float)r[3]} + b0;
@@ -740,7 +757,7 @@ __global__ __launch_bounds__(256) void gemm_splitk_reduce_kernel(const float* __
         keds_stat_t* stats = reinterpret_cast<keds_stat_t*>(const_cast<float*>(aux));
         if (stats) row_stats_add(stats + 2 * (size_t)m, sum8(v0, v1), sum8(v0 * v0, v1 * v1), per_row);
     } else {
-        epilogue_store<EPI>(v0 + b0, v1 + b1, out, m, n, N, aux, aux_i, ldc);
+        epilogue_store<epi_base(EPI)>(v0 + b0, v1 + b1, out, m, n, N, aux, aux_i, ldc, guard);
     }
 }
 
@@ -940,7 +957,7 @@ __global__ __launch_bounds__(512, 2) void gemm_bt_pair_kernel(const bf16_t* __re
     const int wrow = OP_BYTES + (64 * wn + c) * 128;               // + ni * 2048
 
     f32x4 acc[4][8];
-    constexpr bool RESID_IN = RP != 0 && EPI == KEDS_EPI_RESID_STATS_F16 && STAMP == 0;
+    constexpr bool RESID_IN = RP != 0 && epi_resid16(EPI) && STAMP == 0;
     if constexpr (!RESID_IN) {
 #pragma unroll
         for (int ni = 0; ni < 4; ++ni)
@@ -994,7 +1011,7 @@ __global__ __launch_bounds__(512, 2) void gemm_bt_pair_kernel(const bf16_t* __re
             asm volatile("global_load_dword %0, %1, off" : "=v"(pc) : "v"(cp) : "memory");
         }
     }
-    if constexpr (EPI == KEDS_EPI_RESID_STATS_F16 && !RESID_IN) {
+    if constexpr (epi_resid16(EPI) && !RESID_IN) {
         if (tid >= 256 && bias) {
             const float* bp = bias + n0 + tid - 256;
             asm volatile("global_load_dword %0, %1, off" : "=v"(pb) : "v"(bp) : "memory");
@@ -1005,7 +1022,7 @@ __global__ __launch_bounds__(512, 2) void gemm_bt_pair_kernel(const bf16_t* __re
     for (int q = 0; q < 8; ++q) issue(0, q);
 #pragma unroll
     for (int q = 0; q < 8; ++q) issue(1, q);
-    if constexpr (EPI == KEDS_EPI_RESID_STATS_F16 && !RESID_IN) asm volatile("s_waitcnt vmcnt(16)" : "+v"(pb)::"memory");
+    if constexpr (epi_resid16(EPI) && !RESID_IN) asm volatile("s_waitcnt vmcnt(16)" : "+v"(pb)::"memory");
     if constexpr (RESID_IN) {
         // everything older than the 16 DMA pieces has landed: x + b becomes the accumulators' initial value while K-tile 0
         // (requested above) is still in flight
@@ -1044,7 +1061,7 @@ __global__ __launch_bounds__(512, 2) void gemm_bt_pair_kernel(const bf16_t* __re
             *reinterpret_cast<float*>(smem + SIDE_OFF + 3072 + (tid - 256) * 4) = pc;
         }
     }
-    if constexpr (EPI == KEDS_EPI_RESID_STATS_F16 && !RESID_IN) {   // bias slice of the tile (zeros without a bias) -> side area
+    if constexpr (epi_resid16(EPI) && !RESID_IN) {   // bias slice of the tile (zeros without a bias) -> side area
         if (tid >= 256) *reinterpret_cast<float*>(smem + SIDE_OFF + 2048 + (tid - 256) * 4) = pb;
     }
     if constexpr (RESID_IN) __builtin_amdgcn_sched_barrier(0);    // the conversions above stay in front of the wait for K-tile 0
@@ -1126,7 +1143,7 @@ __global__ __launch_bounds__(512, 2) void gemm_bt_pair_kernel(const bf16_t* __re
         const unsigned long long t_loop1 = __builtin_amdgcn_s_memtime();
         if constexpr (epi_is_ln(EPI))
             pair_ln_epilogue<EPI, STAMP>(acc, smem + SIDE_OFF, out, m0, n0, N, wm, wn, g, c, nullptr);
-        else if constexpr (EPI == KEDS_EPI_RESID_STATS_F16)
+        else if constexpr (epi_resid16(EPI))
             pair_resid_epilogue<STAMP>(acc, smem + SIDE_OFF, out, m0, n0, N, wm, wn, g, c,
                                        reinterpret_cast<keds_stat_t*>(const_cast<float*>(aux)), smem + (np & 1) * PBUF_BYTES);
         else
@@ -1150,15 +1167,15 @@ __global__ __launch_bounds__(512, 2) void gemm_bt_pair_kernel(const bf16_t* __re
         return;
     }
     if constexpr (epi_is_ln(EPI))
-        pair_ln_epilogue<EPI, 0>(acc, smem + SIDE_OFF, out, m0, n0, N, wm, wn, g, c, aux2);
+        pair_ln_epilogue<EPI, 0>(acc, smem + SIDE_OFF, out, m0, n0, N, wm, wn, g, c, aux2, nullptr, false, guard);
     else if constexpr (RESID_IN)
         pair_resid_epilogue_acc(acc, out, m0, n0, N, wm, wn, g, c, reinterpret_cast<keds_stat_t*>(const_cast<float*>(aux)),
                                 smem + (np & 1) * PBUF_BYTES);
-    else if constexpr (EPI == KEDS_EPI_RESID_STATS_F16)
+    else if constexpr (epi_resid16(EPI))
         pair_resid_epilogue(acc, smem + SIDE_OFF, out, m0, n0, N, wm, wn, g, c,
                             reinterpret_cast<keds_stat_t*>(const_cast<float*>(aux)), smem + (np & 1) * PBUF_BYTES);
     else
-        tile_epilogue<EPI, 8>(acc, bias, out, m0 + 128 * wm + c, M, n0 + 64 * wn + 8 * g, N, K, aux, aux_i, aux2, N, zl, nullptr,
+        tile_epilogue<EPI, 8>(acc, bias, out, m0 + 128 * wm + c, M, n0 + 64 * wn + 8 * g, N, K, aux, aux_i, aux2, N, zl, guard,
                               epi_x3(EPI) ? x3_wscale(w_plane) : 1.0f);
 }
 
@@ -1397,7 +1414,7 @@ __global__ __launch_bounds__(256, 1) void gemm_bt_quad_kernel(const bf16_t* __re
             asm volatile("global_load_dword %0, %1, off" : "=v"(pb) : "v"(bp) : "memory");
             asm volatile("global_load_dword %0, %1, off" : "=v"(pc) : "v"(cp) : "memory");
         }
-        if constexpr (EPI == KEDS_EPI_RESID_STATS_F16) {
+        if constexpr (epi_resid16(EPI)) {
             if (bias) {
                 const float* bp = bias + n0_ + tid;
                 asm volatile("global_load_dword %0, %1, off" : "=v"(pb) : "v"(bp) : "memory");
@@ -1405,7 +1422,7 @@ __global__ __launch_bounds__(256, 1) void gemm_bt_quad_kernel(const bf16_t* __re
         }
     };
     auto side_write = [&](char* side, int n0_) {                   // (the requested values have landed: caller waited)
-        if constexpr (EPI == KEDS_EPI_RESID_STATS_F16) *reinterpret_cast<float*>(side + 2048 + tid * 4) = pb;
+        if constexpr (epi_resid16(EPI)) *reinterpret_cast<float*>(side + 2048 + tid * 4) = pb;
         if constexpr (epi_is_ln(EPI)) {
             float rs, nm;
             ln_coeff_from((keds_stat_t)(((unsigned long long)st_raw[1] << 32) | st_raw[0]),
@@ -1429,7 +1446,7 @@ __global__ __launch_bounds__(256, 1) void gemm_bt_quad_kernel(const bf16_t* __re
 #pragma unroll
     for (int q = 0; q < 16; ++q) issue(1, q);
     if constexpr (epi_is_ln(EPI)) asm volatile("s_waitcnt vmcnt(32)" : "+v"(st_raw), "+v"(pb), "+v"(pc)::"memory");
-    if constexpr (EPI == KEDS_EPI_RESID_STATS_F16) asm volatile("s_waitcnt vmcnt(32)" : "+v"(pb)::"memory");
+    if constexpr (epi_resid16(EPI)) asm volatile("s_waitcnt vmcnt(32)" : "+v"(pb)::"memory");
     side_write(smem + qd::SIDE0, n0);
     asm volatile("s_waitcnt vmcnt(16) lgkmcnt(0)\n\ts_barrier" ::: "memory");
 
@@ -1441,7 +1458,7 @@ __global__ __launch_bounds__(256, 1) void gemm_bt_quad_kernel(const bf16_t* __re
     [[maybe_unused]] bool have_pend = false;
     // (not the QuickGELU form: its epilogue is 2 x 256 transcendentals per lane long and its stores leave under them; deferring
     // 12 of them costs c_fc 3 us -- 242.8 vs 239.8 -- even with the quarter-wise read-back that keeps the registers free)
-    constexpr bool DEFER = PERSIST && epi_is_ln(EPI) && epi_base(EPI) != KEDS_EPI_BIAS_QGELU_BF16 && !STAMP;
+    constexpr bool DEFER = PERSIST && epi_is_ln(EPI) && !epi_qgelu(EPI) && !STAMP;
     for (int it = 0;; ++it) {
         char* side = smem + qd::SIDE0 + (it & 1) * 4096;
         if constexpr (STAMP) t_loop0 = __builtin_amdgcn_s_memtime();
@@ -1512,7 +1529,7 @@ __global__ __launch_bounds__(256, 1) void gemm_bt_quad_kernel(const bf16_t* __re
                 pb = bias[nn0 + tid];
                 pc = bias[N + nn0 + tid];
             }
-            if constexpr (EPI == KEDS_EPI_RESID_STATS_F16) pb = bias ? bias[nn0 + tid] : 0.f;
+            if constexpr (epi_resid16(EPI)) pb = bias ? bias[nn0 + tid] : 0.f;
             xrs = make_rsx(X + (size_t)nm0 * K);
             wrs = make_rsw(W + (size_t)nn0 * K);
 #pragma unroll
@@ -1537,17 +1554,17 @@ __global__ __launch_bounds__(256, 1) void gemm_bt_quad_kernel(const bf16_t* __re
         [[maybe_unused]] char* red = smem + qd::RED_OFF;
 #define KEDS_QUAD_EPI(h)                                                                                               \
     if constexpr (epi_is_ln(EPI))                                                                                      \
-        pair_ln_epilogue<EPI, 0>(av, side, out, m0, n0, N, wm, 2 * wn2 + h, g, c, aux2e);                              \
-    else if constexpr (EPI == KEDS_EPI_RESID_STATS_F16)                                                                \
+        pair_ln_epilogue<EPI, 0>(av, side, out, m0, n0, N, wm, 2 * wn2 + h, g, c, aux2e, nullptr, false, guard);        \
+    else if constexpr (epi_resid16(EPI))                                                                \
         pair_resid_epilogue<0, false>(av, side, out, m0, n0, N, wm, 2 * wn2 + h, g, c, stats, red);                    \
     else                                                                                                               \
-        tile_epilogue<EPI, 8>(av, bias, out, m0 + 128 * wm + c, M, n0 + 64 * (2 * wn2 + h) + 8 * g, N, K, aux, aux_i, aux2e, N, g == 0, nullptr, \
+        tile_epilogue<EPI, 8>(av, bias, out, m0 + 128 * wm + c, M, n0 + 64 * (2 * wn2 + h) + 8 * g, N, K, aux, aux_i, aux2e, N, g == 0, guard, \
                               epi_x3(EPI) ? x3_wscale(w_plane) : 1.0f);
         if constexpr (DEFER) {
             // one 32-column quarter at a time: 64 read-back registers live instead of 128 leave room for the deferred stores
 #define KEDS_QUAD_EPQ(h, p)                                                                                             \
     KEDS_QUAD_READ_Q##h##p(av)                                                                                          \
-    pair_ln_epilogue<EPI, 0, QUAD_ND, h, p>(av, side, out, m0, n0, N, wm, 2 * wn2 + h, g, c, aux2e, pend, defer_now);    \
+    pair_ln_epilogue<EPI, 0, QUAD_ND, h, p>(av, side, out, m0, n0, N, wm, 2 * wn2 + h, g, c, aux2e, pend, defer_now, guard); \
     __builtin_amdgcn_sched_barrier(0);
             KEDS_QUAD_EPQ(0, 0)
             KEDS_QUAD_EPQ(0, 1)
@@ -1566,7 +1583,7 @@ __global__ __launch_bounds__(256, 1) void gemm_bt_quad_kernel(const bf16_t* __re
             have_pend = defer_now;
             pend_base = reinterpret_cast<char*>(out) + ((size_t)m0 * N + n0) * 2;
         }
-        if constexpr (EPI == KEDS_EPI_RESID_STATS_F16) {
+        if constexpr (epi_resid16(EPI)) {
             if (stats) {                                                    // kernel-uniform
                 __syncthreads();
                 const f32x2* rr = reinterpret_cast<const f32x2*>(red) + tid;
@@ -1617,7 +1634,7 @@ __global__ __launch_bounds__(256, 1) void gemm_bt_quad3_kernel(const bf16_t* __r
                                                                const float* __restrict__ bias, void* __restrict__ out,
                                                                int M, int N, int K, int n_tiles,
                                                                const float* __restrict__ aux, int ntiles) {
-    static_assert(EPI == KEDS_EPI_RESID_STATS_F16, "three-deep A ring: residual epilogue only");
+    static_assert(epi_resid16(EPI), "three-deep A ring: residual epilogue only");
     using namespace pr;
     extern __shared__ __attribute__((aligned(16))) char smem[];
     constexpr int DBG = 0;
@@ -1855,7 +1872,7 @@ static bool x3_quad_env() {
 template <int EPI>
 bool quad_by_shape(int N, int K) {
     if constexpr (epi_is_ln(EPI)) return K >= 512;
-    if constexpr (EPI == KEDS_EPI_RESID_STATS_F16) return K >= resid_quad_min_k();
+    if constexpr (epi_resid16(EPI)) return K >= resid_quad_min_k();
     if constexpr (epi_x3(EPI)) return x3_quad_env();               // split-operand GEMMs: a K-loop of 3 K / 64 K-tiles, the form that wins where the K-loop dominates
     return false;
 }
@@ -1932,14 +1949,14 @@ int launch_big(const void* A, const void* W, const float* bias, void* out, int M
         // the tile loop no longer spills (209 VGPRs), and still does not pay: out-proj 66.7 vs 66.3 us, c_proj 216 vs 203.5 on
         // its three-deep ring -- two tiles per workgroup leave one prologue to hide, and the epilogue's residual loads queue
         // behind the 32 DMA pieces of the next tile in the in-order vmcnt)
-        if (quad == 2 && ntiles > cus && cus >= 8 && EPI != KEDS_EPI_RESID_STATS_F16 && EPI != KEDS_EPI_X3_RESID_F32) {
+        if (quad == 2 && ntiles > cus && cus >= 8 && !epi_resid16(EPI) && EPI != KEDS_EPI_X3_RESID_F32) {
             if (int rc = keds_func_lds_once((const void*)gemm_bt_quad_kernel<EPI, 0, 1>, qd::LDS_BYTES, "gemm_bt_quad_kernel")) return rc;
             KEDS_LAUNCH((gemm_bt_quad_kernel<EPI, 0, 1>), cus, 256, qd::LDS_BYTES, st, (const bf16_t*)A, (const bf16_t*)W, bias, out, M, N, K,
                         n_tiles, aux, (int)(epi_is_ln(EPI) ? (g_quad_defer && quad_defer_env()) : aux_i), aux2,
                         keds_numerics_guard(), ntiles, g_x3_aplane, g_x3_wplane);
             return keds_check_launch("gemm_bt_quad_kernel<persistent>");
         }
-        if constexpr (EPI == KEDS_EPI_RESID_STATS_F16) {
+        if constexpr (epi_resid16(EPI)) {
             if (g_quad3 && K >= 1024 && K / pr::TK >= 4) {               // long K: A operand through a three-deep ring
                 if (int rc = keds_func_lds_once((const void*)gemm_bt_quad3_kernel<EPI>, 5 * pr::OP_BYTES, "gemm_bt_quad3_kernel")) return rc;
                 KEDS_LAUNCH((gemm_bt_quad3_kernel<EPI>), ntiles, 256, 5 * pr::OP_BYTES, st, (const bf16_t*)A, (const bf16_t*)W, bias, out, M, N, K,
@@ -1952,7 +1969,7 @@ int launch_big(const void* A, const void* W, const float* bias, void* out, int M
                     aux, aux_i, aux2, keds_numerics_guard(), ntiles, g_x3_aplane, g_x3_wplane);
         return keds_check_launch("gemm_bt_quad_kernel");
     }
-    if constexpr (EPI == KEDS_EPI_RESID_STATS_F16) {
+    if constexpr (epi_resid16(EPI)) {
         if (g_resid_prologue) {
             if (int rc = keds_func_lds_once((const void*)gemm_bt_pair_kernel<EPI, 0, 1>, pr::LDS_BYTES, "gemm_bt_pair_kernel")) return rc;
             KEDS_LAUNCH((gemm_bt_pair_kernel<EPI, 0, 1>), m_tiles * n_tiles, 512, pr::LDS_BYTES, st,
@@ -1998,14 +2015,14 @@ int launch_gemm(const void* A, const void* W, const float* bias, void* out, int 
     // the 256^2 kernel runs one workgroup per CU: use it when its full tiles keep >= 85% of the CU-rounds busy (a single
     // round counts: 19,712 x 768 x 3072 runs at 1.13 PF on 231 tiles vs 0.96 on 924 tiles of 128^2); otherwise the
     // 128^2 kernel's finer tiles quantise better
-    const bool big_ok = big_tiles_ok(M, N, K) && lda == K && ldc == N && (EPI != KEDS_EPI_PATCH_F32 || M % pr::TM == 0) &&
+    const bool big_ok = big_tiles_ok(M, N, K) && lda == K && ldc == N && (epi_base(EPI) != KEDS_EPI_PATCH_F32 || M % pr::TM == 0) &&
                         EPI != KEDS_EPI_BIAS_BF16_HEADF32;      // (its fp32 head rows are numbered from row 0 of the launch)
     if (!big_ok) return launch_small<EPI>(A, W, bias, out, M, N, K, aux, aux_i, aux2, lda, ldc, st);
     const int m_main = M / pr::TM * pr::TM;
     int rc = launch_big<EPI>(A, W, bias, out, m_main, N, K, aux, aux_i, aux2, st);
     if (rc || m_main == M || g_skip_tail) return rc;
-    const size_t esz = (EPI == KEDS_EPI_BIAS_RESID_F32 || EPI == KEDS_EPI_BIAS_F32 || EPI == KEDS_EPI_RESID_STATS_F32 ||
-                        EPI == KEDS_EPI_X3_BIAS_F32 || EPI == KEDS_EPI_X3_RESID_F32) ? 4 : 2;
+    const size_t esz = (epi_base(EPI) == KEDS_EPI_BIAS_RESID_F32 || epi_base(EPI) == KEDS_EPI_BIAS_F32 || EPI == KEDS_EPI_RESID_STATS_F32)
+                           ? 4 : 2;
     // the remainder launch numbers its rows from 0: move the per-row side buffers along
     const float* aux_t = aux;
     void* aux2_t = aux2;
@@ -2015,7 +2032,7 @@ int launch_gemm(const void* A, const void* W, const float* bias, void* out, int 
     } else if constexpr (EPI == KEDS_EPI_RESID_STATS_F32) {
         aux_t = (const float*)((const keds_stat_t*)aux + 2 * (size_t)m_main);
         aux2_t = (char*)aux2 + (size_t)m_main * N * 2;
-    } else if constexpr (EPI == KEDS_EPI_RESID_STATS_F16) {
+    } else if constexpr (epi_resid16(EPI)) {
         if (aux) aux_t = (const float*)((const keds_stat_t*)aux + 2 * (size_t)m_main);
     }
     return launch_small<EPI>((const char*)A + (size_t)m_main * K * 2, W, bias, (char*)out + (size_t)m_main * N * esz,
@@ -2051,7 +2068,7 @@ extern "C" int keds_gemm_bt_ex2(const void* A, int64_t lda, const void* W, const
     KEDS_REQUIRE(N % BN == 0, "keds_gemm_bt: N=%d must be a multiple of %d", N, BN);
     KEDS_REQUIRE(K % BK == 0, "keds_gemm_bt: K=%d must be a multiple of %d", K, BK);
     KEDS_REQUIRE(lda >= K && ldc >= N && lda % 8 == 0 && ldc % 8 == 0, "keds_gemm_bt: bad row strides");
-    KEDS_REQUIRE(epilogue != KEDS_EPI_PATCH_F32 || ldc == N, "keds_gemm_bt: EPI_PATCH needs a dense output");
+    KEDS_REQUIRE((epilogue != KEDS_EPI_PATCH_F32 && epilogue != KEDS_EPI_PATCH_F32_H) || ldc == N, "keds_gemm_bt: EPI_PATCH needs a dense output");
     hipStream_t st = (hipStream_t)stream;
 #define KEDS_GEMM_CASE(E) case E: return launch_gemm<E>(A, W, bias, out, M, N, K, aux, aux_i, aux2, lda, ldc, st);
     switch (epilogue) {
@@ -2079,6 +2096,20 @@ extern "C" int keds_gemm_bt_ex2(const void* A, int64_t lda, const void* W, const
             KEDS_REQUIRE(aux && aux2, "keds_gemm_bt: EPI_RESID_STATS needs aux = statistics and aux2 = bf16 copy");
             return launch_gemm<KEDS_EPI_RESID_STATS_F32>(A, W, bias, out, M, N, K, aux, aux_i, aux2, lda, ldc, st);
         KEDS_GEMM_CASE(KEDS_EPI_RESID_STATS_F16)
+        // the fp16 operating point (fp16 A and W)
+        KEDS_GEMM_CASE(KEDS_EPI_RESID_STATS_F16_H)
+        KEDS_GEMM_CASE(KEDS_EPI_BIAS_RESID_F32_H)
+        KEDS_GEMM_CASE(KEDS_EPI_BIAS_QGELU_F16_H)
+        KEDS_GEMM_CASE(KEDS_EPI_BIAS_F32_H)
+        case KEDS_EPI_PATCH_F32_H:
+            KEDS_REQUIRE(aux && aux_i > 0, "keds_gemm_bt: EPI_PATCH needs the positional embedding and G");
+            return launch_gemm<KEDS_EPI_PATCH_F32_H>(A, W, bias, out, M, N, K, aux, aux_i, aux2, lda, ldc, st);
+        case KEDS_EPI_LN_BIAS_F16_H:
+        case KEDS_EPI_LN_QGELU_F16_H:
+            KEDS_REQUIRE(bias && aux, "keds_gemm_bt: EPI_LN_* needs bias = [bias' | colsum] and aux = row statistics");
+            if (epilogue == KEDS_EPI_LN_BIAS_F16_H)
+                return launch_gemm<KEDS_EPI_LN_BIAS_F16_H>(A, W, bias, out, M, N, K, aux, aux_i, aux2, lda, ldc, st);
+            return launch_gemm<KEDS_EPI_LN_QGELU_F16_H>(A, W, bias, out, M, N, K, aux, aux_i, aux2, lda, ldc, st);
         case KEDS_EPI_BIAS_BF16_HEADF32:
             KEDS_REQUIRE(aux && aux_i >= 0, "keds_gemm_bt: EPI_BIAS_BF16_HEADF32 needs the fp32 head buffer and its row count");
             return launch_gemm<KEDS_EPI_BIAS_BF16_HEADF32>(A, W, bias, out, M, N, K, aux, aux_i, aux2, lda, ldc, st);

@@ -178,8 +178,9 @@ struct Loader {
 
 // resblocks of one tower (model.py:305-326): keys <prefix>transformer.resblocks.<i>.*
 // f32: 0 = bf16 / fp8 flows, 1 = KEDS_F32 (weights as stored), 2 = KEDS_F32X3 (the four weights as fp16 planes [2][N][K])
+// f16: KEDS_F16 compute (the fp16 operating point): the four weights as fp16 (plus the fp16 folded in_proj / c_fc as always)
 int load_blocks(const Loader& L, const std::string& prefix, int width, int layers, std::vector<keds_block_params>& blocks,
-                bool fp8, int f32 = 0) {
+                bool fp8, int f32 = 0, bool f16 = false) {
     blocks.assign(layers, keds_block_params{});
     for (int i = 0; i < layers; ++i) {
         const std::string b = prefix + "transformer.resblocks." + std::to_string(i) + ".";
@@ -221,17 +222,30 @@ int load_blocks(const Loader& L, const std::string& prefix, int width, int layer
             p.proj_w = f;
             continue;
         }
-        if ((rc = L.mat<bf16_t>(b + "attn.in_proj_weight", 3 * width, width, &m))) return rc;
-        p.qkv_w = m;
-        if ((rc = L.mat<bf16_t>(b + "attn.out_proj.weight", width, width, &m))) return rc;
-        p.out_w = m;
-        if ((rc = L.mat<bf16_t>(b + "mlp.c_fc.weight", 4 * width, width, &m))) return rc;
-        p.fc_w = m;
-        if ((rc = L.mat<bf16_t>(b + "mlp.c_proj.weight", width, 4 * width, &m))) return rc;
-        p.proj_w = m;
+        if (f16) {   // KEDS_F16: fp16 weights, rounded as stored (convert_weights, model.py:927-948)
+            const f16_t* h;
+            if ((rc = L.mat<f16_t>(b + "attn.in_proj_weight", 3 * width, width, &h))) return rc;
+            p.qkv_w = h;
+            if ((rc = L.mat<f16_t>(b + "attn.out_proj.weight", width, width, &h))) return rc;
+            p.out_w = h;
+            if ((rc = L.mat<f16_t>(b + "mlp.c_fc.weight", 4 * width, width, &h))) return rc;
+            p.fc_w = h;
+            if ((rc = L.mat<f16_t>(b + "mlp.c_proj.weight", width, 4 * width, &h))) return rc;
+            p.proj_w = h;
+        } else {
+            if ((rc = L.mat<bf16_t>(b + "attn.in_proj_weight", 3 * width, width, &m))) return rc;
+            p.qkv_w = m;
+            if ((rc = L.mat<bf16_t>(b + "attn.out_proj.weight", width, width, &m))) return rc;
+            p.out_w = m;
+            if ((rc = L.mat<bf16_t>(b + "mlp.c_fc.weight", 4 * width, width, &m))) return rc;
+            p.fc_w = m;
+            if ((rc = L.mat<bf16_t>(b + "mlp.c_proj.weight", width, 4 * width, &m))) return rc;
+            p.proj_w = m;
+        }
         // ln_1 folded into in_proj, ln_2 into c_fc (keds_fold_layernorm): fp32 copies of the two weights are temporary.
         // KEDS_DETERMINISTIC=1 keeps the separate LayerNorm kernels (A/B reference; the folded path is reproducible too).
         const char* det = getenv("KEDS_DETERMINISTIC");
+        KEDS_REQUIRE(!(f16 && det && det[0] == '1'), "%s: KEDS_F16 needs the folded LayerNorm path (KEDS_DETERMINISTIC=1 is set)", L.what);
         if (det && det[0] == '1') continue;
         Arena tmp;
         Loader T{L.w, tmp, L.what};
@@ -414,8 +428,8 @@ extern "C" int keds_ctx_destroy(keds_ctx* ctx) {
 extern "C" int keds_vit_create(keds_ctx* ctx, const keds_tensor* weights, int n, int compute, keds_vit** out) {
     const char* what = "keds_vit_create";
     KEDS_REQUIRE(weights && n > 0 && out, "%s: bad argument", what);
-    KEDS_REQUIRE(compute == KEDS_BF16 || compute == KEDS_FP8 || compute == KEDS_F32 || compute == KEDS_F32X3,
-                 "%s: compute dtype must be KEDS_BF16, KEDS_FP8, KEDS_F32 or KEDS_F32X3", what);
+    KEDS_REQUIRE(compute == KEDS_BF16 || compute == KEDS_F16 || compute == KEDS_FP8 || compute == KEDS_F32 || compute == KEDS_F32X3,
+                 "%s: compute dtype must be KEDS_BF16, KEDS_F16, KEDS_FP8, KEDS_F32 or KEDS_F32X3", what);
     int rc = use_device(ctx, what);
     if (rc) return rc;
     Weights W(weights, n);
@@ -448,7 +462,8 @@ extern "C" int keds_vit_create(keds_ctx* ctx, const keds_tensor* weights, int n,
         return fail(KEDS_E_ARG);
     }
     const int f32 = compute == KEDS_F32 ? 1 : compute == KEDS_F32X3 ? 2 : 0;
-    if ((rc = load_blocks(L, "visual.", width, layers, v->blocks, fp8, f32))) return fail(rc);
+    const bool f16 = compute == KEDS_F16;
+    if ((rc = load_blocks(L, "visual.", width, layers, v->blocks, fp8, f32, f16))) return fail(rc);
     keds_vit_params& p = v->p;
     memset(&p, 0, sizeof(p));
     p.tower.width = width;
@@ -460,6 +475,7 @@ extern "C" int keds_vit_create(keds_ctx* ctx, const keds_tensor* weights, int n,
     p.tower.last_cls_only = 1;
     p.tower.fp8 = fp8 ? 1 : 0;
     p.tower.f32 = f32;
+    p.tower.f16 = f16 ? 1 : 0;
     p.resolution = grid * patch;
     p.patch = patch;
     const int kreal = 3 * patch * patch;
@@ -469,22 +485,28 @@ extern "C" int keds_vit_create(keds_ctx* ctx, const keds_tensor* weights, int n,
         float* conv_w;
         if ((rc = pack_tensor<float>(v->mem, conv, width, kreal, kreal, 1, p.kpad, &conv_w, what))) return fail(rc);
         p.conv_w = conv_w;
+    } else if (f16) {
+        f16_t* conv_w;
+        if ((rc = pack_tensor<f16_t>(v->mem, conv, width, kreal, kreal, 1, p.kpad, &conv_w, what))) return fail(rc);
+        p.conv_w = conv_w;
     } else {
         bf16_t* conv_w;   // [width, 3*P*P] zero padded to kpad columns (im2col order == the conv weight's own order)
         if ((rc = pack_tensor<bf16_t>(v->mem, conv, width, kreal, kreal, 1, p.kpad, &conv_w, what))) return fail(rc);
         p.conv_w = conv_w;
     }
     const bf16_t* proj_t = nullptr;
+    const f16_t* proj_t16 = nullptr;
     const float* proj_t32 = nullptr;
     if ((rc = L.vec("visual.class_embedding", width, &p.class_emb)) ||
         (rc = L.mat<float>("visual.positional_embedding", p.tower.seq, width, &p.pos_emb)) ||
         (rc = L.vec("visual.ln_pre.weight", width, &p.ln_pre_g)) || (rc = L.vec("visual.ln_pre.bias", width, &p.ln_pre_b)) ||
         (rc = L.vec("visual.ln_post.weight", width, &p.ln_post_g)) ||
         (rc = L.vec("visual.ln_post.bias", width, &p.ln_post_b)) ||
-        (rc = f32 ? L.mat<float>("visual.proj", embed, width, &proj_t32, /*transpose=*/true)
-                  : L.mat<bf16_t>("visual.proj", embed, width, &proj_t, /*transpose=*/true)))
+        (rc = f32   ? L.mat<float>("visual.proj", embed, width, &proj_t32, /*transpose=*/true)
+              : f16 ? L.mat<f16_t>("visual.proj", embed, width, &proj_t16, /*transpose=*/true)
+                    : L.mat<bf16_t>("visual.proj", embed, width, &proj_t, /*transpose=*/true)))
         return fail(rc);
-    p.proj_t = f32 ? (const void*)proj_t32 : (const void*)proj_t;
+    p.proj_t = f32 ? (const void*)proj_t32 : f16 ? (const void*)proj_t16 : (const void*)proj_t;
     *out = v;
     return KEDS_OK;
 }
@@ -531,8 +553,8 @@ extern "C" int keds_vit_forward(keds_vit* vit, const void* image, int img_dtype,
 extern "C" int keds_text_create(keds_ctx* ctx, const keds_tensor* weights, int n, int compute, keds_text** out) {
     const char* what = "keds_text_create";
     KEDS_REQUIRE(weights && n > 0 && out, "%s: bad argument", what);
-    KEDS_REQUIRE(compute == KEDS_BF16 || compute == KEDS_FP8 || compute == KEDS_F32 || compute == KEDS_F32X3,
-                 "%s: compute dtype must be KEDS_BF16, KEDS_FP8, KEDS_F32 or KEDS_F32X3", what);
+    KEDS_REQUIRE(compute == KEDS_BF16 || compute == KEDS_F16 || compute == KEDS_FP8 || compute == KEDS_F32 || compute == KEDS_F32X3,
+                 "%s: compute dtype must be KEDS_BF16, KEDS_F16, KEDS_FP8, KEDS_F32 or KEDS_F32X3", what);
     int rc = use_device(ctx, what);
     if (rc) return rc;
     Weights W(weights, n);
@@ -559,7 +581,8 @@ extern "C" int keds_text_create(keds_ctx* ctx, const keds_tensor* weights, int n
     }
     const bool fp8 = compute == KEDS_FP8 && width % 256 == 0;
     const int f32 = compute == KEDS_F32 ? 1 : compute == KEDS_F32X3 ? 2 : 0;
-    if ((rc = load_blocks(L, "", width, layers, t->blocks, fp8, f32))) return fail(rc);
+    const bool f16 = compute == KEDS_F16;
+    if ((rc = load_blocks(L, "", width, layers, t->blocks, fp8, f32, f16))) return fail(rc);
     keds_text_params& p = t->p;
     memset(&p, 0, sizeof(p));
     p.tower.width = width;
@@ -571,17 +594,20 @@ extern "C" int keds_text_create(keds_ctx* ctx, const keds_tensor* weights, int n
     p.tower.last_cls_only = 0;
     p.tower.fp8 = fp8 ? 1 : 0;
     p.tower.f32 = f32;
+    p.tower.f16 = f16 ? 1 : 0;
     p.vocab = vocab;
     p.embed_dim = embed;
     const bf16_t* proj_t = nullptr;
+    const f16_t* proj_t16 = nullptr;
     const float* proj_t32 = nullptr;
     if ((rc = L.mat<float>("token_embedding.weight", vocab, width, &p.token_emb)) ||
         (rc = L.mat<float>("positional_embedding", context, width, &p.pos_emb)) ||
         (rc = L.vec("ln_final.weight", width, &p.ln_final_g)) || (rc = L.vec("ln_final.bias", width, &p.ln_final_b)) ||
-        (rc = f32 ? L.mat<float>("text_projection", embed, width, &proj_t32, /*transpose=*/true)
-                  : L.mat<bf16_t>("text_projection", embed, width, &proj_t, /*transpose=*/true)))
+        (rc = f32   ? L.mat<float>("text_projection", embed, width, &proj_t32, /*transpose=*/true)
+              : f16 ? L.mat<f16_t>("text_projection", embed, width, &proj_t16, /*transpose=*/true)
+                    : L.mat<bf16_t>("text_projection", embed, width, &proj_t, /*transpose=*/true)))
         return fail(rc);
-    p.proj_t = f32 ? (const void*)proj_t32 : (const void*)proj_t;
+    p.proj_t = f32 ? (const void*)proj_t32 : f16 ? (const void*)proj_t16 : (const void*)proj_t;
     *out = t;
     return KEDS_OK;
 }

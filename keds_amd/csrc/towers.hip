@@ -27,6 +27,8 @@ int keds_tower_forward_f32(const keds_tower_params* p, float* x, int B, void* ws
 size_t keds_readout_f32_workspace_bytes(int B, int d);
 int keds_readout_f32(const float* x, int S, const int32_t* row, const float* gamma, const float* beta, const float* proj_t,
                      float* out, int B, int d, int E, int normalize, void* workspace, hipStream_t st);
+int keds_readout_impl(const float* x, int S, const int32_t* row, const float* gamma, const float* beta, const void* proj_t,
+                      float* out, int B, int d, int E, int normalize, void* workspace, size_t workspace_bytes, void* stream, bool f16);
 
 namespace {
 
@@ -133,22 +135,35 @@ struct RowSpan {
 // The four GEMMs of a block on a span of rows, LayerNorm folded (keds_hip.h, KEDS_EPI_LN_*).  The residual stream lives
 // in t.h as fp16 (the reference's own storage type after convert_weights, model.py:531-548): one copy that the residual
 // GEMMs update in place (fp32 sum, rounded once) and the LN-folded GEMMs read as their fp16 operand.
-int qkv_rows(const TowerWs& t, const keds_block_params& k, int w, RowSpan s) {
+// h (keds_tower_params.f16, the "fp16" operating point): every operand fp16 -- qkv, the attention output and the MLP hidden layer
+// are fp16 and out_w / proj_w fp16 weights (KEDS_EPI_*_F16_H); otherwise those are bf16.
+int qkv_rows(const TowerWs& t, const keds_block_params& k, int w, RowSpan s, bool h) {
     return keds_gemm_bt_ex2(t.h + s.r0 * w, w, k.qkv_wf, k.qkv_bc, t.qkv + s.r0 * 3 * w, 3 * w, s.n, 3 * w, w,
-                            KEDS_EPI_LN_BIAS_BF16_H, (const float*)(t.st1 + 2 * s.r0), 0, t.st2 + 2 * s.r0, s.st);
+                            h ? KEDS_EPI_LN_BIAS_F16_H : KEDS_EPI_LN_BIAS_BF16_H, (const float*)(t.st1 + 2 * s.r0), 0, t.st2 + 2 * s.r0,
+                            s.st);
 }
-int out_rows(const TowerWs& t, const keds_block_params& k, int w, RowSpan s) {
-    return keds_gemm_bt_ex2(t.att + s.r0 * w, w, k.out_w, k.out_b, t.h + s.r0 * w, w, s.n, w, w, KEDS_EPI_RESID_STATS_F16,
-                            (const float*)(t.st2 + 2 * s.r0), 0, nullptr, s.st);
+int out_rows(const TowerWs& t, const keds_block_params& k, int w, RowSpan s, bool h) {
+    return keds_gemm_bt_ex2(t.att + s.r0 * w, w, k.out_w, k.out_b, t.h + s.r0 * w, w, s.n, w, w,
+                            h ? KEDS_EPI_RESID_STATS_F16_H : KEDS_EPI_RESID_STATS_F16, (const float*)(t.st2 + 2 * s.r0), 0, nullptr, s.st);
 }
-int fc_rows(const TowerWs& t, const keds_block_params& k, int w, RowSpan s) {
+int fc_rows(const TowerWs& t, const keds_block_params& k, int w, RowSpan s, bool h) {
     return keds_gemm_bt_ex2(t.h + s.r0 * w, w, k.fc_wf, k.fc_bc, t.hid + s.r0 * 4 * w, 4 * w, s.n, 4 * w, w,
-                            KEDS_EPI_LN_QGELU_BF16_H, (const float*)(t.st2 + 2 * s.r0), 0, t.st1 + 2 * s.r0, s.st);
+                            h ? KEDS_EPI_LN_QGELU_F16_H : KEDS_EPI_LN_QGELU_BF16_H, (const float*)(t.st2 + 2 * s.r0), 0, t.st1 + 2 * s.r0,
+                            s.st);
 }
 // (the last block's output feeds no further ln_1: no statistics)
-int proj_rows(const TowerWs& t, const keds_block_params& k, int w, bool last, RowSpan s) {
+int proj_rows(const TowerWs& t, const keds_block_params& k, int w, bool last, RowSpan s, bool h) {
     return keds_gemm_bt_ex2(t.hid + s.r0 * 4 * w, 4 * w, k.proj_w, k.proj_b, t.h + s.r0 * w, w, s.n, w, 4 * w,
-                            KEDS_EPI_RESID_STATS_F16, last ? nullptr : (const float*)(t.st1 + 2 * s.r0), 0, nullptr, s.st);
+                            h ? KEDS_EPI_RESID_STATS_F16_H : KEDS_EPI_RESID_STATS_F16, last ? nullptr : (const float*)(t.st1 + 2 * s.r0),
+                            0, nullptr, s.st);
+}
+// the attention of the 16-bit flows: bf16 or (h) fp16 qkv / output
+int attention16(bool h, const void* qkv, void* out, int B, int S, int heads, int causal, int q_limit, hipStream_t st) {
+    return h ? keds_attention_h(qkv, out, B, S, heads, causal, q_limit, st) : keds_attention_ex(qkv, out, B, S, heads, causal, q_limit, st);
+}
+int attention16_packed(bool h, const void* qkv, void* out, int B, int s_max, const int32_t* off, int heads, int causal, hipStream_t st) {
+    return h ? keds_attention_packed_h(qkv, out, B, s_max, off, heads, causal, st)
+             : keds_attention_packed(qkv, out, B, s_max, off, heads, causal, st);
 }
 
 // After the last block only token 0 of every sample is read (ln_post(x[:,0,:]), model.py:412), so the attention
@@ -158,13 +173,17 @@ int cls_rows_tail(const keds_tower_params* p, const keds_block_params& k, const 
                   hipStream_t st) {
     const int w = p->width, S = p->seq;
     const long long ld = (long long)S * w;
+    const bool h = p->f16;
+    const int resid = h ? KEDS_EPI_BIAS_RESID_F32_H : KEDS_EPI_BIAS_RESID_F32;
     int rc;
     if (x16 && (rc = keds_cast_rows_f16_f32_impl(x16, x, B, w, ld, st))) return rc;
-    if ((rc = keds_attention_ex(t.qkv, t.att, B, S, p->heads, p->causal, 1, st))) return rc;
-    if ((rc = keds_gemm_bt_ex(t.att, ld, k.out_w, k.out_b, x, ld, B, w, w, KEDS_EPI_BIAS_RESID_F32, nullptr, 0, st))) return rc;
-    if ((rc = keds_layernorm_impl(x, w, nullptr, S, k.ln2_g, k.ln2_b, t.h, 0, B, w, st))) return rc;
-    if ((rc = keds_gemm_bt(t.h, k.fc_w, k.fc_b, t.hid, B, 4 * w, w, KEDS_EPI_BIAS_QGELU_BF16, nullptr, 0, st))) return rc;
-    return keds_gemm_bt_ex(t.hid, 4 * w, k.proj_w, k.proj_b, x, ld, B, w, 4 * w, KEDS_EPI_BIAS_RESID_F32, nullptr, 0, st);
+    if ((rc = attention16(h, t.qkv, t.att, B, S, p->heads, p->causal, 1, st))) return rc;
+    if ((rc = keds_gemm_bt_ex(t.att, ld, k.out_w, k.out_b, x, ld, B, w, w, resid, nullptr, 0, st))) return rc;
+    if ((rc = keds_layernorm_impl(x, w, nullptr, S, k.ln2_g, k.ln2_b, t.h, h ? 2 : 0, B, w, st))) return rc;
+    if ((rc = keds_gemm_bt(t.h, k.fc_w, k.fc_b, t.hid, B, 4 * w, w, h ? KEDS_EPI_BIAS_QGELU_F16_H : KEDS_EPI_BIAS_QGELU_BF16, nullptr, 0,
+                           st)))
+        return rc;
+    return keds_gemm_bt_ex(t.hid, 4 * w, k.proj_w, k.proj_b, x, ld, B, w, 4 * w, resid, nullptr, 0, st);
 }
 
 // The text tower's form of the same cut: after the last block only ONE row of every sample is read -- the EOT column
@@ -177,19 +196,23 @@ int cls_rows_tail(const keds_tower_params* p, const keds_block_params& k, const 
 int rows_tail(const keds_tower_params* p, const keds_block_params& k, const TowerWs& t, float* x, const void* x16, int B,
               const int32_t* rows, hipStream_t st, const PackedRows* pk = nullptr) {
     const int w = p->width, S = p->seq;
+    const bool h = p->f16;
+    const int resid = h ? KEDS_EPI_BIAS_RESID_F32_H : KEDS_EPI_BIAS_RESID_F32;
     int rc;
-    if (pk) rc = keds_attention_packed(t.qkv, t.att, B, S, pk->off, p->heads, p->causal, st);
-    else rc = keds_attention(t.qkv, t.att, B, S, p->heads, p->causal, st);
+    if (pk) rc = attention16_packed(h, t.qkv, t.att, B, S, pk->off, p->heads, p->causal, st);
+    else rc = attention16(h, t.qkv, t.att, B, S, p->heads, p->causal, S, st);
     if (rc) return rc;
-    bf16_t* att_c = t.qkv;                                               // [B, w] bf16 (2 w bytes per row: a multiple of 256)
+    bf16_t* att_c = t.qkv;                                               // [B, w] 16-bit (2 w bytes per row: a multiple of 256)
     float* x_c = (float*)((char*)t.qkv + (size_t)B * w * 2);             // [B, w] fp32; 6 B w <= the buffer's 6 w pad256(B S)
     const int bound = pk ? pk->valid : S;
     if ((rc = keds_gather_rows_impl(t.att, att_c, rows, bound, B, w, 0, st, pk != nullptr))) return rc;
     if ((rc = keds_gather_rows_impl(x16 ? x16 : (const void*)x, x_c, rows, bound, B, w, x16 ? 1 : 2, st, pk != nullptr))) return rc;
-    if ((rc = keds_gemm_bt_ex(att_c, w, k.out_w, k.out_b, x_c, w, B, w, w, KEDS_EPI_BIAS_RESID_F32, nullptr, 0, st))) return rc;
-    if ((rc = keds_layernorm_impl(x_c, w, nullptr, 1, k.ln2_g, k.ln2_b, t.h, 0, B, w, st))) return rc;
-    if ((rc = keds_gemm_bt(t.h, k.fc_w, k.fc_b, t.hid, B, 4 * w, w, KEDS_EPI_BIAS_QGELU_BF16, nullptr, 0, st))) return rc;
-    if ((rc = keds_gemm_bt_ex(t.hid, 4 * w, k.proj_w, k.proj_b, x_c, w, B, w, 4 * w, KEDS_EPI_BIAS_RESID_F32, nullptr, 0, st))) return rc;
+    if ((rc = keds_gemm_bt_ex(att_c, w, k.out_w, k.out_b, x_c, w, B, w, w, resid, nullptr, 0, st))) return rc;
+    if ((rc = keds_layernorm_impl(x_c, w, nullptr, 1, k.ln2_g, k.ln2_b, t.h, h ? 2 : 0, B, w, st))) return rc;
+    if ((rc = keds_gemm_bt(t.h, k.fc_w, k.fc_b, t.hid, B, 4 * w, w, h ? KEDS_EPI_BIAS_QGELU_F16_H : KEDS_EPI_BIAS_QGELU_BF16, nullptr, 0,
+                           st)))
+        return rc;
+    if ((rc = keds_gemm_bt_ex(t.hid, 4 * w, k.proj_w, k.proj_b, x_c, w, B, w, 4 * w, resid, nullptr, 0, st))) return rc;
     if (hipMemcpyAsync(x, x_c, (size_t)B * w * sizeof(float), hipMemcpyDeviceToDevice, st) != hipSuccess) {
         keds_set_error("keds_tower_forward: read-out rows: %s", hipGetErrorString(hipGetLastError()));
         return KEDS_E_LAUNCH;
@@ -260,7 +283,7 @@ int tower_forward_fp8(const keds_tower_params* p, float* x, int B, const TowerWs
         if ((rc = keds_gemm_mxfp8_ex(t.xq, t.xs, Mm, k.qkv_q8, k.qkv_s8, 3 * w, k.qkv_bc8, t.qkv, Mm, 3 * w, w,
                                      KEDS_FP8_EPI_LN_BIAS_BF16, (float*)t.st1, (float*)t.st2, nullptr, nullptr, 0, st)))
             return rc;
-        if (Mt && (rc = qkv_rows(t, k, w, rem))) return rc;
+        if (Mt && (rc = qkv_rows(t, k, w, rem, false))) return rc;
         if ((rc = lanes.to_main())) return rc;
         if (last && last_rows) return rows_tail(p, k, t, x, t.h, B, last_rows, st);
         if (last && p->last_cls_only) return cls_rows_tail(p, k, t, x, t.h, B, st);
@@ -270,15 +293,15 @@ int tower_forward_fp8(const keds_tower_params* p, float* x, int B, const TowerWs
         if ((rc = keds_gemm_mxfp8_ex(t.aq, t.as, Mm, k.out_q8, k.out_s8, w, k.out_b, t.h, Mm, w, w,
                                      KEDS_FP8_EPI_RESID_STATS_MX_H, (float*)t.st2, nullptr, t.xq, t.xs, Mm, st)))
             return rc;
-        if (Mt && (rc = out_rows(t, k, w, rem))) return rc;
+        if (Mt && (rc = out_rows(t, k, w, rem, false))) return rc;
         if ((rc = keds_gemm_mxfp8_ex(t.xq, t.xs, Mm, k.fc_q8, k.fc_s8, 4 * w, k.fc_bc8, nullptr, Mm, 4 * w, w,
                                      KEDS_FP8_EPI_LN_QGELU_MX, (float*)t.st2, (float*)t.st1, t.hq, t.hs, Mm, st)))
             return rc;
-        if (Mt && (rc = fc_rows(t, k, w, rem))) return rc;
+        if (Mt && (rc = fc_rows(t, k, w, rem, false))) return rc;
         if ((rc = keds_gemm_mxfp8_ex(t.hq, t.hs, Mm, k.proj_q8, k.proj_s8, w, k.proj_b, t.h, Mm, w, 4 * w,
                                      KEDS_FP8_EPI_RESID_STATS_MX_H, (float*)t.st1, nullptr, t.xq, t.xs, Mm, st)))
             return rc;
-        if (Mt && (rc = proj_rows(t, k, w, last, rem))) return rc;
+        if (Mt && (rc = proj_rows(t, k, w, last, rem, false))) return rc;
     }
     if ((rc = lanes.to_main())) return rc;
     return keds_cast_rows_f16_f32_impl(t.h, x, M, w, w, st);       // the caller reads x in fp32
@@ -312,8 +335,13 @@ int tower_forward(const keds_tower_params* p, float* x, int B, void* ws, hipStre
         return KEDS_E_ARG;
     }
     const bool fp8 = p->fp8 && Mm > 0;             // fewer than 256 rows: everything is "remainder rows" (bf16 kernels)
+    const bool h = p->f16;                         // the fp16 operating point: every 16-bit operand fp16 (folded flow only)
+    if (h && (p->fp8 || p->f32 || !folded)) {
+        keds_set_error("keds_tower_forward: f16 needs the folded weights and excludes fp8 / f32");
+        return KEDS_E_ARG;
+    }
     if (pk && (p->fp8 || !p->causal || !last_rows)) {
-        keds_set_error("keds_tower_forward: packed rows need a causal bf16 tower with a read-out row per sample");
+        keds_set_error("keds_tower_forward: packed rows need a causal 16-bit (bf16 / fp16) tower with a read-out row per sample");
         return KEDS_E_ARG;
     }
     if (pk && pk->rows > pk->valid &&
@@ -322,8 +350,8 @@ int tower_forward(const keds_tower_params* p, float* x, int B, void* ws, hipStre
         return KEDS_E_LAUNCH;
     }
     auto attention = [&](hipStream_t s_) {           // the block's attention on all samples
-        return pk ? keds_attention_packed(t.qkv, t.att, B, S, pk->off, p->heads, p->causal, s_)
-                  : keds_attention(t.qkv, t.att, B, S, p->heads, p->causal, s_);
+        return pk ? attention16_packed(h, t.qkv, t.att, B, S, pk->off, p->heads, p->causal, s_)
+                  : attention16(h, t.qkv, t.att, B, S, p->heads, p->causal, S, s_);
     };
     if (fp8) return tower_forward_fp8(p, x, B, t, Mm, st, last_rows);
     if (folded) {
@@ -366,29 +394,29 @@ int tower_forward(const keds_tower_params* p, float* x, int B, void* ws, hipStre
         for (int l = 0; l < p->layers; ++l) {
             const keds_block_params& k = p->blocks[l];
             const bool last = l == p->layers - 1;
-            if ((rc = qkv_rows(t, k, w, body))) return rc;
-            if (rem.n && (rc = qkv_rows(t, k, w, rem))) return rc;
+            if ((rc = qkv_rows(t, k, w, body, h))) return rc;
+            if (rem.n && (rc = qkv_rows(t, k, w, rem, h))) return rc;
             if (last && (p->last_cls_only || last_rows)) {
                 if ((rc = lanes.to_main())) return rc;
                 return last_rows ? rows_tail(p, k, t, x, t.h, B, last_rows, st, pk) : cls_rows_tail(p, k, t, x, t.h, B, st);
             }
             if (tail_side) {
                 if ((rc = lanes.to_side())) return rc;               // side: behind the main in_proj
-                if ((rc = keds_attention(t.qkv, t.att, b_tail, S, p->heads, p->causal, st))) return rc;
-                if ((rc = keds_attention(t.qkv + (size_t)b_tail * S * 3 * w, t.att + (size_t)b_tail * S * w, B - b_tail, S, p->heads,
-                                         p->causal, lanes.side)))
+                if ((rc = attention16(h, t.qkv, t.att, b_tail, S, p->heads, p->causal, S, st))) return rc;
+                if ((rc = attention16(h, t.qkv + (size_t)b_tail * S * 3 * w, t.att + (size_t)b_tail * S * w, B - b_tail, S, p->heads,
+                                      p->causal, S, lanes.side)))
                     return rc;
                 if ((rc = lanes.to_main())) return rc;               // main: behind the tail samples' attention
             } else {
                 if ((rc = lanes.to_main())) return rc;
                 if ((rc = lanes.attention_then_side([&] { return attention(st); }))) return rc;
             }
-            if ((rc = out_rows(t, k, w, body))) return rc;
-            if (rem.n && (rc = out_rows(t, k, w, rem))) return rc;
-            if ((rc = fc_rows(t, k, w, body))) return rc;
-            if (rem.n && (rc = fc_rows(t, k, w, rem))) return rc;
-            if ((rc = proj_rows(t, k, w, last, body))) return rc;
-            if (rem.n && (rc = proj_rows(t, k, w, last, rem))) return rc;
+            if ((rc = out_rows(t, k, w, body, h))) return rc;
+            if (rem.n && (rc = out_rows(t, k, w, rem, h))) return rc;
+            if ((rc = fc_rows(t, k, w, body, h))) return rc;
+            if (rem.n && (rc = fc_rows(t, k, w, rem, h))) return rc;
+            if ((rc = proj_rows(t, k, w, last, body, h))) return rc;
+            if (rem.n && (rc = proj_rows(t, k, w, last, rem, h))) return rc;
         }
         if ((rc = lanes.to_main())) return rc;
         return keds_cast_rows_f16_f32_impl(t.h, x, M, w, w, st);   // the caller reads x in fp32
@@ -421,6 +449,10 @@ int check_tower(const keds_tower_params* p, const char* who) {
     }
     if (p->seq < 1 || p->seq > 288) {
         keds_set_error("%s: sequence length %d unsupported", who, p->seq);
+        return KEDS_E_ARG;
+    }
+    if (p->f16 && (p->fp8 || p->f32)) {
+        keds_set_error("%s: f16 (the fp16 operating point) excludes fp8 and f32", who);
         return KEDS_E_ARG;
     }
     return KEDS_OK;
@@ -529,15 +561,17 @@ extern "C" int keds_vit_run(const keds_vit_params* p, const float* image, int B,
         return keds_readout_f32(v.x, S, nullptr, p->ln_post_g, p->ln_post_b, (const float*)p->proj_t, out, B, w, p->embed_dim,
                                 normalize, v.ro, st);
     }
-    if ((rc = keds_im2col(image, col, B, p->resolution, p->patch, p->kpad, stream))) return rc;
-    if ((rc = keds_gemm_bt(col, p->conv_w, nullptr, v.x, B * G, w, p->kpad, KEDS_EPI_PATCH_F32, p->pos_emb, G, stream)))
+    const bool h = p->tower.f16;                  // (conv_w / proj_t fp16 too)
+    if ((rc = keds_im2col_ex(image, col, h ? 1 : 0, B, p->resolution, p->patch, p->kpad, stream))) return rc;
+    if ((rc = keds_gemm_bt(col, p->conv_w, nullptr, v.x, B * G, w, p->kpad, h ? KEDS_EPI_PATCH_F32_H : KEDS_EPI_PATCH_F32, p->pos_emb, G,
+                           stream)))
         return rc;
     if ((rc = keds_cls_rows_impl(v.x, p->class_emb, p->pos_emb, B, S, w, st))) return rc;
     // ln_pre in place (each wave holds its whole row in registers before it stores)
     if ((rc = keds_layernorm_impl(v.x, w, nullptr, 1, p->ln_pre_g, p->ln_pre_b, v.x, 1, B * S, w, st))) return rc;
     if ((rc = tower_forward(&p->tower, v.x, B, v.tower, st, true))) return rc;
-    return keds_readout(v.x, S, nullptr, p->ln_post_g, p->ln_post_b, p->proj_t, out, B, w, p->embed_dim, normalize, v.ro,
-                        keds_readout_workspace_bytes(B, w), stream);
+    return keds_readout_impl(v.x, S, nullptr, p->ln_post_g, p->ln_post_b, p->proj_t, out, B, w, p->embed_dim, normalize, v.ro,
+                             keds_readout_workspace_bytes(B, w), stream, h);
 }
 
 // ---- text ------------------------------------------------------------------------------------
@@ -628,8 +662,8 @@ extern "C" int keds_text_run_ex(const keds_text_params* p, const int32_t* tokens
                                 (const float*)p->proj_t, out, B, w, p->embed_dim, normalize, v.ro, (hipStream_t)stream);
     }
     if ((rc = tower_forward(&tp, v.x, B, v.tower, (hipStream_t)stream, true, last_rows))) return rc;
-    return keds_readout(v.x, last_rows ? 1 : Lx, last_rows ? nullptr : readout_row, p->ln_final_g, p->ln_final_b, p->proj_t, out,
-                        B, w, p->embed_dim, normalize, v.ro, keds_readout_workspace_bytes(B, w), stream);
+    return keds_readout_impl(v.x, last_rows ? 1 : Lx, last_rows ? nullptr : readout_row, p->ln_final_g, p->ln_final_b, p->proj_t, out,
+                             B, w, p->embed_dim, normalize, v.ro, keds_readout_workspace_bytes(B, w), stream, tp.f16);
 }
 
 // The same on PACKED rows (round 6).  Captions end at different columns and under the causal mask (model.py:543-549) a column to
@@ -681,8 +715,8 @@ extern "C" int keds_text_run_packed(const keds_text_params* p, const int32_t* to
                                 v.ro, (hipStream_t)stream);
     }
     if ((rc = tower_forward(&tp, v.x, B, v.tower, (hipStream_t)stream, false, readout_global, &pk))) return rc;
-    return keds_readout(v.x, 1, nullptr, p->ln_final_g, p->ln_final_b, p->proj_t, out, B, w, p->embed_dim, normalize, v.ro,
-                        keds_readout_workspace_bytes(B, w), stream);
+    return keds_readout_impl(v.x, 1, nullptr, p->ln_final_g, p->ln_final_b, p->proj_t, out, B, w, p->embed_dim, normalize, v.ro,
+                             keds_readout_workspace_bytes(B, w), stream, tp.f16);
 }
 
 extern "C" int keds_text_run(const keds_text_params* p, const int32_t* tokens, const int32_t* readout_row,

@@ -34,6 +34,10 @@ def _bf16(t: torch.Tensor) -> torch.Tensor:
     return t.detach().to(torch.bfloat16).contiguous()
 
 
+def _f16(t: torch.Tensor) -> torch.Tensor:
+    return t.detach().to(torch.float16).contiguous()
+
+
 def _f32(t: torch.Tensor) -> torch.Tensor:
     return t.detach().to(torch.float32).contiguous()
 
@@ -82,7 +86,7 @@ class VisualTransformer(nn.Module):
 
 
 def _pack_tower(tr: Transformer, seq: int, causal: bool, keep: list, cls_only: bool = False,
-                fp8: bool = False, folded: bool = True, f32: bool = False) -> _lib.TowerParams:
+                fp8: bool = False, folded: bool = True, f32: bool = False, f16: bool = False) -> _lib.TowerParams:
     blocks = (_lib.BlockParams * tr.layers)()
     # f32 = 1: the fp32-accurate flow (csrc/f32path.hip) multiplies the weights as stored; f32 = 2 ("fp32x3"): the four block
     # weights as PAIRS of fp16 planes [2, N, K] of w 2^e (hi + lo to 22 bits; keds_split_f16_weight picks the exact per-matrix
@@ -97,8 +101,11 @@ def _pack_tower(tr: Transformer, seq: int, causal: bool, keep: list, cls_only: b
         check(load().keds_split_f16_weight(ptr(w32), n, k, ptr(out), n * k, C.byref(e), stream()), "keds_split_f16_weight")
         x3_exps.append(int(e.value))
         return out
-    wcast = _planes if f32 == 2 else _f32 if f32 else _bf16
+    # f16 ("fp16"): the four weights rounded to fp16 as stored (convert_weights' own rounding); needs the folded flow
+    wcast = _planes if f32 == 2 else _f32 if f32 else _f16 if f16 else _bf16
     folded = folded and not f32
+    if f16 and not folded:
+        raise ValueError("fp16 needs the folded LayerNorm path")
     for i, blk in enumerate(tr.resblocks):
         del x3_exps[:]                                          # (filled in the order qkv, out, fc, proj below)
         t = dict(
@@ -148,11 +155,11 @@ def _pack_tower(tr: Transformer, seq: int, causal: bool, keep: list, cls_only: b
         keep.append(t)
     keep.append(blocks)
     return _lib.TowerParams(tr.width, tr.layers, tr.heads, seq, 1 if causal else 0, blocks, 1 if fp8 else 0,
-                            1 if cls_only else 0, int(f32))
+                            1 if cls_only else 0, int(f32), 1 if f16 else 0)
 
 
 class _Packed:
-    """bf16/fp32 device copies of the weights in the layout the kernels want + the ABI structs."""
+    """bf16/fp16/fp32 device copies of the weights in the layout the kernels want + the ABI structs."""
 
     def __init__(self, clip: "CLIP", folded: bool = True):
         self.keep: list = []
@@ -164,9 +171,10 @@ class _Packed:
         self.kpad = (kreal + 63) // 64 * 64
         prec = getattr(clip, "precision", "bf16")
         f32 = 2 if prec == "fp32x3" else 1 if prec == "fp32" else 0      # (2: the block GEMMs on split fp16 operands, the rest as 1)
-        wdt = torch.float32 if f32 else torch.bfloat16
-        wcast = _f32 if f32 else _bf16
-        self.f32 = f32
+        f16 = prec == "fp16"                                            # every 16-bit operand fp16, conv / projections included
+        wdt = torch.float32 if f32 else torch.float16 if f16 else torch.bfloat16
+        wcast = _f32 if f32 else _f16 if f16 else _bf16
+        self.f32, self.f16 = f32, f16
         conv = torch.zeros((width, self.kpad), dtype=wdt, device=v.conv1.weight.device)
         conv[:, :kreal] = v.conv1.weight.detach().reshape(width, kreal).to(wdt)
         g = v.input_resolution // P
@@ -176,7 +184,7 @@ class _Packed:
         self.keep.append(t)
         fp8 = getattr(clip, "precision", "bf16") == "fp8"
         self.vit = _lib.VitParams(_pack_tower(v.transformer, g * g + 1, False, self.keep, cls_only=True, fp8=fp8, folded=folded,
-                                              f32=f32),
+                                              f32=f32, f16=f16),
                                   v.input_resolution, P,
                                   self.kpad, v.output_dim, *[ptr(t[k]) for k in (
                                       "conv_w", "class_emb", "pos_emb", "ln_pre_g", "ln_pre_b", "ln_post_g",
@@ -186,7 +194,8 @@ class _Packed:
                   proj_t=wcast(clip.text_projection.detach().t()))
         self.keep.append(tt)
         self.text = _lib.TextParams(_pack_tower(clip.transformer, clip.context_length, True, self.keep,
-                                                fp8=fp8 and clip.transformer.width % 256 == 0, folded=folded, f32=f32),
+                                                fp8=fp8 and clip.transformer.width % 256 == 0, folded=folded, f32=f32,
+                                                f16=f16),
                                     clip.vocab_size, clip.embed_dim,
                                     *[ptr(tt[k]) for k in ("token_emb", "pos_emb", "ln_final_g", "ln_final_b", "proj_t")])
         self.device = conv.device
@@ -286,11 +295,24 @@ class CLIP(nn.Module):
         "fp32x3" (round 5): the same fp32 flow with the four GEMMs of every block on SPLIT fp16 operands -- x = hi + lo
         (22 significant bits), hi.hi + hi.lo + lo.hi on the fp16 matrix instruction, fp32 accumulate: fp32-grade embeddings
         (Recall@k equal) at more than twice "fp32"'s throughput; values beyond the fp16 range (|x| >= 65504) send the model
-        back to "fp32" by themselves."""
-        if precision not in ("bf16", "fp8", "fp32", "fp32x3"):
-            raise ValueError("precision must be 'bf16', 'fp8', 'fp32' or 'fp32x3'")
+        back to "fp32" by themselves.
+        "fp16": the reference's `--precision fp16` (convert_weights, model.py:927-948): EVERY GEMM operand of both towers is
+        fp16 -- weights rounded as stored, qkv, attention probabilities and output, MLP hidden layer, patches and read-out rows --
+        on the fp16 matrix instruction (the bf16 rate), fp32 accumulate, LayerNorm folded as in "bf16".  Needs the folded path
+        (not with set_numerics("safe")).  Under numerics "auto" a value beyond the fp16 range (or a statistics trip) moves the
+        model to "fp32x3" -- a RuntimeWarning, `fp16_range_trips` += 1 -- and the pass runs again there.  The knowledge
+        modules run their exact fp32 path (compose_query_features)."""
+        if precision not in ("bf16", "fp16", "fp8", "fp32", "fp32x3"):
+            raise ValueError("precision must be 'bf16', 'fp16', 'fp8', 'fp32' or 'fp32x3'")
         if precision == "fp8" and (self.visual.transformer.width % 256 != 0 or self.numerics == "safe"):
             raise ValueError("fp8 needs a vision width that is a multiple of 256 and the folded LayerNorm path")
+        if precision == "fp16" and self.numerics == "safe":
+            raise ValueError("fp16 needs the folded LayerNorm path (numerics 'auto' or 'fast')")
+        # a pass still waiting for its lazy guard check ran at the CURRENT precision: settle it there before switching
+        self._guard_poll(wait=True)
+        if precision == "fp16" and self.numerics_tripped:
+            raise ValueError("fp16 needs the folded LayerNorm path; the numerics guard has moved this model to the fp32-stream "
+                             "flow (set_numerics() resets it)")
         self.precision = precision
         self._packed = None
         return self
@@ -310,15 +332,28 @@ class CLIP(nn.Module):
     def set_numerics(self, mode: str = "auto"):
         if mode not in ("auto", "fast", "safe"):
             raise ValueError("numerics must be 'auto', 'fast' or 'safe'")
-        if mode == "safe" and self.precision == "fp8":
-            raise ValueError("fp8 needs the folded LayerNorm path")
+        if mode == "safe" and self.precision in ("fp8", "fp16"):
+            raise ValueError(f"{self.precision} needs the folded LayerNorm path")
         self._guard_poll(wait=True)
         self.numerics, self.numerics_tripped, self.numerics_late_trip = mode, False, False
+        self._fp16_trip_seen = False
         self._guard_eager_left = GUARD_EAGER_PASSES
         return self
 
     def _guard_trip(self, late: bool):
         import warnings
+        if self.precision == "fp16":
+            # an fp16 operand left the fp16 range (|v| > 65504 / non-finite) or the folded LayerNorm's statistics tripped: the
+            # model moves to "fp32x3" (Recall-equal, no fp16 storage of qkv / hidden values) -- as fp32x3 moves to fp32 on its own trip
+            warnings.warn("keds_amd.CLIP: fp16 tower values left the fp16 range (or |row mean|/std > 32); " +
+                          ("the passes since the last check ran in fp16 (numerics_late_trip); later passes run" if late else
+                           "re-running") + " on precision 'fp32x3' and staying there", RuntimeWarning)
+            self._guard.zero_()
+            self.fp16_range_trips = getattr(self, "fp16_range_trips", 0) + 1
+            self._fp16_trip_seen = True
+            self.numerics_late_trip = self.numerics_late_trip or late
+            self.set_precision("fp32x3")
+            return
         warnings.warn("keds_amd.CLIP: activations left the range the fast tower flow is accurate in (|row mean|/std > 32 or a "
                       "non-finite fp16 residual); " + ("the passes since the last check ran on the fast flow (numerics_late_trip); "
                       "later passes run" if late else "re-running") + " on the fp32-stream flow and staying there", RuntimeWarning)
@@ -339,9 +374,10 @@ class CLIP(nn.Module):
 
     def numerics_sync(self) -> bool:
         """Block until every lazily checked pass has been verified; True when the guard tripped at any point (the model is
-        then on the safe flow; `numerics_late_trip` says whether passes had already been returned from the fast flow)."""
+        then on the safe flow -- or, after an fp16 trip, on precision "fp32x3"; `numerics_late_trip` says whether passes had
+        already been returned from the fast flow)."""
         self._guard_poll(wait=True)
-        return self.numerics_tripped
+        return self.numerics_tripped or getattr(self, "_fp16_trip_seen", False)
 
     def numerics_checked(self, fn):
         """Run `fn()` (any number of encoder passes whose outputs the caller KEEPS: a feature-extraction or evaluation loop)
@@ -408,7 +444,7 @@ class CLIP(nn.Module):
         if int(self._guard.item()) == 0:
             return out
         self._guard_trip(late=False)
-        return run(self._engine())
+        return self._guarded(run)           # (the safe flow -- or, after an fp16 trip, the fp32x3 branch above)
 
     # ---- encoders ------------------------------------------------------------------------------------
     def encode_image(self, image, mid_feature=False, mask_token=False, normalize: bool = False):
