@@ -460,6 +460,19 @@ size_t keds_vit_workspace_bytes(const keds_vit_params* p, int B);
 int keds_vit_run(const keds_vit_params* p, const float* image, int B, float* out, int normalize,
                      void* workspace, size_t workspace_bytes, void* stream);
 
+/* CLIP.encode_image(mid_feature=True) / VisualTransformer.get_tokens (model.py:393-427, 337-342): the same pass as
+ * keds_vit_run with the residual stream written out as out_type (0 bf16, 1 fp32, 2 fp16, as keds_layernorm_ex):
+ *   taps    nullable [layers, B, S, width]: after block l, rows [0, B*S) of the stream at taps + l*B*S*width (sample-major: the
+ *           reference's NLD order), the state before ln_post
+ *   tokens  nullable [B, S, width]: after the last block only
+ *   out     nullable fp32 [B, embed_dim]: the features of the same pass (as keds_vit_run, normalize as there)
+ * At least one of the three.  With taps or tokens the last block runs on every row (keds_tower_params.last_cls_only is ignored)
+ * and the read-out takes the CLS rows of the full stream.  Workspace: keds_vit_workspace_bytes.  The taps are written with
+ * plain stores; keds_tap_store_nt(1) makes them non-temporal (an A/B: measured no faster, tools/bench_tokens.py). */
+int keds_vit_run_tokens(const keds_vit_params* p, const float* image, int B, float* out, int normalize, void* taps, void* tokens,
+                        int out_type, void* workspace, size_t workspace_bytes, void* stream);
+int keds_tap_store_nt(int on);      /* 1: non-temporal tap stores; 0 (default): plain stores */
+
 /* CLIP.encode_text / encode_text_img_retrieval (model.py:577-590, 808-851):
  * tokens int32 [B,L]; readout_row int32 [B]; img_tokens nullable fp32 [B,n_tok,d]. */
 size_t keds_text_workspace_bytes(const keds_text_params* p, int B);
@@ -480,6 +493,11 @@ int keds_text_run_ex(const keds_text_params* p, const int32_t* tokens, const int
                      void* workspace, size_t workspace_bytes, void* stream);
 int keds_text_trim_enable(int on);
 int keds_text_trim_mode(void);      /* the flow in force (0 .. 3 as above) */
+/* CLIP.get_text_tokens (model.py:592-605): out [B, L, width] = ln_final(residual stream after the last block) over ALL L columns,
+ * as out_type (0 bf16, 1 fp32, 2 fp16); no projection.  The rectangular flow whatever keds_text_trim_enable says: no column
+ * cut, no read-out-row tail, no packed rows.  tokens int32 [B, L]; workspace: keds_text_workspace_bytes. */
+int keds_text_run_tokens(const keds_text_params* p, const int32_t* tokens, int B, void* out, int out_type, void* workspace,
+                         size_t workspace_bytes, void* stream);
 /* The text tower on PACKED rows (round 6, ABI 8): captions end at different columns, and under the causal mask sample b needs its
  * columns [0, len_b) only (len_b = its read-out column + 1) -- keds_text_run_ex cuts every sample at the LONGEST caption of the
  * batch, here sample b owns rows [seq_off[b], seq_off[b + 1]) of every activation buffer and the tower runs sum(len_b) rows.

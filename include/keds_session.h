@@ -61,6 +61,11 @@ int keds_vit_destroy(keds_vit* vit);
 int keds_vit_info(const keds_vit* vit, int* width, int* layers, int* resolution, int* patch, int* embed_dim);
 /* image [B,3,R,R] (dtype img_dtype, device) -> out fp32 [B, embed_dim] (not normalised, model.py:412-415) */
 int keds_vit_forward(keds_vit* vit, const void* image, int img_dtype, int B, void* out, void* stream);
+/* the same pass with the token-level outputs of keds_vit_run_tokens (keds_hip.h): out nullable fp32 [B, embed_dim], taps
+ * nullable [layers, B, S, width], tokens nullable [B, S, width] (at least one), out_type 0 bf16 / 1 fp32 / 2 fp16 for taps and
+ * tokens.  CLIP.encode_image(mid_feature=True) / VisualTransformer.get_tokens, model.py:393-427 */
+int keds_vit_forward_tokens(keds_vit* vit, const void* image, int img_dtype, int B, void* out, void* taps, void* tokens,
+                            int out_type, void* stream);
 
 /* ---- text tower: keys token_embedding.weight, positional_embedding, transformer.*, ln_final.*,
  *      text_projection --------------------------------------------------------------------------- */
@@ -83,6 +88,9 @@ int keds_text_forward_used(keds_text* txt, const int32_t* tokens, const void* im
  * result as keds_text_forward within the bf16 flow's own reordering of tiles. */
 int keds_text_forward_packed(keds_text* txt, const int32_t* tokens, const void* img_tokens, int n_img_tok,
                              int insert_idx, const int32_t* readout_host, int B, void* out, void* stream);
+/* CLIP.get_text_tokens (model.py:592-605): tokens int32 [B, context] -> out [B, context, width] = ln_final of every column after
+ * the last block, as out_type (0 bf16, 1 fp32, 2 fp16); no projection (keds_text_run_tokens, keds_hip.h) */
+int keds_text_forward_tokens(keds_text* txt, const int32_t* tokens, int B, void* out, int out_type, void* stream);
 
 /* ---- knowledge injection of ONE stream: IM2TEXT keys (layers.{i}.0.{weight,bias}, fc_out.*) and two
  *      CrossFormers (cross_layers.{i}.to_{q,k,v}.*, to_out.0.*): retrieval_fuse, text_condition ---- */

@@ -100,12 +100,14 @@ SIGNATURES = {
     "keds_vit_destroy": (i32, [vp]),
     "keds_vit_info": (i32, [vp] + [C.POINTER(i32)] * 5),
     "keds_vit_forward": (i32, [vp, vp, i32, i32, vp, vp]),
+    "keds_vit_forward_tokens": (i32, [vp, vp, i32, i32, vp, vp, vp, i32, vp]),
     "keds_text_create": (i32, [vp, C.POINTER(Tensor), i32, i32, pp]),
     "keds_text_destroy": (i32, [vp]),
     "keds_text_info": (i32, [vp] + [C.POINTER(i32)] * 5),
     "keds_text_forward": (i32, [vp, vp, vp, i32, i32, vp, i32, vp, vp]),
     "keds_text_forward_used": (i32, [vp, vp, vp, i32, i32, vp, i32, i32, vp, vp]),
     "keds_text_forward_packed": (i32, [vp, vp, vp, i32, i32, vp, i32, vp, vp]),
+    "keds_text_forward_tokens": (i32, [vp, vp, i32, vp, i32, vp]),
     "keds_knowledge_create": (i32, [vp, C.POINTER(Tensor), i32, C.POINTER(Tensor), i32, C.POINTER(Tensor), i32, pp]),
     "keds_knowledge_destroy": (i32, [vp]),
     "keds_knowledge_forward": (i32, [vp, vp, vp, vp, i32, i32, vp, vp]),
@@ -216,6 +218,10 @@ SIGNATURES = {
     "keds_tower_forward": (i32, [C.POINTER(TowerParams), vp, i32, vp, sz, vp]),
     "keds_vit_workspace_bytes": (sz, [C.POINTER(VitParams), i32]),
     "keds_vit_run": (i32, [C.POINTER(VitParams), vp, i32, vp, i32, vp, sz, vp]),
+    # token-level outputs: taps / tokens out_type 0 bf16, 1 fp32, 2 fp16
+    "keds_vit_run_tokens": (i32, [C.POINTER(VitParams), vp, i32, vp, i32, vp, vp, i32, vp, sz, vp]),
+    "keds_tap_store_nt": (i32, [i32]),
+    "keds_text_run_tokens": (i32, [C.POINTER(TextParams), vp, i32, vp, i32, vp, sz, vp]),
     "keds_text_workspace_bytes": (sz, [C.POINTER(TextParams), i32]),
     "keds_text_run": (i32, [C.POINTER(TextParams), vp, vp, vp, i32, i32, i32, vp, i32, vp, sz, vp]),
     "keds_text_run_ex": (i32, [C.POINTER(TextParams), vp, vp, vp, i32, i32, i32, i32, vp, i32, vp, sz, vp]),

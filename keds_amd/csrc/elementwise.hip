@@ -150,17 +150,47 @@ __global__ __launch_bounds__(256) void fold_layernorm_kernel(const float* __rest
     }
 }
 
-// rows of the fp16 residual stream back to fp32 (row r at r * stride elements in both): one thread per 8 elements
-__global__ __launch_bounds__(256) void cast_rows_f16_f32_kernel(const f16_t* __restrict__ x16, float* __restrict__ x32,
-                                                                int rows, int dim, long long stride) {
+// rows of a residual stream into another buffer and type (row r at r * stride elements in both): one thread per 8 elements,
+// 16-byte loads and stores.  SRC f16_t (the folded flow's stream) or float; DST float, f16_t or bf16_t (round to nearest even).
+// NT: non-temporal stores (the per-block taps of keds_vit_run_tokens are written once and never read back by the tower).  Measured
+// at B = 128 ViT-L/14 (tools/bench_tokens.py, profiles/tokens_bench.txt): an fp32 tap of 32,768 rows takes 43.0 us with NT stores
+// and 35.0 us (5.75 TB/s) with plain ones, an fp16 tap 20.6 vs 20.8 us -- so the taps go out as plain stores;
+// keds_tap_store_nt(1) keeps the A/B
+// (NT a template argument: a run-time flag lets the two stores merge into one plain store before inlining)
+template <bool NT, typename T>
+__device__ __forceinline__ void cast_store16(T v, void* p) {
+    if constexpr (NT) __builtin_nontemporal_store(__builtin_bit_cast(u32x4, v), reinterpret_cast<u32x4*>(p));
+    else *reinterpret_cast<u32x4*>(p) = __builtin_bit_cast(u32x4, v);
+}
+template <typename SRC, typename DST, bool NT>
+__global__ __launch_bounds__(256) void cast_rows_kernel(const SRC* __restrict__ src, DST* __restrict__ dst, int rows, int dim,
+                                                        long long stride) {
     const int per_row = dim >> 3;
     const long long id = (long long)blockIdx.x * 256 + threadIdx.x;
     if (id >= (long long)rows * per_row) return;
     const int r = (int)(id / per_row), i = (int)(id - (long long)r * per_row) << 3;
-    const f16x8 v = *reinterpret_cast<const f16x8*>(x16 + (size_t)r * stride + i);
-    float* o = x32 + (size_t)r * stride + i;
-    *reinterpret_cast<f32x4*>(o) = f32x4{(float)v[0], (float)v[1], (float)v[2], (float)v[3]};
-    *reinterpret_cast<f32x4*>(o + 4) = f32x4{(float)v[4], (float)v[5], (float)v[6], (float)v[7]};
+    const SRC* s = src + (size_t)r * stride + i;
+    float v[8];
+    if constexpr (sizeof(SRC) == 2) {
+        const f16x8 h = *reinterpret_cast<const f16x8*>(s);
+#pragma unroll
+        for (int e = 0; e < 8; ++e) v[e] = (float)h[e];
+    } else {
+        const f32x4 a = *reinterpret_cast<const f32x4*>(s), b = *reinterpret_cast<const f32x4*>(s + 4);
+#pragma unroll
+        for (int e = 0; e < 4; ++e) v[e] = a[e], v[4 + e] = b[e];
+    }
+    DST* o = dst + (size_t)r * stride + i;
+    if constexpr (sizeof(DST) == 4) {
+        cast_store16<NT>(f32x4{v[0], v[1], v[2], v[3]}, o);
+        cast_store16<NT>(f32x4{v[4], v[5], v[6], v[7]}, o + 4);
+    } else {
+        typedef __attribute__((ext_vector_type(8))) DST dst8;
+        dst8 q;
+#pragma unroll
+        for (int e = 0; e < 8; ++e) q[e] = (DST)v[e];
+        cast_store16<NT>(q, o);
+    }
 }
 
 // one row per sample out of a [B, S, dim] stream into a compact [B, dim] buffer: dst[b] = src[b * S + row[b]]
@@ -823,12 +853,56 @@ extern "C" int keds_rowstats_cast(const float* x, void* xb, float* stats, int ro
     return keds_rowstats_cast_ex(x, xb, 0, stats, rows, dim, stream);
 }
 
-int keds_cast_rows_f16_f32_impl(const void* x16, float* x32, int rows, int dim, long long stride, hipStream_t st) {
-    KEDS_REQUIRE(x16 && x32 && rows > 0 && dim % 8 == 0 && stride >= dim, "cast_rows_f16_f32: bad argument");
+// src_type / dst_type as keds_layernorm_ex's out_type (0 bf16, 1 fp32, 2 fp16); the source is fp16 or fp32
+int keds_cast_rows_impl(const void* src, int src_type, void* dst, int dst_type, int rows, int dim, long long stride, bool nt,
+                        hipStream_t st) {
+    KEDS_REQUIRE(src && dst && rows > 0 && dim % 8 == 0 && stride >= dim, "cast_rows: bad argument");
+    KEDS_REQUIRE((src_type == 1 || src_type == 2) && dst_type >= 0 && dst_type <= 2, "cast_rows: types %d -> %d", src_type, dst_type);
     KedsProfScope prof(KEDS_PROF_OTHER, st);
     const long long threads = (long long)rows * (dim / 8);
-    cast_rows_f16_f32_kernel<<<(unsigned)((threads + 255) / 256), 256, 0, st>>>((const f16_t*)x16, x32, rows, dim, stride);
-    return keds_check_launch("cast_rows_f16_f32_kernel");
+    const unsigned grid = (unsigned)((threads + 255) / 256);
+#define KEDS_CAST_ROWS(S, D)                                                                                                    \
+    (nt ? cast_rows_kernel<S, D, true><<<grid, 256, 0, st>>>((const S*)src, (D*)dst, rows, dim, stride)                         \
+        : cast_rows_kernel<S, D, false><<<grid, 256, 0, st>>>((const S*)src, (D*)dst, rows, dim, stride))
+    if (src_type == 2) {
+        if (dst_type == 1) KEDS_CAST_ROWS(f16_t, float);
+        else if (dst_type == 2) KEDS_CAST_ROWS(f16_t, f16_t);
+        else KEDS_CAST_ROWS(f16_t, bf16_t);
+    } else {
+        if (dst_type == 1) KEDS_CAST_ROWS(float, float);
+        else if (dst_type == 2) KEDS_CAST_ROWS(float, f16_t);
+        else KEDS_CAST_ROWS(float, bf16_t);
+    }
+#undef KEDS_CAST_ROWS
+    return keds_check_launch("cast_rows_kernel");
+}
+
+// rows of the fp16 residual stream back to fp32 (the end of every folded tower pass)
+int keds_cast_rows_f16_f32_impl(const void* x16, float* x32, int rows, int dim, long long stride, hipStream_t st) {
+    return keds_cast_rows_impl(x16, 2, x32, 1, rows, dim, stride, false, st);
+}
+
+// ---- per-block taps (keds_vit_run_tokens) ------------------------------------------------------------------------------
+static bool g_tap_nt = false;
+extern "C" int keds_tap_store_nt(int on) {
+    g_tap_nt = on != 0;
+    return KEDS_OK;
+}
+
+int keds_tap_rows(const KedsTaps* tp, int l, int layers, const void* src, int src_type, size_t r0, long long n, int w,
+                  hipStream_t st) {
+    if (!tp || n <= 0 || r0 >= tp->rows) return KEDS_OK;
+    if ((long long)(tp->rows - r0) < n) n = (long long)(tp->rows - r0);      // (filler rows behind the last token are no output)
+    const size_t es = tp->type == 1 ? 4 : 2;
+    const char* s = (const char*)src + r0 * w * (src_type == 1 ? 4 : 2);
+    int rc;
+    if (tp->taps && (rc = keds_cast_rows_impl(s, src_type, (char*)tp->taps + ((size_t)l * tp->rows + r0) * w * es, tp->type, (int)n, w,
+                                              w, g_tap_nt, st)))
+        return rc;
+    if (tp->tokens && l == layers - 1 &&
+        (rc = keds_cast_rows_impl(s, src_type, (char*)tp->tokens + r0 * w * es, tp->type, (int)n, w, w, g_tap_nt, st)))
+        return rc;
+    return KEDS_OK;
 }
 
 int keds_gather_rows_impl(const void* src, void* dst, const int32_t* row, int S, int B, int dim, int mode, hipStream_t st,

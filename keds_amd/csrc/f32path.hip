@@ -361,7 +361,7 @@ bool keds_gemm_splits_rows(int M, int N, int K);
 // time); LayerNorm writes its output as planes, the attention output is split by a pass of its own, c_fc's epilogue writes the
 // MLP hidden layer as planes.  A value beyond the fp16 range raises the caller's numerics guard (the host falls back to f32 = 1).
 static int tower_forward_x3(const keds_tower_params* p, float* x, int B, void* ws, hipStream_t st, const int32_t* last_rows,
-                            const PackedRows* pk) {
+                            const PackedRows* pk, const KedsTaps* tp) {
     const int w = p->width, S = p->seq, M = pk ? pk->rows : B * S;
     const size_t Mp = keds_align_up((size_t)B * S, 256);          // (the buffers are carved for the rectangular layout either way)
     const int32_t* soff = pk ? pk->off : nullptr;
@@ -442,6 +442,7 @@ static int tower_forward_x3(const keds_tower_params* p, float* x, int B, void* w
         if (lane && (rc = keds_stream_order(st, lane->fork, lane->s))) return rc;
         for (int i = 0; i < nspan; ++i) {
             if ((rc = post(k, spans[i]))) return rc;
+            if ((rc = keds_tap_rows(tp, l, p->layers, x, 1, spans[i].r0, spans[i].n, w, spans[i].st))) return rc;
             if (!last && (rc = pre(p->blocks[l + 1], spans[i]))) return rc;
         }
     }
@@ -450,13 +451,14 @@ static int tower_forward_x3(const keds_tower_params* p, float* x, int B, void* w
 
 // last_rows (device int32 [B], nullable): towers.hip, rows_tail -- the text tower's read-out rows; on return x[b] = that row
 // pk (nullable): packed rows of a causal tower with a read-out row per sample (keds_common.h) -- M = pk->rows, last_rows global
+// tp (nullable): per-block taps of the fp32 stream x (keds_vit_run_tokens; the caller clears last_cls_only)
 int keds_tower_forward_f32(const keds_tower_params* p, float* x, int B, void* ws, hipStream_t st, const int32_t* last_rows,
-                           const PackedRows* pk) {
+                           const PackedRows* pk, const KedsTaps* tp) {
     if (pk && (!p->causal || !last_rows)) {
         keds_set_error("keds_tower_forward_f32: packed rows need a causal tower with a read-out row per sample");
         return KEDS_E_ARG;
     }
-    if (p->f32 == 2) return tower_forward_x3(p, x, B, ws, st, last_rows, pk);
+    if (p->f32 == 2) return tower_forward_x3(p, x, B, ws, st, last_rows, pk, tp);
     const int w = p->width, S = p->seq, M = pk ? pk->rows : B * S;
     const size_t Mp = keds_align_up((size_t)B * S, 256);          // (the buffers are carved for the rectangular layout either way)
     const int32_t* soff = pk ? pk->off : nullptr;
@@ -514,6 +516,7 @@ int keds_tower_forward_f32(const keds_tower_params* p, float* x, int B, void* ws
         if ((rc = keds_layernorm_impl(x, w, nullptr, 1, k.ln2_g, k.ln2_b, ln, 1, M, w, st))) return rc;
         if ((rc = keds_gemm_f32(ln, w, fc_w, k.fc_b, hid, 4 * w, M, 4 * w, w, F32_EPI_QGELU, nullptr, 0, st))) return rc;
         if ((rc = keds_gemm_f32(hid, 4 * w, proj_w, k.proj_b, x, w, M, w, 4 * w, F32_EPI_RESID, nullptr, 0, st))) return rc;
+        if ((rc = keds_tap_rows(tp, l, p->layers, x, 1, 0, M, w, st))) return rc;
     }
     return KEDS_OK;
 }

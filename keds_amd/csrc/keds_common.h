@@ -40,6 +40,19 @@ struct PackedRows {
     int valid;              // off[B]: rows [valid, rows) belong to no sample -- zero rows, kept finite (the attention never writes them)
 };
 
+// Per-block outputs of a tower pass (keds_vit_run_tokens): after block l, rows [0, rows) of the residual stream go to
+// taps + l * rows * width and, after the last block, to tokens (either nullable), as bf16 / fp32 / fp16 (type 0 / 1 / 2, the
+// out_type of keds_layernorm_ex).  Each span of rows is tapped on the lane that produced it, so stream order keeps block l + 1's
+// in-place residual update behind tap l.
+struct KedsTaps {
+    void* taps;             // [layers, B, S, width]
+    void* tokens;           // [B, S, width]
+    int type;
+    size_t rows;            // B * S
+};
+// src_type 1: fp32 rows, 2: fp16 rows; rows [r0, r0 + n) of block l (elementwise.hip).  tp == nullptr: nothing is launched
+int keds_tap_rows(const KedsTaps* tp, int l, int layers, const void* src, int src_type, size_t r0, long long n, int w, hipStream_t st);
+
 // ---- error plumbing (host) ---------------------------------------------------------
 void keds_set_error(const char* fmt, ...);
 int keds_check_launch(const char* what);

@@ -529,12 +529,10 @@ extern "C" int keds_vit_info(const keds_vit* vit, int* width, int* layers, int* 
     return KEDS_OK;
 }
 
-extern "C" int keds_vit_forward(keds_vit* vit, const void* image, int img_dtype, int B, void* out, void* stream) {
-    const char* what = "keds_vit_forward";
-    KEDS_REQUIRE(vit && image && out && B > 0, "%s: bad argument", what);
-    hipStream_t st = (hipStream_t)stream;
+// the image as fp32 (a converted copy in the handle's buffer for bf16 / fp16 images) and a workspace for B images
+static int vit_prepare(keds_vit* vit, const void* image, int img_dtype, int B, hipStream_t st, const char* what, const float** img) {
     int rc;
-    const float* img = (const float*)image;
+    *img = (const float*)image;
     if (img_dtype != KEDS_F32) {
         KEDS_REQUIRE(img_dtype == KEDS_BF16 || img_dtype == KEDS_F16, "%s: unknown image dtype", what);
         const long long count = (long long)B * 3 * vit->p.resolution * vit->p.resolution;
@@ -542,11 +540,32 @@ extern "C" int keds_vit_forward(keds_vit* vit, const void* image, int img_dtype,
         pack2d_kernel<float><<<(unsigned)((count + 255) / 256), 256, 0, st>>>(image, img_dtype, 0, 1, 1, (int)count,
                                                                                 (int)count, (float*)vit->img.p);
         if ((rc = keds_check_launch(what))) return rc;
-        img = (const float*)vit->img.p;
+        *img = (const float*)vit->img.p;
     }
     const size_t need = keds_vit_workspace_bytes(&vit->p, B);
-    if ((rc = vit->ws.reserve(need, st, what))) return rc;
+    return vit->ws.reserve(need, st, what);
+}
+
+extern "C" int keds_vit_forward(keds_vit* vit, const void* image, int img_dtype, int B, void* out, void* stream) {
+    const char* what = "keds_vit_forward";
+    KEDS_REQUIRE(vit && image && out && B > 0, "%s: bad argument", what);
+    const float* img;
+    int rc = vit_prepare(vit, image, img_dtype, B, (hipStream_t)stream, what, &img);
+    if (rc) return rc;
     return keds_vit_run(&vit->p, img, B, (float*)out, 0, vit->ws.p, vit->ws.bytes, stream);
+}
+
+extern "C" int keds_vit_forward_tokens(keds_vit* vit, const void* image, int img_dtype, int B, void* out, void* taps, void* tokens,
+                                       int out_type, void* stream) {
+    const char* what = "keds_vit_forward_tokens";
+    KEDS_REQUIRE(B >= 1, "%s: B = %d, at least 1 image", what, B);
+    KEDS_REQUIRE(out || taps || tokens, "%s: no output requested (out, taps and tokens are all null)", what);
+    KEDS_REQUIRE(out_type >= 0 && out_type <= 2, "%s: out_type %d (0 bf16, 1 fp32, 2 fp16)", what, out_type);
+    KEDS_REQUIRE(vit && image, "%s: bad argument", what);
+    const float* img;
+    int rc = vit_prepare(vit, image, img_dtype, B, (hipStream_t)stream, what, &img);
+    if (rc) return rc;
+    return keds_vit_run_tokens(&vit->p, img, B, (float*)out, 0, taps, tokens, out_type, vit->ws.p, vit->ws.bytes, stream);
 }
 
 // ---- text tower -------------------------------------------------------------------------------------
@@ -691,6 +710,18 @@ extern "C" int keds_text_forward_packed(keds_text* txt, const int32_t* tokens, c
     HIP_TRY(hipMemcpyAsync(txt->tok.p, host.data(), (size_t)B * sizeof(int32_t), hipMemcpyHostToDevice, st), what);
     return keds_text_run_ex(&txt->p, tokens, dev, (const float*)img_tokens, n_img_tok, insert_idx, B, seq_used, (float*)out, 0,
                             txt->ws.p, txt->ws.bytes, stream);
+}
+
+extern "C" int keds_text_forward_tokens(keds_text* txt, const int32_t* tokens, int B, void* out, int out_type, void* stream) {
+    const char* what = "keds_text_forward_tokens";
+    KEDS_REQUIRE(B >= 1, "%s: B = %d, at least 1 sequence", what, B);
+    KEDS_REQUIRE(out, "%s: no output requested (out is null)", what);
+    KEDS_REQUIRE(out_type >= 0 && out_type <= 2, "%s: out_type %d (0 bf16, 1 fp32, 2 fp16)", what, out_type);
+    KEDS_REQUIRE(txt && tokens, "%s: bad argument", what);
+    const size_t need = keds_text_workspace_bytes(&txt->p, B);
+    int rc = txt->ws.reserve(need, (hipStream_t)stream, what);
+    if (rc) return rc;
+    return keds_text_run_tokens(&txt->p, tokens, B, out, out_type, txt->ws.p, txt->ws.bytes, stream);
 }
 
 // ---- knowledge injection ------------------------------------------------------------------------------

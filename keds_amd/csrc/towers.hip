@@ -2,6 +2,8 @@
 //   keds_tower_forward : N pre-LN residual blocks        (src/model/model.py:305-326,372-373)
 //   keds_vit_run   : CLIP.encode_image, ViT branch   (src/model/model.py:569-575,393-415)
 //   keds_text_run  : CLIP.encode_text / encode_text_img_retrieval (src/model/model.py:577-590,808-851)
+//   keds_vit_run_tokens / keds_text_run_tokens : encode_image(mid_feature=True), VisualTransformer.get_tokens,
+//                    CLIP.get_text_tokens (model.py:337-342, 393-427, 592-605): per-block taps / all tokens of the same passes
 // Host code only: every launch is asynchronous on the caller's stream, the caller owns the
 // workspace, nothing is allocated or synchronised here.
 #include "keds_common.h"
@@ -23,7 +25,7 @@ void keds_gemm_small_lds(int on);                  // gemm.hip: small GEMM launc
 // f32path.hip: the fp32-accurate flow (keds_tower_params.f32)
 size_t keds_tower_f32_workspace_bytes(int width, int seq, int B);
 int keds_tower_forward_f32(const keds_tower_params* p, float* x, int B, void* ws, hipStream_t st, const int32_t* last_rows = nullptr,
-                           const PackedRows* pk = nullptr);
+                           const PackedRows* pk = nullptr, const KedsTaps* tp = nullptr);
 size_t keds_readout_f32_workspace_bytes(int B, int d);
 int keds_readout_f32(const float* x, int S, const int32_t* row, const float* gamma, const float* beta, const float* proj_t,
                      float* out, int B, int d, int E, int normalize, void* workspace, hipStream_t st);
@@ -267,7 +269,7 @@ constexpr int tower_fill_rows(int, int) { return 0; }      // (the product libra
 // produced by the GEMM epilogues themselves (the attention output by the attention kernel).  Rows beyond the last full
 // 256-row tile (128 of 32,896 at B = 128) keep the bf16 path, on the side lane: every producer has a bf16 twin for them.
 int tower_forward_fp8(const keds_tower_params* p, float* x, int B, const TowerWs& t, int Mm, hipStream_t st,
-                      const int32_t* last_rows) {
+                      const int32_t* last_rows, const KedsTaps* tp) {
     const int w = p->width, S = p->seq;
     const int M = B * S, Mt = M - Mm;
     RowLanes lanes;
@@ -301,7 +303,9 @@ int tower_forward_fp8(const keds_tower_params* p, float* x, int B, const TowerWs
         if ((rc = keds_gemm_mxfp8_ex(t.hq, t.hs, Mm, k.proj_q8, k.proj_s8, w, k.proj_b, t.h, Mm, w, 4 * w,
                                      KEDS_FP8_EPI_RESID_STATS_MX_H, (float*)t.st1, nullptr, t.xq, t.xs, Mm, st)))
             return rc;
+        if ((rc = keds_tap_rows(tp, l, p->layers, t.h, 2, 0, Mm, w, st))) return rc;
         if (Mt && (rc = proj_rows(t, k, w, last, rem, false))) return rc;
+        if (Mt && (rc = keds_tap_rows(tp, l, p->layers, t.h, 2, rem.r0, rem.n, w, rem.st))) return rc;
     }
     if ((rc = lanes.to_main())) return rc;
     return keds_cast_rows_f16_f32_impl(t.h, x, M, w, w, st);       // the caller reads x in fp32
@@ -312,8 +316,9 @@ int tower_forward_fp8(const keds_tower_params* p, float* x, int B, const TowerWs
 // last_rows (device int32 [B], nullable): the one row of every sample that is read after the last block (rows_tail): on
 // return x[b] (row b of the first B rows) holds that row of sample b; without it x holds every row as before
 // pk (nullable): packed rows -- M = pk->rows <= B * seq, the workspace is carved for B * seq
+// tp (nullable): per-block taps (KedsTaps, keds_vit_run_tokens); the caller clears last_cls_only for such a pass
 int tower_forward(const keds_tower_params* p, float* x, int B, void* ws, hipStream_t st, bool allow_fill,
-                  const int32_t* last_rows = nullptr, const PackedRows* pk = nullptr) {
+                  const int32_t* last_rows = nullptr, const PackedRows* pk = nullptr, const KedsTaps* tp = nullptr) {
     const int w = p->width, S = p->seq;
     const int M = pk ? pk->rows : B * S;
     TowerWs t = carve_tower(ws, w, S, B);
@@ -353,7 +358,7 @@ int tower_forward(const keds_tower_params* p, float* x, int B, void* ws, hipStre
         return pk ? attention16_packed(h, t.qkv, t.att, B, S, pk->off, p->heads, p->causal, s_)
                   : attention16(h, t.qkv, t.att, B, S, p->heads, p->causal, S, s_);
     };
-    if (fp8) return tower_forward_fp8(p, x, B, t, Mm, st, last_rows);
+    if (fp8) return tower_forward_fp8(p, x, B, t, Mm, st, last_rows, tp);
     if (folded) {
         // When every GEMM of the block would split into full 256-row tiles + a remainder launch anyway, the remainder
         // rows become their own chain on the side lane; otherwise one span covers all rows.
@@ -416,7 +421,9 @@ int tower_forward(const keds_tower_params* p, float* x, int B, void* ws, hipStre
             if ((rc = fc_rows(t, k, w, body, h))) return rc;
             if (rem.n && (rc = fc_rows(t, k, w, rem, h))) return rc;
             if ((rc = proj_rows(t, k, w, last, body, h))) return rc;
+            if ((rc = keds_tap_rows(tp, l, p->layers, t.h, 2, body.r0, body.n, w, body.st))) return rc;
             if (rem.n && (rc = proj_rows(t, k, w, last, rem, h))) return rc;
+            if (rem.n && (rc = keds_tap_rows(tp, l, p->layers, t.h, 2, rem.r0, rem.n, w, rem.st))) return rc;
         }
         if ((rc = lanes.to_main())) return rc;
         return keds_cast_rows_f16_f32_impl(t.h, x, M, w, w, st);   // the caller reads x in fp32
@@ -434,6 +441,7 @@ int tower_forward(const keds_tower_params* p, float* x, int B, void* ws, hipStre
         if ((rc = keds_layernorm_impl(x, w, nullptr, 1, k.ln2_g, k.ln2_b, t.h, 0, M, w, st))) return rc;
         if ((rc = keds_gemm_bt(t.h, k.fc_w, k.fc_b, t.hid, M, 4 * w, w, KEDS_EPI_BIAS_QGELU_BF16, nullptr, 0, st))) return rc;
         if ((rc = keds_gemm_bt(t.hid, k.proj_w, k.proj_b, x, M, w, 4 * w, KEDS_EPI_BIAS_RESID_F32, nullptr, 0, st))) return rc;
+        if ((rc = keds_tap_rows(tp, l, p->layers, x, 1, 0, M, w, st))) return rc;
     }
     return KEDS_OK;
 }
@@ -532,20 +540,30 @@ extern "C" size_t keds_vit_workspace_bytes(const keds_vit_params* p, int B) {
     return carve_vit(p, B, nullptr).bytes;
 }
 
-extern "C" int keds_vit_run(const keds_vit_params* p, const float* image, int B, float* out, int normalize,
-                                void* workspace, size_t workspace_bytes, void* stream) {
-    KEDS_REQUIRE(p && image && out && workspace && B > 0, "keds_vit_run: bad argument");
-    int rc = check_tower(&p->tower, "keds_vit_run");
+namespace {
+// keds_vit_run and keds_vit_run_tokens.  tp (nullable): per-block taps / last-block tokens -- the last block then runs on every row
+// (a local copy of the tower parameters with last_cls_only cleared) and the CLS read-out comes from the full stream; out nullable
+// (no read-out) only with tp
+int vit_run(const keds_vit_params* p, const float* image, int B, float* out, int normalize, void* workspace, size_t workspace_bytes,
+            void* stream, const KedsTaps* tp, const char* who) {
+    int rc = check_tower(&p->tower, who);
     if (rc) return rc;
     const int w = p->tower.width, S = p->tower.seq, G = S - 1;
     const int g = p->resolution / p->patch;
-    KEDS_REQUIRE(p->resolution % p->patch == 0 && g * g == G, "keds_vit_run: seq must be (res/patch)^2 + 1");
-    KEDS_REQUIRE(p->kpad % 64 == 0 && p->kpad >= 3 * p->patch * p->patch, "keds_vit_run: bad kpad");
-    KEDS_REQUIRE(p->embed_dim % 128 == 0, "keds_vit_run: embed_dim must be a multiple of 128");
+    KEDS_REQUIRE(p->resolution % p->patch == 0 && g * g == G, "%s: seq must be (res/patch)^2 + 1", who);
+    KEDS_REQUIRE(p->kpad % 64 == 0 && p->kpad >= 3 * p->patch * p->patch, "%s: bad kpad", who);
+    KEDS_REQUIRE(p->embed_dim % 128 == 0, "%s: embed_dim must be a multiple of 128", who);
     VitWs v = carve_vit(p, B, workspace);
     if (workspace_bytes < v.bytes) {
-        keds_set_error("keds_vit_run: workspace %zu < %zu", workspace_bytes, v.bytes);
+        keds_set_error("%s: workspace %zu < %zu", who, workspace_bytes, v.bytes);
         return KEDS_E_WORKSPACE;
+    }
+    keds_tower_params full;
+    const keds_tower_params* tw = &p->tower;
+    if (tp) {
+        full = p->tower;
+        full.last_cls_only = 0;
+        tw = &full;
     }
     hipStream_t st = (hipStream_t)stream;
     void* col = v.tower;
@@ -557,7 +575,8 @@ extern "C" int keds_vit_run(const keds_vit_params* p, const float* image, int B,
             return rc;
         if ((rc = keds_cls_rows_impl(v.x, p->class_emb, p->pos_emb, B, S, w, st))) return rc;
         if ((rc = keds_layernorm_impl(v.x, w, nullptr, 1, p->ln_pre_g, p->ln_pre_b, v.x, 1, B * S, w, st))) return rc;
-        if ((rc = keds_tower_forward_f32(&p->tower, v.x, B, v.tower, st))) return rc;
+        if ((rc = keds_tower_forward_f32(tw, v.x, B, v.tower, st, nullptr, nullptr, tp))) return rc;
+        if (!out) return KEDS_OK;
         return keds_readout_f32(v.x, S, nullptr, p->ln_post_g, p->ln_post_b, (const float*)p->proj_t, out, B, w, p->embed_dim,
                                 normalize, v.ro, st);
     }
@@ -569,9 +588,31 @@ extern "C" int keds_vit_run(const keds_vit_params* p, const float* image, int B,
     if ((rc = keds_cls_rows_impl(v.x, p->class_emb, p->pos_emb, B, S, w, st))) return rc;
     // ln_pre in place (each wave holds its whole row in registers before it stores)
     if ((rc = keds_layernorm_impl(v.x, w, nullptr, 1, p->ln_pre_g, p->ln_pre_b, v.x, 1, B * S, w, st))) return rc;
-    if ((rc = tower_forward(&p->tower, v.x, B, v.tower, st, true))) return rc;
+    if ((rc = tower_forward(tw, v.x, B, v.tower, st, true, nullptr, nullptr, tp))) return rc;
+    if (!out) return KEDS_OK;
     return keds_readout_impl(v.x, S, nullptr, p->ln_post_g, p->ln_post_b, p->proj_t, out, B, w, p->embed_dim, normalize, v.ro,
                              keds_readout_workspace_bytes(B, w), stream, h);
+}
+}  // namespace
+
+extern "C" int keds_vit_run(const keds_vit_params* p, const float* image, int B, float* out, int normalize,
+                                void* workspace, size_t workspace_bytes, void* stream) {
+    KEDS_REQUIRE(p && image && out && workspace && B > 0, "keds_vit_run: bad argument");
+    return vit_run(p, image, B, out, normalize, workspace, workspace_bytes, stream, nullptr, "keds_vit_run");
+}
+
+// CLIP.encode_image(mid_feature=True) / VisualTransformer.get_tokens (model.py:393-427): the same pass with the residual stream
+// after every block (taps [layers, B, S, w]) and / or after the last one (tokens [B, S, w]) written out as out_type.  Same
+// workspace as keds_vit_run.
+extern "C" int keds_vit_run_tokens(const keds_vit_params* p, const float* image, int B, float* out, int normalize, void* taps,
+                                   void* tokens, int out_type, void* workspace, size_t workspace_bytes, void* stream) {
+    const char* who = "keds_vit_run_tokens";
+    KEDS_REQUIRE(B >= 1, "%s: B = %d, at least 1 image", who, B);
+    KEDS_REQUIRE(out || taps || tokens, "%s: no output requested (out, taps and tokens are all null)", who);
+    KEDS_REQUIRE(out_type >= 0 && out_type <= 2, "%s: out_type %d (0 bf16, 1 fp32, 2 fp16)", who, out_type);
+    KEDS_REQUIRE(p && image && workspace, "%s: bad argument (null params, image or workspace)", who);
+    const KedsTaps tp{taps, tokens, out_type, (size_t)B * p->tower.seq};
+    return vit_run(p, image, B, out, normalize, workspace, workspace_bytes, stream, taps || tokens ? &tp : nullptr, who);
 }
 
 // ---- text ------------------------------------------------------------------------------------
@@ -717,6 +758,34 @@ extern "C" int keds_text_run_packed(const keds_text_params* p, const int32_t* to
     if ((rc = tower_forward(&tp, v.x, B, v.tower, (hipStream_t)stream, false, readout_global, &pk))) return rc;
     return keds_readout_impl(v.x, 1, nullptr, p->ln_final_g, p->ln_final_b, p->proj_t, out, B, w, p->embed_dim, normalize, v.ro,
                              keds_readout_workspace_bytes(B, w), stream, tp.f16);
+}
+
+// CLIP.get_text_tokens (model.py:592-605): ln_final over the residual stream of ALL L columns of every sample after the last block,
+// out [B, L, w] as out_type -- the rectangular flow whatever keds_text_trim_enable / KEDS_TEXT_TRIM say (no column cut, no
+// read-out-row tail, no packed rows; every column is an output), no projection.  Workspace: keds_text_workspace_bytes.
+extern "C" int keds_text_run_tokens(const keds_text_params* p, const int32_t* tokens, int B, void* out, int out_type, void* workspace,
+                                    size_t workspace_bytes, void* stream) {
+    const char* who = "keds_text_run_tokens";
+    KEDS_REQUIRE(B >= 1, "%s: B = %d, at least 1 sequence", who, B);
+    KEDS_REQUIRE(out, "%s: no output requested (out is null)", who);
+    KEDS_REQUIRE(out_type >= 0 && out_type <= 2, "%s: out_type %d (0 bf16, 1 fp32, 2 fp16)", who, out_type);
+    KEDS_REQUIRE(p && tokens && workspace, "%s: bad argument (null params, tokens or workspace)", who);
+    int rc = check_tower(&p->tower, who);
+    if (rc) return rc;
+    TextWs v = carve_text(p, B, workspace);
+    if (workspace_bytes < v.bytes) {
+        keds_set_error("%s: workspace %zu < %zu", who, workspace_bytes, v.bytes);
+        return KEDS_E_WORKSPACE;
+    }
+    const int w = p->tower.width, L = p->tower.seq;
+    hipStream_t st = (hipStream_t)stream;
+    keds_tower_params tp = p->tower;
+    tp.last_cls_only = 0;
+    if ((rc = keds_embed_tokens_impl(tokens, p->token_emb, p->pos_emb, nullptr, 0, 0, v.x, B, L, L, w, stream))) return rc;
+    if (tp.f32) rc = keds_tower_forward_f32(&tp, v.x, B, v.tower, st);
+    else rc = tower_forward(&tp, v.x, B, v.tower, st, true);
+    if (rc) return rc;
+    return keds_layernorm_impl(v.x, w, nullptr, 1, p->ln_final_g, p->ln_final_b, out, out_type, B * L, w, st);
 }
 
 extern "C" int keds_text_run(const keds_text_params* p, const int32_t* tokens, const int32_t* readout_row,

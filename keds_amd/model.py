@@ -11,14 +11,17 @@ fp16 with LayerNorm folded into the GEMMs (fp32 stream + stand-alone LayerNorm i
 selected automatically by the numerics guard), fp32 LayerNorm / softmax statistics.  There is no PyTorch compute path and no CPU fallback:
 calling a forward without the library or without a GPU raises RuntimeError.
 
-Out of scope: ModifiedResNet towers, `mid_feature`,
-`encode_text_img_vis`, the training-only splice variants and `forward(extra=True)` (undefined
-in the reference itself, App. B).
+Token-level outputs run in the library as well: ``encode_image(mid_feature=True)`` (the residual stream after
+every block), ``VisualTransformer.forward`` / ``get_tokens`` and ``get_text_tokens``.
+
+Out of scope: ModifiedResNet towers, `encode_text_img_vis`, the
+training-only splice variants and `forward(extra=True)` (undefined in the reference itself, App. B).
 """
 from __future__ import annotations
 
 import ctypes as C
 import os
+import weakref
 from collections import OrderedDict
 from typing import Dict, List, Optional, Tuple, Union
 
@@ -83,6 +86,29 @@ class VisualTransformer(nn.Module):
         self.transformer = Transformer(width, layers, heads)
         self.ln_post = LayerNorm(width)
         self.proj = nn.Parameter(scale * torch.randn(width, output_dim))
+
+    # The tower runs through the engine of the CLIP model that owns it: CLIP.__init__ leaves a weak reference here (no
+    # submodule, no state_dict key).
+    def _owner(self) -> "CLIP":
+        ref = self.__dict__.get("_clip_ref")
+        clip = ref() if ref is not None else None
+        if clip is None:
+            raise RuntimeError("keds_amd.VisualTransformer runs through the CLIP model that owns it (model.visual)")
+        return clip
+
+    def __getstate__(self):
+        state = super().__getstate__()
+        state.pop("_clip_ref", None)             # (a weak reference does not pickle; CLIP.__setstate__ sets it again)
+        return state
+
+    def forward(self, x, mid_feature=False):
+        """model.py:393-415: [B, embed_dim], or with mid_feature (features, [residual stream after each block [B, S, width]]
+        x layers) -- CLIP.encode_image."""
+        return self._owner().encode_image(x, mid_feature=mid_feature)
+
+    def get_tokens(self, x):
+        """model.py:418-427: all S tokens after the last block, before ln_post: [B, S, width] in the model's dtype."""
+        return self._owner()._image_pass(x, False, "tokens")
 
 
 def _pack_tower(tr: Transformer, seq: int, causal: bool, keep: list, cls_only: bool = False,
@@ -201,6 +227,7 @@ class _Packed:
         self.device = conv.device
 
 
+_OUT_TYPE = {torch.bfloat16: 0, torch.float32: 1, torch.float16: 2}     # out_type of the token entry points (keds_hip.h)
 TEXT_PACKED = True          # the text tower on packed rows when captions end at different columns (tests switch it off for an A/B)
 GUARD_EAGER_PASSES = 8      # numerics = "auto": tower passes whose guard flag is read back at once (see CLIP.__init__)
 
@@ -219,6 +246,7 @@ class CLIP(nn.Module):
         self.share_projection_layer, self.has_extra = share_projection_layer, False
         self.visual = VisualTransformer(image_resolution, vision_patch_size, vision_width, vision_layers,
                                         vision_width // 64, embed_dim)
+        object.__setattr__(self.visual, "_clip_ref", weakref.ref(self))
         self.transformer_width = transformer_width
         self.transformer = Transformer(transformer_width, transformer_layers, transformer_heads,
                                        attn_mask=self.build_attention_mask())
@@ -271,6 +299,11 @@ class CLIP(nn.Module):
     @property
     def dtype(self):
         return self.visual.conv1.weight.dtype
+
+    def __setstate__(self, state):
+        super().__setstate__(state)
+        if "visual" in self._modules:                # (unpickled / deep-copied: the tower's link to THIS model)
+            object.__setattr__(self.visual, "_clip_ref", weakref.ref(self))
 
     # ---- weight packing -------------------------------------------------------------------------
     def _apply(self, fn, *a, **k):
@@ -414,7 +447,8 @@ class CLIP(nn.Module):
                 out = run(eng)
             finally:
                 check(lib.keds_numerics_guard_set(None), "keds_numerics_guard_set")
-            if int(self._guard.item()) == 0 and bool(torch.isfinite(out).all()):
+            first = out[0] if isinstance(out, tuple) else out       # (token passes: the features, or the tokens)
+            if int(self._guard.item()) == 0 and bool(torch.isfinite(first).all()):
                 return out
             self._guard.zero_()
             self.x3_range_trips = getattr(self, "x3_range_trips", 0) + 1
@@ -448,9 +482,13 @@ class CLIP(nn.Module):
 
     # ---- encoders ------------------------------------------------------------------------------------
     def encode_image(self, image, mid_feature=False, mask_token=False, normalize: bool = False):
-        """model.py:569-575 -> VisualTransformer.forward :393-415.  image [B,3,R,R] -> [B, embed_dim]."""
-        if mid_feature:
-            raise NotImplementedError("mid_feature is a training/ablation path (out of scope)")
+        """model.py:569-575 -> VisualTransformer.forward :393-415.  image [B,3,R,R] -> [B, embed_dim].
+        mid_feature=True (:337-342, 393-410): (features [B, embed_dim], [the residual stream after each block, [B, S, width]]
+        x layers) from ONE pass, all in the model's dtype; the list holds views of one [layers, B, S, width] tensor."""
+        return self._image_pass(image, normalize, "mid" if mid_feature else "features")
+
+    def _image_pass(self, image, normalize, mode):
+        """mode "features": encode_image; "mid": features + per-block taps; "tokens": the last block's tokens only."""
         eng = self._engine()
         if image.dim() != 4 or image.shape[1] != 3 or image.shape[2] != self.visual.input_resolution \
                 or image.shape[3] != self.visual.input_resolution:
@@ -458,25 +496,51 @@ class CLIP(nn.Module):
                                f"got {tuple(image.shape)}")
         img = image.to(eng.device, dtype=torch.float32).contiguous()
         B = img.shape[0]
+        tr = self.visual.transformer
+        S = (self.visual.input_resolution // self.visual.patch_size) ** 2 + 1
+        dt = self.dtype
         if B == 0:                                    # an empty last batch of a loader: the reference returns [0, embed_dim]
-            return torch.empty((0, self.embed_dim), dtype=self.dtype, device=eng.device)
+            feats = torch.empty((0, self.embed_dim), dtype=dt, device=eng.device)
+            if mode == "features":
+                return feats
+            if mode == "tokens":
+                return torch.empty((0, S, tr.width), dtype=dt, device=eng.device)
+            return feats, list(torch.empty((tr.layers, 0, S, tr.width), dtype=dt, device=eng.device).unbind(0))
         if self.precision == "fp32x3":
             # the split-operand GEMMs address their planes with 32-bit byte offsets (keds_gemm_x3): the MLP hidden planes of one call
             # must stay below 2 GiB -- rows * 4 * width * 2 bytes.  Larger batches run in chunks (rows are independent between samples).
             rows_max = (1 << 31) // (8 * self.visual.transformer.width) - 512
             chunk = max(1, rows_max // ((self.visual.input_resolution // self.visual.conv1.kernel_size[0]) ** 2 + 1))
             if B > chunk:
-                return torch.cat([self.encode_image(img[i:i + chunk], normalize=normalize) for i in range(0, B, chunk)])
+                parts = [self._image_pass(img[i:i + chunk], normalize, mode) for i in range(0, B, chunk)]
+                if mode == "mid":
+                    return (torch.cat([p[0] for p in parts]),
+                            [torch.cat([p[1][l] for p in parts]) for l in range(tr.layers)])
+                return torch.cat(parts)
         lib = load()
+        if mode != "features" and dt not in _OUT_TYPE:
+            raise RuntimeError(f"token outputs come as fp32, fp16 or bf16, not {dt}")
 
         def run(eng):
             nbytes = lib.keds_vit_workspace_bytes(C.byref(eng.vit), B)
             ws = self._ws.get(nbytes, eng.device)
-            out = torch.empty((B, self.embed_dim), dtype=torch.float32, device=eng.device)
-            check(lib.keds_vit_run(C.byref(eng.vit), ptr(img), B, ptr(out), 1 if normalize else 0, ptr(ws), ws.numel(),
-                                   stream()), "keds_vit_run")
-            return out
-        return self._guarded(run).to(self.dtype)
+            if mode == "features":
+                out = torch.empty((B, self.embed_dim), dtype=torch.float32, device=eng.device)
+                check(lib.keds_vit_run(C.byref(eng.vit), ptr(img), B, ptr(out), 1 if normalize else 0, ptr(ws), ws.numel(),
+                                       stream()), "keds_vit_run")
+                return out
+            out = torch.empty((B, self.embed_dim), dtype=torch.float32, device=eng.device) if mode == "mid" else None
+            taps = torch.empty((tr.layers, B, S, tr.width), dtype=dt, device=eng.device) if mode == "mid" else None
+            toks = torch.empty((B, S, tr.width), dtype=dt, device=eng.device) if mode == "tokens" else None
+            check(lib.keds_vit_run_tokens(C.byref(eng.vit), ptr(img), B, ptr(out), 1 if normalize else 0, ptr(taps), ptr(toks),
+                                          _OUT_TYPE[dt], ptr(ws), ws.numel(), stream()), "keds_vit_run_tokens")
+            return (out, taps) if mode == "mid" else toks
+        res = self._guarded(run)
+        if mode == "features":
+            return res.to(self.dtype)
+        if mode == "tokens":
+            return res
+        return res[0].to(self.dtype), list(res[1].unbind(0))
 
     def _host_tokens(self, text: torch.Tensor) -> torch.Tensor:
         """The token rows on the HOST for the argument checks the reference's own indexing performs (one EOT per row, ids
@@ -604,7 +668,38 @@ class CLIP(nn.Module):
         return self._run_text(squeezed, eot, img_tokens, ins, normalize)
 
     def get_text_tokens(self, text):
-        raise NotImplementedError("get_text_tokens is not on the retrieval path")
+        """model.py:592-605.  text int [B, L] -> (ln_final(tokens after the last block) [B, L, width] over ALL L columns, in the
+        model's dtype; collect_ind int64 = (text == end_id).nonzero()[:, 1], the column of every EOT token).  No projection."""
+        eng = self._engine()
+        if text.dim() != 2 or text.shape[1] != self.context_length:
+            raise RuntimeError(f"expected tokens [B,{self.context_length}], got {tuple(text.shape)}")
+        th = self._host_tokens(text)
+        collect_ind = (th == self.end_id).nonzero()[:, 1].to(eng.device)
+        B, L, W = text.shape[0], self.context_length, self.transformer_width
+        dt = self.dtype
+        if dt not in _OUT_TYPE:
+            raise RuntimeError(f"token outputs come as fp32, fp16 or bf16, not {dt}")
+        if B == 0:
+            return torch.empty((0, L, W), dtype=dt, device=eng.device), collect_ind
+        return self._text_tokens(text, eng), collect_ind
+
+    def _text_tokens(self, text, eng):
+        B, L, W = text.shape[0], self.context_length, self.transformer_width
+        if self.precision == "fp32x3":                       # (see encode_image: the planes of one call stay below 2 GiB)
+            chunk = max(1, ((1 << 31) // (8 * W) - 512) // L)
+            if B > chunk:
+                return torch.cat([self._text_tokens(text[i:i + chunk], eng) for i in range(0, B, chunk)])
+        lib = load()
+        tok = text.to(eng.device, dtype=torch.int32).contiguous()           # (ids were range-checked on the host: _host_tokens)
+
+        def run(eng):
+            nbytes = lib.keds_text_workspace_bytes(C.byref(eng.text), B)
+            ws = self._ws.get(nbytes, eng.device)
+            out = torch.empty((B, L, W), dtype=self.dtype, device=eng.device)
+            check(lib.keds_text_run_tokens(C.byref(eng.text), ptr(tok), B, ptr(out), _OUT_TYPE[self.dtype], ptr(ws), ws.numel(),
+                                           stream()), "keds_text_run_tokens")
+            return out
+        return self._guarded(run)
 
     def forward(self, image, text, extra=False):
         """model.py:894-911 (extra=True is broken in the reference: undefined encode_text_extra)."""

@@ -107,6 +107,21 @@ class Vit(_Handle):
         check(load().keds_vit_forward(self.h, ptr(image), dt, image.shape[0], ptr(out), stream()), "keds_vit_forward")
         return out
 
+    def forward_tokens(self, image: torch.Tensor, taps: bool = True, tokens: bool = False, features: bool = True,
+                       dtype: torch.dtype = torch.float32):
+        """keds_vit_forward_tokens: (features fp32 [B, embed_dim] or None, taps [layers, B, S, width] or None,
+        tokens [B, S, width] or None) of one pass; taps / tokens in `dtype` (fp32, fp16 or bf16)."""
+        dt = {torch.float32: _lib.DT_F32, torch.bfloat16: _lib.DT_BF16, torch.float16: _lib.DT_F16}[image.dtype]
+        ot = {torch.bfloat16: 0, torch.float32: 1, torch.float16: 2}[dtype]
+        image = image.contiguous()
+        B, S = image.shape[0], (self.resolution // self.patch) ** 2 + 1
+        out = torch.empty((B, self.embed_dim), dtype=torch.float32, device=image.device) if features else None
+        tp = torch.empty((self.layers, B, S, self.width), dtype=dtype, device=image.device) if taps else None
+        tk = torch.empty((B, S, self.width), dtype=dtype, device=image.device) if tokens else None
+        check(load().keds_vit_forward_tokens(self.h, ptr(image), dt, B, ptr(out), ptr(tp), ptr(tk), ot, stream()),
+              "keds_vit_forward_tokens")
+        return out, tp, tk
+
 
 class Text(_Handle):
     """CLIP.encode_text / encode_text_img_retrieval (src/model/model.py:577-590, 808-851)."""
@@ -141,6 +156,14 @@ class Text(_Handle):
                                             int(seq_used), tok.shape[0], ptr(out), stream()), "keds_text_forward")
         return out
 
+
+    def forward_tokens(self, tokens: torch.Tensor, dtype: torch.dtype = torch.float32) -> torch.Tensor:
+        """keds_text_forward_tokens: ln_final of every column after the last block, [B, context, width] in `dtype`."""
+        tok = tokens.to(torch.int32).contiguous()
+        ot = {torch.bfloat16: 0, torch.float32: 1, torch.float16: 2}[dtype]
+        out = torch.empty((tok.shape[0], self.context, self.width), dtype=dtype, device=tok.device)
+        check(load().keds_text_forward_tokens(self.h, ptr(tok), tok.shape[0], ptr(out), ot, stream()), "keds_text_forward_tokens")
+        return out
 
 class Knowledge(_Handle):
     """img2text + retrieval_fuse + text_condition of one stream (src/eval_utils.py:661-672)."""
