@@ -30,7 +30,8 @@ extern "C" {
 #define KEDS_E_LAUNCH (-2)   /* HIP launch or runtime error */
 #define KEDS_E_WORKSPACE (-3)/* workspace too small */
 
-#define KEDS_ABI_VERSION 9        /* 9: the "fp16" operating point -- keds_tower_params.f16, KEDS_EPI_*_F16_H / *_F32_H epilogues, keds_attention_h /
+#define KEDS_ABI_VERSION 10       /* 10: keds_block_source, keds_block_pack_bytes, keds_block_pack (one weight-packing routine for both loaders);
+                                     9: the "fp16" operating point -- keds_tower_params.f16, KEDS_EPI_*_F16_H / *_F32_H epilogues, keds_attention_h /
                                      keds_attention_packed_h, keds_im2col_ex, keds_layernorm_ex, keds_cast_f16;
                                      8 (round 6): keds_gemm_x3 takes w_exp, keds_split_f16_weight, keds_block_params.x3_exp, keds_text_run_packed / keds_attention_packed; keds_gemm_duo_enable left the product */
 
@@ -386,6 +387,34 @@ typedef struct {
     /* keds_tower_params.f32 == 2 only: the exponents keds_split_f16_weight returned for qkv_w, out_w, fc_w, proj_w */
     int x3_exp[4];
 } keds_block_params;
+
+/* the twelve tensors of one ResidualAttentionBlock: fp32, device, dense, as stored in the checkpoint */
+typedef struct {
+    const float *ln1_g, *ln1_b, *ln2_g, *ln2_b;
+    const float *qkv_w, *qkv_b, *out_w, *out_b, *fc_w, *fc_b, *proj_w, *proj_b;
+} keds_block_source;
+
+/* Weight preparation of one block, the same for every loader (ABI 10): builds every array keds_block_params points to from
+ * `src` into the caller-owned device buffer `buf` (256-byte aligned, keds_block_pack_bytes bytes) and fills `out` completely --
+ * fields the mode does not use are null, x3_exp is zero unless f32 == 2.  All arrays are copies (out never aliases src) and
+ * start on 256-byte boundaries.  fp8 / f32 / f16 as in keds_tower_params; folded: LayerNorm folded into in_proj / c_fc (ignored
+ * when f32 != 0).  With d = width and the GEMMs (N, K) = qkv (3d, d), out (d, d), fc (4d, d), proj (d, 4d), the buffer holds, in
+ * this order, each rounded up to 256 bytes:
+ *   ln1_g, ln1_b, ln2_g, ln2_b    4 d bytes each (fp32)
+ *   qkv_b, out_b, fc_b, proj_b    4 N (fp32)
+ *   qkv_w, out_w, fc_w, proj_w    2 N K (bf16; fp16 as keds_cast_f16 rounds when f16), 4 N K when f32 == 1 (fp32 as stored) or
+ *                                 f32 == 2 (two fp16 planes of keds_split_f16_weight, exponents in x3_exp)
+ *   folded and f32 == 0:          qkv_wf, fc_wf 2 N K (fp16), then qkv_bc, fc_bc 8 N (keds_fold_layernorm_ex, out_f16 = 1)
+ *   fp8:                          the four *_q8 N K, the four *_s8 keds_mxfp8_scale_bytes(N, K), qkv_bc8, fc_bc8 8 N
+ *                                 (keds_fold_layernorm_mxfp8), and 8 d bytes of scratch for the {bias, column sums} of out-proj /
+ *                                 c_proj, which no kernel reads
+ * Rules (KEDS_E_ARG from keds_block_pack, 0 from keds_block_pack_bytes, with a message): width % 128 == 0; fp8 needs folded and
+ * width % 256 == 0; f16 needs folded and excludes fp8 and f32; fp8 excludes f32.
+ * Asynchronous on `stream`, except that f32 == 2 waits for it (keds_split_f16_weight); `src` stays alive until the caller has
+ * synchronised. */
+size_t keds_block_pack_bytes(int width, int fp8, int f32, int f16, int folded);
+int keds_block_pack(const keds_block_source* src, int width, int fp8, int f32, int f16, int folded,
+                    void* buf, size_t buf_bytes, keds_block_params* out, void* stream);
 
 typedef struct {
     int width, layers, heads, seq;                  /* seq = tokens per sample (257 / 77) */

@@ -17,7 +17,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "csrc", "libkeds_hip.so")
 
 # ---- constants mirrored from keds_hip.h ------------------------------------------------------
-ABI_VERSION = 9
+ABI_VERSION = 10
 METRIC_L2, METRIC_IP = 0, 1
 EPI_BIAS_BF16, EPI_BIAS_QGELU_BF16, EPI_BIAS_RELU_BF16, EPI_BIAS_RESID_F32, EPI_BIAS_F32, EPI_PATCH_F32 = range(6)
 EPI_LN_BIAS_BF16, EPI_LN_QGELU_BF16, EPI_RESID_STATS_F32, EPI_RESID_STATS_F16 = 6, 7, 8, 9
@@ -40,6 +40,12 @@ class BlockParams(C.Structure):
                                   "qkv_b", "out_b", "fc_b", "proj_b", "qkv_wf", "fc_wf", "qkv_bc", "fc_bc",
                                   "qkv_q8", "out_q8", "fc_q8", "proj_q8", "qkv_s8", "out_s8", "fc_s8", "proj_s8",
                                   "qkv_bc8", "fc_bc8")] + [("x3_exp", i32 * 4)]      # (f32 == 2: exponents of the split weights)
+
+
+class BlockSource(C.Structure):
+    """keds_block_source: the twelve fp32 device tensors of one block as stored (input of keds_block_pack)."""
+    _fields_ = [(n, vp) for n in ("ln1_g", "ln1_b", "ln2_g", "ln2_b", "qkv_w", "qkv_b", "out_w", "out_b", "fc_w", "fc_b",
+                                  "proj_w", "proj_b")]
 
 
 class TowerParams(C.Structure):
@@ -235,6 +241,9 @@ SIGNATURES = {
     "keds_im2col_ex": (i32, [vp, vp, i32, i32, i32, i32, i32, vp]),
     "keds_layernorm_ex": (i32, [vp, i64, vp, vp, vp, i32, i32, i32, vp]),
     "keds_cast_f16": (i32, [vp, vp, i64, vp]),
+    # one weight-packing routine for both loaders (ABI 10)
+    "keds_block_pack_bytes": (sz, [i32, i32, i32, i32, i32]),
+    "keds_block_pack": (i32, [C.POINTER(BlockSource), i32, i32, i32, i32, i32, vp, sz, C.POINTER(BlockParams), vp]),
     "keds_im2text_workspace_bytes": (sz, [C.POINTER(Im2TextParams), i32]),
     "keds_im2text_forward": (i32, [C.POINTER(Im2TextParams), vp, i32, vp, vp, sz, vp]),
     "keds_crossformer_workspace_bytes": (sz, [C.POINTER(CrossFormerParams), i32, i32]),

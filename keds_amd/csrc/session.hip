@@ -135,6 +135,11 @@ int pack_tensor(Arena& mem, const keds_tensor* t, int rows, int cols, long long 
     return KEDS_OK;
 }
 
+// operating point of a tower: the fp8 / f32 / f16 fields of keds_tower_params
+struct Mode {
+    int fp8, f32, f16;
+};
+
 struct Loader {
     const Weights& w;
     Arena& mem;
@@ -174,121 +179,66 @@ struct Loader {
         *out = d;
         return KEDS_OK;
     }
+    // t viewed as [rows, cols] (transpose: stored as [cols, rows]) -> dense [rows, dcols], zero padded, in the GEMM operand
+    // type of the operating point: fp32, fp16 or bf16.  The caller has checked the shape.
+    int operand(const keds_tensor* t, const Mode& m, int rows, int cols, bool transpose, int dcols, const void** out) const {
+        const long long rs = transpose ? 1 : cols, cs = transpose ? rows : 1;
+        return m.f32   ? typed<float>(t, rows, cols, rs, cs, dcols, out)
+               : m.f16 ? typed<f16_t>(t, rows, cols, rs, cs, dcols, out)
+                       : typed<bf16_t>(t, rows, cols, rs, cs, dcols, out);
+    }
+    template <typename DST>
+    int typed(const keds_tensor* t, int rows, int cols, long long rs, long long cs, int dcols, const void** out) const {
+        DST* d;
+        const int rc = pack_tensor<DST>(mem, t, rows, cols, rs, cs, dcols, &d, what);
+        if (!rc) *out = d;
+        return rc;
+    }
 };
 
-// resblocks of one tower (model.py:305-326): keys <prefix>transformer.resblocks.<i>.*
-// f32: 0 = bf16 / fp8 flows, 1 = KEDS_F32 (weights as stored), 2 = KEDS_F32X3 (the four weights as fp16 planes [2][N][K])
-// f16: KEDS_F16 compute (the fp16 operating point): the four weights as fp16 (plus the fp16 folded in_proj / c_fc as always)
+int decode_compute(int compute, const char* what, Mode* m) {
+    KEDS_REQUIRE(compute == KEDS_BF16 || compute == KEDS_F16 || compute == KEDS_FP8 || compute == KEDS_F32 || compute == KEDS_F32X3,
+                 "%s: compute dtype must be KEDS_BF16, KEDS_F16, KEDS_FP8, KEDS_F32 or KEDS_F32X3", what);
+    *m = Mode{compute == KEDS_FP8, compute == KEDS_F32 ? 1 : compute == KEDS_F32X3 ? 2 : 0, compute == KEDS_F16};
+    return KEDS_OK;
+}
+
+// KEDS_DETERMINISTIC=1 keeps the separate LayerNorm kernels (A/B reference; the folded path is reproducible too)
+int folded_flow(const Mode& m, const char* what, bool* folded) {
+    const char* det = getenv("KEDS_DETERMINISTIC");
+    *folded = !(det && det[0] == '1');
+    KEDS_REQUIRE(!m.f16 || *folded, "%s: KEDS_F16 needs the folded LayerNorm path (KEDS_DETERMINISTIC=1 is set)", what);
+    return KEDS_OK;
+}
+
+// resblocks of one tower (model.py:305-326): keys <prefix>transformer.resblocks.<i>.*, packed by keds_block_pack (keds_hip.h) --
+// the routine the torch facade calls too -- from fp32 copies of a block's twelve tensors that live until the block is packed
 int load_blocks(const Loader& L, const std::string& prefix, int width, int layers, std::vector<keds_block_params>& blocks,
-                bool fp8, int f32 = 0, bool f16 = false) {
+                const Mode& m, bool folded) {
+    const size_t bytes = keds_block_pack_bytes(width, m.fp8, m.f32, m.f16, folded);
+    if (!bytes) return KEDS_E_ARG;                              // (the message is keds_block_pack_bytes' own)
     blocks.assign(layers, keds_block_params{});
     for (int i = 0; i < layers; ++i) {
         const std::string b = prefix + "transformer.resblocks." + std::to_string(i) + ".";
-        keds_block_params& p = blocks[i];
-        int rc;
-        const bf16_t* m;
-        if ((rc = L.vec(b + "ln_1.weight", width, &p.ln1_g)) || (rc = L.vec(b + "ln_1.bias", width, &p.ln1_b)) ||
-            (rc = L.vec(b + "ln_2.weight", width, &p.ln2_g)) || (rc = L.vec(b + "ln_2.bias", width, &p.ln2_b)) ||
-            (rc = L.vec(b + "attn.in_proj_bias", 3 * width, &p.qkv_b)) ||
-            (rc = L.vec(b + "attn.out_proj.bias", width, &p.out_b)) ||
-            (rc = L.vec(b + "mlp.c_fc.bias", 4 * width, &p.fc_b)) || (rc = L.vec(b + "mlp.c_proj.bias", width, &p.proj_b)))
-            return rc;
-        if (f32 == 2) {      // fp32x3: every weight as its fp16 planes; the fp32 copies are temporary (round 5 kept them: 1.2 GB for ViT-L/14)
-            const char* names[4] = {"attn.in_proj_weight", "attn.out_proj.weight", "mlp.c_fc.weight", "mlp.c_proj.weight"};
-            const void** slots[4] = {&p.qkv_w, &p.out_w, &p.fc_w, &p.proj_w};
-            const int n[4] = {3 * width, width, 4 * width, width}, k[4] = {width, width, width, 4 * width};
-            for (int j = 0; j < 4; ++j) {
-                Arena tmp;
-                Loader T{L.w, tmp, L.what};
-                const float* f;
-                if ((rc = T.mat<float>(b + names[j], n[j], k[j], &f))) return rc;
-                void* planes = L.mem.alloc((size_t)2 * n[j] * k[j] * 2);
-                KEDS_REQUIRE(planes, "%s: out of device memory", L.what);
-                if ((rc = keds_split_f16_weight(f, n[j], k[j], planes, (int64_t)n[j] * k[j], &p.x3_exp[j], nullptr))) return rc;
-                *slots[j] = planes;
-                HIP_TRY(hipDeviceSynchronize(), L.what);            // (the split has read `f` before tmp frees it)
-            }
-            continue;
-        }
-        if (f32) {   // KEDS_F32 compute (the fp32-accurate flow, f32path.hip): the four weights stay fp32, nothing is folded
-            const float* f;
-            if ((rc = L.mat<float>(b + "attn.in_proj_weight", 3 * width, width, &f))) return rc;
-            p.qkv_w = f;
-            if ((rc = L.mat<float>(b + "attn.out_proj.weight", width, width, &f))) return rc;
-            p.out_w = f;
-            if ((rc = L.mat<float>(b + "mlp.c_fc.weight", 4 * width, width, &f))) return rc;
-            p.fc_w = f;
-            if ((rc = L.mat<float>(b + "mlp.c_proj.weight", width, 4 * width, &f))) return rc;
-            p.proj_w = f;
-            continue;
-        }
-        if (f16) {   // KEDS_F16: fp16 weights, rounded as stored (convert_weights, model.py:927-948)
-            const f16_t* h;
-            if ((rc = L.mat<f16_t>(b + "attn.in_proj_weight", 3 * width, width, &h))) return rc;
-            p.qkv_w = h;
-            if ((rc = L.mat<f16_t>(b + "attn.out_proj.weight", width, width, &h))) return rc;
-            p.out_w = h;
-            if ((rc = L.mat<f16_t>(b + "mlp.c_fc.weight", 4 * width, width, &h))) return rc;
-            p.fc_w = h;
-            if ((rc = L.mat<f16_t>(b + "mlp.c_proj.weight", width, 4 * width, &h))) return rc;
-            p.proj_w = h;
-        } else {
-            if ((rc = L.mat<bf16_t>(b + "attn.in_proj_weight", 3 * width, width, &m))) return rc;
-            p.qkv_w = m;
-            if ((rc = L.mat<bf16_t>(b + "attn.out_proj.weight", width, width, &m))) return rc;
-            p.out_w = m;
-            if ((rc = L.mat<bf16_t>(b + "mlp.c_fc.weight", 4 * width, width, &m))) return rc;
-            p.fc_w = m;
-            if ((rc = L.mat<bf16_t>(b + "mlp.c_proj.weight", width, 4 * width, &m))) return rc;
-            p.proj_w = m;
-        }
-        // ln_1 folded into in_proj, ln_2 into c_fc (keds_fold_layernorm): fp32 copies of the two weights are temporary.
-        // KEDS_DETERMINISTIC=1 keeps the separate LayerNorm kernels (A/B reference; the folded path is reproducible too).
-        const char* det = getenv("KEDS_DETERMINISTIC");
-        KEDS_REQUIRE(!(f16 && det && det[0] == '1'), "%s: KEDS_F16 needs the folded LayerNorm path (KEDS_DETERMINISTIC=1 is set)", L.what);
-        if (det && det[0] == '1') continue;
         Arena tmp;
         Loader T{L.w, tmp, L.what};
-        const float *wq, *wf;
-        if ((rc = T.mat<float>(b + "attn.in_proj_weight", 3 * width, width, &wq)) ||
-            (rc = T.mat<float>(b + "mlp.c_fc.weight", 4 * width, width, &wf)))
+        keds_block_source s;
+        int rc;
+        if ((rc = T.vec(b + "ln_1.weight", width, &s.ln1_g)) || (rc = T.vec(b + "ln_1.bias", width, &s.ln1_b)) ||
+            (rc = T.vec(b + "ln_2.weight", width, &s.ln2_g)) || (rc = T.vec(b + "ln_2.bias", width, &s.ln2_b)) ||
+            (rc = T.mat<float>(b + "attn.in_proj_weight", 3 * width, width, &s.qkv_w)) ||
+            (rc = T.vec(b + "attn.in_proj_bias", 3 * width, &s.qkv_b)) ||
+            (rc = T.mat<float>(b + "attn.out_proj.weight", width, width, &s.out_w)) ||
+            (rc = T.vec(b + "attn.out_proj.bias", width, &s.out_b)) ||
+            (rc = T.mat<float>(b + "mlp.c_fc.weight", 4 * width, width, &s.fc_w)) ||
+            (rc = T.vec(b + "mlp.c_fc.bias", 4 * width, &s.fc_b)) ||
+            (rc = T.mat<float>(b + "mlp.c_proj.weight", width, 4 * width, &s.proj_w)) ||
+            (rc = T.vec(b + "mlp.c_proj.bias", width, &s.proj_b)))
             return rc;
-        void* qf = L.mem.alloc((size_t)3 * width * width * 2);
-        void* ff = L.mem.alloc((size_t)4 * width * width * 2);
-        float* qb = (float*)L.mem.alloc((size_t)2 * 3 * width * sizeof(float));
-        float* fb = (float*)L.mem.alloc((size_t)2 * 4 * width * sizeof(float));
-        KEDS_REQUIRE(qf && ff && qb && fb, "%s: out of device memory", L.what);
-        if ((rc = keds_fold_layernorm_ex(wq, p.qkv_b, p.ln1_g, p.ln1_b, 3 * width, width, qf, 1, qb, nullptr)) ||
-            (rc = keds_fold_layernorm_ex(wf, p.fc_b, p.ln2_g, p.ln2_b, 4 * width, width, ff, 1, fb, nullptr)))
-            return rc;
-        HIP_TRY(hipDeviceSynchronize(), L.what);
-        p.qkv_wf = qf;
-        p.fc_wf = ff;
-        p.qkv_bc = qb;
-        p.fc_bc = fb;
-        if (fp8) {   // MXFP8 copies of the four weights (keds_fold_layernorm_mxfp8; KEDS_FP8 compute, BASELINE config 5)
-            const float *wo, *wp;
-            if ((rc = T.mat<float>(b + "attn.out_proj.weight", width, width, &wo)) ||
-                (rc = T.mat<float>(b + "mlp.c_proj.weight", width, 4 * width, &wp)))
-                return rc;
-            struct Item { const float* w; const float* bias; const float* g; const float* be; int n, k; const void** q; const void** s; const float** bc; };
-            const float* scratch_bc = nullptr;
-            Item items[4] = {{wq, p.qkv_b, p.ln1_g, p.ln1_b, 3 * width, width, &p.qkv_q8, &p.qkv_s8, &p.qkv_bc8},
-                             {wo, p.out_b, nullptr, nullptr, width, width, &p.out_q8, &p.out_s8, &scratch_bc},
-                             {wf, p.fc_b, p.ln2_g, p.ln2_b, 4 * width, width, &p.fc_q8, &p.fc_s8, &p.fc_bc8},
-                             {wp, p.proj_b, nullptr, nullptr, width, 4 * width, &p.proj_q8, &p.proj_s8, &scratch_bc}};
-            for (const Item& it : items) {
-                void* q = L.mem.alloc((size_t)it.n * it.k);
-                void* sc = L.mem.alloc(keds_mxfp8_scale_bytes(it.n, it.k));
-                float* bc = (float*)L.mem.alloc((size_t)2 * it.n * sizeof(float));
-                KEDS_REQUIRE(q && sc && bc, "%s: out of device memory", L.what);
-                if ((rc = keds_fold_layernorm_mxfp8(it.w, it.bias, it.g, it.be, it.n, it.k, it.n, q, sc, bc, nullptr))) return rc;
-                *it.q = q;
-                *it.s = sc;
-                *it.bc = bc;
-            }
-            HIP_TRY(hipDeviceSynchronize(), L.what);
-        }
+        void* buf = L.mem.alloc(bytes);
+        KEDS_REQUIRE(buf, "%s: out of device memory", L.what);
+        if ((rc = keds_block_pack(&s, width, m.fp8, m.f32, m.f16, folded, buf, bytes, &blocks[i], nullptr))) return rc;
+        HIP_TRY(hipDeviceSynchronize(), L.what);               // (the pack has read the sources before tmp frees them)
     }
     return KEDS_OK;
 }
@@ -428,10 +378,10 @@ extern "C" int keds_ctx_destroy(keds_ctx* ctx) {
 extern "C" int keds_vit_create(keds_ctx* ctx, const keds_tensor* weights, int n, int compute, keds_vit** out) {
     const char* what = "keds_vit_create";
     KEDS_REQUIRE(weights && n > 0 && out, "%s: bad argument", what);
-    KEDS_REQUIRE(compute == KEDS_BF16 || compute == KEDS_F16 || compute == KEDS_FP8 || compute == KEDS_F32 || compute == KEDS_F32X3,
-                 "%s: compute dtype must be KEDS_BF16, KEDS_F16, KEDS_FP8, KEDS_F32 or KEDS_F32X3", what);
-    int rc = use_device(ctx, what);
-    if (rc) return rc;
+    Mode m;
+    bool folded;
+    int rc;
+    if ((rc = decode_compute(compute, what, &m)) || (rc = folded_flow(m, what, &folded)) || (rc = use_device(ctx, what))) return rc;
     Weights W(weights, n);
     const keds_tensor *conv, *pos, *proj;
     keds_vit* v = new keds_vit();
@@ -456,14 +406,7 @@ extern "C" int keds_vit_create(keds_ctx* ctx, const keds_tensor* weights, int n,
                        layers);
         return fail(KEDS_E_ARG);
     }
-    const bool fp8 = compute == KEDS_FP8;
-    if (fp8 && width % 256 != 0) {
-        keds_set_error("%s: KEDS_FP8 needs a width that is a multiple of 256", what);
-        return fail(KEDS_E_ARG);
-    }
-    const int f32 = compute == KEDS_F32 ? 1 : compute == KEDS_F32X3 ? 2 : 0;
-    const bool f16 = compute == KEDS_F16;
-    if ((rc = load_blocks(L, "visual.", width, layers, v->blocks, fp8, f32, f16))) return fail(rc);
+    if ((rc = load_blocks(L, "visual.", width, layers, v->blocks, m, folded))) return fail(rc);
     keds_vit_params& p = v->p;
     memset(&p, 0, sizeof(p));
     p.tower.width = width;
@@ -473,40 +416,23 @@ extern "C" int keds_vit_create(keds_ctx* ctx, const keds_tensor* weights, int n,
     p.tower.causal = 0;
     p.tower.blocks = v->blocks.data();
     p.tower.last_cls_only = 1;
-    p.tower.fp8 = fp8 ? 1 : 0;
-    p.tower.f32 = f32;
-    p.tower.f16 = f16 ? 1 : 0;
+    p.tower.fp8 = m.fp8;
+    p.tower.f32 = m.f32;
+    p.tower.f16 = m.f16;
     p.resolution = grid * patch;
     p.patch = patch;
     const int kreal = 3 * patch * patch;
     p.kpad = (kreal + 63) / 64 * 64;
     p.embed_dim = embed;
-    if (f32) {
-        float* conv_w;
-        if ((rc = pack_tensor<float>(v->mem, conv, width, kreal, kreal, 1, p.kpad, &conv_w, what))) return fail(rc);
-        p.conv_w = conv_w;
-    } else if (f16) {
-        f16_t* conv_w;
-        if ((rc = pack_tensor<f16_t>(v->mem, conv, width, kreal, kreal, 1, p.kpad, &conv_w, what))) return fail(rc);
-        p.conv_w = conv_w;
-    } else {
-        bf16_t* conv_w;   // [width, 3*P*P] zero padded to kpad columns (im2col order == the conv weight's own order)
-        if ((rc = pack_tensor<bf16_t>(v->mem, conv, width, kreal, kreal, 1, p.kpad, &conv_w, what))) return fail(rc);
-        p.conv_w = conv_w;
-    }
-    const bf16_t* proj_t = nullptr;
-    const f16_t* proj_t16 = nullptr;
-    const float* proj_t32 = nullptr;
+    // [width, 3*P*P] zero padded to kpad columns (im2col order == the conv weight's own order)
+    if ((rc = L.operand(conv, m, width, kreal, false, p.kpad, &p.conv_w))) return fail(rc);
     if ((rc = L.vec("visual.class_embedding", width, &p.class_emb)) ||
         (rc = L.mat<float>("visual.positional_embedding", p.tower.seq, width, &p.pos_emb)) ||
         (rc = L.vec("visual.ln_pre.weight", width, &p.ln_pre_g)) || (rc = L.vec("visual.ln_pre.bias", width, &p.ln_pre_b)) ||
         (rc = L.vec("visual.ln_post.weight", width, &p.ln_post_g)) ||
         (rc = L.vec("visual.ln_post.bias", width, &p.ln_post_b)) ||
-        (rc = f32   ? L.mat<float>("visual.proj", embed, width, &proj_t32, /*transpose=*/true)
-              : f16 ? L.mat<f16_t>("visual.proj", embed, width, &proj_t16, /*transpose=*/true)
-                    : L.mat<bf16_t>("visual.proj", embed, width, &proj_t, /*transpose=*/true)))
+        (rc = L.operand(proj, m, embed, width, /*transpose=*/true, width, &p.proj_t)))
         return fail(rc);
-    p.proj_t = f32 ? (const void*)proj_t32 : f16 ? (const void*)proj_t16 : (const void*)proj_t;
     *out = v;
     return KEDS_OK;
 }
@@ -572,10 +498,10 @@ extern "C" int keds_vit_forward_tokens(keds_vit* vit, const void* image, int img
 extern "C" int keds_text_create(keds_ctx* ctx, const keds_tensor* weights, int n, int compute, keds_text** out) {
     const char* what = "keds_text_create";
     KEDS_REQUIRE(weights && n > 0 && out, "%s: bad argument", what);
-    KEDS_REQUIRE(compute == KEDS_BF16 || compute == KEDS_F16 || compute == KEDS_FP8 || compute == KEDS_F32 || compute == KEDS_F32X3,
-                 "%s: compute dtype must be KEDS_BF16, KEDS_F16, KEDS_FP8, KEDS_F32 or KEDS_F32X3", what);
-    int rc = use_device(ctx, what);
-    if (rc) return rc;
+    Mode m;
+    bool folded;
+    int rc;
+    if ((rc = decode_compute(compute, what, &m)) || (rc = folded_flow(m, what, &folded)) || (rc = use_device(ctx, what))) return rc;
     Weights W(weights, n);
     keds_text* t = new keds_text();
     t->ctx = ctx;
@@ -598,10 +524,8 @@ extern "C" int keds_text_create(keds_ctx* ctx, const keds_tensor* weights, int n
         keds_set_error("%s: inconsistent text tower shapes (width %d, context %d, layers %d)", what, width, context, layers);
         return fail(KEDS_E_ARG);
     }
-    const bool fp8 = compute == KEDS_FP8 && width % 256 == 0;
-    const int f32 = compute == KEDS_F32 ? 1 : compute == KEDS_F32X3 ? 2 : 0;
-    const bool f16 = compute == KEDS_F16;
-    if ((rc = load_blocks(L, "", width, layers, t->blocks, fp8, f32, f16))) return fail(rc);
+    m.fp8 = m.fp8 && width % 256 == 0;      // (a text tower of another width stays bf16 next to an fp8 image tower)
+    if ((rc = load_blocks(L, "", width, layers, t->blocks, m, folded))) return fail(rc);
     keds_text_params& p = t->p;
     memset(&p, 0, sizeof(p));
     p.tower.width = width;
@@ -611,22 +535,16 @@ extern "C" int keds_text_create(keds_ctx* ctx, const keds_tensor* weights, int n
     p.tower.causal = 1;
     p.tower.blocks = t->blocks.data();
     p.tower.last_cls_only = 0;
-    p.tower.fp8 = fp8 ? 1 : 0;
-    p.tower.f32 = f32;
-    p.tower.f16 = f16 ? 1 : 0;
+    p.tower.fp8 = m.fp8;
+    p.tower.f32 = m.f32;
+    p.tower.f16 = m.f16;
     p.vocab = vocab;
     p.embed_dim = embed;
-    const bf16_t* proj_t = nullptr;
-    const f16_t* proj_t16 = nullptr;
-    const float* proj_t32 = nullptr;
     if ((rc = L.mat<float>("token_embedding.weight", vocab, width, &p.token_emb)) ||
         (rc = L.mat<float>("positional_embedding", context, width, &p.pos_emb)) ||
         (rc = L.vec("ln_final.weight", width, &p.ln_final_g)) || (rc = L.vec("ln_final.bias", width, &p.ln_final_b)) ||
-        (rc = f32   ? L.mat<float>("text_projection", embed, width, &proj_t32, /*transpose=*/true)
-              : f16 ? L.mat<f16_t>("text_projection", embed, width, &proj_t16, /*transpose=*/true)
-                    : L.mat<bf16_t>("text_projection", embed, width, &proj_t, /*transpose=*/true)))
+        (rc = L.operand(proj, m, embed, width, /*transpose=*/true, width, &p.proj_t)))
         return fail(rc);
-    p.proj_t = f32 ? (const void*)proj_t32 : f16 ? (const void*)proj_t16 : (const void*)proj_t;
     *out = t;
     return KEDS_OK;
 }

@@ -113,72 +113,26 @@ class VisualTransformer(nn.Module):
 
 def _pack_tower(tr: Transformer, seq: int, causal: bool, keep: list, cls_only: bool = False,
                 fp8: bool = False, folded: bool = True, f32: bool = False, f16: bool = False) -> _lib.TowerParams:
+    """Every block's weights in the layout and operand types of the operating point, built by the library's
+    keds_block_pack (include/keds_hip.h) -- the routine the handle ABI's loader calls too -- into one device buffer per block."""
+    lib = load()
     blocks = (_lib.BlockParams * tr.layers)()
-    # f32 = 1: the fp32-accurate flow (csrc/f32path.hip) multiplies the weights as stored; f32 = 2 ("fp32x3"): the four block
-    # weights as PAIRS of fp16 planes [2, N, K] of w 2^e (hi + lo to 22 bits; keds_split_f16_weight picks the exact per-matrix
-    # power of two that keeps the low plane of small weights out of the fp16 subnormals) for the split-operand GEMMs
-    x3_exps = []
-
-    def _planes(w):
-        w32 = _f32(w)
-        n, k = w32.shape
-        out = torch.empty((2, n, k), dtype=torch.float16, device=w32.device)
-        e = C.c_int32(0)
-        check(load().keds_split_f16_weight(ptr(w32), n, k, ptr(out), n * k, C.byref(e), stream()), "keds_split_f16_weight")
-        x3_exps.append(int(e.value))
-        return out
-    # f16 ("fp16"): the four weights rounded to fp16 as stored (convert_weights' own rounding); needs the folded flow
-    wcast = _planes if f32 == 2 else _f32 if f32 else _f16 if f16 else _bf16
-    folded = folded and not f32
-    if f16 and not folded:
-        raise ValueError("fp16 needs the folded LayerNorm path")
+    mode = (tr.width, 1 if fp8 else 0, int(f32), 1 if f16 else 0, 1 if folded else 0)
+    nbytes = lib.keds_block_pack_bytes(*mode)
+    if not nbytes:
+        raise ValueError(_lib.last_error())
     for i, blk in enumerate(tr.resblocks):
-        del x3_exps[:]                                          # (filled in the order qkv, out, fc, proj below)
-        t = dict(
+        src = dict(
             ln1_g=_f32(blk.ln_1.weight), ln1_b=_f32(blk.ln_1.bias), ln2_g=_f32(blk.ln_2.weight), ln2_b=_f32(blk.ln_2.bias),
-            qkv_w=wcast(blk.attn.in_proj_weight), out_w=wcast(blk.attn.out_proj.weight),
-            fc_w=wcast(blk.mlp.c_fc.weight), proj_w=wcast(blk.mlp.c_proj.weight),
-            qkv_b=_f32(blk.attn.in_proj_bias), out_b=_f32(blk.attn.out_proj.bias),
-            fc_b=_f32(blk.mlp.c_fc.bias), proj_b=_f32(blk.mlp.c_proj.bias))
-        # ln_1 folded into in_proj, ln_2 into c_fc (keds_fold_layernorm): the tower then runs without LayerNorm passes.
-        # The row statistics cross workgroups as 64-bit fixed-point integer atomics (order independent: reproducible bits);
-        # KEDS_DETERMINISTIC=1 keeps the separate LayerNorm kernels as an A/B reference.
-        lib = load()
-        folds = (("qkv", blk.attn.in_proj_weight, t["qkv_b"], ("ln1_g", "ln1_b")),
-                 ("fc", blk.mlp.c_fc.weight, t["fc_b"], ("ln2_g", "ln2_b")))
-        if not folded:
-            folds = ()
-        for name, lin_w, lin_b, ln in folds:
-            w32 = _f32(lin_w)
-            n, k = w32.shape
-            wf = torch.empty((n, k), dtype=torch.float16, device=w32.device)     # fp16: multiplies the fp16 residual stream
-            bc = torch.empty(2 * n, dtype=torch.float32, device=w32.device)
-            check(lib.keds_fold_layernorm_ex(ptr(w32), ptr(lin_b), ptr(t[ln[0]]), ptr(t[ln[1]]), n, k, ptr(wf), 1, ptr(bc),
-                                             stream()), "keds_fold_layernorm")
-            t[name + "_wf"], t[name + "_bc"] = wf, bc
-        if fp8 and folds:
-            # BASELINE config 5: MXFP8 copies of the four weights (in_proj / c_fc with their LayerNorm folded in)
-            for name, lin_w, lin_b, ln in (("qkv", blk.attn.in_proj_weight, t["qkv_b"], ("ln1_g", "ln1_b")),
-                                           ("out", blk.attn.out_proj.weight, t["out_b"], None),
-                                           ("fc", blk.mlp.c_fc.weight, t["fc_b"], ("ln2_g", "ln2_b")),
-                                           ("proj", blk.mlp.c_proj.weight, t["proj_b"], None)):
-                w32 = _f32(lin_w)
-                n, k = w32.shape
-                q8 = torch.empty((n, k), dtype=torch.uint8, device=w32.device)
-                s8 = torch.empty((k // 128, n, 4), dtype=torch.uint8, device=w32.device)
-                bc8 = torch.empty(2 * n, dtype=torch.float32, device=w32.device)
-                check(lib.keds_fold_layernorm_mxfp8(ptr(w32), ptr(lin_b), ptr(t[ln[0]]) if ln else None,
-                                                    ptr(t[ln[1]]) if ln else None, n, k, n, ptr(q8), ptr(s8), ptr(bc8),
-                                                    stream()), "keds_fold_layernorm_mxfp8")
-                t[name + "_q8"], t[name + "_s8"] = q8, s8
-                if ln:
-                    t[name + "_bc8"] = bc8
-        torch.cuda.current_stream().synchronize()          # the fp32 temporaries die here
-        for k, v in t.items():
-            setattr(blocks[i], k, ptr(v))
-        if f32 == 2:
-            blocks[i].x3_exp = (C.c_int32 * 4)(*x3_exps)
-        keep.append(t)
+            qkv_w=_f32(blk.attn.in_proj_weight), qkv_b=_f32(blk.attn.in_proj_bias),
+            out_w=_f32(blk.attn.out_proj.weight), out_b=_f32(blk.attn.out_proj.bias),
+            fc_w=_f32(blk.mlp.c_fc.weight), fc_b=_f32(blk.mlp.c_fc.bias),
+            proj_w=_f32(blk.mlp.c_proj.weight), proj_b=_f32(blk.mlp.c_proj.bias))
+        buf = torch.empty(nbytes, dtype=torch.uint8, device=src["qkv_w"].device)
+        check(lib.keds_block_pack(C.byref(_lib.BlockSource(**{k: ptr(v) for k, v in src.items()})), *mode, ptr(buf), nbytes,
+                                  C.byref(blocks[i]), stream()), "keds_block_pack")
+        torch.cuda.current_stream().synchronize()          # the fp32 views of a 16-bit checkpoint die here
+        keep.append(buf)
     keep.append(blocks)
     return _lib.TowerParams(tr.width, tr.layers, tr.heads, seq, 1 if causal else 0, blocks, 1 if fp8 else 0,
                             1 if cls_only else 0, int(f32), 1 if f16 else 0)
@@ -917,7 +871,8 @@ class KnowledgeStream:
 # ---------------------------------------------------------------------------------------------------
 def convert_weights(model: nn.Module):
     """fp16 cast of Linear/Conv/MHA/projection weights (model.py:927-948).  Kept for API parity: it
-    changes the checkpoint dtype (`model.dtype`), the kernels always compute bf16 x bf16 -> fp32."""
+    changes the checkpoint dtype (`model.dtype`) and rounds the stored weights to fp16; the GEMM operand types are those of
+    the operating point (`CLIP.set_precision`), not of the checkpoint."""
     def _cast(l):
         if isinstance(l, (nn.Conv1d, nn.Conv2d, nn.Linear)):
             l.weight.data = l.weight.data.half()

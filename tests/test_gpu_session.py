@@ -322,3 +322,154 @@ def test_handle_lifetimes_and_batch_sequences(tiny):
     assert I[:, 0].tolist() == [0, 1, 2, 3, 4]
     c.close()                                                       # context first ...
     a.close(); b.close(); idx.close()                               # ... handles afterwards
+
+
+# ---- keds_block_pack: the one weight-packing routine behind both loaders (include/keds_hip.h) --------------------------
+def _block_source(d, seed):
+    """The twelve fp32 tensors of one block: N(0, 0.05) weights with a few planted entries of magnitude ~3 (far above the rest:
+    they set the fp32x3 exponent and the MXFP8 block scales) and ~1e-6 (fp16 subnormals), gamma = 1 + 0.1 n, beta = 0.1 n."""
+    g = torch.Generator().manual_seed(seed)
+
+    def mat(n, k):
+        w = 0.05 * torch.randn(n, k, generator=g)
+        at = torch.randperm(n * k, generator=g)[:8]
+        w.view(-1)[at] = torch.tensor([3.0, -3.1, 2.9, -3.0, 1e-6, -1.1e-6, 0.9e-6, -1e-6])
+        return w
+
+    def vec(n, std, mean=0.0):
+        return mean + std * torch.randn(n, generator=g)
+
+    src = dict(ln1_g=vec(d, 0.1, 1.0), ln1_b=vec(d, 0.1), ln2_g=vec(d, 0.1, 1.0), ln2_b=vec(d, 0.1),
+               qkv_w=mat(3 * d, d), qkv_b=vec(3 * d, 0.05), out_w=mat(d, d), out_b=vec(d, 0.05),
+               fc_w=mat(4 * d, d), fc_b=vec(4 * d, 0.05), proj_w=mat(d, 4 * d), proj_b=vec(d, 0.05))
+    return {k: v.cuda().contiguous() for k, v in src.items()}
+
+
+def _expected_block(src, fp8, f32, f16, folded):
+    """What the facade's _pack_tower built before keds_block_pack existed: torch casts and direct calls of the primitives.
+    Returns ({field: tensor}, x3_exp)."""
+    lib, st = _lib.load(), _lib.stream()
+    want = {k: src[k] for k in ("ln1_g", "ln1_b", "ln2_g", "ln2_b", "qkv_b", "out_b", "fc_b", "proj_b")}
+    x3 = [0, 0, 0, 0]
+    for j, name in enumerate(("qkv", "out", "fc", "proj")):
+        w = src[name + "_w"]
+        n, k = w.shape
+        if f32 == 2:
+            planes = torch.empty((2, n, k), dtype=torch.float16, device="cuda")
+            e = _lib.i32(0)
+            _lib.check(lib.keds_split_f16_weight(_lib.ptr(w), n, k, _lib.ptr(planes), n * k, e, st), "keds_split_f16_weight")
+            want[name + "_w"], x3[j] = planes, int(e.value)
+        else:
+            want[name + "_w"] = w if f32 else w.to(torch.float16) if f16 else w.to(torch.bfloat16)
+    lns = dict(qkv=("ln1_g", "ln1_b"), fc=("ln2_g", "ln2_b"))
+    if folded and not f32:
+        for name, (ga, be) in lns.items():
+            w = src[name + "_w"]
+            n, k = w.shape
+            wf = torch.empty((n, k), dtype=torch.float16, device="cuda")
+            bc = torch.empty(2 * n, dtype=torch.float32, device="cuda")
+            _lib.check(lib.keds_fold_layernorm_ex(_lib.ptr(w), _lib.ptr(src[name + "_b"]), _lib.ptr(src[ga]), _lib.ptr(src[be]),
+                                                  n, k, _lib.ptr(wf), 1, _lib.ptr(bc), st), "keds_fold_layernorm_ex")
+            want[name + "_wf"], want[name + "_bc"] = wf, bc
+    if fp8:
+        for name in ("qkv", "out", "fc", "proj"):
+            w = src[name + "_w"]
+            n, k = w.shape
+            ga, be = lns.get(name, (None, None))
+            q8 = torch.empty((n, k), dtype=torch.uint8, device="cuda")
+            s8 = torch.empty((k // 128, n, 4), dtype=torch.uint8, device="cuda")
+            bc8 = torch.empty(2 * n, dtype=torch.float32, device="cuda")
+            _lib.check(lib.keds_fold_layernorm_mxfp8(_lib.ptr(w), _lib.ptr(src[name + "_b"]), _lib.ptr(src[ga]) if ga else None,
+                                                     _lib.ptr(src[be]) if be else None, n, k, n, _lib.ptr(q8), _lib.ptr(s8),
+                                                     _lib.ptr(bc8), st), "keds_fold_layernorm_mxfp8")
+            want[name + "_q8"], want[name + "_s8"] = q8, s8
+            if ga:
+                want[name + "_bc8"] = bc8
+    torch.cuda.synchronize()
+    return want, x3
+
+
+@pytest.fixture(scope="module")
+def block_sources():
+    return {d: _block_source(d, seed=100 + d) for d in (128, 256)}
+
+
+@pytest.mark.parametrize("name,width,fp8,f32,f16,folded", [
+    ("bf16_folded", 128, 0, 0, 0, 1), ("bf16_unfolded", 128, 0, 0, 0, 0), ("fp16", 128, 0, 0, 1, 1),
+    ("fp32", 128, 0, 1, 0, 1), ("fp32x3", 128, 0, 2, 0, 1), ("fp8", 256, 1, 0, 0, 1)])       # fp8: K = 256 and 1024
+def test_block_pack_reproduces_the_primitives_byte_for_byte(block_sources, name, width, fp8, f32, f16, folded):
+    """keds_block_pack builds exactly what the torch casts and direct keds_fold_layernorm_ex / keds_fold_layernorm_mxfp8 /
+    keds_split_f16_weight calls give (raw bytes of every field, x3_exp included), every array 256-byte aligned inside the
+    caller's buffer, disjoint, copies of the source; fields the mode does not use are null; bad combinations are KEDS_E_ARG."""
+    lib = _lib.load()
+    src = block_sources[width]
+    want, x3 = _expected_block(src, fp8, f32, f16, folded)
+    nbytes = lib.keds_block_pack_bytes(width, fp8, f32, f16, folded)
+    assert nbytes > 0
+    buf = torch.full((nbytes,), 0xA5, dtype=torch.uint8, device="cuda")
+    bsrc = _lib.BlockSource(**{k: _lib.ptr(v) for k, v in src.items()})
+    out = _lib.BlockParams()
+    _lib.check(lib.keds_block_pack(bsrc, width, fp8, f32, f16, folded, _lib.ptr(buf), nbytes, out, _lib.stream()), "keds_block_pack")
+    torch.cuda.synchronize()
+    base, spans = buf.data_ptr(), []
+    for field, _ in _lib.BlockParams._fields_[:-1]:
+        p = getattr(out, field)
+        if field not in want:
+            assert p is None, f"{name}: {field} must be null"
+            continue
+        raw = want[field].contiguous().view(torch.uint8).reshape(-1)
+        assert p is not None and p % 256 == 0 and base <= p and p + raw.numel() <= base + nbytes, f"{name}: {field} placement"
+        assert torch.equal(buf[p - base:p - base + raw.numel()], raw), f"{name}: {field} differs from the primitives' bytes"
+        spans.append((p, p + raw.numel()))
+    assert list(out.x3_exp) == x3 and (f32 == 2 or x3 == [0, 0, 0, 0])
+    spans.sort()
+    assert all(a[1] <= b[0] for a, b in zip(spans, spans[1:])), f"{name}: arrays overlap"
+    srcs = [(v.data_ptr(), v.data_ptr() + v.numel() * 4) for v in src.values()]
+    assert all(hi <= lo2 or hi2 <= lo for lo, hi in spans for lo2, hi2 in srcs), f"{name}: an output aliases the source"
+    # the argument rules, through keds_block_pack itself (the mode is refused before anything is read or written)
+    for w, bad in ((128, (1, 0, 0, 1)),            # fp8 at width 128
+                   (256, (1, 0, 0, 0)),            # fp8 unfolded
+                   (128, (0, 0, 1, 0)),            # f16 unfolded
+                   (128, (0, 1, 1, 1)),            # f16 with f32
+                   (256, (1, 1, 0, 1))):           # fp8 with f32
+        assert lib.keds_block_pack_bytes(w, *bad) == 0
+        rc = lib.keds_block_pack(bsrc, w, *bad, _lib.ptr(buf), nbytes, _lib.BlockParams(), _lib.stream())
+        assert rc == -1 and _lib.last_error().startswith("keds_block_pack:"), (w, bad, rc, _lib.last_error())
+
+
+WIDE = dict(TINY, vision_width=256, transformer_width=256)          # the smallest width the MXFP8 weights allow
+
+
+@pytest.mark.parametrize("compute,precision,cfg,safe", [
+    (_lib.DT_BF16, "bf16", "tiny", False), (_lib.DT_F16, "fp16", "tiny", False), (_lib.DT_F32, "fp32", "tiny", False),
+    (_lib.DT_F32X3, "fp32x3", "tiny", False), (_lib.DT_FP8, "fp8", "wide", False), (_lib.DT_BF16, "bf16", "tiny", True)],
+    ids=["bf16", "fp16", "fp32", "fp32x3", "fp8", "safe"])
+def test_handle_and_facade_give_the_same_bits_in_every_compute_mode(ctx, tiny, monkeypatch, compute, precision, cfg, safe):
+    """Both loaders pack through keds_block_pack, so a handle and the facade at the matching set_precision hold the same
+    weights and return the same bits -- image and text tower, every compute mode, and the unfolded ("safe") flow.
+    fp8: 16 images = 272 rows, one full MXFP8 row tile plus 16 remainder rows, so the MXFP8 weights and their 16-bit twins are
+    both read."""
+    g, sd, _ = tiny
+    if cfg == "wide":
+        sd = O.synth_clip_state_dict(**WIDE, seed=7)
+        img = torch.from_numpy(np.random.RandomState(11).standard_normal((16, 3, 56, 56)).astype(np.float32)).cuda()
+    else:
+        img = torch.from_numpy(g["image"]).cuda()
+    text = torch.from_numpy(g["text"]).cuda()
+    eot = (text == 511).int().argmax(dim=1)
+    m = keds_amd.build_model(dict(sd), fp16=False).cuda()
+    if safe:
+        m.set_numerics("safe")
+        monkeypatch.setenv("KEDS_DETERMINISTIC", "1")           # read by keds_vit_create / keds_text_create
+    m.set_precision(precision)
+    host = {k: v.numpy() for k, v in sd.items()}
+    vit, txt = session.Vit(ctx, host, compute), session.Text(ctx, host, compute)
+    fi, ft = m.encode_image(img), m.encode_text(text)
+    assert m.precision == precision and not m.numerics_tripped         # (no guard trip moved the facade elsewhere)
+    hi, ht = vit.forward(img), txt.forward(text, eot)
+    assert torch.isfinite(hi).all() and torch.isfinite(ht).all()
+    assert torch.equal(hi, fi), f"{precision}: image tower, handle vs facade max |d| {max_abs(hi, fi):.3e}"
+    assert torch.equal(ht, ft), f"{precision}: text tower, handle vs facade max |d| {max_abs(ht, ft):.3e}"
+    if safe:
+        assert m._engine().vit.tower.blocks[0].qkv_wf is None
+    vit.close(); txt.close()
