@@ -40,6 +40,7 @@ __device__ __forceinline__ int ax_vpos(int o) {          // key offset in its 32
 }
 
 constexpr float AX_L2E = 1.44269502162933349609375f;     // log2 e
+constexpr float AX_PSHIFT = 6.0f;                        // log2 of the smallest row maximum of p (key_tile)
 // the two 32-lane halves of a wave hold the two halves of a query's keys: all-VALU exchange (a __shfl_xor is an LDS round trip)
 __device__ __forceinline__ float ax_halves_max(float x) {
     auto b = __builtin_amdgcn_permlane32_swap(__float_as_uint(x), __float_as_uint(x), false, false);
@@ -211,10 +212,14 @@ __global__ __launch_bounds__(64 * AX_WAVES) void attention_x3_kernel(const float
         float tmax = sc[0];
 #pragma unroll
         for (int r = 1; r < 16; ++r) tmax = fmaxf(tmax, sc[r]);
-        const float tl = ax_halves_max(tmax) * AX_L2E;
+        // The reference point sits AX_PSHIFT below the row maximum: the largest probability of a row is 2^6 .. 2^14, not 1.  The
+        // low plane of a value below 2^-3 is an fp16 subnormal (absolute 2^-25): relative to a maximum of 1 that floor, once per
+        // key, outweighed the fp32 rounding on rows whose heavy key has a v near zero (tests/test_gpu_attention_edges.py: 2x to
+        // 50x the float32 yardstick); relative to 2^6 it is 2^-31.  The common factor leaves with the final 1 / l.
+        const float tl = ax_halves_max(tmax) * AX_L2E - AX_PSHIFT;
         // The reference point m (log2 units) only moves when some query's maximum has grown by more than 8: until then the
-        // probabilities are taken relative to the old one (<= 2^8: exact scaling, the planes keep their relative precision) and
-        // the rescale of the 32 output registers is skipped -- the same sums, one wave-uniform branch.
+        // probabilities are taken relative to the old one (<= 2^14 < fp16's 2^16: exact scaling, the planes keep their relative
+        // precision) and the rescale of the 32 output registers is skipped -- the same sums, one wave-uniform branch.
         if (__builtin_amdgcn_ballot_w64(tl > m + 8.0f)) {
             const float mnew = fmaxf(m, tl);
             const float resc = __builtin_amdgcn_exp2f(m - mnew);                 // first tile: 2^(-1e30 - m) = 0
