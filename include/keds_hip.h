@@ -300,6 +300,19 @@ int keds_split_f16_pair(const float* x, int64_t ld, int64_t rows, int cols, void
  * falls into the fp16 subnormals and keeps 14-17.  Pass *w_exp to keds_gemm_x3.  Packing-time call: waits for the stream once. */
 int keds_split_f16_weight(const float* w, int64_t n, int k, void* out, int64_t plane, int* w_exp, void* stream);
 int keds_gemm_force_small(int on);
+/* test hook: what the last keds_gemm_bt* / keds_gemm_x3 call of the calling thread launched.  info[8] (host ints, written):
+ * [0] kernel form of the main launch, [1] of the remainder-row launch behind a 256 x 256 main launch (KEDS_GEMM_FORM_NONE: there
+ * was none), [2] / [3] their LDS ring depths (K-tiles of the A operand in flight: 2, 3 or 4), [4] / [5] their split-K slice counts
+ * (1 = no split, no reduce kernel), [6] 1 = the main launch was persistent (one workgroup per CU walks the tiles),
+ * [7] KEDS_GEMM_FLAG_* of the main launch. */
+#define KEDS_GEMM_FORM_NONE 0
+#define KEDS_GEMM_FORM_SMALL 1   /* 128 x 128 tiles, 4 waves */
+#define KEDS_GEMM_FORM_PAIR 2    /* 256 x 256 tiles, 8 waves */
+#define KEDS_GEMM_FORM_QUAD 3    /* 256 x 256 tiles, 4 waves */
+#define KEDS_GEMM_FORM_QUAD3 4   /* 256 x 256 tiles, 4 waves, three-deep A ring (fp16-residual epilogues) */
+#define KEDS_GEMM_FLAG_DEFER 1           /* persistent LayerNorm form: part of a tile's stores leave inside the next tile's K-loop */
+#define KEDS_GEMM_FLAG_RESID_PROLOGUE 2  /* residual tile + bias as the accumulators' initial value (bit 10 of the hook above) */
+int keds_gemm_last_launch(int* info);
 
 /* y = LayerNorm(x) * gamma + beta over the last dim (fp32 statistics, eps 1e-5).
  * x fp32 [rows, dim] with row stride x_stride (elements); out bf16 (out_f32 == 0) or fp32,

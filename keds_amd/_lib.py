@@ -175,6 +175,7 @@ SIGNATURES = {
     "keds_gemm_bt": (i32, [vp, vp, vp, vp, i32, i32, i32, i32, vp, i32, vp]),
     "keds_gemm_set_workspace": (i32, [vp, sz]),
     "keds_gemm_force_small": (i32, [i32]),
+    "keds_gemm_last_launch": (i32, [vp]),
     "keds_gemm_x3": (i32, [vp, C.c_int64, C.c_int64, vp, C.c_int64, vp, vp, C.c_int64, i32, i32, i32, i32, i32, i32, vp]),
     "keds_split_f16_pair": (i32, [vp, C.c_int64, C.c_int64, i32, vp, C.c_int64, vp, vp]),
     "keds_split_f16_weight": (i32, [vp, C.c_int64, i32, vp, C.c_int64, C.POINTER(i32), vp]),

@@ -768,12 +768,30 @@ __global__ __launch_bounds__(256) void gemm_splitk_reduce_kernel(const float* __
 // (split-operand GEMMs: the planes' strides of the keds_gemm_x3 call in progress on this thread)
 thread_local long long g_x3_aplane = 0, g_x3_wplane = 0;
 
+// What the last keds_gemm_bt* / keds_gemm_x3 call of this thread launched (keds_gemm_last_launch, keds_hip.h): slot 0 = the main
+// launch, slot 1 = the remainder-row launch behind a 256^2 main launch.  A few stores to a thread-local per call.
+struct GemmLaunchRecord {
+    int form[2], ring[2], splits[2], persistent, flags;
+};
+thread_local GemmLaunchRecord tl_rec = {};
+thread_local int tl_rec_slot = 0;
+inline void rec_launch(int form, int ring, int splits, int persistent = 0, int flags = 0) {
+    tl_rec.form[tl_rec_slot] = form;
+    tl_rec.ring[tl_rec_slot] = ring;
+    tl_rec.splits[tl_rec_slot] = splits;
+    if (tl_rec_slot == 0) {
+        tl_rec.persistent = persistent;
+        tl_rec.flags = flags;
+    }
+}
+
 template <int EPI, int NST>
 int launch_small_nst(const void* A, const void* W, const float* bias, void* out, int M, int N, int K, const float* aux,
                      int aux_i, void* aux2, int splits, long long lda, long long ldc, hipStream_t st) {
     if (int rc = keds_func_lds_once((const void*)gemm_bt_kernel<EPI, NST>, NST * BUF_BYTES, "gemm_bt_kernel")) return rc;
     const int m_tiles = (M + BM - 1) / BM, n_tiles = N / BN;
     const int tiles = m_tiles * n_tiles;
+    rec_launch(KEDS_GEMM_FORM_SMALL, NST, splits);
     if (splits > 1) {
         float* g_ws = nullptr;
         size_t g_ws_bytes = 0;
@@ -1951,6 +1969,8 @@ int launch_big(const void* A, const void* W, const float* bias, void* out, int M
         // behind the 32 DMA pieces of the next tile in the in-order vmcnt)
         if (quad == 2 && ntiles > cus && cus >= 8 && !epi_resid16(EPI) && EPI != KEDS_EPI_X3_RESID_F32) {
             if (int rc = keds_func_lds_once((const void*)gemm_bt_quad_kernel<EPI, 0, 1>, qd::LDS_BYTES, "gemm_bt_quad_kernel")) return rc;
+            rec_launch(KEDS_GEMM_FORM_QUAD, 2, 1, 1,
+                       epi_is_ln(EPI) && !epi_qgelu(EPI) && g_quad_defer && quad_defer_env() && K / pr::TK >= 8 ? KEDS_GEMM_FLAG_DEFER : 0);
             KEDS_LAUNCH((gemm_bt_quad_kernel<EPI, 0, 1>), cus, 256, qd::LDS_BYTES, st, (const bf16_t*)A, (const bf16_t*)W, bias, out, M, N, K,
                         n_tiles, aux, (int)(epi_is_ln(EPI) ? (g_quad_defer && quad_defer_env()) : aux_i), aux2,
                         keds_numerics_guard(), ntiles, g_x3_aplane, g_x3_wplane);
@@ -1959,12 +1979,14 @@ int launch_big(const void* A, const void* W, const float* bias, void* out, int M
         if constexpr (epi_resid16(EPI)) {
             if (g_quad3 && K >= 1024 && K / pr::TK >= 4) {               // long K: A operand through a three-deep ring
                 if (int rc = keds_func_lds_once((const void*)gemm_bt_quad3_kernel<EPI>, 5 * pr::OP_BYTES, "gemm_bt_quad3_kernel")) return rc;
+                rec_launch(KEDS_GEMM_FORM_QUAD3, 3, 1);
                 KEDS_LAUNCH((gemm_bt_quad3_kernel<EPI>), ntiles, 256, 5 * pr::OP_BYTES, st, (const bf16_t*)A, (const bf16_t*)W, bias, out, M, N, K,
                             n_tiles, aux, ntiles);
                 return keds_check_launch("gemm_bt_quad3_kernel");
             }
         }
         if (int rc = keds_func_lds_once((const void*)gemm_bt_quad_kernel<EPI>, qd::LDS_BYTES, "gemm_bt_quad_kernel")) return rc;
+        rec_launch(KEDS_GEMM_FORM_QUAD, 2, 1);
         KEDS_LAUNCH((gemm_bt_quad_kernel<EPI>), ntiles, 256, qd::LDS_BYTES, st, (const bf16_t*)A, (const bf16_t*)W, bias, out, M, N, K, n_tiles,
                     aux, aux_i, aux2, keds_numerics_guard(), ntiles, g_x3_aplane, g_x3_wplane);
         return keds_check_launch("gemm_bt_quad_kernel");
@@ -1972,11 +1994,13 @@ int launch_big(const void* A, const void* W, const float* bias, void* out, int M
     if constexpr (epi_resid16(EPI)) {
         if (g_resid_prologue) {
             if (int rc = keds_func_lds_once((const void*)gemm_bt_pair_kernel<EPI, 0, 1>, pr::LDS_BYTES, "gemm_bt_pair_kernel")) return rc;
+            rec_launch(KEDS_GEMM_FORM_PAIR, 2, 1, 0, KEDS_GEMM_FLAG_RESID_PROLOGUE);
             KEDS_LAUNCH((gemm_bt_pair_kernel<EPI, 0, 1>), m_tiles * n_tiles, 512, pr::LDS_BYTES, st,
                         (const bf16_t*)A, (const bf16_t*)W, bias, out, M, N, K, n_tiles, aux, aux_i, aux2, keds_numerics_guard(), 0LL, 0LL);
             return keds_check_launch("gemm_bt_pair_kernel");
         }
     }
+    rec_launch(KEDS_GEMM_FORM_PAIR, 2, 1);
     KEDS_LAUNCH((gemm_bt_pair_kernel<EPI>), m_tiles * n_tiles, 512, pr::LDS_BYTES, st, (const bf16_t*)A, (const bf16_t*)W, bias, out,
                 M, N, K, n_tiles, aux, aux_i, aux2, keds_numerics_guard(), g_x3_aplane, g_x3_wplane);
     return keds_check_launch("gemm_bt_pair_kernel");
@@ -2010,6 +2034,8 @@ int launch_gemm(const void* A, const void* W, const float* bias, void* out, int 
                 int aux_i, void* aux2, long long lda, long long ldc, hipStream_t st) {
     KedsProfScope prof(KEDS_PROF_GEMM, st, /*lazy: the launches bind the event pair (KEDS_LAUNCH)*/ true);
     prof.work(2.0 * M * N * K);
+    tl_rec = GemmLaunchRecord{};
+    tl_rec_slot = 0;
     // Large problems: full 256-row tiles go to the 256^2 kernel, the remainder rows (< 256) to the 128^2 one.
     // (ViT-L/14 at B=128: M = 32896 = 128*256 + 128, so 512..2048 big tiles = whole rounds on 256 CUs.)
     // the 256^2 kernel runs one workgroup per CU: use it when its full tiles keep >= 85% of the CU-rounds busy (a single
@@ -2021,6 +2047,7 @@ int launch_gemm(const void* A, const void* W, const float* bias, void* out, int 
     const int m_main = M / pr::TM * pr::TM;
     int rc = launch_big<EPI>(A, W, bias, out, m_main, N, K, aux, aux_i, aux2, st);
     if (rc || m_main == M || g_skip_tail) return rc;
+    tl_rec_slot = 1;
     const size_t esz = (epi_base(EPI) == KEDS_EPI_BIAS_RESID_F32 || epi_base(EPI) == KEDS_EPI_BIAS_F32 || EPI == KEDS_EPI_RESID_STATS_F32)
                            ? 4 : 2;
     // the remainder launch numbers its rows from 0: move the per-row side buffers along
@@ -2046,6 +2073,14 @@ int launch_gemm(const void* A, const void* W, const float* bias, void* out, int 
 bool keds_gemm_splits_rows(int M, int N, int K) { return big_tiles_ok(M, N, K) && M % pr::TM != 0; }
 // (towers.hip) small GEMM launches of the calling thread take the 64 KiB-LDS kernel form while `on`
 void keds_gemm_small_lds(int on) { tl_small_lds = on; }
+
+extern "C" int keds_gemm_last_launch(int* info) {
+    KEDS_REQUIRE(info, "keds_gemm_last_launch: null pointer");
+    const int v[8] = {tl_rec.form[0], tl_rec.form[1], tl_rec.ring[0], tl_rec.ring[1], tl_rec.splits[0], tl_rec.splits[1],
+                      tl_rec.persistent, tl_rec.flags};
+    for (int i = 0; i < 8; ++i) info[i] = v[i];
+    return KEDS_OK;
+}
 
 extern "C" int keds_gemm_force_small(int on) {
     g_force_small = on & 1;

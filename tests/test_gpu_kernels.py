@@ -546,7 +546,9 @@ def test_gemm_quad_kernel_bit_identical_to_the_eight_wave_kernel(M, K):
     the same MFMA chains in the same k order and the same epilogues as the 8-wave kernel: every epilogue the towers use must
     give the same bits (plain bias -> bf16, LayerNorm-folded bias / QuickGELU on fp16 operands, fp16 residual + statistics).
     Its persistent form (one workgroup per CU walks the tiles; M = 12288 / 11008 here: 768 / 688 tiles = three rounds, the last
-    one ragged -- fewer tiles than 85 % of whole rounds go to the 128 x 128 kernel and would not test it)
+    one ragged -- big_tiles_ok (gemm.hip) sends a launch to the 128 x 128 kernel, which would not test it, when its 256 x 256 tiles fill
+    less than 85 % of whole rounds, or since round 5 less than 50 % where M % 256 == 0 and K <= 1024; what each run really launched is
+    asserted per case in tests/test_gpu_gemm_edges.py through keds_gemm_last_launch)
     must as well -- including the LayerNorm epilogue's deferred stores (K >= 512: 18 of a lane's 32 stores of a tile are issued
     from inside the next tile's K-loop; K = 256 is too short for the trickle and stores everything in the epilogue).
     What the dispatcher picks by shape (`default`) must give the same bits too, with the other statistics buffer cleared for
