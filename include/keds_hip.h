@@ -281,10 +281,6 @@ int keds_fold_layernorm_mxfp8(const float* W, const float* bias, const float* ga
  * without it they run unsplit.  The buffer must stay valid until it is replaced; pass NULL to unregister. */
 int keds_gemm_set_workspace(void* ptr, size_t bytes);
 
-/* test/bench hook: bit 0 routes every GEMM through the 128x128 kernel, bit 8 skips the remainder-row launch (timing
- * only), bit 9 disables split-K; A/B switches of the 256x256 kernels: bit 10 residual tile as the accumulators' initial
- * value, bits 11-12 kernel form (1 = 4 waves, 2 = 4 waves persistent, 3 = 8 waves; 0 = by shape), bits 13-15 stamped
- * diagnostic build, bit 16 no three-deep A ring, bit 17 no deferred epilogue stores in the persistent kernel */
 /* out = epilogue(A . W^T 2^-w_exp + bias) on split fp16 operands (KEDS_EPI_X3_*): A_hi = a, A_lo = a + a_plane elements (rows of
  * lda elements), W_hi = w, W_lo = w + w_plane (dense [N, K]); the W planes hold W 2^w_exp (keds_split_f16_weight; 0 for planes
  * of the matrix as stored).  M, N, K as keds_gemm_bt_ex2; ldc in elements of the output type. */
@@ -299,8 +295,17 @@ int keds_split_f16_pair(const float* x, int64_t ld, int64_t rows, int cols, void
  * in [2^13, 2^14): small weights (|w| ~ 1e-2 .. 1e-3 in real checkpoints) then keep 22 bits -- split as stored their low plane
  * falls into the fp16 subnormals and keeps 14-17.  Pass *w_exp to keds_gemm_x3.  Packing-time call: waits for the stream once. */
 int keds_split_f16_weight(const float* w, int64_t n, int k, void* out, int64_t plane, int* w_exp, void* stream);
+/* Which kernel form a keds_gemm_bt* / keds_gemm_x3 call gets is decided in one host function (csrc/gemm_plan.h: the rules;
+ * docs/kernels.md: the table of forms).  The three entries below steer it, report what it led to, and ask it without a GPU.
+ *
+ * test/bench hook, process-wide, `on` replaces the previous call's bits: bit 0 routes every GEMM through the 128x128 kernel,
+ * bit 8 skips the remainder-row launch (timing only), bit 9 disables split-K; A/B switches of the 256x256 kernels: bit 10
+ * residual tile as the accumulators' initial value, bits 11-12 kernel form (1 = 4 waves, 2 = 4 waves persistent, 3 = 8 waves;
+ * 0 = by shape), bits 13-15 stamped diagnostic build (launched outside the plan: nothing is recorded for it), bit 16 no
+ * three-deep A ring, bit 17 no deferred epilogue stores in the persistent kernel */
 int keds_gemm_force_small(int on);
-/* test hook: what the last keds_gemm_bt* / keds_gemm_x3 call of the calling thread launched.  info[8] (host ints, written):
+/* test hook: what the last keds_gemm_bt* / keds_gemm_x3 call of the calling thread launched -- written where each kernel is
+ * launched, not copied from the plan; a call whose launches differ from its plan fails with KEDS_E_LAUNCH.  info[8] (host ints, written):
  * [0] kernel form of the main launch, [1] of the remainder-row launch behind a 256 x 256 main launch (KEDS_GEMM_FORM_NONE: there
  * was none), [2] / [3] their LDS ring depths (K-tiles of the A operand in flight: 2, 3 or 4), [4] / [5] their split-K slice counts
  * (1 = no split, no reduce kernel), [6] 1 = the main launch was persistent (one workgroup per CU walks the tiles),
@@ -313,6 +318,15 @@ int keds_gemm_force_small(int on);
 #define KEDS_GEMM_FLAG_DEFER 1           /* persistent LayerNorm form: part of a tile's stores leave inside the next tile's K-loop */
 #define KEDS_GEMM_FLAG_RESID_PROLOGUE 2  /* residual tile + bias as the accumulators' initial value (bit 10 of the hook above) */
 int keds_gemm_last_launch(int* info);
+/* The plan of the call keds_gemm_bt_ex2 / keds_gemm_x3 (epilogue, M, N, K, lda, ldc) on a device of `cus` compute units, with
+ * `splitk_bytes` of split-K scratch registered (0: none) and, small_lds != 0, inside a composite that asked for the 64 KiB-LDS
+ * form of the 128 x 128 kernel; under the switches keds_gemm_force_small set.  info[8] as keds_gemm_last_launch.  Touches no
+ * device.  The shape rules of keds_gemm_bt_ex2 apply (N % 128, K % 64, row strides, a dense EPI_PATCH output). */
+int keds_gemm_plan_query(int epilogue, int M, int N, int K, int64_t lda, int64_t ldc, int cus, size_t splitk_bytes, int small_lds,
+                         int* info);
+/* the same for n calls at once (a sweep from Python costs its ctypes calls otherwise): cases [n][9] host int64 = {epilogue, M, N,
+ * K, lda, ldc, cus, splitk_bytes, small_lds}, info [n][8].  Stops at the first case keds_gemm_plan_query rejects. */
+int keds_gemm_plan_query_many(int64_t n, const int64_t* cases, int* info);
 
 /* y = LayerNorm(x) * gamma + beta over the last dim (fp32 statistics, eps 1e-5).
  * x fp32 [rows, dim] with row stride x_stride (elements); out bf16 (out_f32 == 0) or fp32,

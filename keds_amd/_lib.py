@@ -176,6 +176,8 @@ SIGNATURES = {
     "keds_gemm_set_workspace": (i32, [vp, sz]),
     "keds_gemm_force_small": (i32, [i32]),
     "keds_gemm_last_launch": (i32, [vp]),
+    "keds_gemm_plan_query": (i32, [i32, i32, i32, i32, i64, i64, i32, sz, i32, vp]),
+    "keds_gemm_plan_query_many": (i32, [i64, vp, vp]),
     "keds_gemm_x3": (i32, [vp, C.c_int64, C.c_int64, vp, C.c_int64, vp, vp, C.c_int64, i32, i32, i32, i32, i32, i32, vp]),
     "keds_split_f16_pair": (i32, [vp, C.c_int64, C.c_int64, i32, vp, C.c_int64, vp, vp]),
     "keds_split_f16_weight": (i32, [vp, C.c_int64, i32, vp, C.c_int64, C.POINTER(i32), vp]),

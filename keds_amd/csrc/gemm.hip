@@ -14,13 +14,6 @@
 #include <cstdlib>
 #include "gemm_shared.h"
 #include "gemm_quad_gen.h"
-#ifdef KEDS_EXPERIMENTS
-// tools/experiments/gemm_duo.hip (round 5, a measured negative: docs/findings_r05.md section 1): the two-accumulator-set kernel
-// (LayerNorm-folded epilogues under the next unit's MFMAs); only the experiment build links it
-bool keds_gemm_duo_ok(int epi, int M, int N, int K);
-int keds_gemm_duo_launch(int epi, const void* A, const void* W, const float* bias, void* out, int M, int N, int K, const float* aux,
-                         void* aux2, hipStream_t st);
-#endif
 
 #ifndef KEDS_QUAD_NOEPI
 #define KEDS_QUAD_NOEPI 0
@@ -765,98 +758,6 @@ __global__ __launch_bounds__(256) void gemm_splitk_reduce_kernel(const float* __
 // every DMA lane group fetch half cache lines, the texture-address path saturates, and the 256 x 256 x 64 kernel below
 // replaced it: +16 % DMA rate from full-line fetches.  profiles/r01_gemm_pmc_ring_kernel.txt keeps its counters.)
 
-// (split-operand GEMMs: the planes' strides of the keds_gemm_x3 call in progress on this thread)
-thread_local long long g_x3_aplane = 0, g_x3_wplane = 0;
-
-// What the last keds_gemm_bt* / keds_gemm_x3 call of this thread launched (keds_gemm_last_launch, keds_hip.h): slot 0 = the main
-// launch, slot 1 = the remainder-row launch behind a 256^2 main launch.  A few stores to a thread-local per call.
-struct GemmLaunchRecord {
-    int form[2], ring[2], splits[2], persistent, flags;
-};
-thread_local GemmLaunchRecord tl_rec = {};
-thread_local int tl_rec_slot = 0;
-inline void rec_launch(int form, int ring, int splits, int persistent = 0, int flags = 0) {
-    tl_rec.form[tl_rec_slot] = form;
-    tl_rec.ring[tl_rec_slot] = ring;
-    tl_rec.splits[tl_rec_slot] = splits;
-    if (tl_rec_slot == 0) {
-        tl_rec.persistent = persistent;
-        tl_rec.flags = flags;
-    }
-}
-
-template <int EPI, int NST>
-int launch_small_nst(const void* A, const void* W, const float* bias, void* out, int M, int N, int K, const float* aux,
-                     int aux_i, void* aux2, int splits, long long lda, long long ldc, hipStream_t st) {
-    if (int rc = keds_func_lds_once((const void*)gemm_bt_kernel<EPI, NST>, NST * BUF_BYTES, "gemm_bt_kernel")) return rc;
-    const int m_tiles = (M + BM - 1) / BM, n_tiles = N / BN;
-    const int tiles = m_tiles * n_tiles;
-    rec_launch(KEDS_GEMM_FORM_SMALL, NST, splits);
-    if (splits > 1) {
-        float* g_ws = nullptr;
-        size_t g_ws_bytes = 0;
-        keds_splitk_scratch(&g_ws, &g_ws_bytes);
-        const int m_pad = m_tiles * BM;
-        KEDS_LAUNCH((gemm_bt_kernel<EPI, NST>), tiles * splits, 256, NST * BUF_BYTES, st, (const bf16_t*)A, (const bf16_t*)W, bias, out,
-                    M, N, K, n_tiles, aux, aux_i, g_ws, K / splits, tiles, m_pad, lda, ldc, aux2, (int*)nullptr, 0LL, 0LL);
-        int rc = keds_check_launch("gemm_bt_kernel(split-K)");
-        if (rc) return rc;
-        const int threads = M * (N / 8);
-        KEDS_LAUNCH((gemm_splitk_reduce_kernel<EPI>), (threads + 255) / 256, 256, 0, st, (const float*)g_ws, splits, m_pad, bias, out, M, N, K,
-                    aux, aux_i, ldc, aux2, keds_numerics_guard());
-        return keds_check_launch("gemm_splitk_reduce_kernel");
-    }
-    KEDS_LAUNCH((gemm_bt_kernel<EPI, NST>), tiles, 256, NST * BUF_BYTES, st, (const bf16_t*)A, (const bf16_t*)W, bias, out, M, N, K,
-                n_tiles, aux, aux_i, (float*)nullptr, 0, tiles, 0, lda, ldc, aux2, keds_numerics_guard(), g_x3_aplane, g_x3_wplane);
-    return keds_check_launch("gemm_bt_kernel");
-}
-
-int g_no_split = 0;   // test hook
-static bool nosplit_env() {     // KEDS_NO_SPLITK=1 in the environment (A/B): no split-K anywhere
-    static int v = -1;
-    if (v < 0) {
-        const char* e = keds_exp_env("KEDS_NO_SPLITK");
-        v = e && e[0] == '1';
-    }
-    return v != 0;
-}
-// thread-local request of the calling composite (towers.hip): small launches take the 64 KiB kernel form; KEDS_SMALL_NST=2 in the
-// environment forces it everywhere (A/B)
-thread_local int tl_small_lds = 0;
-bool keds_small_lds_scope() {
-    static int env = -1;
-    if (env < 0) {
-        const char* e = keds_exp_env("KEDS_SMALL_NST");
-        env = e && e[0] == '2';
-    }
-    return env || tl_small_lds;
-}
-
-template <int EPI>
-int launch_small(const void* A, const void* W, const float* bias, void* out, int M, int N, int K, const float* aux,
-                 int aux_i, void* aux2, long long lda, long long ldc, hipStream_t st) {
-    const long tiles = (long)((M + BM - 1) / BM) * (N / BN);
-    // too few tiles to fill 256 CUs: split K so that ~128+ workgroups stream the weights in parallel
-    float* g_ws = nullptr;
-    size_t g_ws_bytes = 0;
-    if (tiles <= 64 && K >= 2048 && !g_no_split && !nosplit_env() && !epi_x3(EPI)) keds_splitk_scratch(&g_ws, &g_ws_bytes);
-    if (g_ws) {   // (tiles <= 64 && K >= 2048; at K = 1024 the second launch costs what the split saves)
-        int splits = 1;
-        while (splits < 16 && tiles * splits * 2 <= 256 && K % (splits * 2 * BK) == 0 && K / (splits * 2) >= 2 * BK) splits *= 2;
-        const size_t need = (size_t)splits * ((M + BM - 1) / BM * BM) * N * sizeof(float);
-        if (splits > 1 && need <= g_ws_bytes)
-            return keds_small_lds_scope() ? launch_small_nst<EPI, 2>(A, W, bias, out, M, N, K, aux, aux_i, aux2, splits, lda, ldc, st)
-                                          : launch_small_nst<EPI, 4>(A, W, bias, out, M, N, K, aux, aux_i, aux2, splits, lda, ldc, st);
-    }
-    // fewer workgroups than 2 per CU: nothing else hides the DMA latency, so use the deep ring -- unless the launch is meant to run
-    // BESIDE another kernel's workgroups (the towers' remainder-row chain beside the attention launch, round 5): the deep ring's
-    // 128 KiB of LDS needs an EMPTY CU, the two-deep ring's 64 KiB fits next to one resident attention workgroup (74 KiB)
-    // (round 6: the deep ring only while ONE round of it holds the launch.  Its 128 KiB of LDS mean one workgroup per CU, 256 at a
-    // time: 324 workgroups -- the packed text tower's c_proj -- ran two rounds, the second a quarter full, where the two-deep form's
-    // 512 slots take them in one and the second resident workgroup hides the DMA latency the deep ring was there for)
-    if (tiles <= 256 && !keds_small_lds_scope()) return launch_small_nst<EPI, 4>(A, W, bias, out, M, N, K, aux, aux_i, aux2, 1, lda, ldc, st);
-    return launch_small_nst<EPI, 2>(A, W, bias, out, M, N, K, aux, aux_i, aux2, 1, lda, ldc, st);
-}
 
 namespace pr {
 constexpr int TM = 256, TN = 256, TK = 64;
@@ -1839,91 +1740,201 @@ __global__ __launch_bounds__(256, 1) void gemm_bt_quad3_kernel(const bf16_t* __r
 // cycle counts; the only changes that paid this round removed memory traffic) this says the kernel is bound by what the
 // chip can power, not by its schedule: idle cycles removed come back as clock.  Not kept.
 
-int g_skip_tail = 0;      // timing-only: skip the remainder-row launch
-static int quad_defer_env() {     // KEDS_QUAD_DEFER=0 in the environment: no deferred epilogue stores (whole-step A/B)
-    static int v = -1;
-    if (v < 0) {
-        const char* e = keds_exp_env("KEDS_QUAD_DEFER");
-        v = !(e && e[0] == '0');
-    }
-    return v;
+// ---- host: every launch is planned by gemm_plan() (gemm_plan.h), one launch_* per kernel form runs the plan ----------------------
+
+// the library's switches (gemm_plan.h): the defaults -- in an experiment build what the KEDS_* environment said, read once --
+// under the bits of the last keds_gemm_force_small call
+const GemmSwitches& gemm_env_switches() {
+    static const GemmSwitches env = [] {
+        const auto is = [](const char* name, char c) {
+            const char* e = keds_exp_env(name);
+            return e && e[0] == c;
+        };
+        const auto num = [](const char* name, int dflt) {
+            const char* e = keds_exp_env(name);
+            return e && e[0] ? atoi(e) : dflt;
+        };
+        GemmSwitches s;
+        s.no_split = is("KEDS_NO_SPLITK", '1');
+        s.small_lds = is("KEDS_SMALL_NST", '2');
+        s.quad_defer = !is("KEDS_QUAD_DEFER", '0');
+        s.quad = num("KEDS_GEMM_QUAD", s.quad);
+        s.resid_quad_min_k = num("KEDS_RESID_QUAD_K", s.resid_quad_min_k);
+        s.x3_quad = !is("KEDS_X3_QUAD", '0');
+        s.big_tiles_pct = num("KEDS_BIG_TILES_PCT", s.big_tiles_pct);
+        return s;
+    }();
+    return env;
 }
-int g_quad_defer = 1;     // persistent 4-wave kernel, LayerNorm epilogue: 12 of a tile's 32 stores per lane wait for the next K-loop (bit 17: off)
-int g_quad3 = 1;          // 4-wave kernel, residual epilogue: three-deep A ring (bit 16 of keds_gemm_force_small's argument: off)
-// 256^2 tiles on the 4-wave kernel: -1 = by shape (quad_by_shape: persistent form), 0 = never, 1 = always, one tile per
-// workgroup, 2 = always, persistent (one workgroup per CU walks the tiles, next tile's first K-tiles under the epilogue)
-// (bits 11-12 of keds_gemm_force_small's argument force 1 / 2, 3 = never; KEDS_GEMM_QUAD=0/1/2 in the environment overrides
-// the default)
-int g_quad = -1;
-int quad_env() {
-    static int v = -2;
-    if (v == -2) {
-        const char* e = keds_exp_env("KEDS_GEMM_QUAD");
-        v = e && e[0] ? atoi(e) : -1;
-    }
-    return v;
+GemmSwitches& gemm_switches() {
+    static GemmSwitches sw = gemm_env_switches();
+    return sw;
 }
-// Same-process A/B on the ViT-L/14 shapes at B = 128 (tools/ab_quad.py, medians of 5 x 20 launches, round 3; 8 waves /
-// 4 waves / 4 waves persistent, us): qkv 189.4 / 184.1 / 179.2, c_fc 243.6 / 239.5 / 236.3, c_proj 216.3 / 214.7 / (212.5),
-// out-proj 66.3 / 67.7 / -- : the 4-wave kernel wins where the K-loop dominates the tile and its persistent form where the
-// LayerNorm epilogues (no loads of their own) leave registers for the tile loop; out-proj (K = 1024, a tile that is mostly
-// read-modify-write epilogue, which one wave per SIMD runs with nothing beside it) stays on the 8-wave kernel.
-// residual GEMMs go to the 4-wave kernel (three-deep A ring) from this K on (KEDS_RESID_QUAD_K in the environment: A/B)
-static int resid_quad_min_k() {
-    static int v = -1;
-    if (v < 0) {
-        const char* e = keds_exp_env("KEDS_RESID_QUAD_K");
-        v = e && e[0] ? atoi(e) : 1024;       // round 4: out-proj too (+0.35 % on the headline in four same-box pairs: its A operand,
-                                              // the attention output, is cold in the step and the three-deep ring tolerates that)
+// request of the calling composite (towers.hip, keds_gemm_small_lds): 128^2 launches of this thread take the 64 KiB-LDS kernel form
+thread_local int tl_small_lds = 0;
+
+// What the last keds_gemm_bt* / keds_gemm_x3 call of this thread launched (keds_gemm_last_launch, keds_hip.h): slot 0 = the main
+// launch, slot 1 = the remainder-row launch behind a 256^2 main launch.  A few stores to a thread-local per call; written at each
+// launch site with the literal form of the kernel launched there, and compared with the plan afterwards (launch_gemm).
+struct GemmLaunchRecord {
+    int form[2], ring[2], splits[2], persistent, flags;
+    void info(int out[8]) const {       // the layout of keds_gemm_last_launch (and of GemmPlan::info)
+        const int v[8] = {form[0], form[1], ring[0], ring[1], splits[0], splits[1], persistent, flags};
+        for (int i = 0; i < 8; ++i) out[i] = v[i];
     }
-    return v;
-}
-// (KEDS_X3_QUAD=0 in the environment: the 8-wave kernel for the split-operand GEMMs, A/B)
-static bool x3_quad_env() {
-    static int v = -1;
-    if (v < 0) {
-        const char* e = keds_exp_env("KEDS_X3_QUAD");
-        v = !(e && e[0] == '0');
+};
+thread_local GemmLaunchRecord tl_rec = {};
+thread_local int tl_rec_slot = 0;
+inline void rec_launch(int form, int ring, int splits, int persistent = 0, int flags = 0) {
+    tl_rec.form[tl_rec_slot] = form;
+    tl_rec.ring[tl_rec_slot] = ring;
+    tl_rec.splits[tl_rec_slot] = splits;
+    if (tl_rec_slot == 0) {
+        tl_rec.persistent = persistent;
+        tl_rec.flags = flags;
     }
-    return v != 0;
 }
+
+// the arguments of one launch: a call's, or those of its full 256-row tiles / its remainder rows (launch_gemm)
+struct GemmArgs {
+    const void *A, *W;
+    const float* bias;
+    void* out;
+    int M, N, K;
+    const float* aux;
+    int aux_i;
+    void* aux2;
+    long long lda, ldc;
+    hipStream_t st;
+    long long a_plane, w_plane;     // split-operand GEMMs (keds_gemm_x3): the planes' strides, else 0
+    float* splitk;                  // split-K scratch (launch_gemm: looked up only for a shape that can split)
+};
+
+template <int EPI, int NST>
+int launch_small(const GemmArgs& a, const GemmPlan::Part&) {
+    if (int rc = keds_func_lds_once((const void*)gemm_bt_kernel<EPI, NST>, NST * BUF_BYTES, "gemm_bt_kernel")) return rc;
+    const int m_tiles = (a.M + BM - 1) / BM, n_tiles = a.N / BN;
+    const int tiles = m_tiles * n_tiles;
+    rec_launch(KEDS_GEMM_FORM_SMALL, NST, 1);
+    KEDS_LAUNCH((gemm_bt_kernel<EPI, NST>), tiles, 256, NST * BUF_BYTES, a.st, (const bf16_t*)a.A, (const bf16_t*)a.W, a.bias, a.out, a.M, a.N,
+                a.K, n_tiles, a.aux, a.aux_i, (float*)nullptr, 0, tiles, 0, a.lda, a.ldc, a.aux2, keds_numerics_guard(), a.a_plane, a.w_plane);
+    return keds_check_launch("gemm_bt_kernel");
+}
+
+// split-K: fp32 slices to the scratch, then the reduce kernel runs the epilogue
+template <int EPI, int NST>
+int launch_splitk(const GemmArgs& a, const GemmPlan::Part& p) {
+    if (int rc = keds_func_lds_once((const void*)gemm_bt_kernel<EPI, NST>, NST * BUF_BYTES, "gemm_bt_kernel")) return rc;
+    const int m_tiles = (a.M + BM - 1) / BM, n_tiles = a.N / BN;
+    const int tiles = m_tiles * n_tiles, splits = p.splits;
+    const int m_pad = m_tiles * BM;
+    rec_launch(KEDS_GEMM_FORM_SMALL, NST, splits);
+    KEDS_LAUNCH((gemm_bt_kernel<EPI, NST>), tiles * splits, 256, NST * BUF_BYTES, a.st, (const bf16_t*)a.A, (const bf16_t*)a.W, a.bias, a.out,
+                a.M, a.N, a.K, n_tiles, a.aux, a.aux_i, a.splitk, a.K / splits, tiles, m_pad, a.lda, a.ldc, a.aux2, (int*)nullptr, 0LL, 0LL);
+    if (int rc = keds_check_launch("gemm_bt_kernel(split-K)")) return rc;
+    const int threads = a.M * (a.N / 8);
+    KEDS_LAUNCH((gemm_splitk_reduce_kernel<EPI>), (threads + 255) / 256, 256, 0, a.st, (const float*)a.splitk, splits, m_pad, a.bias, a.out, a.M,
+                a.N, a.K, a.aux, a.aux_i, a.ldc, a.aux2, keds_numerics_guard());
+    return keds_check_launch("gemm_splitk_reduce_kernel");
+}
+
+// the 8-wave 256^2 kernel; for the fp16-residual epilogues also with residual + bias as the accumulators' initial value (asked for
+// by the round-2 review, built in round 3 and slower: GemmSwitches::resid_prologue)
 template <int EPI>
-bool quad_by_shape(int N, int K) {
-    if constexpr (epi_is_ln(EPI)) return K >= 512;
-    if constexpr (epi_resid16(EPI)) return K >= resid_quad_min_k();
-    if constexpr (epi_x3(EPI)) return x3_quad_env();               // split-operand GEMMs: a K-loop of 3 K / 64 K-tiles, the form that wins where the K-loop dominates
-    return false;
+int launch_pair(const GemmArgs& a, const GemmPlan::Part& p) {
+    const int m_tiles = a.M / pr::TM, n_tiles = a.N / pr::TN;         // M is a multiple of 256 here
+    if constexpr (epi_resid16(EPI)) {
+        if (p.flags & KEDS_GEMM_FLAG_RESID_PROLOGUE) {
+            if (int rc = keds_func_lds_once((const void*)gemm_bt_pair_kernel<EPI, 0, 1>, pr::LDS_BYTES, "gemm_bt_pair_kernel")) return rc;
+            rec_launch(KEDS_GEMM_FORM_PAIR, 2, 1, 0, KEDS_GEMM_FLAG_RESID_PROLOGUE);
+            KEDS_LAUNCH((gemm_bt_pair_kernel<EPI, 0, 1>), m_tiles * n_tiles, 512, pr::LDS_BYTES, a.st, (const bf16_t*)a.A, (const bf16_t*)a.W,
+                        a.bias, a.out, a.M, a.N, a.K, n_tiles, a.aux, a.aux_i, a.aux2, keds_numerics_guard(), 0LL, 0LL);
+            return keds_check_launch("gemm_bt_pair_kernel");
+        }
+    }
+    if (int rc = keds_func_lds_once((const void*)gemm_bt_pair_kernel<EPI>, pr::LDS_BYTES, "gemm_bt_pair_kernel")) return rc;
+    rec_launch(KEDS_GEMM_FORM_PAIR, 2, 1);
+    KEDS_LAUNCH((gemm_bt_pair_kernel<EPI>), m_tiles * n_tiles, 512, pr::LDS_BYTES, a.st, (const bf16_t*)a.A, (const bf16_t*)a.W, a.bias, a.out,
+                a.M, a.N, a.K, n_tiles, a.aux, a.aux_i, a.aux2, keds_numerics_guard(), a.a_plane, a.w_plane);
+    return keds_check_launch("gemm_bt_pair_kernel");
 }
-// fp16-residual GEMMs: residual + bias as the accumulators' initial value instead of 16 loads per lane in the epilogue (round 3,
-// asked for by the round-2 review).  Built, bit-compatible within the fp32 addition order, and SLOWER in a same-process
-// interleaved A/B (tools/ab_resid_prologue.py, 7 rounds x 20 launches, medians): out-proj 75.5 vs 73.0 us, c_proj 232.4 vs
-// 229.0 us -- the 20 extra loads per lane in front of the first K-tile's DMA pieces delay the K-loop's start by more than the
-// epilogue saves (the loads themselves were never the epilogue's cost: round-2 note above).  Off; bit 10 of
-// keds_gemm_force_small's argument turns it on for an A/B.
-int g_resid_prologue = 0;
-int g_pair_stamp = 0;     // diagnostic: stamped build of the qkv instantiation (aux2 = stamp buffer)
+
+// the 4-wave 256^2 kernel, one tile per workgroup
+template <int EPI>
+int launch_quad(const GemmArgs& a, const GemmPlan::Part&) {
+    const int n_tiles = a.N / pr::TN, ntiles = (a.M / pr::TM) * n_tiles;
+    if (int rc = keds_func_lds_once((const void*)gemm_bt_quad_kernel<EPI>, qd::LDS_BYTES, "gemm_bt_quad_kernel")) return rc;
+    rec_launch(KEDS_GEMM_FORM_QUAD, 2, 1);
+    KEDS_LAUNCH((gemm_bt_quad_kernel<EPI>), ntiles, 256, qd::LDS_BYTES, a.st, (const bf16_t*)a.A, (const bf16_t*)a.W, a.bias, a.out, a.M, a.N,
+                a.K, n_tiles, a.aux, a.aux_i, a.aux2, keds_numerics_guard(), ntiles, a.a_plane, a.w_plane);
+    return keds_check_launch("gemm_bt_quad_kernel");
+}
+
+// its persistent form: one workgroup per CU walks the tiles, the next tile's first K-tiles land under the epilogue.  The LayerNorm
+// epilogues take the deferred-store switch where the others take aux_i
+template <int EPI>
+int launch_quad_persistent(const GemmArgs& a, const GemmPlan::Part& p) {
+    const int n_tiles = a.N / pr::TN, ntiles = (a.M / pr::TM) * n_tiles;
+    if (int rc = keds_func_lds_once((const void*)gemm_bt_quad_kernel<EPI, 0, 1>, qd::LDS_BYTES, "gemm_bt_quad_kernel")) return rc;
+    const int aux_i = epi_is_ln(EPI) ? p.defer : a.aux_i;
+    rec_launch(KEDS_GEMM_FORM_QUAD, 2, 1, 1, epi_is_ln(EPI) && !epi_qgelu(EPI) && aux_i && a.K / pr::TK >= 8 ? KEDS_GEMM_FLAG_DEFER : 0);
+    KEDS_LAUNCH((gemm_bt_quad_kernel<EPI, 0, 1>), p.workgroups, 256, qd::LDS_BYTES, a.st, (const bf16_t*)a.A, (const bf16_t*)a.W, a.bias, a.out,
+                a.M, a.N, a.K, n_tiles, a.aux, aux_i, a.aux2, keds_numerics_guard(), ntiles, a.a_plane, a.w_plane);
+    return keds_check_launch("gemm_bt_quad_kernel<persistent>");
+}
+
+// fp16-residual epilogues at long K: the A operand through a three-deep ring
+template <int EPI>
+int launch_quad3(const GemmArgs& a, const GemmPlan::Part&) {
+    const int n_tiles = a.N / pr::TN, ntiles = (a.M / pr::TM) * n_tiles;
+    if (int rc = keds_func_lds_once((const void*)gemm_bt_quad3_kernel<EPI>, 5 * pr::OP_BYTES, "gemm_bt_quad3_kernel")) return rc;
+    rec_launch(KEDS_GEMM_FORM_QUAD3, 3, 1);
+    KEDS_LAUNCH((gemm_bt_quad3_kernel<EPI>), ntiles, 256, 5 * pr::OP_BYTES, a.st, (const bf16_t*)a.A, (const bf16_t*)a.W, a.bias, a.out, a.M,
+                a.N, a.K, n_tiles, a.aux, ntiles);
+    return keds_check_launch("gemm_bt_quad3_kernel");
+}
 
 template <int EPI>
-int launch_big(const void* A, const void* W, const float* bias, void* out, int M, int N, int K, const float* aux,
-               int aux_i, void* aux2, hipStream_t st) {
+int launch_part(const GemmArgs& a, const GemmPlan::Part& p) {
+    switch (p.form) {
+        case KEDS_GEMM_FORM_SMALL:
+            if (p.splits > 1) return p.ring == 4 ? launch_splitk<EPI, 4>(a, p) : launch_splitk<EPI, 2>(a, p);
+            return p.ring == 4 ? launch_small<EPI, 4>(a, p) : launch_small<EPI, 2>(a, p);
+        case KEDS_GEMM_FORM_PAIR: return launch_pair<EPI>(a, p);
+        case KEDS_GEMM_FORM_QUAD: return p.persistent ? launch_quad_persistent<EPI>(a, p) : launch_quad<EPI>(a, p);
+        case KEDS_GEMM_FORM_QUAD3:
+            if constexpr (epi_resid16(EPI)) return launch_quad3<EPI>(a, p);
+            else break;
+        default: break;
+    }
+    keds_set_error("keds_gemm_bt: no kernel of form %d for epilogue %d", p.form, EPI);
+    return KEDS_E_LAUNCH;
+}
+
+// The two main launches the planner does not model, in place of the planned launch on full 256-row tiles: the stamped diagnostic
+// builds of the qkv / residual GEMMs (bits 13-15 of keds_gemm_force_small: aux2 = stamp buffer; they record nothing) and, in an
+// experiment build, the two-accumulator-set kernel.  False: neither applies, the planned launch runs.
+template <int EPI>
+bool launch_unplanned(const GemmArgs& a, const GemmSwitches& sw, int* rc) {
 #ifdef KEDS_EXPERIMENTS
     if constexpr (EPI == KEDS_EPI_LN_BIAS_BF16_H || EPI == KEDS_EPI_LN_QGELU_BF16_H) {
         // (a forced kernel form -- keds_gemm_force_small bits 11-15, KEDS_GEMM_QUAD -- keeps the round-4 kernels: A/B tools)
-        if (g_quad < 0 && quad_env() < 0 && !g_pair_stamp && keds_gemm_duo_ok(EPI, M, N, K))
-            return keds_gemm_duo_launch(EPI, A, W, bias, out, M, N, K, aux, aux2, st);
+        if (sw.quad < 0 && !sw.stamp && keds_gemm_duo_ok(EPI, a.M, a.N, a.K)) {
+            *rc = keds_gemm_duo_launch(EPI, a.A, a.W, a.bias, a.out, a.M, a.N, a.K, a.aux, a.aux2, a.st);
+            return true;
+        }
     }
 #endif
-    if (int rc = keds_func_lds_once((const void*)gemm_bt_pair_kernel<EPI>, pr::LDS_BYTES, "gemm_bt_pair_kernel")) return rc;
     if constexpr (EPI == KEDS_EPI_LN_BIAS_BF16_H || EPI == KEDS_EPI_RESID_STATS_F16) {
-        if (g_pair_stamp && g_quad > 0) {                            // stamped build of the 4-wave kernel
-            const int ntiles = (M / pr::TM) * (N / pr::TN);
+        const int n_tiles = a.N / pr::TN, ntiles = (a.M / pr::TM) * n_tiles;
+        if (sw.stamp && sw.quad > 0) {                               // stamped build of the 4-wave kernel
 #define KEDS_QSTAMP(V)                                                                                              \
     {                                                                                                              \
         (void)keds_func_lds_once((const void*)gemm_bt_quad_kernel<EPI, V>, qd::LDS_BYTES, "gemm_bt_quad_kernel<stamp>"); \
-        gemm_bt_quad_kernel<EPI, V><<<ntiles, 256, qd::LDS_BYTES, st>>>((const bf16_t*)A, (const bf16_t*)W, bias, out, M, N, K, \
-                                                                        N / pr::TN, aux, aux_i, aux2, nullptr, ntiles); \
+        gemm_bt_quad_kernel<EPI, V><<<ntiles, 256, qd::LDS_BYTES, a.st>>>((const bf16_t*)a.A, (const bf16_t*)a.W, a.bias, a.out, a.M, a.N, \
+                                                                          a.K, n_tiles, a.aux, a.aux_i, a.aux2, nullptr, ntiles); \
     }
-            switch (g_pair_stamp) {
+            switch (sw.stamp) {
                 case 2: KEDS_QSTAMP(2) break;
                 case 3: KEDS_QSTAMP(3) break;
                 case 4: KEDS_QSTAMP(4) break;
@@ -1933,17 +1944,18 @@ int launch_big(const void* A, const void* W, const float* bias, void* out, int M
                 default: KEDS_QSTAMP(1) break;
             }
 #undef KEDS_QSTAMP
-            return keds_check_launch("gemm_bt_quad_kernel<stamp>");
+            *rc = keds_check_launch("gemm_bt_quad_kernel<stamp>");
+            return true;
         }
-        if (g_pair_stamp) {
-            const dim3 grid((M / pr::TM) * (N / pr::TN));
+        if (sw.stamp) {
+            const dim3 grid(ntiles);
 #define KEDS_STAMP_LAUNCH(V)                                                                                       \
     {                                                                                                             \
         (void)keds_func_lds_once((const void*)gemm_bt_pair_kernel<EPI, V>, pr::LDS_BYTES, "gemm_bt_pair_kernel<stamp>"); \
-        gemm_bt_pair_kernel<EPI, V><<<grid, 512, pr::LDS_BYTES, st>>>((const bf16_t*)A, (const bf16_t*)W, bias, out, M, N, K, \
-                                                                       N / pr::TN, aux, aux_i, aux2, nullptr);      \
+        gemm_bt_pair_kernel<EPI, V><<<grid, 512, pr::LDS_BYTES, a.st>>>((const bf16_t*)a.A, (const bf16_t*)a.W, a.bias, a.out, a.M, a.N, \
+                                                                         a.K, n_tiles, a.aux, a.aux_i, a.aux2, nullptr);  \
     }
-            switch (g_pair_stamp) {
+            switch (sw.stamp) {
                 case 2: KEDS_STAMP_LAUNCH(2) break;
                 case 3: KEDS_STAMP_LAUNCH(3) break;
                 case 4: KEDS_STAMP_LAUNCH(4) break;
@@ -1951,208 +1963,151 @@ int launch_big(const void* A, const void* W, const float* bias, void* out, int M
                 default: KEDS_STAMP_LAUNCH(1) break;
             }
 #undef KEDS_STAMP_LAUNCH
-            return keds_check_launch("gemm_bt_pair_kernel<stamp>");
+            *rc = keds_check_launch("gemm_bt_pair_kernel<stamp>");
+            return true;
         }
     }
-    const int m_tiles = M / pr::TM, n_tiles = N / pr::TN;         // M is a multiple of 256 here
-    int quad = g_quad >= 0 ? g_quad : quad_env();
-    if (quad < 0) quad = quad_by_shape<EPI>(N, K) ? 2 : 0;
-    if (quad) {                                   // 1: one tile per workgroup, 2: persistent (one workgroup per CU walks the tiles)
-        const int ntiles = m_tiles * n_tiles;
-        int cus = keds_device_cus();
-        if (cus > 256) cus = 256;
-        cus &= ~7;                                // whole XCD groups: workgroup b and tile ids b, b + grid, ... share an XCD label
-        // (the residual epilogue holds 16 residual chunks per lane beside the read-back accumulators: in the tile loop it spills,
-        // out-proj 94 vs 70 us -- that epilogue keeps one tile per workgroup.  Late in round 3, with the quarter-wise read-back
-        // the tile loop no longer spills (209 VGPRs), and still does not pay: out-proj 66.7 vs 66.3 us, c_proj 216 vs 203.5 on
-        // its three-deep ring -- two tiles per workgroup leave one prologue to hide, and the epilogue's residual loads queue
-        // behind the 32 DMA pieces of the next tile in the in-order vmcnt)
-        if (quad == 2 && ntiles > cus && cus >= 8 && !epi_resid16(EPI) && EPI != KEDS_EPI_X3_RESID_F32) {
-            if (int rc = keds_func_lds_once((const void*)gemm_bt_quad_kernel<EPI, 0, 1>, qd::LDS_BYTES, "gemm_bt_quad_kernel")) return rc;
-            rec_launch(KEDS_GEMM_FORM_QUAD, 2, 1, 1,
-                       epi_is_ln(EPI) && !epi_qgelu(EPI) && g_quad_defer && quad_defer_env() && K / pr::TK >= 8 ? KEDS_GEMM_FLAG_DEFER : 0);
-            KEDS_LAUNCH((gemm_bt_quad_kernel<EPI, 0, 1>), cus, 256, qd::LDS_BYTES, st, (const bf16_t*)A, (const bf16_t*)W, bias, out, M, N, K,
-                        n_tiles, aux, (int)(epi_is_ln(EPI) ? (g_quad_defer && quad_defer_env()) : aux_i), aux2,
-                        keds_numerics_guard(), ntiles, g_x3_aplane, g_x3_wplane);
-            return keds_check_launch("gemm_bt_quad_kernel<persistent>");
-        }
-        if constexpr (epi_resid16(EPI)) {
-            if (g_quad3 && K >= 1024 && K / pr::TK >= 4) {               // long K: A operand through a three-deep ring
-                if (int rc = keds_func_lds_once((const void*)gemm_bt_quad3_kernel<EPI>, 5 * pr::OP_BYTES, "gemm_bt_quad3_kernel")) return rc;
-                rec_launch(KEDS_GEMM_FORM_QUAD3, 3, 1);
-                KEDS_LAUNCH((gemm_bt_quad3_kernel<EPI>), ntiles, 256, 5 * pr::OP_BYTES, st, (const bf16_t*)A, (const bf16_t*)W, bias, out, M, N, K,
-                            n_tiles, aux, ntiles);
-                return keds_check_launch("gemm_bt_quad3_kernel");
-            }
-        }
-        if (int rc = keds_func_lds_once((const void*)gemm_bt_quad_kernel<EPI>, qd::LDS_BYTES, "gemm_bt_quad_kernel")) return rc;
-        rec_launch(KEDS_GEMM_FORM_QUAD, 2, 1);
-        KEDS_LAUNCH((gemm_bt_quad_kernel<EPI>), ntiles, 256, qd::LDS_BYTES, st, (const bf16_t*)A, (const bf16_t*)W, bias, out, M, N, K, n_tiles,
-                    aux, aux_i, aux2, keds_numerics_guard(), ntiles, g_x3_aplane, g_x3_wplane);
-        return keds_check_launch("gemm_bt_quad_kernel");
-    }
-    if constexpr (epi_resid16(EPI)) {
-        if (g_resid_prologue) {
-            if (int rc = keds_func_lds_once((const void*)gemm_bt_pair_kernel<EPI, 0, 1>, pr::LDS_BYTES, "gemm_bt_pair_kernel")) return rc;
-            rec_launch(KEDS_GEMM_FORM_PAIR, 2, 1, 0, KEDS_GEMM_FLAG_RESID_PROLOGUE);
-            KEDS_LAUNCH((gemm_bt_pair_kernel<EPI, 0, 1>), m_tiles * n_tiles, 512, pr::LDS_BYTES, st,
-                        (const bf16_t*)A, (const bf16_t*)W, bias, out, M, N, K, n_tiles, aux, aux_i, aux2, keds_numerics_guard(), 0LL, 0LL);
-            return keds_check_launch("gemm_bt_pair_kernel");
-        }
-    }
-    rec_launch(KEDS_GEMM_FORM_PAIR, 2, 1);
-    KEDS_LAUNCH((gemm_bt_pair_kernel<EPI>), m_tiles * n_tiles, 512, pr::LDS_BYTES, st, (const bf16_t*)A, (const bf16_t*)W, bias, out,
-                M, N, K, n_tiles, aux, aux_i, aux2, keds_numerics_guard(), g_x3_aplane, g_x3_wplane);
-    return keds_check_launch("gemm_bt_pair_kernel");
-}
-
-int g_force_small = 0;   // test hook: route everything through the 128^2 kernel
-
-static int big_tiles_pct() {          // KEDS_BIG_TILES_PCT in the environment (A/B): the fill a 256^2 launch needs, default 85
-    static int v = -1;
-    if (v < 0) {
-        const char* e = keds_exp_env("KEDS_BIG_TILES_PCT");
-        v = e && e[0] ? atoi(e) : 85;
-    }
-    return v;
-}
-// (round 5) A launch whose rows are whole 256-row tiles (no remainder launch behind it) and whose K-loop is short needs only HALF
-// of its last round filled: the 128^2 kernel's alternative is four times the workgroups on 512 slots, and 11,008 x 768 x 768 (the
-// dual workload's 2B-row text pass at 43 columns: 516 workgroups, four more than fit at once) pays a whole second round for
-// them -- 60 us against 30 on 129 tiles of 256^2; in_proj 61 -> 43, c_fc 82 -> 70.  Not for long K (c_proj, K = 3072: 76 us on the
-// one-tile-per-workgroup kernel against 60).  profiles/r05_text_big_tiles_ab.txt
-bool big_tiles_ok(int M, int N, int K) {
-    const long bt = (long)(M / pr::TM) * (N / pr::TN);
-    const long rounds = (bt + 255) / 256;
-    int pct = big_tiles_pct();
-    if (pct == 85 && M % pr::TM == 0 && K <= 1024) pct = 50;
-    return !g_force_small && N % pr::TN == 0 && K % 64 == 0 && K >= 128 && bt > 0 && bt * 100 >= rounds * 256 * pct;
+    return false;
 }
 
 template <int EPI>
-int launch_gemm(const void* A, const void* W, const float* bias, void* out, int M, int N, int K, const float* aux,
-                int aux_i, void* aux2, long long lda, long long ldc, hipStream_t st) {
-    KedsProfScope prof(KEDS_PROF_GEMM, st, /*lazy: the launches bind the event pair (KEDS_LAUNCH)*/ true);
+int launch_gemm(GemmArgs a) {
+    const int M = a.M, N = a.N, K = a.K;
+    KedsProfScope prof(KEDS_PROF_GEMM, a.st, /*lazy: the launches bind the event pair (KEDS_LAUNCH)*/ true);
     prof.work(2.0 * M * N * K);
     tl_rec = GemmLaunchRecord{};
     tl_rec_slot = 0;
-    // Large problems: full 256-row tiles go to the 256^2 kernel, the remainder rows (< 256) to the 128^2 one.
-    // (ViT-L/14 at B=128: M = 32896 = 128*256 + 128, so 512..2048 big tiles = whole rounds on 256 CUs.)
-    // the 256^2 kernel runs one workgroup per CU: use it when its full tiles keep >= 85% of the CU-rounds busy (a single
-    // round counts: 19,712 x 768 x 3072 runs at 1.13 PF on 231 tiles vs 0.96 on 924 tiles of 128^2); otherwise the
-    // 128^2 kernel's finer tiles quantise better
-    const bool big_ok = big_tiles_ok(M, N, K) && lda == K && ldc == N && (epi_base(EPI) != KEDS_EPI_PATCH_F32 || M % pr::TM == 0) &&
-                        EPI != KEDS_EPI_BIAS_BF16_HEADF32;      // (its fp32 head rows are numbered from row 0 of the launch)
-    if (!big_ok) return launch_small<EPI>(A, W, bias, out, M, N, K, aux, aux_i, aux2, lda, ldc, st);
-    const int m_main = M / pr::TM * pr::TM;
-    int rc = launch_big<EPI>(A, W, bias, out, m_main, N, K, aux, aux_i, aux2, st);
-    if (rc || m_main == M || g_skip_tail) return rc;
-    tl_rec_slot = 1;
-    const size_t esz = (epi_base(EPI) == KEDS_EPI_BIAS_RESID_F32 || epi_base(EPI) == KEDS_EPI_BIAS_F32 || EPI == KEDS_EPI_RESID_STATS_F32)
-                           ? 4 : 2;
-    // the remainder launch numbers its rows from 0: move the per-row side buffers along
-    const float* aux_t = aux;
-    void* aux2_t = aux2;
-    if constexpr (epi_is_ln(EPI)) {
-        aux_t = (const float*)((const keds_stat_t*)aux + 2 * (size_t)m_main);
-        if (aux2) aux2_t = (keds_stat_t*)aux2 + 2 * (size_t)m_main;
-    } else if constexpr (EPI == KEDS_EPI_RESID_STATS_F32) {
-        aux_t = (const float*)((const keds_stat_t*)aux + 2 * (size_t)m_main);
-        aux2_t = (char*)aux2 + (size_t)m_main * N * 2;
-    } else if constexpr (epi_resid16(EPI)) {
-        if (aux) aux_t = (const float*)((const keds_stat_t*)aux + 2 * (size_t)m_main);
+    const GemmSwitches& sw = gemm_switches();
+    // the device's CU count and the split-K scratch sit behind a mutex each: asked for only by a shape whose plan reads them
+    const GemmPlanNeeds needs = gemm_plan_needs(EPI, M, N, K, a.lda, a.ldc, sw);
+    size_t splitk_bytes = 0;
+    if (needs.splitk) keds_splitk_scratch(&a.splitk, &splitk_bytes);
+    if (!a.splitk) splitk_bytes = 0;
+    const GemmPlan plan = gemm_plan(EPI, M, N, K, a.lda, a.ldc, needs.cus ? keds_device_cus() : 0, splitk_bytes, tl_small_lds != 0, sw);
+
+    a.M = plan.main.rows;
+    int rc = KEDS_OK;
+    const bool planned = plan.main.form == KEDS_GEMM_FORM_SMALL || !launch_unplanned<EPI>(a, sw, &rc);
+    if (planned) rc = launch_part<EPI>(a, plan.main);
+    if (rc) return rc;
+    if (plan.tail.form != KEDS_GEMM_FORM_NONE) {
+        tl_rec_slot = 1;
+        const size_t m_main = plan.main.rows;
+        const size_t esz = (epi_base(EPI) == KEDS_EPI_BIAS_RESID_F32 || epi_base(EPI) == KEDS_EPI_BIAS_F32 || EPI == KEDS_EPI_RESID_STATS_F32)
+                               ? 4 : 2;
+        // the remainder launch numbers its rows from 0: move the per-row side buffers along
+        if constexpr (epi_is_ln(EPI)) {
+            a.aux = (const float*)((const keds_stat_t*)a.aux + 2 * m_main);
+            if (a.aux2) a.aux2 = (keds_stat_t*)a.aux2 + 2 * m_main;
+        } else if constexpr (EPI == KEDS_EPI_RESID_STATS_F32) {
+            a.aux = (const float*)((const keds_stat_t*)a.aux + 2 * m_main);
+            a.aux2 = (char*)a.aux2 + m_main * N * 2;
+        } else if constexpr (epi_resid16(EPI)) {
+            if (a.aux) a.aux = (const float*)((const keds_stat_t*)a.aux + 2 * m_main);
+        }
+        a.A = (const char*)a.A + m_main * K * 2;
+        a.out = (char*)a.out + m_main * N * esz;
+        a.M = plan.tail.rows;
+        if ((rc = launch_part<EPI>(a, plan.tail))) return rc;
     }
-    return launch_small<EPI>((const char*)A + (size_t)m_main * K * 2, W, bias, (char*)out + (size_t)m_main * N * esz,
-                             M - m_main, N, K, aux_t, aux_i, aux2_t, lda, ldc, st);
+    // keds_gemm_last_launch reports what the launch sites recorded, not the plan: the two must agree
+    int want[8], got[8];
+    plan.info(want);
+    tl_rec.info(got);
+    for (int i = 0; planned && i < 8; ++i) {
+        if (got[i] != want[i]) {
+            keds_set_error("keds_gemm_bt: launched form differs from the plan at [%d]: %d, planned %d (epilogue %d, %d x %d x %d)", i, got[i],
+                           want[i], EPI, M, N, K);
+            return KEDS_E_LAUNCH;
+        }
+    }
+    return KEDS_OK;
 }
 
 }  // namespace
 
-// true when a dense [M,K] x [N,K]^T problem sends its full 256-row tiles to the 256^2 kernel (and M % 256 rows to a
-// second, small launch): the towers then run those remainder rows as their own chain on the side lane
-bool keds_gemm_splits_rows(int M, int N, int K) { return big_tiles_ok(M, N, K) && M % pr::TM != 0; }
-// (towers.hip) small GEMM launches of the calling thread take the 64 KiB-LDS kernel form while `on`
+// (keds_common.h) any epilogue, dense strides: what bf16_rows_split (towers.hip) asks per GEMM shape of a block
+bool keds_gemm_splits_rows(int M, int N, int K) { return gemm_big_tiles_fill(M, N, K, gemm_switches()) && M % 256 != 0; }
 void keds_gemm_small_lds(int on) { tl_small_lds = on; }
 
 extern "C" int keds_gemm_last_launch(int* info) {
     KEDS_REQUIRE(info, "keds_gemm_last_launch: null pointer");
-    const int v[8] = {tl_rec.form[0], tl_rec.form[1], tl_rec.ring[0], tl_rec.ring[1], tl_rec.splits[0], tl_rec.splits[1],
-                      tl_rec.persistent, tl_rec.flags};
-    for (int i = 0; i < 8; ++i) info[i] = v[i];
+    tl_rec.info(info);
     return KEDS_OK;
 }
 
 extern "C" int keds_gemm_force_small(int on) {
-    g_force_small = on & 1;
-    g_no_split = (on >> 9) & 1;         // bit 9: disable split-K (A/B tests)
-    g_skip_tail = (on >> 8) & 1;        // bit 8: timing-only, skip remainder rows
-    g_quad3 = !((on >> 16) & 1);        // bit 16: no three-deep A ring in the 4-wave residual GEMM (A/B)
-    g_quad_defer = !((on >> 17) & 1);   // bit 17: no deferred epilogue stores in the persistent 4-wave kernel (A/B)
-    g_quad = (on >> 11) & 3;            // bits 11-12: 256^2 tiles on the 4-wave kernel (1), its persistent form (2), 3 = never
-    if (g_quad == 0) g_quad = -1;       // (0 = the default: by shape)
-    if (g_quad == 3) g_quad = 0;
-    g_resid_prologue = (on >> 10) & 1;  // bit 10: fp16-residual GEMMs take residual + bias as the accumulators' initial value (A/B)
-    g_pair_stamp = (on >> 13) & 7;      // bits 13-15: stamped diagnostic build of the qkv / residual GEMMs (2: no statistics loads, 3: no stores, 4: no atomics, 5: no residual traffic at all)
+    gemm_switches() = gemm_switches_decode(on, gemm_env_switches());
+    return KEDS_OK;
+}
+
+// the shape rules of keds_gemm_bt_ex2 / keds_gemm_x3 (what the kernels and the planner rely on)
+static int gemm_check_shape(const char* who, int M, int N, int K, int64_t lda, int64_t ldc, int epilogue) {
+    KEDS_REQUIRE(M > 0 && N > 0 && K > 0, "%s: empty problem", who);
+    KEDS_REQUIRE(N % BN == 0, "%s: N=%d must be a multiple of %d", who, N, BN);
+    KEDS_REQUIRE(K % BK == 0, "%s: K=%d must be a multiple of %d", who, K, BK);
+    KEDS_REQUIRE(lda >= K && ldc >= N && lda % 8 == 0 && ldc % 8 == 0, "%s: bad row strides", who);
+    KEDS_REQUIRE(epi_base(epilogue) != KEDS_EPI_PATCH_F32 || ldc == N, "%s: EPI_PATCH needs a dense output", who);
+    return KEDS_OK;
+}
+
+extern "C" int keds_gemm_plan_query(int epilogue, int M, int N, int K, int64_t lda, int64_t ldc, int cus, size_t splitk_bytes,
+                                    int small_lds, int* info) {
+    KEDS_REQUIRE(info, "keds_gemm_plan_query: null pointer");
+    KEDS_REQUIRE(epilogue >= 0 && epilogue <= KEDS_EPI_BIAS_F32_H, "keds_gemm_plan_query: unknown epilogue %d", epilogue);
+    if (int rc = gemm_check_shape("keds_gemm_plan_query", M, N, K, lda, ldc, epilogue)) return rc;
+    gemm_plan(epilogue, M, N, K, lda, ldc, cus, splitk_bytes, small_lds != 0, gemm_switches()).info(info);
+    return KEDS_OK;
+}
+
+extern "C" int keds_gemm_plan_query_many(int64_t n, const int64_t* cases, int* info) {
+    KEDS_REQUIRE(n >= 0 && (n == 0 || (cases && info)), "keds_gemm_plan_query_many: bad argument");
+    for (int64_t i = 0; i < n; ++i) {
+        const int64_t* c = cases + 9 * i;
+        if (int rc = keds_gemm_plan_query((int)c[0], (int)c[1], (int)c[2], (int)c[3], c[4], c[5], (int)c[6], (size_t)c[7], (int)c[8], info + 8 * i))
+            return rc;
+    }
     return KEDS_OK;
 }
 
 extern "C" int keds_gemm_bt_ex2(const void* A, int64_t lda, const void* W, const float* bias, void* out, int64_t ldc,
                                 int M, int N, int K, int epilogue, const float* aux, int aux_i, void* aux2, void* stream) {
     KEDS_REQUIRE(A && W && out, "keds_gemm_bt: null pointer");
-    KEDS_REQUIRE(M > 0 && N > 0 && K > 0, "keds_gemm_bt: empty problem");
-    KEDS_REQUIRE(N % BN == 0, "keds_gemm_bt: N=%d must be a multiple of %d", N, BN);
-    KEDS_REQUIRE(K % BK == 0, "keds_gemm_bt: K=%d must be a multiple of %d", K, BK);
-    KEDS_REQUIRE(lda >= K && ldc >= N && lda % 8 == 0 && ldc % 8 == 0, "keds_gemm_bt: bad row strides");
-    KEDS_REQUIRE((epilogue != KEDS_EPI_PATCH_F32 && epilogue != KEDS_EPI_PATCH_F32_H) || ldc == N, "keds_gemm_bt: EPI_PATCH needs a dense output");
-    hipStream_t st = (hipStream_t)stream;
-#define KEDS_GEMM_CASE(E) case E: return launch_gemm<E>(A, W, bias, out, M, N, K, aux, aux_i, aux2, lda, ldc, st);
+    if (int rc = gemm_check_shape("keds_gemm_bt", M, N, K, lda, ldc, epilogue)) return rc;
+    // what each class of epilogue needs of the auxiliary arguments
+    if (epi_base(epilogue) == KEDS_EPI_PATCH_F32) KEDS_REQUIRE(aux && aux_i > 0, "keds_gemm_bt: EPI_PATCH needs the positional embedding and G");
+    if (epi_is_ln(epilogue)) KEDS_REQUIRE(bias && aux, "keds_gemm_bt: EPI_LN_* needs bias = [bias' | colsum] and aux = row statistics");
+    if (epilogue == KEDS_EPI_RESID_STATS_F32) KEDS_REQUIRE(aux && aux2, "keds_gemm_bt: EPI_RESID_STATS needs aux = statistics and aux2 = bf16 copy");
+    if (epilogue == KEDS_EPI_BIAS_BF16_HEADF32)
+        KEDS_REQUIRE(aux && aux_i >= 0, "keds_gemm_bt: EPI_BIAS_BF16_HEADF32 needs the fp32 head buffer and its row count");
+    if (epi_x3(epilogue)) {
+        keds_set_error("keds_gemm_bt: split-operand epilogues go through keds_gemm_x3");
+        return KEDS_E_ARG;
+    }
+    const GemmArgs g{A, W, bias, out, M, N, K, aux, aux_i, aux2, lda, ldc, (hipStream_t)stream, 0, 0, nullptr};
+#define KEDS_GEMM_CASE(E) case E: return launch_gemm<E>(g);
     switch (epilogue) {
         KEDS_GEMM_CASE(KEDS_EPI_BIAS_BF16)
         KEDS_GEMM_CASE(KEDS_EPI_BIAS_QGELU_BF16)
         KEDS_GEMM_CASE(KEDS_EPI_BIAS_RELU_BF16)
         KEDS_GEMM_CASE(KEDS_EPI_BIAS_RESID_F32)
         KEDS_GEMM_CASE(KEDS_EPI_BIAS_F32)
-        case KEDS_EPI_PATCH_F32:
-            KEDS_REQUIRE(aux && aux_i > 0, "keds_gemm_bt: EPI_PATCH needs the positional embedding and G");
-            return launch_gemm<KEDS_EPI_PATCH_F32>(A, W, bias, out, M, N, K, aux, aux_i, aux2, lda, ldc, st);
-        case KEDS_EPI_LN_BIAS_BF16:
-        case KEDS_EPI_LN_QGELU_BF16:
-        case KEDS_EPI_LN_BIAS_BF16_H:
-        case KEDS_EPI_LN_QGELU_BF16_H:
-            KEDS_REQUIRE(bias && aux, "keds_gemm_bt: EPI_LN_* needs bias = [bias' | colsum] and aux = row statistics");
-            if (epilogue == KEDS_EPI_LN_BIAS_BF16)
-                return launch_gemm<KEDS_EPI_LN_BIAS_BF16>(A, W, bias, out, M, N, K, aux, aux_i, aux2, lda, ldc, st);
-            if (epilogue == KEDS_EPI_LN_BIAS_BF16_H)
-                return launch_gemm<KEDS_EPI_LN_BIAS_BF16_H>(A, W, bias, out, M, N, K, aux, aux_i, aux2, lda, ldc, st);
-            if (epilogue == KEDS_EPI_LN_QGELU_BF16_H)
-                return launch_gemm<KEDS_EPI_LN_QGELU_BF16_H>(A, W, bias, out, M, N, K, aux, aux_i, aux2, lda, ldc, st);
-            return launch_gemm<KEDS_EPI_LN_QGELU_BF16>(A, W, bias, out, M, N, K, aux, aux_i, aux2, lda, ldc, st);
-        case KEDS_EPI_RESID_STATS_F32:
-            KEDS_REQUIRE(aux && aux2, "keds_gemm_bt: EPI_RESID_STATS needs aux = statistics and aux2 = bf16 copy");
-            return launch_gemm<KEDS_EPI_RESID_STATS_F32>(A, W, bias, out, M, N, K, aux, aux_i, aux2, lda, ldc, st);
+        KEDS_GEMM_CASE(KEDS_EPI_PATCH_F32)
+        KEDS_GEMM_CASE(KEDS_EPI_LN_BIAS_BF16)
+        KEDS_GEMM_CASE(KEDS_EPI_LN_QGELU_BF16)
+        KEDS_GEMM_CASE(KEDS_EPI_RESID_STATS_F32)
         KEDS_GEMM_CASE(KEDS_EPI_RESID_STATS_F16)
+        KEDS_GEMM_CASE(KEDS_EPI_LN_BIAS_BF16_H)
+        KEDS_GEMM_CASE(KEDS_EPI_LN_QGELU_BF16_H)
+        KEDS_GEMM_CASE(KEDS_EPI_BIAS_BF16_HEADF32)
         // the fp16 operating point (fp16 A and W)
+        KEDS_GEMM_CASE(KEDS_EPI_LN_BIAS_F16_H)
+        KEDS_GEMM_CASE(KEDS_EPI_LN_QGELU_F16_H)
         KEDS_GEMM_CASE(KEDS_EPI_RESID_STATS_F16_H)
         KEDS_GEMM_CASE(KEDS_EPI_BIAS_RESID_F32_H)
         KEDS_GEMM_CASE(KEDS_EPI_BIAS_QGELU_F16_H)
+        KEDS_GEMM_CASE(KEDS_EPI_PATCH_F32_H)
         KEDS_GEMM_CASE(KEDS_EPI_BIAS_F32_H)
-        case KEDS_EPI_PATCH_F32_H:
-            KEDS_REQUIRE(aux && aux_i > 0, "keds_gemm_bt: EPI_PATCH needs the positional embedding and G");
-            return launch_gemm<KEDS_EPI_PATCH_F32_H>(A, W, bias, out, M, N, K, aux, aux_i, aux2, lda, ldc, st);
-        case KEDS_EPI_LN_BIAS_F16_H:
-        case KEDS_EPI_LN_QGELU_F16_H:
-            KEDS_REQUIRE(bias && aux, "keds_gemm_bt: EPI_LN_* needs bias = [bias' | colsum] and aux = row statistics");
-            if (epilogue == KEDS_EPI_LN_BIAS_F16_H)
-                return launch_gemm<KEDS_EPI_LN_BIAS_F16_H>(A, W, bias, out, M, N, K, aux, aux_i, aux2, lda, ldc, st);
-            return launch_gemm<KEDS_EPI_LN_QGELU_F16_H>(A, W, bias, out, M, N, K, aux, aux_i, aux2, lda, ldc, st);
-        case KEDS_EPI_BIAS_BF16_HEADF32:
-            KEDS_REQUIRE(aux && aux_i >= 0, "keds_gemm_bt: EPI_BIAS_BF16_HEADF32 needs the fp32 head buffer and its row count");
-            return launch_gemm<KEDS_EPI_BIAS_BF16_HEADF32>(A, W, bias, out, M, N, K, aux, aux_i, aux2, lda, ldc, st);
-        case KEDS_EPI_X3_BIAS_F32:
-        case KEDS_EPI_X3_RESID_F32:
-        case KEDS_EPI_X3_QGELU_PAIR:
-            keds_set_error("keds_gemm_bt: split-operand epilogues go through keds_gemm_x3");
-            return KEDS_E_ARG;
         default: keds_set_error("keds_gemm_bt: unknown epilogue %d", epilogue); return KEDS_E_ARG;
     }
 #undef KEDS_GEMM_CASE
@@ -2165,18 +2120,15 @@ extern "C" int keds_gemm_x3(const void* a, int64_t a_plane, int64_t lda, const v
     // buffer offsets are 32-bit: a plane must be reachable from a tile's first row
     KEDS_REQUIRE(a_plane > 0 && w_plane > 0 && a_plane * 2 + 256LL * lda * 2 < (1LL << 31) && w_plane * 2 + 256LL * K * 2 < (1LL << 31),
                  "keds_gemm_x3: plane strides out of range");
-    hipStream_t st = (hipStream_t)stream;
-    g_x3_aplane = a_plane;
     KEDS_REQUIRE(w_exp >= -100 && w_exp <= 100, "keds_gemm_x3: w_exp %d out of range", w_exp);
-    g_x3_wplane = x3_pack_wplane(w_plane, w_exp);
+    const GemmArgs g{a, w, bias, out, M, N, K, nullptr, epilogue == KEDS_EPI_X3_QGELU_PAIR ? aux_i : 0, nullptr, lda, ldc, (hipStream_t)stream,
+                     a_plane, x3_pack_wplane(w_plane, w_exp), nullptr};
     switch (epilogue) {
-        case KEDS_EPI_X3_BIAS_F32:
-            return launch_gemm<KEDS_EPI_X3_BIAS_F32>(a, w, bias, out, M, N, K, nullptr, 0, nullptr, lda, ldc, st);
-        case KEDS_EPI_X3_RESID_F32:
-            return launch_gemm<KEDS_EPI_X3_RESID_F32>(a, w, bias, out, M, N, K, nullptr, 0, nullptr, lda, ldc, st);
+        case KEDS_EPI_X3_BIAS_F32: return launch_gemm<KEDS_EPI_X3_BIAS_F32>(g);
+        case KEDS_EPI_X3_RESID_F32: return launch_gemm<KEDS_EPI_X3_RESID_F32>(g);
         case KEDS_EPI_X3_QGELU_PAIR:
             KEDS_REQUIRE(aux_i > 0, "keds_gemm_x3: KEDS_EPI_X3_QGELU_PAIR needs the output planes' stride");
-            return launch_gemm<KEDS_EPI_X3_QGELU_PAIR>(a, w, bias, out, M, N, K, nullptr, aux_i, nullptr, lda, ldc, st);
+            return launch_gemm<KEDS_EPI_X3_QGELU_PAIR>(g);
         default: keds_set_error("keds_gemm_x3: epilogue %d is not a split-operand epilogue", epilogue); return KEDS_E_ARG;
     }
 }

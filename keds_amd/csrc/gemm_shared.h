@@ -3,6 +3,15 @@
 #pragma once
 #include "keds_common.h"
 #include <math.h>
+#include "gemm_plan.h"      // the epilogue classes (epi_*), shared with the host-only planner
+
+#ifdef KEDS_EXPERIMENTS
+// tools/experiments/gemm_duo.hip (round 5, a measured negative: docs/findings_r05.md section 1): the two-accumulator-set kernel
+// (LayerNorm-folded epilogues under the next unit's MFMAs); only the experiment build links it
+bool keds_gemm_duo_ok(int epi, int M, int N, int K);
+int keds_gemm_duo_launch(int epi, const void* A, const void* W, const float* bias, void* out, int M, int N, int K, const float* aux,
+                         void* aux2, hipStream_t st);
+#endif
 
 namespace {
 
@@ -18,36 +27,6 @@ __device__ __forceinline__ int perm_w(int R) {
     return 64 * (t >> 2) + 32 * ((t >> 1) & 1) + 8 * (i >> 2) + 4 * (t & 1) + (i & 3);
 }
 
-// KEDS_EPI_LN_*_H: the same epilogues with fp16 operands (A = the fp16 residual stream, W' folded to fp16)
-// KEDS_EPI_X3_*: split-operand GEMMs (keds_hip.h): fp16 MFMA, three K segments (hi.hi, hi.lo, lo.hi) over two operand planes
-constexpr bool epi_x3(int e) { return e == KEDS_EPI_X3_BIAS_F32 || e == KEDS_EPI_X3_RESID_F32 || e == KEDS_EPI_X3_QGELU_PAIR; }
-// KEDS_EPI_*_F16_H / *_F32_H ("fp16" operating point): fp16 A and W; the LN / QuickGELU forms store fp16 (range-guarded)
-constexpr bool epi_ln_h(int e) {
-    return e == KEDS_EPI_LN_BIAS_BF16_H || e == KEDS_EPI_LN_QGELU_BF16_H || e == KEDS_EPI_LN_BIAS_F16_H || e == KEDS_EPI_LN_QGELU_F16_H;
-}
-constexpr bool epi_h16(int e) {        // the fp16 operating point's own ids (16..22)
-    return e == KEDS_EPI_LN_BIAS_F16_H || e == KEDS_EPI_LN_QGELU_F16_H || e == KEDS_EPI_RESID_STATS_F16_H || e == KEDS_EPI_BIAS_RESID_F32_H ||
-           e == KEDS_EPI_BIAS_QGELU_F16_H || e == KEDS_EPI_PATCH_F32_H || e == KEDS_EPI_BIAS_F32_H;
-}
-constexpr bool epi_f16(int e) { return epi_ln_h(e) || epi_x3(e) || epi_h16(e); }          // fp16 (not bf16) MFMA operands
-constexpr bool epi_is_ln(int e) { return e == KEDS_EPI_LN_BIAS_BF16 || e == KEDS_EPI_LN_QGELU_BF16 || epi_ln_h(e); }
-// the fp16-residual epilogue (residual stream read-modify-written in fp16 + row statistics), bf16 or fp16 A / W
-constexpr bool epi_resid16(int e) { return e == KEDS_EPI_RESID_STATS_F16 || e == KEDS_EPI_RESID_STATS_F16_H; }
-// library-internal: the plain fp16-output store the LN-folded fp16 epilogue ends in (no public id)
-constexpr int EPI_INT_BIAS_F16 = 100;
-constexpr int epi_base(int e) {
-    return (e == KEDS_EPI_LN_BIAS_BF16 || e == KEDS_EPI_LN_BIAS_BF16_H)     ? KEDS_EPI_BIAS_BF16
-           : (e == KEDS_EPI_LN_QGELU_BF16 || e == KEDS_EPI_LN_QGELU_BF16_H) ? KEDS_EPI_BIAS_QGELU_BF16
-           : e == KEDS_EPI_LN_BIAS_F16_H                                    ? EPI_INT_BIAS_F16
-           : e == KEDS_EPI_LN_QGELU_F16_H                                   ? KEDS_EPI_BIAS_QGELU_F16_H
-           : e == KEDS_EPI_X3_BIAS_F32 || e == KEDS_EPI_BIAS_F32_H          ? KEDS_EPI_BIAS_F32
-           : e == KEDS_EPI_X3_RESID_F32 || e == KEDS_EPI_BIAS_RESID_F32_H   ? KEDS_EPI_BIAS_RESID_F32
-           : e == KEDS_EPI_PATCH_F32_H                                      ? KEDS_EPI_PATCH_F32
-                                                                            : e;
-}
-constexpr bool epi_qgelu(int e) { return epi_base(e) == KEDS_EPI_BIAS_QGELU_BF16 || epi_base(e) == KEDS_EPI_BIAS_QGELU_F16_H; }
-// epilogues that store fp16 values: the range guard applies (|v| > 65504 or non-finite raises the numerics-guard flag)
-constexpr bool epi_out_f16(int e) { return epi_base(e) == EPI_INT_BIAS_F16 || epi_base(e) == KEDS_EPI_BIAS_QGELU_F16_H; }
 // running maximum of |v| as bit patterns: NaN patterns lie above inf, so one unsigned compare catches both
 __device__ __forceinline__ unsigned f16_range_max(unsigned mx, f32x4 a, f32x4 b) {
 #pragma unroll

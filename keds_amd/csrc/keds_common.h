@@ -148,6 +148,13 @@ void keds_splitk_scratch(float** p, size_t* bytes);   // innermost scope of this
 // ---- numerics guard (host): device int32 flag of the calling thread's current composite call, or nullptr -----------
 int* keds_numerics_guard();
 
+// ---- GEMM dispatch as the composites see it (gemm.hip; the rules: gemm_plan.h) ------------------------------------------------
+// true when a dense [M,K] x [N,K]^T problem sends its full 256-row tiles to a 256^2 kernel and its M % 256 rows to a second, small
+// launch: the towers then run those remainder rows as their own chain on the side lane
+bool keds_gemm_splits_rows(int M, int N, int K);
+// 128^2 GEMM launches of the calling thread take the 64 KiB-LDS kernel form while `on`
+void keds_gemm_small_lds(int on);
+
 // ---- output-tile stores (device) -----------------------------------------------------------------------------------
 // 16-byte store of an output tile that ANOTHER kernel reads next.  Policy per site class, compile-time (same-box A/B:
 // tools/ab_nt.sh rebuilds with -DKEDS_ST_<class>=<policy>):

@@ -19,9 +19,6 @@ int keds_embed_tokens_impl(const int32_t* tokens, const float* table, const floa
                            int n_tok, int insert_col, float* x, int B, int L, int Lx, int d, void* stream,
                            const int32_t* seq_off = nullptr);
 
-bool keds_gemm_splits_rows(int M, int N, int K);   // gemm.hip
-void keds_gemm_small_lds(int on);                  // gemm.hip: small GEMM launches of this thread take the 64 KiB-LDS kernel form
-
 // f32path.hip: the fp32-accurate flow (keds_tower_params.f32)
 size_t keds_tower_f32_workspace_bytes(int width, int seq, int B);
 int keds_tower_forward_f32(const keds_tower_params* p, float* x, int B, void* ws, hipStream_t st, const int32_t* last_rows = nullptr,
@@ -739,7 +736,7 @@ extern "C" int keds_text_run_packed(const keds_text_params* p, const int32_t* to
     v = carve_text_cols(p, B, seq_max, workspace);
     // the tower runs WHOLE 256-row tiles: the rows between rows_total and the next multiple of 256 are zero rows that belong to no
     // sample (no attention reads them, nothing gathers them).  A ragged last tile would send every GEMM of every block through the
-    // remainder-row launches and the stricter fill rule of the 256 x 256 kernels (gemm.hip, big_tiles_ok).
+    // remainder-row launches and the stricter fill rule of the 256 x 256 kernels (gemm_plan.h, gemm_big_tiles_fill).
     int rows_run = (rows_total + 255) / 256 * 256;
     if ((size_t)rows_run > pad_rows((size_t)B * seq_max)) rows_run = rows_total;
     if (rows_run > rows_total &&
