@@ -271,6 +271,11 @@ int keds_gemm_mxfp8(const void* Aq, const void* As, int m_pad, const void* Wq, c
 int keds_gemm_mxfp8_ex(const void* Aq, const void* As, int m_pad, const void* Wq, const void* Ws, int n_pad,
                        const float* bias, void* out, int M, int N, int K, int epilogue, float* aux, float* aux2,
                        void* qout, void* qscale, int q_pad, void* stream);
+/* What the last keds_gemm_mxfp8 / keds_gemm_mxfp8_ex call of this thread launched (thread-local, written at the launch sites; all
+ * zero after a call that launched nothing): info[4] = {form, grid size, 256 x 256 tiles, persistent (grid < tiles)}. */
+#define KEDS_FP8_FORM_PAIR 1    /* gemm_mxfp8_kernel: 8 waves, one tile per workgroup */
+#define KEDS_FP8_FORM_QUAD 2    /* gemm_mxfp8_quad_kernel: 4 waves, one tile per workgroup or persistent */
+int keds_gemm_mxfp8_last_launch(int* info);
 /* Weight preparation for the fp8 tower: W fp32 [N,K] (times diag(gamma) when a LayerNorm is folded in) -> MXFP8 wq / wscale,
  * bias_csum fp32 [2N] = [bias + W beta | row sums of the dequantised weight].  gamma = beta = NULL: plain quantisation. */
 int keds_fold_layernorm_mxfp8(const float* W, const float* bias, const float* gamma, const float* beta, int N, int K,

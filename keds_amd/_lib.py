@@ -191,6 +191,7 @@ SIGNATURES = {
     "keds_quantize_mxfp8": (i32, [vp, i32, i32, i32, i32, vp, vp, vp]),
     "keds_gemm_mxfp8": (i32, [vp, vp, i32, vp, vp, i32, vp, vp, i32, i32, i32, vp]),
     "keds_gemm_mxfp8_ex": (i32, [vp, vp, i32, vp, vp, i32, vp, vp, i32, i32, i32, i32, vp, vp, vp, vp, i32, vp]),
+    "keds_gemm_mxfp8_last_launch": (i32, [vp]),
     "keds_fold_layernorm_mxfp8": (i32, [vp, vp, vp, vp, i32, i32, i32, vp, vp, vp, vp]),
     "keds_gemm_bt_ex": (i32, [vp, i64, vp, vp, vp, i64, i32, i32, i32, i32, vp, i32, vp]),
     "keds_layernorm": (i32, [vp, i64, vp, vp, vp, i32, i32, i32, vp]),

@@ -969,11 +969,19 @@ extern "C" int keds_quantize_mxfp8(const void* x, int x_is_bf16, int rows, int K
 }
 
 namespace {
+// What the last keds_gemm_mxfp8* call of this thread launched (keds_gemm_mxfp8_last_launch, keds_hip.h): written at the two launch
+// sites with the literal form of the kernel launched there, in the spirit of gemm.hip's record
+struct Fp8LaunchRecord {
+    int form, grid, tiles;
+};
+thread_local Fp8LaunchRecord tl_fp8_rec = {};
+
 template <int EPI, int DBG>
 int launch_mxfp8(const void* Aq, const void* As, int m_pad, const void* Wq, const void* Ws, int n_pad, const float* bias,
                  void* out, int M, int N, int K, float* aux, float* aux2, void* qout, void* qscale, int q_pad, hipStream_t st) {
     if (int rc = keds_func_lds_once((const void*)gemm_mxfp8_kernel<EPI, DBG>, LDS_BYTES, "gemm_mxfp8_kernel")) return rc;
     const int m_tiles = M / TM, n_tiles = N / TN;
+    tl_fp8_rec = Fp8LaunchRecord{KEDS_FP8_FORM_PAIR, m_tiles * n_tiles, m_tiles * n_tiles};
     KEDS_LAUNCH((gemm_mxfp8_kernel<EPI, DBG>), m_tiles * n_tiles, 512, LDS_BYTES, st,
                 (const unsigned char*)Aq, (const unsigned char*)As, (const unsigned char*)Wq, (const unsigned char*)Ws, bias, out, M, N, K,
                 n_tiles, m_pad, n_pad, aux, aux2, (unsigned char*)qout, (unsigned char*)qscale, q_pad);
@@ -1001,6 +1009,7 @@ int launch_mxfp8_quad(const void* Aq, const void* As, int m_pad, const void* Wq,
     // small launches slot in between them: the GEMM class takes 0.5 ms more per step, the gaps in front of the attention launches
     // shrink by as much -- 14.87-15.06 against 14.92-15.00 ms per step, four alternating runs on one box)
     const int grid = (cus >= 8 && ntiles > cus) ? cus : ntiles;
+    tl_fp8_rec = Fp8LaunchRecord{KEDS_FP8_FORM_QUAD, grid, ntiles};
     KEDS_LAUNCH((gemm_mxfp8_quad_kernel<EPI>), grid, 256, fq::LDS_BYTES, st,
                 (const unsigned char*)Aq, (const unsigned char*)As, (const unsigned char*)Wq, (const unsigned char*)Ws, bias, out, M, N, K,
                 n_tiles, m_pad, n_pad, aux, aux2, (unsigned char*)qout, (unsigned char*)qscale, q_pad, ntiles);
@@ -1011,6 +1020,7 @@ int launch_mxfp8_quad(const void* Aq, const void* As, int m_pad, const void* Wq,
 extern "C" int keds_gemm_mxfp8_ex(const void* Aq, const void* As, int m_pad, const void* Wq, const void* Ws, int n_pad,
                                   const float* bias, void* out, int M, int N, int K, int epilogue, float* aux, float* aux2,
                                   void* qout, void* qscale, int q_pad, void* stream) {
+    tl_fp8_rec = Fp8LaunchRecord{};               // a call that launches nothing records nothing
     KEDS_REQUIRE(Aq && As && Wq && Ws, "keds_gemm_mxfp8: null pointer");
     KEDS_REQUIRE(M > 0 && M % TM == 0 && N > 0 && N % TN == 0, "keds_gemm_mxfp8: M and N must be multiples of 256 (M=%d N=%d)", M, N);
     KEDS_REQUIRE(K % TKB == 0 && K >= 2 * TKB, "keds_gemm_mxfp8: K=%d must be a multiple of 128, >= 256", K);
@@ -1051,6 +1061,15 @@ extern "C" int keds_gemm_mxfp8_ex(const void* Aq, const void* As, int m_pad, con
         default: keds_set_error("keds_gemm_mxfp8: unknown epilogue %d", epilogue); return KEDS_E_ARG;
     }
 #undef KEDS_FP8_GO
+}
+
+extern "C" int keds_gemm_mxfp8_last_launch(int* info) {
+    KEDS_REQUIRE(info, "keds_gemm_mxfp8_last_launch: null pointer");
+    info[0] = tl_fp8_rec.form;
+    info[1] = tl_fp8_rec.grid;
+    info[2] = tl_fp8_rec.tiles;
+    info[3] = tl_fp8_rec.grid < tl_fp8_rec.tiles;
+    return KEDS_OK;
 }
 
 extern "C" int keds_gemm_mxfp8(const void* Aq, const void* As, int m_pad, const void* Wq, const void* Ws, int n_pad,

@@ -10,6 +10,7 @@ import pytest
 import torch
 
 from keds_amd import _lib
+from tests import mx_check
 from tests.gpu_util import rel_l2, report
 
 pytestmark = pytest.mark.gpu
@@ -57,6 +58,77 @@ def test_quantizer_matches_ocp_mx_rule(rows, K, dtype):
     err = rel_l2(_dequantize(q, s), x.float())
     report("mxfp8_quantizer", rows=rows, K=K, rel_l2=err)
     assert err <= 6e-2
+
+
+def _edge_blocks(dtype):
+    """constructed 32-element blocks at the edges of the OCP MX rule, [rows, 256] (eight blocks a row) of `dtype`: per scale 2^s --
+    amax exactly 2^n | one ulp (of the input type) below it | entries in (448, 512) 2^E, which saturate | exact ties between e4m3
+    neighbours, normal and subnormal, entries below half the smallest subnormal, of both signs | an all-zero block -- and one block
+    of fp32 denormals (the exponent clamps at -127, the bytes are zero)"""
+    g = torch.Generator().manual_seed(3)
+    fill = lambda: torch.randint(-100, 101, (32,), generator=g).double()                      # noqa: E731
+    below = 256.0 * (1 - 2.0 ** -24) if dtype == torch.float32 else 255.0
+    blocks = []
+    for s in (-20, 0, 9, 40):
+        pow2, under, sat, ties = fill(), fill(), fill(), torch.zeros(32, dtype=torch.float64)
+        pow2[3], under[3] = 256.0, below
+        sat[:8] = torch.tensor([450.0, -470.0, 500.0, 510.0, 448.0, -452.0, 300.0, -511.0 if dtype == torch.float32 else -508.0])
+        ties[:20] = torch.tensor([256.0, 17.0, -17.0, 34.0, 38.0, 1.0625, 1.1875, -1.1875, 2.0 ** -10, -2.0 ** -10, 3 * 2.0 ** -10, 0.4 * 2.0 ** -9,
+                                  -0.4 * 2.0 ** -9, 1.25 * 2.0 ** -10, 5 * 2.0 ** -9, 2.0 ** -6, 2.0 ** -6 - 2.0 ** -10, -(2.0 ** -6 + 2.0 ** -10), 240.0, -208.0])
+        blocks += [b * 2.0 ** s for b in (pow2, under, sat, ties, torch.zeros(32, dtype=torch.float64))]
+    den = torch.zeros(32, dtype=torch.float64)
+    den[:3] = torch.tensor([2.0 ** -130, 2.0 ** -133, 2.0 ** -131])
+    blocks.append(den)
+    blocks += [torch.zeros(32, dtype=torch.float64)] * (-len(blocks) % 8)
+    return torch.stack(blocks).reshape(-1, 256).to(dtype).cuda()
+
+
+@pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16], ids=["fp32", "bf16"])
+def test_quantizer_edges_bit_for_bit(dtype):
+    """keds_quantize_mxfp8 on the constructed blocks against mx_check.quantize, the frexp-based restatement of the rule (floor(log2)
+    from the exponent field: torch.log2 rounds 2 - 2^-23 up to 1.0 in fp32), with rows_pad > rows: the scale slabs' pad rows and the
+    rows behind the output keep their sentinel"""
+    lib = _lib.load()
+    x = _edge_blocks(dtype)
+    rows, K = x.shape
+    assert rows % 4 != 0                                           # the last workgroup has rows to skip
+    rows_pad = rows + 5
+    q = torch.full((rows + 4, K), 0xAB, dtype=torch.uint8, device="cuda")
+    s = torch.full((K // 128, rows_pad, 4), 0xCD, dtype=torch.uint8, device="cuda")
+    _lib.check(lib.keds_quantize_mxfp8(_lib.ptr(x), 1 if dtype == torch.bfloat16 else 0, rows, K, rows_pad, _lib.ptr(q), _lib.ptr(s),
+                                       _lib.stream()), "quantize")
+    wq, we = mx_check.quantize(x.float())
+    assert int(we.min()) == -127 and int((wq & 0x7F).max()) == 0x7E                   # the clamp and the saturation are in the data
+    assert torch.equal(mx_check.unpack_scales(s, rows), we)
+    assert torch.equal(q[:rows], wq)
+    assert bool((q[rows:] == 0xAB).all()) and bool((s[:, rows:, :] == 0xCD).all())
+    assert bool((q[:rows].reshape(rows, 8, 32)[we == -127] == 0).all())               # zero and denormal blocks: zero bytes
+
+
+def test_fold_layernorm_mxfp8_edges_bit_for_bit():
+    """keds_fold_layernorm_mxfp8 quantises W diag(gamma) by the same rule: the constructed blocks as W, plain and with a gamma of
+    powers of two (W / gamma is exact, so the product the kernel rounds is the block itself), n_pad > N"""
+    lib = _lib.load()
+    x = _edge_blocks(torch.float32)
+    N, K = x.shape
+    n_pad = N + 7
+    wq_want, we_want = mx_check.quantize(x)
+    gamma = torch.exp2((torch.arange(K, device="cuda") % 5 - 2).float())
+    for w, gm, bt in ((x, None, None), (x / gamma, gamma, torch.zeros(K, device="cuda"))):
+        w = w.contiguous()
+        if gm is not None:
+            keep = torch.isfinite(w).all(1) & ((w * gamma) == x).all(1)                # (a row whose 2^-133 / gamma left the fp32 range)
+        else:
+            keep = torch.ones(N, dtype=torch.bool, device="cuda")
+        assert int(keep.sum()) >= N - 1
+        wq = torch.full((N + 4, K), 0xAB, dtype=torch.uint8, device="cuda")
+        ws = torch.full((K // 128, n_pad, 4), 0xCD, dtype=torch.uint8, device="cuda")
+        bc = torch.zeros(2 * N, device="cuda")
+        _lib.check(lib.keds_fold_layernorm_mxfp8(_lib.ptr(w), None, _lib.ptr(gm), _lib.ptr(bt), N, K, n_pad, _lib.ptr(wq), _lib.ptr(ws),
+                                                 _lib.ptr(bc), _lib.stream()), "fold fp8")
+        assert torch.equal(mx_check.unpack_scales(ws, N)[keep], we_want[keep])
+        assert torch.equal(wq[:N][keep], wq_want[keep])
+        assert bool((wq[N:] == 0xAB).all()) and bool((ws[:, N:, :] == 0xCD).all())
 
 
 @pytest.mark.parametrize("M,N,K", [(256, 256, 256), (512, 768, 1024), (2048, 1024, 4096)])
