@@ -638,7 +638,11 @@ __global__ __launch_bounds__(256) void split_f16_pair_kernel(const float* __rest
     bool bad = false;
 #pragma unroll
     for (int j = 0; j < 8; ++j) {
-        const float v = (j < 4 ? a[j] : b[j - 4]) * scale;
+        float v = (j < 4 ? a[j] : b[j - 4]) * scale;
+        // hi = fp16(v) and lo = fp16(v - hi) as IEEE evaluates them, on ONE rounded product v: left to see the multiply, the compiler
+        // contracts v - hi into fma(x, scale, -hi') and takes hi' from a mixed-precision fma(x, scale, +0) -- for x = -0 that is +0 beside
+        // the stored hi = -0, and lo came out -0 where v - hi is +0 (tests/test_gpu_x3_gemm_edges.py compares the planes bit for bit)
+        asm volatile("" : "+v"(v));
         bad |= !(fabsf(v) < 65504.0f);
         hi[j] = (f16_t)v;
         lo[j] = (f16_t)(v - (float)hi[j]);

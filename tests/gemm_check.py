@@ -52,7 +52,32 @@ one rounding more) + (N / 8) 2^-29 (one fixed-point rounding per partial sum add
 the statistics were taken of: every value may then differ by u |x| (+ 2^-25), which is added.
 
 CPU model: emulate() accumulates per 64-wide K-tile in fp32, forwards or backwards, in 1 .. 16 split-K slices summed in fp32, and
-applies the epilogue's fp32 operations as the kernels order them.  MUTATIONS are deliberate defects of it."""
+applies the epilogue's fp32 operations as the kernels order them.  MUTATIONS are deliberate defects of it.
+
+fp32 operands (keds_gemm_f32, gemm_f32_kernel of f32path.hip): Case(..., torch.float32) with the epilogue table F32_EPILOGUES (the
+KEDS_F32_EPI_* codes 0 - 4 collide with the bf16 codes; epilogues(case) picks the table).  K-tiles of 16.  The bound is the one above:
+C_ACC (K + 16) u32 S covers a chain of K multiply-adds, fused or not.  Regimes integer (exact), random, tail, head.
+
+Split operands (keds_gemm_x3, epilogues 13 - 15 = X3_EPILOGUES): X3Case is built directly in the kernel's format, four fp16 planes
+ah, al [M, K], wh, wl [N, K] and an exponent w_exp; what the kernel is specified to compute is
+    acc = (ah wh^T + ah wl^T + al wh^T) 2^-w_exp,     S = (|ah| |wh|^T + |ah| |wl|^T + |al| |wh|^T) 2^-w_exp
+in a K-loop of 3 K / 64 tiles (segment 0 hi.hi, 1 hi.lo, 2 lo.hi).  fp16 x fp16 products are exact in fp32, so the bound carries over
+with e_acc = C_ACC (3 K + 16) u32 S.  The kernel cannot know whether its planes are a true split, so the planes are drawn
+INDEPENDENTLY in every regime but `split`: each segment then weighs the same and a wrong plane, a wrong K offset at a seam or a
+fourth lo.lo segment is gross.
+  integer  all four planes, bias and residual small integers (_int_amp), S 2^w_exp + 32 < 2^24 asserted; 2^-w_exp is an exact
+           scaling: epilogues 13 and 14 to the bit, for any w_exp
+  random   independent N(0, 1) / N(0, 1 / K) 2^w_exp planes
+  spike    random, with K-tile p of the 3 K / 64 carrying the output (about half of S up to K = 1024; spike_share): p in segment 0
+           scales that tile's columns of both hi planes by 2^3, in segment 1 wl's by 2^6, in segment 2 al's by 2^6
+  split    true splits of fp32 data (A ~ 2 N(0, 1) with every 97th column x 30, W ~ std N(0, 1)) made by `splitter` -- the
+           library's own split kernels on the GPU, their torch evaluation split_ref / weight_exp_ref here.  The reference is the
+           FULL product (ah + al) (wh + wl)^T 2^-w_exp and the bound gets the dropped term |al| |wl|^T 2^-w_exp added: the
+           fp32-grade claim, per element.
+  rowscale (any regime but integer) A's rows x 2^6 on every other 256-row tile: a prefetched K-tile of the wrong tile is gross.
+X3_QGELU_PAIR: hi + lo against the reference within e (1 + 2 u) + 2^-22 |ref| + 2^-25 + 2^-126 (hi rounded to 11 bits, the
+remainder to 11 more, a subnormal lo absolutely), and |lo| <= ulp_fp16(hi) / 2 per element: the planes are a split, not two numbers
+that happen to sum right.  X3_MUTATIONS are the defects of the split-operand loop."""
 import math
 
 import torch
@@ -98,6 +123,14 @@ NAMES = {0: "BIAS_BF16", 1: "BIAS_QGELU_BF16", 2: "BIAS_RELU_BF16", 3: "BIAS_RES
          16: "LN_BIAS_F16_H", 17: "LN_QGELU_F16_H", 18: "RESID_STATS_F16_H", 19: "BIAS_RESID_F32_H", 20: "BIAS_QGELU_F16_H",
          21: "PATCH_F32_H", 22: "BIAS_F32_H"}
 LINEAR = ("bias", "relu", "resid", "patch", "headf32", "resid_stats")       # exact in the integer regime
+# the fp32-operand kernel's own codes (KEDS_F32_EPI_*) and the split-operand ones (keds_gemm_x3)
+F32_EPILOGUES = {0: (F32, F32, "bias"), 1: (F32, F32, "qgelu"), 2: (F32, F32, "resid"), 3: (F32, F32, "relu"), 4: (F32, F32, "patch")}
+F32_NAMES = {0: "F32_BIAS", 1: "F32_QGELU", 2: "F32_RESID", 3: "F32_RELU", 4: "F32_PATCH"}
+F32_REGIMES = ("integer", "random", "tail", "head")
+X3_EPILOGUES = {13: (HF, F32, "bias"), 14: (HF, F32, "resid"), 15: (HF, HF, "qgelu_pair")}
+X3_NAMES = {13: "X3_BIAS_F32", 14: "X3_RESID_F32", 15: "X3_QGELU_PAIR"}
+X3_REGIMES = ("integer", "random", "spike", "split")
+X3_MUTATIONS = ("x3_drop_lo", "x3_stale_lo", "x3_hi_for_lo", "x3_koff_runs_on", "x3_lo_lo", "x3_scale_after_bias", "x3_lo_zero", "drop_store")
 MUTATIONS = ("drop_ktile", "stale_ktile", "swap_rows", "shift_side", "bias_per_slice", "drop_store", "resid_twice", "ln_row_plus1",
              "stats_miss16", "stats_twice")
 
@@ -114,9 +147,10 @@ class Case:
     LayerNorm side data of A's rows: stats int64 [M, 2] (fixed point), csum fp32 [N] (row sums of W), mean, var, rstd float64 [M, 1]."""
 
     def __init__(self, M, N, K, regime, dtype, seed=0, device="cpu"):
-        assert K % TILE_K == 0 and N % 8 == 0 and regime in REGIMES
+        self.tile_k = 16 if dtype == F32 else TILE_K               # gemm_f32_kernel walks K in tiles of 16
+        assert K % self.tile_k == 0 and N % 8 == 0 and regime in REGIMES
         self.M, self.N, self.K, self.regime, self.dtype, self.device = M, N, K, regime, dtype, device
-        self.name = f"{M}x{N}x{K}.{regime}.{'bf16' if dtype == BF else 'fp16'}"
+        self.name = f"{M}x{N}x{K}.{regime}.{ {BF: 'bf16', HF: 'fp16', F32: 'fp32'}[dtype]}"
         g = torch.Generator(device=device).manual_seed(seed * 1000003 + M * 7919 + N * 31 + K)      # (drawn on `device`: seeded per device type)
         kw = dict(generator=g, device=device)
         if regime == "integer":
@@ -179,15 +213,142 @@ class Case:
     def patch_out_rows(self):
         return (self.M + PATCH_G - 1) // PATCH_G * (PATCH_G + 1)
 
+    def without_bias(self):
+        """the same case for a launch with bias = NULL (fp32-operand kernel): shares every tensor but the bias"""
+        c = Case.__new__(Case)
+        c.__dict__.update(self.__dict__)
+        c.bias, c.name = torch.zeros_like(self.bias), self.name + ".nobias"
+        c.__dict__.pop("_model_acc", None)
+        return c
+
+
+def split_ref(x, e=0):
+    """what keds_split_f16_pair (e = 0) / keds_split_f16_weight compute, in IEEE arithmetic: hi = fp16(x 2^e), lo = fp16(x 2^e - hi)"""
+    s = x.float() * torch.tensor(2.0 ** e, dtype=torch.float32, device=x.device)
+    hi = s.half()
+    return hi, (s - hi.float()).half()
+
+
+def weight_exp_ref(w):
+    """keds_split_f16_weight's exponent: max |w| 2^e in [2^13, 2^14), clamped to [-100, 40]; 0 for an all-zero matrix"""
+    mx = float(w.abs().max())
+    return 0 if mx == 0.0 else max(-100, min(40, 13 - (math.frexp(mx)[1] - 1)))
+
+
+def _split_ref_pair(a, w):
+    e = weight_exp_ref(w)
+    return split_ref(a), split_ref(w, e), e
+
+
+def x3_seg(p, np1):
+    """K-tile p of 3 np1 -> (K-tile inside the plane, A reads its lo plane, W reads its lo plane): x3_seg of gemm_shared.h"""
+    seg = p // np1
+    return p - seg * np1, seg == 2, seg == 1
+
+
+class X3Case:
+    """One split-operand problem in the kernel's format and its float64 reference (module docstring).  regime `spike`: p = the K-tile
+    of 3 K / 64 that carries the output; `split`: std = the weights' standard deviation, splitter(a fp32, w fp32) -> ((ah, al), (wh, wl),
+    w_exp); rowscale: A's rows x 2^6 on every other 256-row tile."""
+
+    def __init__(self, M, N, K, regime, w_exp=0, p=None, std=1.0, rowscale=False, seed=0, device="cpu", splitter=_split_ref_pair):
+        assert K % TILE_K == 0 and N % 8 == 0 and regime in X3_REGIMES and not (rowscale and regime == "integer")
+        self.M, self.N, self.K, self.regime, self.device, self.dtype = M, N, K, regime, device, HF
+        np1 = K // TILE_K
+        g = torch.Generator(device=device).manual_seed(seed * 1000003 + M * 7919 + N * 31 + K + 17 * (p or 0))
+        kw = dict(generator=g, device=device)
+        self.extra = None
+        if regime == "integer":
+            a, w = _int_amp(K)
+            ah, al = (torch.randint(-a, a + 1, (M, K), **kw).half() for _ in range(2))
+            wh, wl = (torch.randint(-w, w + 1, (N, K), **kw).half() for _ in range(2))
+            bias = torch.randint(-4, 5, (N,), **kw).float()
+            resid = torch.randint(-8, 9, (M, N), **kw).float()
+        elif regime == "split":
+            a = torch.randn(M, K, dtype=torch.float32, **kw) * 2.0
+            a[:, ::97] *= 30.0
+            w = torch.randn(N, K, dtype=torch.float32, **kw) * std
+            (ah, al), (wh, wl), w_exp = splitter(a, w)
+            bias = torch.randn(N, dtype=torch.float32, **kw) * (0.5 * std * K ** 0.5)
+            resid = torch.randn(M, N, dtype=torch.float32, **kw) * (2.0 * std * K ** 0.5)
+        else:
+            ah, al = (torch.randn(M, K, dtype=torch.float64, **kw) for _ in range(2))
+            wh, wl = (torch.randn(N, K, dtype=torch.float64, **kw) * (K ** -0.5 * 2.0 ** w_exp) for _ in range(2))
+            bias = (torch.randn(N, dtype=torch.float64, **kw) * 0.5).float()
+            resid = (torch.randn(M, N, dtype=torch.float64, **kw) * 2.0).float()
+            if regime == "spike":
+                assert 0 <= p < 3 * np1
+                kt, a_lo, w_lo = x3_seg(p, np1)
+                ks = slice(kt * TILE_K, (kt + 1) * TILE_K)
+                if w_lo:
+                    wl[:, ks] *= 64.0
+                elif a_lo:
+                    al[:, ks] *= 64.0
+                else:
+                    ah[:, ks] *= 8.0
+                    wh[:, ks] *= 8.0
+            ah, al, wh, wl = ah.half(), al.half(), wh.half(), wl.half()
+        if rowscale:
+            up = ((torch.arange(M, device=device) // 256) % 2 == 1).unsqueeze(1)
+            ah, al = (torch.where(up, t * 64.0, t) for t in (ah, al))
+        self.ah, self.al, self.wh, self.wl, self.w_exp, self.p, self.np1 = ah, al, wh, wl, int(w_exp), p, np1
+        self.bias, self.resid = bias, resid
+        tag = {"spike": f"spike{p}", "split": f"split{std:g}"}.get(regime, regime)
+        self.name = f"{M}x{N}x{K}.x3.{tag}.e{self.w_exp}" + (".rowscale" if rowscale else "")
+        sc = 2.0 ** -self.w_exp
+        AH, AL, WH, WL = ah.double(), al.double(), wh.double(), wl.double()
+        self.S = (AH.abs() @ (WH.abs() + WL.abs()).t() + AL.abs() @ WH.abs().t()) * sc
+        if regime == "split":
+            self.acc = ((AH + AL) @ (WH + WL).t()) * sc
+            self.extra = (AL.abs() @ WL.abs().t()) * sc                    # the dropped lo.lo term, exactly bounded
+        else:
+            self.acc = (AH @ (WH + WL).t() + AL @ WH.t()) * sc
+        if regime == "integer":
+            raw = float(self.S.max()) / sc                                 # what the accumulators hold
+            assert raw + 32 < 2.0 ** 24, "integer regime: a partial sum could leave the exact range"
+            assert (raw * sc + 32) * max(1.0, 1.0 / sc) < 2.0 ** 24, "integer regime: the scaled sum + bias + residual is not exact in fp32"
+        self._e_acc = None
+
+    @property
+    def exact(self):
+        return self.regime == "integer"
+
+    def e_acc(self):
+        if self._e_acc is None:
+            self._e_acc = torch.zeros_like(self.S) if self.exact else C_ACC * (3 * self.K + 16) * U32 * self.S
+            if self.extra is not None:
+                self._e_acc = self._e_acc + self.extra
+        return self._e_acc
+
+    def spike_share(self):
+        """the share of S that K-tile p carries, averaged over the outputs"""
+        kt, a_lo, w_lo = x3_seg(self.p, self.np1)
+        ks = slice(kt * TILE_K, (kt + 1) * TILE_K)
+        a, w = (self.al if a_lo else self.ah)[:, ks].double().abs(), (self.wl if w_lo else self.wh)[:, ks].double().abs()
+        return float(((a @ w.t()) * 2.0 ** -self.w_exp / self.S).mean())
+
+    def rows(self, m):
+        return torch.arange(m, device=self.device)
+
+
+def epilogues(case):
+    """the epilogue table of a case's kernel"""
+    return X3_EPILOGUES if isinstance(case, X3Case) else F32_EPILOGUES if case.dtype == F32 else EPILOGUES
+
+
+def epilogue_name(case, code):
+    return (X3_NAMES if isinstance(case, X3Case) else F32_NAMES if case.dtype == F32 else NAMES)[code]
+
 
 class Expected:
     """ref float64 [M, N] (before the output rounding), bound float64 [M, N], pre_bound (the bound without the output rounding: what
     the fp32 value the statistics see may be off by), bits: the output to the bit (integer regime, linear families) or None"""
 
-    def __init__(self, ref, e, out_dtype, exact_bits):
+    def __init__(self, ref, e, out_dtype, exact_bits, pair=False):
         u = UNIT[out_dtype]
         self.ref, self.pre_bound, self.out_dtype = ref, e, out_dtype
-        self.bound = e * (1 + 2 * u) + u * ref.abs() + TINY[out_dtype] + FLUSH
+        # (pair: two fp16 planes, hi rounded to 11 bits and the remainder to 11 more; a subnormal lo rounds absolutely)
+        self.bound = e * (1 + 2 * u) + (2.0 ** -22 if pair else u) * ref.abs() + TINY[out_dtype] + FLUSH
         self.bits = ref.to(out_dtype) if exact_bits else None      # float64 -> type: one rounding of the exact sum
 
     def first_rows(self, h):
@@ -199,9 +360,11 @@ class Expected:
 
 def expected(case, code, out_dtype=None):
     """what epilogue `code` must give on `case`.  out_dtype: override (the fp32 head rows of BIAS_BF16_HEADF32)"""
-    op, od, fam = EPILOGUES[code]
+    op, od, fam = epilogues(case)[code]
     assert op == case.dtype, f"epilogue {code} takes {op} operands"
     od = od if out_dtype is None else out_dtype
+    pair = fam == "qgelu_pair"
+    fam = "qgelu" if pair else fam
     acc, S, bias = case.acc, case.S, case.bias.double()
     if fam in ("ln", "ln_qgelu"):
         mean, rstd, csum = case.mean, case.rstd, case.csum.double()
@@ -223,7 +386,7 @@ def expected(case, code, out_dtype=None):
         y = pre * sg
         e = QGELU_LIPSCHITZ * e + pre.abs() * (sg * (1 - sg) * (U_FN + 2 * z * math.log(2.0) * U32) + sg * (U_FN + 2 * U32)) + U32 * y.abs()
         e = e + torch.where(QGELU_Z * pre >= 126.0, y.abs(), torch.zeros_like(y))       # exp2 overflows: the kernel's y is -0
-        return Expected(y, e, od, False)
+        return Expected(y, e, od, False, pair=pair)
     return Expected(pre, e, od, case.exact and fam in LINEAR)
 
 
@@ -323,9 +486,13 @@ def emulate(case, code, order="forward", splits=1, mutation=None, at=None):
     for the RESID_STATS families, copy bf16 for RESID_STATS_F32, head fp32 for HEADF32).  fp32 throughout, as the kernels: per
     64-wide K-tile, `order` forward / reverse, `splits` slices summed in fp32 by a second pass that then applies the epilogue.
     mutation: one of MUTATIONS, placed by `at` = dict(row=, col=, kt=): the 8-row piece that contains `row`, K-tile kt."""
-    op, od, fam = EPILOGUES[code]
+    if isinstance(case, X3Case):
+        assert splits == 1
+        return _emulate_x3(case, code, order, mutation, at)
+    op, od, fam = epilogues(case)[code]
     assert str(case.device) == "cpu" and op == case.dtype
     M, N, K = case.M, case.N, case.K
+    TILE_K = case.tile_k                                                      # 64; 16 for fp32 operands
     nk = K // TILE_K
     at = dict(row=0, col=0, kt=nk - 1) | (at or {})
     r, c, ktm = at["row"], at["col"], at["kt"]
@@ -384,7 +551,10 @@ def emulate(case, code, order="forward", splits=1, mutation=None, at=None):
     if fam == "relu":
         v = v.clamp_min(0.0)
     if fam in ("qgelu", "ln_qgelu"):
-        v = v * (1.0 / (1.0 + torch.exp2(torch.tensor(QGELU_Z, dtype=torch.float32) * v)))
+        if op == F32:                                                         # gemm_f32_kernel: expf and a division
+            v = v / (1.0 + torch.exp(-1.702 * v))
+        else:
+            v = v * (1.0 / (1.0 + torch.exp2(torch.tensor(QGELU_Z, dtype=torch.float32) * v)))
     if mutation == "swap_rows" and M >= 2:
         r2 = r + 1 if r + 1 < M else r - 1
         v = v.clone()
@@ -418,12 +588,101 @@ def emulate(case, code, order="forward", splits=1, mutation=None, at=None):
     return res
 
 
+def _x3_acc(case, rows, order, mutation, at):
+    """the fp32 accumulators of rows `rows` (a slice) of a split-operand launch: 3 K / 64 K-tiles, segment by segment"""
+    np1, K = case.np1, case.K
+    A = (case.ah[rows].float(), case.al[rows].float())
+    W = (case.wh.float(), case.wl.float())
+    acc = torch.zeros(A[0].shape[0], case.N)
+    tile = lambda t, kt: t[:, kt * TILE_K:(kt + 1) * TILE_K]                   # noqa: E731
+    ps = list(range(3 * np1)) + ([3 * np1 + i for i in range(np1)] if mutation == "x3_lo_lo" else [])
+    for p in (ps if order == "forward" else reversed(ps)):
+        kt, a_lo, w_lo = x3_seg(p, np1) if p < 3 * np1 else (p - 3 * np1, True, True)
+        a, w = tile(A[a_lo], kt), tile(W[w_lo], kt)
+        if p == np1 and mutation == "x3_hi_for_lo":                            # the seam's first tile still reads W's hi plane
+            w = tile(W[0], kt)
+        if p == np1 and mutation == "x3_koff_runs_on":                         # ... or counts its K offset on from segment 0: K-tile np1
+            nxt = lambda t: torch.cat([t[1:], torch.zeros_like(t[:1])]).contiguous()   # noqa: E731  (dense rows: the next row's first tile)
+            full_a = case.ah.float()
+            a = tile(nxt(full_a), 0)[rows]
+            w = tile(nxt(W[1]), 0)
+        if mutation == "x3_drop_lo" and p == np1 + at["kt"]:
+            continue
+        if mutation == "x3_stale_lo" and p == 2 * np1 + at["kt"]:              # the ring still holds A of the K-tile two back
+            if p < 2:
+                continue
+            k2, a2_lo, _ = x3_seg(p - 2, np1)
+            a = tile(A[a2_lo], k2)
+        acc += a @ w.t()
+    return acc
+
+
+def _emulate_x3(case, code, order, mutation, at):
+    """emulate() for an X3Case -> dict(out fp32 [M, N]) or dict(hi, lo fp16 [M, N]) for X3_QGELU_PAIR"""
+    assert str(case.device) == "cpu" and mutation in (None,) + X3_MUTATIONS
+    _, od, fam = X3_EPILOGUES[code]
+    M, N = case.M, case.N
+    at = dict(row=0, col=0, kt=case.np1 - 1) | (at or {})
+    r, c = at["row"], at["col"]
+    piece = slice(r // 8 * 8, min(r // 8 * 8 + 8, M))
+    cols = slice(c // 256 * 256, min(c // 256 * 256 + 256, N))
+    cache = case.__dict__.setdefault("_model_acc", {})
+    whole = mutation in ("x3_hi_for_lo", "x3_koff_runs_on", "x3_lo_lo")
+    if whole:
+        acc = _x3_acc(case, slice(0, M), order, mutation, at)
+    else:
+        if order not in cache:
+            cache[order] = _x3_acc(case, slice(0, M), order, None, at)
+        acc = cache[order]
+        if mutation in ("x3_drop_lo", "x3_stale_lo"):
+            acc = acc.clone()
+            acc[piece, cols] = _x3_acc(case, piece, order, mutation, at)[:, cols]
+    ws = torch.tensor(2.0 ** -case.w_exp, dtype=torch.float32)
+    v = (acc + case.bias) * ws if mutation == "x3_scale_after_bias" else acc * ws + case.bias
+    if fam == "resid":
+        v = case.resid + v
+    if fam != "qgelu_pair":
+        out = v.clone()
+        if mutation == "drop_store":
+            out[r, c // 4 * 4:c // 4 * 4 + 4] = SENTINEL
+        return {"out": out}
+    v = v / (1.0 + torch.exp(-1.702 * v))
+    hi = v.half()
+    lo = (v - hi.float()).half()
+    if mutation == "x3_lo_zero":
+        lo = torch.zeros_like(lo)
+    if mutation == "drop_store":
+        hi[r, c // 8 * 8:c // 8 * 8 + 8] = SENTINEL
+    return {"hi": hi, "lo": lo}
+
+
+def fp16_ulp(h):
+    """the spacing of fp16 at |h| (float64): 2^(floor(log2 |h|) - 10), 2^-24 below 2^-14"""
+    _, ex = torch.frexp(h.double().abs())
+    return torch.exp2((ex - 1).clamp_min(-14).double() - 10.0)
+
+
+def _x3_failures(case, code, res):
+    exp = expected(case, code)
+    tag = f"{case.name}.{X3_NAMES[code]}"
+    if code != 15:
+        fs = [verify(res["out"][:case.M], exp, tag)]
+    else:
+        hi, lo = res["hi"][:case.M].double(), res["lo"][:case.M].double()
+        fs = [check(hi + lo, exp, tag + " hi + lo"),
+              _collect(lo.abs() / (0.5 * fp16_ulp(hi)), tag + " |lo| against ulp(hi) / 2")]
+    # (the ratio reported is the bound's; |lo| reaches ulp(hi) / 2 exactly at every tie and says nothing more than pass or fail)
+    return [f for f in fs if f], max(f.worst for f in fs if f or f is fs[0])
+
+
 def model_failures(case, code, res):
     """every check of one launch's results `res` (emulate's dict, or the same built from a kernel's buffers) -> list of Failures,
     the failing ones only, and the worst ratio of all"""
-    op, od, fam = EPILOGUES[code]
+    if isinstance(case, X3Case):
+        return _x3_failures(case, code, res)
+    op, od, fam = epilogues(case)[code]
     exp = expected(case, code)
-    tag = f"{case.name}.{NAMES[code]}"
+    tag = f"{case.name}.{epilogue_name(case, code)}"
     out = res["out"][case.patch_rows()] if fam == "patch" else res["out"][:case.M]
     fs = [verify(out, exp, tag)]
     if fam == "headf32":

@@ -1,6 +1,7 @@
 """Proof, on the CPU, that the per-element GEMM check (tests/gemm_check.py) passes a faithful model of the kernels' rounding in every
 order the kernels may add in, and catches each defect class of gemm_check.MUTATIONS with room to spare -- while today's whole-tensor
-rel-L2 does not see the single-piece ones."""
+rel-L2 does not see the single-piece ones.  The same for the fp32-operand kernel (K-tiles of 16) and for the split-operand loop of
+keds_gemm_x3 (three segments over two planes per operand, gemm_check.X3_MUTATIONS)."""
 import functools
 
 import pytest
@@ -121,3 +122,165 @@ def test_failure_report_names_tiles_and_groups():
     assert f.count == 8 and [(m, n) for m, n, _ in f][:2] == [(13, 296), (13, 297)]
     s = str(f)
     assert "8 elements" in s and "tile256 (0, 1) row 13 col 40" in s and "tile128 (0, 2)" in s and "group8 37" in s
+
+
+# ---- fp32 operands (gemm_f32_kernel) ---------------------------------------------------------------------------------------------
+F32_KS = (16, 64, 1024)                # one K-tile of 16 (no prefetch, no second buffer), four, sixty-four
+
+
+@pytest.mark.parametrize("K", F32_KS)
+@pytest.mark.parametrize("regime", gc.F32_REGIMES)
+def test_f32_model_passes_every_epilogue(regime, K):
+    """K-tiles of 16, forwards and backwards, with and without a bias: inside the bound, the integer cases to the bit"""
+    case = _case(K, regime, gc.F32)
+    for c in (case, case.without_bias()):
+        for code, (_, _, fam) in gc.F32_EPILOGUES.items():
+            for order in ("forward", "reverse"):
+                res = gc.emulate(c, code, order=order)
+                fails, worst = gc.model_failures(c, code, res)
+                assert not fails and worst <= 1.0, "\n".join(map(str, fails))
+                if regime == "integer" and fam in gc.LINEAR:
+                    out = res["out"][c.patch_rows()] if fam == "patch" else res["out"]
+                    assert torch.equal(out, gc.expected(c, code).bits)
+
+
+@pytest.mark.parametrize("K", F32_KS)
+@pytest.mark.parametrize("mutation", ("drop_ktile", "stale_ktile", "swap_rows", "shift_side", "drop_store", "resid_twice"))
+def test_f32_each_mutation_misses_the_bound_by_a_factor(mutation, K):
+    """the defects of the 16-bit kernels that gemm_f32_kernel can have too, on its own K-tile of 16 (K = 16: the only tile)"""
+    regimes, codes = {"drop_ktile": (("tail", "head", "integer"), (0, 1, 2, 3, 4)), "stale_ktile": (("tail", "integer"), (0, 2)),
+                      "swap_rows": (("random", "integer"), (0, 4)), "shift_side": (("random", "integer"), (0, 1, 3)),
+                      "drop_store": (("random", "integer"), (0, 1, 4)), "resid_twice": (("random", "integer"), (2,))}[mutation]
+    nk = K // 16
+    for regime in regimes:
+        for code in codes:
+            case = _case(K, regime, gc.F32)
+            fails, worst = _worst(case, code, mutation=mutation, at=dict(row=13, col=300, kt=0 if regime == "head" else nk - 1))
+            assert fails and worst >= FACTOR, f"{mutation} on {case.name} code {code}: worst ratio {worst:.3g}"
+
+
+# ---- split operands (keds_gemm_x3) -----------------------------------------------------------------------------------------------
+X3_KS = (64, 128, 1024, 4096)
+
+
+def _spikes(K):
+    n = K // gc.TILE_K
+    return sorted({0, n - 1, n, 2 * n - 1, 2 * n, 3 * n - 1})           # the first and last K-tile and both sides of both seams
+
+
+@functools.lru_cache(maxsize=None)
+def _x3(K, regime, w_exp=0, p=None, std=1.0, m=M, n=N):
+    return gc.X3Case(m, n, K, regime, w_exp=w_exp, p=p, std=std, seed=K)
+
+
+def _x3_cases(K):
+    """every regime: integer at w_exp 0, 5, -3; random; every spike; true splits of weights at std 1, 1e-2, 3e-5"""
+    return ([_x3(K, "integer", w_exp=e) for e in (0, 5, -3)] + [_x3(K, "random", w_exp=7)] + [_x3(K, "spike", p=p) for p in _spikes(K)] +
+            [_x3(K, "split", std=s) for s in (1.0, 1e-2, 3e-5)])
+
+
+@pytest.mark.parametrize("K", X3_KS)
+def test_x3_model_passes_every_epilogue_in_every_regime(K):
+    """three segments of K / 64 K-tiles forwards and backwards, 2^-e before the bias, the pair epilogue: inside the bound in every
+    regime; epilogues 13 and 14 of the integer cases to the bit for every w_exp.  A spike tile carries half of S up to K = 1024
+    (64 of 64 + 16 + 3 K / 64 - 3 equal shares in segment 0, of 64 + 3 K / 64 - 1 in segments 1 and 2)."""
+    for case in _x3_cases(K):
+        if case.regime == "spike" and K <= 1024:
+            assert case.spike_share() >= 0.5, (case.name, case.spike_share())
+        if case.regime == "split":
+            assert 2.0 ** 13 <= float(torch.maximum(case.wh.float().abs().max(), torch.tensor(0.0))) < 2.0 ** 14, case.name
+        for code in gc.X3_EPILOGUES:
+            for order in ("forward", "reverse"):
+                res = gc.emulate(case, code, order=order)
+                fails, worst = gc.model_failures(case, code, res)
+                assert not fails and worst <= 1.0, "\n".join(map(str, fails))
+                if case.exact and code != 15:
+                    assert torch.equal(res["out"], gc.expected(case, code).bits)
+
+
+X3_PLAN = {            # mutation -> the epilogues it can show in
+    "x3_drop_lo": (13, 14, 15), "x3_stale_lo": (13, 14, 15), "x3_hi_for_lo": (13, 14, 15), "x3_koff_runs_on": (13, 14, 15), "x3_lo_lo": (13, 14, 15),
+    "x3_scale_after_bias": (13, 14, 15), "x3_lo_zero": (15,), "drop_store": (13, 14, 15),
+}
+
+
+@pytest.mark.parametrize("K", X3_KS)
+@pytest.mark.parametrize("mutation", gc.X3_MUTATIONS)
+def test_x3_each_mutation_misses_the_bound_by_a_factor(mutation, K):
+    """Each defect of the split-operand loop fails by >= 4 x the bound, or by bits, in at least one regime at every K and in every
+    epilogue it can show in: an 8-row piece that drops a K-tile of segment 1 or reads the K-tile two back in segment 2, K-tile np
+    reading hi for lo or counting its K offset on from segment 0, a fourth lo.lo segment, 2^-e behind the bias (regimes with
+    w_exp != 0), a zero lo output plane, one lost 16-byte store.  The single-piece ones fail inside their piece only.  On TRUE
+    splits the lo-segment defects weigh 2^-11 of a hi tile and pass from K = 1024 on (printed): that is why the planes of the
+    other regimes are independent."""
+    nk = K // gc.TILE_K
+    for code in X3_PLAN[mutation]:
+        best, where = 0.0, None
+        for case in _x3_cases(K):
+            kt = nk - 1 if case.regime != "spike" else gc.x3_seg(case.p, nk)[0]
+            fails, worst = _worst(case, code, mutation=mutation, at=dict(row=13, col=300, kt=kt))
+            if case.regime == "split":
+                print(f"{mutation} K={K} code {code} on {case.name}: worst ratio {worst:.3g}")
+                continue
+            if worst > best:
+                best, where = worst, case.name
+            if fails and mutation in ("x3_drop_lo", "x3_stale_lo", "drop_store"):
+                assert all(8 <= f[0] < 16 for fl in fails for f in fl), (mutation, case.name, code)
+        assert best >= FACTOR, f"{mutation} code {code} K={K}: caught by only {best:.3g} x the bound (on {where})"
+
+
+def test_lo_segment_mutations_on_true_splits_against_the_whole_tensor_limits():
+    """One 8-row piece that drops a K-tile of segment 1, or reads the K-tile two back in segment 2, on TRUE-split data at
+    4448 x 1024 x 1024 (a shape of test_gemm_x3_every_epilogue_against_float64, its data recipe, weights split as stored), through
+    that test's own assertions against float64 on the ORIGINAL fp32 operands: rel-L2 <= 2e-6 and max err / sum |a||w| <= 1.5e-6.
+    The values are printed and recorded in docs/kernels.md.  rel-L2 passes both defects wherever they sit (asserted).  The
+    per-element limit does NOT pass them, contrary to what was expected when this test was planned: a lo plane is about 2^-12 of its
+    hi plane and one K-tile 1 / 16 of the K-loop here, of the order of 1e-5 of sum |a||w| -- measured 0.9e-5 to 4.7e-5 against the
+    limit's 1.5e-6 -- in K-tile 7, which holds one of A's x 30 columns, and in K-tile 8, which holds none (asserted too, so that the
+    document stays true).  The per-element BOUND of this module, against the planes' own product, passes them on true splits (ratio
+    0.02 to 0.13: 2 (3 K + 16) 2^-24 = 3.7e-4 of S is what 3 K fp32 additions may cost in the worst case); it catches them on the
+    independent planes of the other regimes."""
+    Mx, Nx, Kx = 4448, 1024, 1024
+    g = torch.Generator().manual_seed(Mx + Nx + Kx)
+    a = torch.randn(Mx, Kx, generator=g) * 2.0
+    a[:, ::97] *= 30.0
+    w = torch.randn(Nx, Kx, generator=g) * Kx ** -0.5
+    b = torch.randn(Nx, generator=g) * 0.1
+    case = gc.X3Case(Mx, Nx, Kx, "split", seed=1, splitter=lambda _a, _w: (gc.split_ref(a), gc.split_ref(w), 0))
+    case.bias = b
+    want = a.double() @ w.double().t() + b.double()
+    scale = a.double().abs() @ w.double().abs().t() + 1e-30
+    exp = gc.expected(case, 13)
+
+    def measure(mutation, kt):
+        got = gc.emulate(case, 13, mutation=mutation, at=dict(row=1000, col=600, kt=kt))["out"]
+        err, rel = float(((got.double() - want).abs() / scale).max()), gc.rel_l2(got, want)
+        f = gc.check(got, exp, str(mutation))
+        print(f"{mutation} K-tile {kt}: max err / sum|a||w| {err:.3e} (limit 1.5e-6), rel_l2 {rel:.3e} (limit 2e-6); per element against the "
+              f"planes' own product: {f.count} beyond the bound, worst {f.worst:.3g}")
+        return err, rel
+    err, rel = measure(None, 0)
+    assert err <= 1.5e-6 and rel <= 2e-6
+    for mutation in ("x3_drop_lo", "x3_stale_lo"):
+        for kt in (7, 8):
+            err, rel = measure(mutation, kt)
+            assert rel <= 2e-6, "the whole-tensor number saw it"
+            assert err > 1.5e-6, "the per-element limit of test_gpu_fp32.py passed it after all: correct docs/kernels.md"
+
+
+def test_split_reference_carries_22_bits_or_an_absolute_2_to_minus_25():
+    """hi = (x 2^e).half(), lo = (x 2^e - hi.float()).half(), the evaluation the split kernels are held to bit for bit on the GPU:
+    |hi + lo - x 2^e| <= 2^-22 |x 2^e| + 2^-25 -- hi is x to 11 bits, the remainder (exact in fp32) is rounded to 11 more, absolutely
+    to 2^-25 where lo is an fp16 subnormal -- and |lo| <= ulp(hi) / 2."""
+    g = torch.Generator().manual_seed(5)
+    x = torch.cat([torch.randn(4096, generator=g) * s for s in (1.0, 30.0, 1e-2, 1e-4, 3e-5, 1e3)] +
+                  [torch.tensor([0.0, 1.0, -2.5, 2.0 ** -14, 2.0 ** -24, 1.0 + 2.0 ** -11, 1.0 + 3 * 2.0 ** -11, 65503.9, -65503.9, 2.0 ** -3 + 2.0 ** -26])])
+    for e in (0, 5, 12):
+        xs = x if e == 0 else x[x.abs() * 2.0 ** e < 65504.0]
+        hi, lo = gc.split_ref(xs, e)
+        s = xs.double() * 2.0 ** e
+        assert bool(((hi.double() + lo.double() - s).abs() <= 2.0 ** -22 * s.abs() + 2.0 ** -25).all())
+        assert bool((lo.double().abs() <= 0.5 * gc.fp16_ulp(hi)).all())
+    assert gc.weight_exp_ref(torch.tensor([0.0, 0.0])) == 0
+    for mx, e in [(1.0, 13), (1.99, 13), (2.0, 12), (2.0 ** -30, 40), (2.0 ** -27, 40), (2.0 ** -26, 39), (2.0 ** 20, -7), (2.0 ** 120, -100), (3e-5, 29)]:
+        assert gc.weight_exp_ref(torch.tensor([mx, -mx / 3])) == e, (mx, e)

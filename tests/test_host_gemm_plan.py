@@ -240,6 +240,66 @@ def test_row_remainder_launch_behind_big_tiles(lib):
             _has(query(lib, code, M, N, K), main=SMALL, tail=NONE, ring=2, splits=1)
 
 
+# ---- docs/kernels.md: the split-operand table (keds_gemm_x3, epilogues 13 - 15), one test per row ----------------------------------
+X3_ROWS = ("128², ring 4", "128², ring 2", "no split-K", "256², 8 waves", "256², 4 waves, one tile per workgroup", "256², 4 waves, persistent",
+           "big tiles + remainder")
+X3_BIG_K = (128, 192, 1024)
+
+
+def test_the_document_has_exactly_these_split_operand_rows():
+    text = open(os.path.join(ROOT, "docs", "kernels.md"), encoding="utf-8").read()
+    assert text.index("| form (recorded) | reached by |") < text.index("| form of `keds_gemm_x3` (recorded) | reached by |")
+    table = text[text.index("| form of `keds_gemm_x3` (recorded) | reached by |"):]
+    table = table[:table.index("\n\n")]
+    assert tuple(re.findall(r"^\| ([^|]+?) \|", table, flags=re.M)[1:]) == X3_ROWS
+
+
+def test_x3_row_small_kernel_ring_4(lib):
+    for cus, _ in CUS_T:
+        for M, N, K, code in itertools.product((1, 7, 127, 128, 129, 255, 256, 257), (128, 384), (64, 128, 192, 320), X3):
+            _has(query(lib, code, M, N, K, cus=cus), main=SMALL, tail=NONE, ring=4, splits=1, persistent=0, flags=0)
+            _has(query(lib, code, M, N, K, cus=cus, lda=K + 72, ldc=N + 40), main=SMALL, tail=NONE, ring=4, splits=1, persistent=0, flags=0)
+
+
+def test_x3_row_small_kernel_ring_2(lib):
+    for (cus, _), K, code in itertools.product(CUS_T, (64, 128), X3):
+        _has(query(lib, code, 2170, 2048, K, force=F_SMALL, cus=cus), main=SMALL, tail=NONE, ring=2, splits=1, persistent=0, flags=0)
+
+
+def test_x3_row_no_split_k(lib):
+    """16 tiles at K = 2048 with the workspace registered: every other epilogue splits, gemm_may_split excludes these"""
+    for (cus, _), code in itertools.product(CUS_T, X3):
+        _has(query(lib, code, 129, 1024, 2048, cus=cus), main=SMALL, tail=NONE, ring=4, splits=1, persistent=0, flags=0)
+    assert query(lib, 19, 129, 1024, 2048)["splits"] > 1
+
+
+def test_x3_row_eight_wave_kernel(lib):
+    for (cus, _), K, code in itertools.product(CUS_T, X3_BIG_K, X3):
+        _has(query(lib, code, BIG_M, BIG_N, K, force=F_PAIR, cus=cus), main=PAIR, tail=NONE, ring=2, splits=1, persistent=0, flags=0)
+
+
+def test_x3_row_four_wave_kernel_one_tile_per_workgroup(lib):
+    for (cus, T), K, code in itertools.product(CUS_T, X3_BIG_K, X3):
+        assert BIG_M // 256 * (BIG_N // 256) <= T
+        _has(query(lib, code, BIG_M, BIG_N, K, cus=cus), main=QUAD, tail=NONE, ring=2, splits=1, persistent=0, flags=0)
+
+
+def test_x3_row_four_wave_kernel_persistent(lib):
+    for cus, T in CUS_T:
+        for M, N in [((T + 1) * 256, 256), (3 * T // 8 * 256, 1024), ((2 * T + 8) * 256, 256)]:
+            assert (M // 256) * (N // 256) > T
+            for K, code in itertools.product((128, 192, 576, 1024), X3):
+                _has(query(lib, code, M, N, K, cus=cus), main=QUAD, tail=NONE, ring=2, splits=1, persistent=int(code != 14), flags=0)
+        for code in X3:                                                                              # T tiles: one each
+            _has(query(lib, code, T * 256, 256, 576, cus=cus), main=QUAD, persistent=0)
+
+
+def test_x3_row_remainder_launch_behind_big_tiles(lib):
+    for (cus, T), r, K, code in itertools.product(CUS_T, (1, 127, 129, 255), (256, 1024), X3):
+        _has(query(lib, code, 3584 + r, 4096, K, cus=cus), main=QUAD, tail=SMALL, ring=2, tail_ring=4, splits=1, tail_splits=1,
+             persistent=int(224 > T and code != 14), flags=0)
+
+
 # ---- keds_gemm_splits_rows: whether a tower runs two lanes (towers.hip, bf16_rows_split) -----------------------------------------
 def test_splits_rows_is_the_models_remainder_launch(lib):
     splits_rows = getattr(lib, "_Z21keds_gemm_splits_rowsiii")      # bool keds_gemm_splits_rows(int, int, int): library-internal, C++
