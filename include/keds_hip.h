@@ -342,6 +342,30 @@ int keds_layernorm(const float* x, int64_t x_stride, const float* gamma, const f
 int keds_layernorm_ex(const float* x, int64_t x_stride, const float* gamma, const float* beta,
                       void* out, int out_type, int rows, int dim, void* stream);
 
+/* Every form of the LayerNorm kernel: output row r reads source row r * row_mul + row_map[r] (row_map int32 [rows], NULL: r * row_mul
+ * -- row_mul = S reads the CLS row of every sample), rows x_stride elements apart; out dense [rows, dim], out_type as above.  A row
+ * whose map entry is outside [0, row_mul) comes out as NaN in every element. */
+int keds_layernorm_rows(const float* x, int64_t x_stride, const int32_t* row_map, int row_mul, const float* gamma, const float* beta,
+                        void* out, int out_type, int rows, int dim, void* stream);
+/* LayerNorm into a PAIR of fp16 planes, y = hi + lo to 22 bits (the A operand of a split-operand GEMM): hi dense [rows, dim] at out,
+ * lo at out + plane elements; plane % 4 == 0, plane >= rows * dim, x_stride % 4 == 0.  form 0: the library's choice (a wave walks
+ * several rows at dim 512 / 1024, rows >= 2048, plane % 8 == 0), 1: one row per wave at any row count. */
+int keds_layernorm_pair(const float* x, int64_t x_stride, const float* gamma, const float* beta, void* out, int64_t plane, int rows,
+                        int dim, int form, void* stream);
+/* what this thread's last pair LayerNorm launched: 0 one row per wave, 1 a wave walks several rows; -1 before the first */
+int keds_layernorm_pair_last_form(void);
+
+/* rows of a [rows, stride] buffer into another of the same shape and another type: types as out_type above, the source fp32 or
+ * fp16; dim % 8 == 0, stride >= dim (columns >= dim are neither read nor written); nt != 0: non-temporal stores */
+int keds_cast_rows(const void* src, int src_type, void* dst, int dst_type, int rows, int dim, int64_t stride, int nt, void* stream);
+/* one row per sample: dst[b] = src[b * S + row[b]] (global_rows != 0: src[row[b]], S = the rows src holds); mode 0: 16-bit elements
+ * copied, 1: fp16 -> fp32, 2: fp32 copied; dim % 8 == 0.  A row outside [0, S) comes out as NaN.  (The name without `token` is the
+ * index's gather.) */
+int keds_gather_token_rows(const void* src, void* dst, const int32_t* row, int S, int B, int dim, int mode, int global_rows,
+                           void* stream);
+/* x[b * S, :] = cls + pos[0]: the class-token rows of a [B, S, d] stream; every other row is left alone */
+int keds_cls_rows(float* x, const float* cls, const float* pos, int B, int S, int d, void* stream);
+
 /* timing-only ablation hook of the S > 96 attention kernel (0 = product path) */
 int keds_attention_debug(int variant);
 /* diagnostic: device buffer of B * heads * 64 uint64 that the stamped build (keds_attention_debug(64 + 8)) of the S = 257
@@ -380,6 +404,11 @@ int keds_im2col_ex(const float* image, void* out, int out_f16, int B, int R, int
 int keds_embed_tokens(const int32_t* tokens, const float* table, const float* pos,
                       const float* img_tokens, int n_tok, int insert_col,
                       float* x, int B, int L, int d, void* stream);
+
+/* the same with only the first Lx <= L columns written (x [B, Lx, d]; a splice that reaches beyond Lx is cut there) and, seq_off
+ * int32 [B + 1] not NULL, packed rows: sample b writes its first seq_off[b + 1] - seq_off[b] columns to rows seq_off[b] ... of x */
+int keds_embed_tokens_ex(const int32_t* tokens, const float* table, const float* pos, const float* img_tokens, int n_tok,
+                         int insert_col, float* x, int B, int L, int Lx, int d, const int32_t* seq_off, void* stream);
 
 /* read-out: out[b,:] = LayerNorm(x[b*S + row[b], :]) . proj  (+ optional L2 normalisation)
  * (model.py:412-414, 586-589, 841-849).  proj_t bf16 [E, d] (the projection transposed),

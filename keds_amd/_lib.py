@@ -245,6 +245,14 @@ SIGNATURES = {
     "keds_im2col_ex": (i32, [vp, vp, i32, i32, i32, i32, i32, vp]),
     "keds_layernorm_ex": (i32, [vp, i64, vp, vp, vp, i32, i32, i32, vp]),
     "keds_cast_f16": (i32, [vp, vp, i64, vp]),
+    # the row kernels' forms that only a tower pass reached (tests/test_gpu_row_kernels_edges.py)
+    "keds_layernorm_rows": (i32, [vp, i64, vp, i32, vp, vp, vp, i32, i32, i32, vp]),
+    "keds_layernorm_pair": (i32, [vp, i64, vp, vp, vp, i64, i32, i32, i32, vp]),
+    "keds_layernorm_pair_last_form": (i32, []),
+    "keds_cast_rows": (i32, [vp, i32, vp, i32, i32, i32, i64, i32, vp]),
+    "keds_gather_token_rows": (i32, [vp, vp, vp, i32, i32, i32, i32, i32, vp]),
+    "keds_cls_rows": (i32, [vp, vp, vp, i32, i32, i32, vp]),
+    "keds_embed_tokens_ex": (i32, [vp, vp, vp, vp, i32, i32, vp, i32, i32, i32, i32, vp, vp]),
     # one weight-packing routine for both loaders (ABI 10)
     "keds_block_pack_bytes": (sz, [i32, i32, i32, i32, i32]),
     "keds_block_pack": (i32, [C.POINTER(BlockSource), i32, i32, i32, i32, i32, vp, sz, C.POINTER(BlockParams), vp]),

@@ -602,20 +602,26 @@ static bool ln_stream_env() {          // KEDS_LN_STREAM=0 in the environment: t
     return v != 0;
 }
 
+// what the last keds_layernorm_pair_impl call of this thread launched (keds_layernorm_pair_last_form): 0 one row per wave, 1 stream
+static thread_local int tl_ln_pair_form = -1;
+
 // LayerNorm whose output is a pair of fp16 planes (hi = out, lo = out + plane elements; dense rows of `dim`)
+// form: 0 the library's choice, 1 the one-row-per-wave form at any row count (keds_layernorm_pair)
 int keds_layernorm_pair_impl(const float* x, long long x_stride, const float* gamma, const float* beta, void* out, long long plane,
-                             int rows, int dim, hipStream_t st) {
+                             int rows, int dim, hipStream_t st, int form = 0) {
     KedsProfScope prof(KEDS_PROF_LN, st);
-    if ((dim == 1024 || dim == 512) && rows >= 2048 && x_stride % 4 == 0 && plane % 8 == 0 && ln_stream_env()) {
+    if (form != 1 && (dim == 1024 || dim == 512) && rows >= 2048 && x_stride % 4 == 0 && plane % 8 == 0 && ln_stream_env()) {
         // every wave resident at once (82 VGPRs: five per SIMD, five blocks per CU); at 32,768 rows a wave walks six or seven
         const int cus = keds_device_cus();
         int grid = cus * 5;
         if (grid * 4 > rows) grid = (rows + 3) / 4;
         if (dim == 1024) layernorm_pair_stream_kernel<2><<<grid, 256, 0, st>>>(x, x_stride, gamma, beta, (f16_t*)out, plane, rows);
         else layernorm_pair_stream_kernel<1><<<grid, 256, 0, st>>>(x, x_stride, gamma, beta, (f16_t*)out, plane, rows);
+        tl_ln_pair_form = 1;
         return keds_check_launch("layernorm_pair_stream_kernel");
     }
     ln_launch<2>(x, x_stride, nullptr, 1, gamma, beta, out, rows, dim, st, plane);
+    tl_ln_pair_form = 0;
     return keds_check_launch("layernorm_kernel<pair>");
 }
 
@@ -735,6 +741,28 @@ extern "C" int keds_layernorm_ex(const float* x, int64_t x_stride, const float* 
     return keds_layernorm_impl(x, x_stride, nullptr, 1, gamma, beta, out, out_type, rows, dim, (hipStream_t)stream);
 }
 
+// every form of layernorm_kernel: gathered rows (source row = r * row_mul + row_map[r]; row_map NULL: r * row_mul), strided rows
+extern "C" int keds_layernorm_rows(const float* x, int64_t x_stride, const int32_t* row_map, int row_mul, const float* gamma,
+                                   const float* beta, void* out, int out_type, int rows, int dim, void* stream) {
+    KEDS_REQUIRE(out_type >= 0 && out_type <= 2, "keds_layernorm_rows: out_type %d (0 bf16, 1 fp32, 2 fp16)", out_type);
+    KEDS_REQUIRE(x && gamma && beta && out && rows > 0 && row_mul > 0, "keds_layernorm_rows: bad argument");
+    KEDS_REQUIRE(ln_dim_ok(dim), "keds_layernorm_rows: dim %d unsupported", dim);
+    KEDS_REQUIRE(x_stride % 4 == 0, "keds_layernorm_rows: row stride must be a multiple of 4");
+    return keds_layernorm_impl(x, x_stride, row_map, row_mul, gamma, beta, out, out_type, rows, dim, (hipStream_t)stream);
+}
+
+extern "C" int keds_layernorm_pair(const float* x, int64_t x_stride, const float* gamma, const float* beta, void* out, int64_t plane,
+                                   int rows, int dim, int form, void* stream) {
+    KEDS_REQUIRE(x && gamma && beta && out && rows > 0 && (form == 0 || form == 1), "keds_layernorm_pair: bad argument");
+    KEDS_REQUIRE(ln_dim_ok(dim), "keds_layernorm_pair: dim %d unsupported", dim);
+    KEDS_REQUIRE(x_stride % 4 == 0, "keds_layernorm_pair: row stride must be a multiple of 4");
+    // (the one-row form stores 8-byte vectors at out + plane)
+    KEDS_REQUIRE(plane % 4 == 0 && plane >= (int64_t)rows * dim, "keds_layernorm_pair: plane must be a multiple of 4 and hold rows * dim");
+    return keds_layernorm_pair_impl(x, x_stride, gamma, beta, out, plane, rows, dim, (hipStream_t)stream, form);
+}
+
+extern "C" int keds_layernorm_pair_last_form(void) { return tl_ln_pair_form; }
+
 extern "C" int keds_im2col_ex(const float* image, void* out, int out_f16, int B, int R, int P, int Kpad, void* stream) {
     KEDS_REQUIRE(image && out && B > 0 && P > 0 && R % P == 0, "keds_im2col: bad argument");
     KEDS_REQUIRE(Kpad >= 3 * P * P && Kpad % 64 == 0, "keds_im2col: Kpad must cover 3*P*P and be a multiple of 64");
@@ -757,6 +785,16 @@ int keds_cls_rows_impl(float* x, const float* cls, const float* pos, int B, int 
 int keds_embed_tokens_impl(const int32_t* tokens, const float* table, const float* pos, const float* img_tokens,
                            int n_tok, int insert_col, float* x, int B, int L, int Lx, int d, void* stream,
                            const int32_t* seq_off = nullptr);
+
+extern "C" int keds_cls_rows(float* x, const float* cls, const float* pos, int B, int S, int d, void* stream) {
+    KEDS_REQUIRE(x && cls && pos && B > 0 && S > 0 && d > 0, "keds_cls_rows: bad argument");
+    return keds_cls_rows_impl(x, cls, pos, B, S, d, (hipStream_t)stream);
+}
+
+extern "C" int keds_embed_tokens_ex(const int32_t* tokens, const float* table, const float* pos, const float* img_tokens, int n_tok,
+                                    int insert_col, float* x, int B, int L, int Lx, int d, const int32_t* seq_off, void* stream) {
+    return keds_embed_tokens_impl(tokens, table, pos, img_tokens, n_tok, insert_col, x, B, L, Lx, d, stream, seq_off);
+}
 
 extern "C" int keds_embed_tokens(const int32_t* tokens, const float* table, const float* pos, const float* img_tokens,
                                  int n_tok, int insert_col, float* x, int B, int L, int d, void* stream) {
@@ -881,6 +919,11 @@ int keds_cast_rows_impl(const void* src, int src_type, void* dst, int dst_type, 
     return keds_check_launch("cast_rows_kernel");
 }
 
+extern "C" int keds_cast_rows(const void* src, int src_type, void* dst, int dst_type, int rows, int dim, int64_t stride, int nt,
+                              void* stream) {
+    return keds_cast_rows_impl(src, src_type, dst, dst_type, rows, dim, stride, nt != 0, (hipStream_t)stream);
+}
+
 // rows of the fp16 residual stream back to fp32 (the end of every folded tower pass)
 int keds_cast_rows_f16_f32_impl(const void* x16, float* x32, int rows, int dim, long long stride, hipStream_t st) {
     return keds_cast_rows_impl(x16, 2, x32, 1, rows, dim, stride, false, st);
@@ -919,6 +962,11 @@ int keds_gather_rows_impl(const void* src, void* dst, const int32_t* row, int S,
     else if (mode == 1) gather_rows_kernel<1><<<grid, 256, 0, st>>>(src, dst, row, S, B, dim, gr);
     else gather_rows_kernel<2><<<grid, 256, 0, st>>>(src, dst, row, S, B, dim, gr);
     return keds_check_launch("gather_rows_kernel");
+}
+
+extern "C" int keds_gather_token_rows(const void* src, void* dst, const int32_t* row, int S, int B, int dim, int mode, int global_rows,
+                                      void* stream) {
+    return keds_gather_rows_impl(src, dst, row, S, B, dim, mode, (hipStream_t)stream, global_rows != 0);
 }
 
 extern "C" int keds_fold_layernorm_ex(const float* W, const float* bias, const float* gamma, const float* beta, int N, int K,

@@ -350,7 +350,7 @@ int keds_gather_rows_impl(const void* src, void* dst, const int32_t* row, int S,
                           bool global_rows = false);
 
 int keds_layernorm_pair_impl(const float* x, long long x_stride, const float* gamma, const float* beta, void* out, long long plane,
-                             int rows, int dim, hipStream_t st);
+                             int rows, int dim, hipStream_t st, int form = 0);
 
 // keds_tower_params.f32 == 2: the "fp32x3" operating point (round 5).  The same fp32 flow -- fp32 residual stream, fp32
 // LayerNorm / attention / QuickGELU -- with the four block GEMMs on SPLIT fp16 operands (keds_gemm_x3: x = hi + lo to 22 bits,
