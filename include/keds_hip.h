@@ -122,6 +122,48 @@ int keds_index_search_packed(const void* packed, const float* db, int64_t n, int
                       float* D, int64_t* I, float* rows_out,
                       void* workspace, size_t workspace_bytes, void* stream);
 
+/* The shape arithmetic of one launch set of keds_index_search_packed_ex (at most 1,024 queries), as pure host code that the
+ * search itself launches from: out[KEDS_SEARCH_PLAN_FIELDS] = {two_phase, stagesA (stages of the threshold pass), nqb (query
+ * blocks of 128), nwgA, nwgB (scan workgroups per query block of the threshold / candidate pass), depthA (list depth of the
+ * threshold pass), ncand, chunk_rows, nchunks (exact pass), total_stages}.  `cus` above 256 counts as 256.  keds_scan_debug bits
+ * 4 and 7-9 are honoured.  -1 where the search would be refused (exact-pass budget, a 2 GiB key stream). */
+#define KEDS_SEARCH_PLAN_FIELDS 10
+int keds_index_search_plan_query(int nq_set, int dim, int64_t n, int k, int cus, int32_t* out);
+
+/* The stages of the search one at a time on caller-owned device buffers: the kernels and launch helpers of
+ * keds_index_search_packed_ex (tests/test_gpu_search_kernels_edges.py).  A bad argument returns -1 before any launch.
+ *   qprep  : queries [nq, dim] (nq <= 1024) -> qn [nq, dim] fp32 (normalised if asked), qb [ceil(nq/128)*128, dim] bf16 (rows >= nq
+ *            zero), qstat [nq][4] = {||qn||^2, ||qn - qb|| rounded up, ||qb|| rounded up, 0}; clears counters[0].
+ *   scan   : stages [0, stages) of the image of n rows, nqb query blocks of qb, thr [nqb*128] or NULL, depth 1 / 4 / 16, nwg in
+ *            [1, min(stages, 256)] -> pairs [nqb*128][nwg][4*depth] (ord_key(score) << 32 | row), meta [nqb*128][nwg][2] = {entries,
+ *            largest last-slot key of the segment's full lists or 0}.  Slots at or behind the count are not written.
+ *   merge  : pairs / meta of nq queries (nwg <= 256 segments of `slots` = 4 / 16 / 64) -> cand_idx / cand_val [nq, ncand] (ncand 64 /
+ *            256; fillers -1 / -inf), thr_out [nq] (nullable), sbound [nq] (nullable); thr_in [nq] nullable.
+ *   rerank : cand_d [nq, ncand] = exact fp32 distance of qn[q] to db[cand_idx] (id < 0: +inf L2 / -inf IP).
+ *   certify: top-k by (distance, id) of the candidates -> D, I (+ id_base) [nq, k], and the certificate from qstat, sbound and
+ *            the image's trailer: fslot [nq] (-1 certified, else the query's place in fail_ids), dk [nq] of the failed,
+ *            counters[0] += failed (counters: int32 [8 + nq], [8 + f] = 0 per failed slot), status[0 / 1] += certified / failed
+ *            (nullable).  force_fail != 0 fails every query.
+ *   exact  : the exact pass over all n rows in chunks of chunk_rows in [1, 16384] (at most 2,048 chunks) for the counters[0]
+ *            queries of fail_ids, pruned by dk: plist uint64 [failed][nchunks][k], pcnt int32 [failed][nchunks]; rows of D / I
+ *            of other queries are untouched. */
+int keds_search_qprep(const float* queries, int nq, int dim, int normalize, float* qn, void* qb, float* qstat, int32_t* counters,
+                      void* stream);
+int keds_search_scan(const void* packed, int64_t n, int dim, int stages, const void* qb, int nqb, const float* thr /* nullable */,
+                     int depth, int nwg, uint64_t* pairs, uint32_t* meta, void* stream);
+int keds_search_merge(const uint64_t* pairs, const uint32_t* meta, int nq, int nwg, int slots, int ncand,
+                      const float* thr_in /* nullable */, int32_t* cand_idx, float* cand_val, float* thr_out /* nullable */,
+                      float* sbound /* nullable */, void* stream);
+int keds_search_rerank(const float* db, int dim, int metric, const float* qn, const int32_t* cand_idx, int nq, int ncand,
+                       float* cand_d, void* stream);
+int keds_search_certify(const void* packed, int64_t n, int dim, const int32_t* cand_idx, const float* cand_d, int nq, int ncand,
+                        int metric, int k, int64_t id_base, const float* qstat, const float* sbound, float* D, int64_t* I,
+                        int32_t* counters, int32_t* fail_ids, int32_t* fslot, float* dk, int32_t* status /* nullable */,
+                        int force_fail, void* stream);
+int keds_search_exact(const float* db, int64_t n, int dim, int metric, const float* qn, int32_t* counters, const int32_t* fail_ids,
+                      const float* dk, int chunk_rows, int k, int64_t id_base, uint64_t* plist, int32_t* pcnt, float* D, int64_t* I,
+                      void* stream);
+
 /* merge `parts` partial results [parts, nq, k] (each sorted) into the global top-k
  * (multi-GPU: after the all-gather of per-shard results).  Keyed on (D, I). */
 int keds_topk_merge_parts(const float* D_parts, const int64_t* I_parts, int parts, int nq, int k,

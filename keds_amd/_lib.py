@@ -164,6 +164,14 @@ SIGNATURES = {
     "keds_index_search_workspace_bytes_ex": (sz, [i32, i32, i64, i32]),
     "keds_index_search_packed_ex": (i32, [vp, vp, i64, i32, i32, vp, i32, i32, i32, i64, vp, vp, vp, vp, sz, vp, vp]),
     "keds_index_search_packed": (i32, [vp, vp, i64, i32, i32, vp, i32, i32, i32, i64, vp, vp, vp, vp, sz, vp]),
+    # the search's stages one at a time and its launch plan (tests/test_gpu_search_kernels_edges.py)
+    "keds_index_search_plan_query": (i32, [i32, i32, i64, i32, i32, vp]),
+    "keds_search_qprep": (i32, [vp, i32, i32, i32, vp, vp, vp, vp, vp]),
+    "keds_search_scan": (i32, [vp, i64, i32, i32, vp, i32, vp, i32, i32, vp, vp, vp]),
+    "keds_search_merge": (i32, [vp, vp, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp]),
+    "keds_search_rerank": (i32, [vp, i32, i32, vp, vp, i32, i32, vp, vp]),
+    "keds_search_certify": (i32, [vp, i64, i32, vp, vp, i32, i32, i32, i32, i64, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, vp]),
+    "keds_search_exact": (i32, [vp, i64, i32, i32, vp, vp, vp, vp, i32, i32, i64, vp, vp, vp, vp, vp]),
     "keds_topk_merge_parts": (i32, [vp, vp, i32, i32, i32, i32, vp, vp, vp]),
     "keds_exchange_pack": (i32, [vp, vp, vp, i32, i32, i32, i32, i64, vp, vp]),
     "keds_exchange_merge": (i32, [vp, i32, i32, i32, i32, i64, i32, vp, vp, vp, vp]),

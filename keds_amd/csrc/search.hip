@@ -81,6 +81,16 @@ __device__ __forceinline__ unsigned ord_key(float f) {
     const unsigned u = __float_as_uint(f);
     return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
 }
+// The certificate's bound on what the scan's score loses at the magnitude of the L2 bias b = -0.5||x||^2 (IP: no bias, 0): b is an
+// fp32 sum of dim squares (pack_kernel: a lane adds dim/64 of them, the butterfly 6 more, the square and the halving round once
+// each: (dim/64 + 8) u |b|), and it enters the MFMA chain as C-in, so each of the dim/32 steps rounds its sum at that magnitude
+// again (dim/32 u |b|; the dot product's own share is inside the 2e-4 ||q~|| max||x~|| term).  With |b| <= 0.5 max||x||^2:
+//   (3 dim/64 + 8) 2^-24 0.5 max||x||^2.
+// On unit rows it is 1e-6 of a score; with row norms of 2^7 and queries of norm 2^-7 it is 3x the rest of eps -- the scan's scores
+// of such rows were measured 1.04 eps away from their exact scores without it (tests/test_gpu_search_kernels_edges.py).
+__device__ __forceinline__ float bias_err(int dim, int metric, float xmax) {
+    return metric == KEDS_METRIC_L2 ? (float)(3 * dim / 64 + 8) * 5.9604645e-8f * 0.5f * xmax * xmax : 0.f;
+}
 __device__ __forceinline__ float key_float(unsigned k) { return __uint_as_float((k & 0x80000000u) ? (k & 0x7FFFFFFFu) : ~k); }
 
 // NT: LDS-DMA cache policy of the key stream (aux = 2: non-temporal -- the image is read once per search and is far larger
@@ -722,7 +732,7 @@ __global__ __launch_bounds__(MERGE_THREADS) void merge_pairs_kernel(const unsign
         const float d = act ? s_cd[t] : 0.f;
         const int id = act ? s_cid[t] : -1;
         const f32x4 qs = ta.qstat[q];
-        const float xt = ta.bounds->xt, rm = ta.bounds->r;
+        const float xt = ta.bounds->xt, rm = ta.bounds->r, xm = ta.bounds->x;
         const float key = metric == KEDS_METRIC_L2 ? d : -d;           // smaller is better
         int rank = 0;
         if (act) {
@@ -753,7 +763,7 @@ __global__ __launch_bounds__(MERGE_THREADS) void merge_pairs_kernel(const unsign
             if (ta.force_fail) ok = false;
             else if (!ok && nvalid >= k) {
                 const float tk = metric == KEDS_METRIC_L2 ? 0.5f * (qs[0] - s_dk) : s_dk;
-                const float eps = (qs[1] * xt + qs[2] * rm + qs[1] * rm + 2e-4f * qs[2] * xt) * 1.01f +
+                const float eps = (qs[1] * xt + qs[2] * rm + qs[1] * rm + 2e-4f * qs[2] * xt + bias_err(dim, metric, xm)) * 1.01f +
                                   1e-6f * (fabsf(tk) + qs[0] + 1.0f);
                 ok = tk - eps > sb;
             }
@@ -813,7 +823,8 @@ __global__ __launch_bounds__(256) void rerank_kernel(const float* __restrict__ d
 //   its exact score t = q.x - 0.5||x||^2 (L2) or q.x (IP) obeys  |t - s| <= eps(q)
 //       eps(q) = ||q - q~|| max||x~|| + ||q~|| max||x - x~|| + ||q - q~|| max||x - x~||  (Cauchy-Schwarz on
 //       q.x - q~.x~ = (q - q~).x~ + q~.(x - x~) + (q - q~).(x - x~); q~, x~ = the bf16 roundings the scan multiplies)
-//       + 2e-4 ||q~|| max||x~||  (fp32 accumulation of the MFMA chain: 768 adds x 2^-24 relative, 4x margin)
+//       + 2e-4 ||q~|| max||x~||  (fp32 accumulation of the MFMA chain: dim <= 1024 adds x 2^-24 relative, 3x margin)
+//       + (3 dim/64 + 8) 2^-24 0.5 max||x||^2  (L2: the bias's own fp32 sum and its way through the chain as C-in, bias_err)
 //   so if the k-th best candidate's exact score t_k satisfies  t_k - eps(q) > sbound[q],  every outside row is strictly
 //   worse than k candidates: the result is the exact top-k, ties included.  Otherwise the query goes to the exact
 //   fallback (exact_chunk_kernel, which also merges) with the pruning bound dk = the k-th candidate distance.
@@ -825,7 +836,7 @@ __global__ __launch_bounds__(256) void certify_select_kernel(const int* __restri
                                                              const DbBounds* __restrict__ bounds, int* __restrict__ counters,
                                                              int* __restrict__ fail_ids, int* __restrict__ fslot,
                                                              float* __restrict__ dk, int* __restrict__ status,
-                                                             int force_fail) {
+                                                             int force_fail, int dim) {
     __shared__ float s_key[NCAND_WIDE];
     __shared__ int s_id[NCAND_WIDE];
     __shared__ int s_nvalid;
@@ -836,7 +847,7 @@ __global__ __launch_bounds__(256) void certify_select_kernel(const int* __restri
     // (loaded up front by every thread: the certificate at the end then waits for no further memory round trip)
     const f32x4 qs = qstat[q];
     const float sb = sbound[q];
-    const float xt = bounds->xt, rm = bounds->r;
+    const float xt = bounds->xt, rm = bounds->r, xm = bounds->x;
     const float key = metric == KEDS_METRIC_L2 ? d : -d;           // smaller is better
     s_key[t] = key;
     s_id[t] = id;
@@ -871,7 +882,7 @@ __global__ __launch_bounds__(256) void certify_select_kernel(const int* __restri
         if (force_fail) ok = false;          // test hook (keds_scan_debug bit 5): every query takes the exact pass
         else if (!ok && nvalid >= k) {
             const float tk = metric == KEDS_METRIC_L2 ? 0.5f * (qs[0] - s_dk) : s_dk;
-            const float eps = (qs[1] * xt + qs[2] * rm + qs[1] * rm + 2e-4f * qs[2] * xt) * 1.01f +
+            const float eps = (qs[1] * xt + qs[2] * rm + qs[1] * rm + 2e-4f * qs[2] * xt + bias_err(dim, metric, xm)) * 1.01f +
                               1e-6f * (fabsf(tk) + qs[0] + 1.0f);
             ok = tk - eps > sb;
         }
@@ -1266,6 +1277,110 @@ bool dim_supported(int dim) { return dim == 128 || dim == 256 || dim == 512 || d
 
 size_t stage_bytes(int dim) { return (size_t)STAGE_KEYS * dim * 2 + 128; }
 
+// one scan launch of list depth `depth` (1 / 4: threshold pass, LISTK: candidate pass) over stages [0, stages)
+template <int D>
+int launch_scan_depth(int depth, const void* packed, int stages, const bf16_t* qb, const float* thr, unsigned long long* lval,
+                      uint2* lidx, int nwg, int nqb, hipStream_t st) {
+    if (depth == 1) return launch_scan<D, 1>(packed, 0, stages, qb, thr, lval, lidx, nwg, nqb, st);
+    if (depth == 4) return launch_scan<D, 4>(packed, 0, stages, qb, thr, lval, lidx, nwg, nqb, st);
+    return launch_scan<D, LISTK>(packed, 0, stages, qb, thr, lval, lidx, nwg, nqb, st);
+}
+
+int scan_dispatch(int dim, int depth, const void* packed, int stages, const bf16_t* qb, const float* thr, unsigned long long* lval,
+                  uint2* lidx, int nwg, int nqb, hipStream_t st) {
+    switch (dim) {
+        case 128: return launch_scan_depth<128>(depth, packed, stages, qb, thr, lval, lidx, nwg, nqb, st);
+        case 256: return launch_scan_depth<256>(depth, packed, stages, qb, thr, lval, lidx, nwg, nqb, st);
+        case 512: return launch_scan_depth<512>(depth, packed, stages, qb, thr, lval, lidx, nwg, nqb, st);
+        case 768: return launch_scan_depth<768>(depth, packed, stages, qb, thr, lval, lidx, nwg, nqb, st);
+        default: return launch_scan_depth<1024>(depth, packed, stages, qb, thr, lval, lidx, nwg, nqb, st);
+    }
+}
+
+// launch_scan's refusal as a predicate: the longest stage span of a workgroup (+ 1 stage) stays below the 2 GiB descriptor
+bool scan_span_ok(int stages, int nwg, int dim) {
+    return nwg > 0 && ((long long)(stages + nwg - 1) / nwg + 1) * (long long)stage_bytes(dim) < (1LL << 31);
+}
+
+int launch_qprep(const float* queries, int nb, int dim, int normalize, float* qn, bf16_t* qb, f32x4* qstat, int* counters,
+                 hipStream_t st) {
+    const int nqb = (nb + QBLOCK - 1) / QBLOCK;
+    qprep_kernel<<<nqb * QBLOCK / 4, 256, 0, st>>>(queries, nb, dim, normalize, qn, qb, nqb * QBLOCK, qstat, counters);
+    return keds_check_launch("qprep_kernel");
+}
+
+int launch_exact(const float* db, int64_t n, int dim, int metric, const float* qn, const int* counters, const int* fail_ids,
+                 const float* dk, int chunk_rows, int nchunks, int k, unsigned long long* plist, int* pcnt, int* done,
+                 long long id_base, float* Dq, long long* Iq, int cus, hipStream_t st) {
+    const size_t lds = (size_t)dim * 4 + (size_t)chunk_rows * 8;
+    if (int rc = keds_func_lds_once((const void*)exact_chunk_kernel, (int)lds, "exact_chunk_kernel")) return rc;
+    exact_chunk_kernel<<<4 * cus, 256, lds, st>>>(db, n, dim, metric, qn, counters, fail_ids, dk, chunk_rows, nchunks, k, plist, pcnt,
+                                                 done, id_base, Dq, Iq);
+    return keds_check_launch("exact_chunk_kernel");
+}
+
+// ---- the shape arithmetic of one launch set (<= MAXQB * QBLOCK queries), pure host code: keds_index_search_packed_ex launches
+// from it and keds_index_search_plan_query reports it.  `cus` is clipped to 256 (the merge's thread count = the most workgroups
+// whose lists a query can have).
+struct SearchPlan {
+    int two_phase, stagesA, nqb, nwgA, nwgB, depthA, ncand, chunk_rows, nchunks, total_stages, cus;
+    bool span_ok;
+};
+
+int scan_sample_div() {                     // KEDS_SCAN_SAMPLE_DIV=<d> forces a 1/d sample (A/B; experiments build only)
+    static int sample_div = -1;
+    if (sample_div < 0) {
+        const char* e = keds_exp_env("KEDS_SCAN_SAMPLE_DIV");
+        sample_div = e && atoi(e) >= 2 ? atoi(e) : 0;
+    }
+    return sample_div;
+}
+
+SearchPlan search_plan(int nq_set, int dim, int64_t n, int k, int cus) {
+    SearchPlan p;
+    p.total_stages = (int)((n + STAGE_KEYS - 1) / STAGE_KEYS);
+    p.ncand = k > LISTK ? NCAND_WIDE : NCAND;
+    p.cus = cus > 256 ? 256 : cus;
+    // Two phases so that list inserts are rare for ANY data: phase A scans the first 1/16 of the stages with empty
+    // lists (every lane fills its list: insert-heavy, but on 6 % of the bytes), the merge of phase A yields the
+    // ncand-th best score per query, and phase B scans everything accepting only scores above that threshold
+    // (expected accept rate 64 / rows(A): ~0.2 % at 0.5 M rows).  Small databases use one phase.
+    // (Measured, round 2: the sample size is flat around 1/16 -- 1/8 and 1/12 give the same whole-search time, 1/32 +8 us,
+    // 1/64 +45 us, 1/128 +75 us at 0.5 M rows: at a 0.2 % accept rate one compare in eight still takes the 16-slot insert for
+    // its whole wave, which is what a larger sample buys back.)
+    p.two_phase = g_scan_phases != 1 && p.total_stages >= 16 * 64;
+    // The sample: 1/16 of the rows, but at least 16 k rows (512 stages) where a quarter of the database allows it.  Round 4: at the
+    // 8-GPU shard shape (1,024 queries x 62.5 k rows) a 1/16 sample is 3.9 k rows, the accept rate 64 / 3.9 k = 1.6 % instead of
+    // the 0.2 % of the 0.5 M-row search, and with eight query blocks per launch set nothing hides the inserts: the candidate
+    // pass took 236 us of which 125 were list updates (keds_scan_debug ablations under rocprofv3).  Whole search at that shape with
+    // 1/16, 1/8, 1/6, 1/4, 1/3 of the rows sampled: 342, 301, 294, 292, 299 us; the 0.5 M-row search is unchanged (its 1/16 is 31 k
+    // rows).
+    const int sample_div = scan_sample_div();
+    p.stagesA = p.total_stages / 16;
+    if (sample_div) p.stagesA = p.total_stages / sample_div;
+    else if (p.stagesA < 512) p.stagesA = p.total_stages / 4 < 512 ? p.total_stages / 4 : 512;
+    // Up to MAXQB query blocks (1024 queries) share one set of launches: grid.y = query block, and the `cus`
+    // workgroups are divided between the blocks, each block's workgroups splitting the stage range.  A row-sharded
+    // multi-GPU search (every rank scans its small shard for ALL ranks' queries) then costs one launch set, and the
+    // shard is re-streamed per block from the Infinity Cache rather than HBM.
+    p.nqb = (nq_set + QBLOCK - 1) / QBLOCK;
+    int per = p.cus / p.nqb;
+    if (per < 1) per = 1;
+    p.nwgA = p.stagesA < per ? (p.stagesA < 1 ? 1 : p.stagesA) : per;
+    p.nwgB = p.total_stages < per ? p.total_stages : per;
+    // Threshold pass list depth.  Round 3: ONE entry per lane (its running maximum) wherever that still leaves 4 x ncand
+    // lane maxima per query: the ncand-th largest of nwgA * 4 group maxima is reached by ncand distinct rows (all a
+    // threshold has to guarantee), and with ~30 rows per group it sits within a few places of the exact ncand-th best of
+    // the sample -- the top ncand rows fall into distinct groups almost surely -- while the pass drops from an
+    // insert-bound 2.2 TB/s (depth-4 lists filling from empty) to streaming speed and its merge reads a quarter of the
+    // entries.  Few workgroups per query block (row-sharded search of many query blocks) keep depth 4.
+    p.depthA = g_thr_depth ? g_thr_depth : ((long)p.nwgA * 4 >= 4L * p.ncand ? 1 : 4);
+    p.chunk_rows = exact_chunk_rows(n, nq_set, k);
+    p.nchunks = p.chunk_rows ? (int)((n + p.chunk_rows - 1) / p.chunk_rows) : 0;
+    p.span_ok = scan_span_ok(p.total_stages, p.nwgB, dim) && (!p.two_phase || scan_span_ok(p.stagesA, p.nwgA, dim));
+    return p;
+}
+
 }  // namespace
 
 extern "C" int keds_merge_stamp_buffer(void* buf) {     // diagnostic: >= 8 uint64 per query; nullptr switches the stamps off
@@ -1342,97 +1457,33 @@ extern "C" int keds_index_search_packed_ex(const void* packed, const float* db, 
         return KEDS_E_WORKSPACE;
     }
     hipStream_t st = (hipStream_t)stream;
-    const int total_stages = (int)((n + STAGE_KEYS - 1) / STAGE_KEYS);
+    const int cus = device_cus();
+    const SearchPlan p0 = search_plan(nq < MAXQB * QBLOCK ? nq : MAXQB * QBLOCK, dim, n, k, cus);   // the call's largest launch set
+    const int total_stages = p0.total_stages, ncand = p0.ncand;
     const DbBounds* bounds = (const DbBounds*)((const char*)packed + (size_t)total_stages * stage_bytes(dim));
-    const int ncand = k > LISTK ? NCAND_WIDE : NCAND;
-    int cus = device_cus();
-    if (cus > 256) cus = 256;
-    // Two phases so that list inserts are rare for ANY data: phase A scans the first 1/16 of the stages with empty
-    // lists (every lane fills its list: insert-heavy, but on 6 % of the bytes), the merge of phase A yields the
-    // ncand-th best score per query, and phase B scans everything accepting only scores above that threshold
-    // (expected accept rate 64 / rows(A): ~0.2 % at 0.5 M rows).  Small databases use one phase.
-    // (Measured, round 2: the sample size is flat around 1/16 -- 1/8 and 1/12 give the same whole-search time, 1/32 +8 us,
-    // 1/64 +45 us, 1/128 +75 us at 0.5 M rows: at a 0.2 % accept rate one compare in eight still takes the 16-slot insert for
-    // its whole wave, which is what a larger sample buys back.)
-    const bool two_phase = g_scan_phases != 1 && total_stages >= 16 * 64;
-    // The sample: 1/16 of the rows, but at least 16 k rows (512 stages) where a quarter of the database allows it.  Round 4: at the
-    // 8-GPU shard shape (1,024 queries x 62.5 k rows) a 1/16 sample is 3.9 k rows, the accept rate 64 / 3.9 k = 1.6 % instead of
-    // the 0.2 % of the 0.5 M-row search, and with eight query blocks per launch set nothing hides the inserts: the candidate
-    // pass took 236 us of which 125 were list updates (keds_scan_debug ablations under rocprofv3).  Whole search at that shape with
-    // 1/16, 1/8, 1/6, 1/4, 1/3 of the rows sampled: 342, 301, 294, 292, 299 us; the 0.5 M-row search is unchanged (its 1/16 is 31 k
-    // rows).  KEDS_SCAN_SAMPLE_DIV=<d> forces 1/d (A/B).
-    static int sample_div = -1;
-    if (sample_div < 0) {
-        const char* e = keds_exp_env("KEDS_SCAN_SAMPLE_DIV");
-        sample_div = e && atoi(e) >= 2 ? atoi(e) : 0;
-    }
-    int stagesA = total_stages / 16;
-    if (sample_div) stagesA = total_stages / sample_div;
-    else if (stagesA < 512) stagesA = total_stages / 4 < 512 ? total_stages / 4 : 512;
     int rc;
-    // Up to MAXQB query blocks (1024 queries) share one set of launches: grid.y = query block, and the `cus`
-    // workgroups are divided between the blocks, each block's workgroups splitting the stage range.  A row-sharded
-    // multi-GPU search (every rank scans its small shard for ALL ranks' queries) then costs one launch set, and the
-    // shard is re-streamed per block from the Infinity Cache rather than HBM.
     for (int q0 = 0; q0 < nq; q0 += MAXQB * QBLOCK) {
         const int nb = nq - q0 < MAXQB * QBLOCK ? nq - q0 : MAXQB * QBLOCK;      // queries in this launch set
-        const int nqb = (nb + QBLOCK - 1) / QBLOCK;
-        int per = cus / nqb;
-        if (per < 1) per = 1;
-        const int nwgA = stagesA < per ? (stagesA < 1 ? 1 : stagesA) : per;
-        const int nwgB = total_stages < per ? total_stages : per;
+        const SearchPlan p = search_plan(nb, dim, n, k, cus);                    // (chunk lists: sized once per call, p0 / carve)
+        const bool two_phase = p.two_phase;
         float* qn = w.qn + (size_t)q0 * dim;
-        qprep_kernel<<<nqb * QBLOCK / 4, 256, 0, st>>>(queries + (size_t)q0 * dim, nb, dim, normalize_q, qn, w.qb,
-                                                      nqb * QBLOCK, w.qstat, w.counters);
-        if ((rc = keds_check_launch("qprep_kernel"))) return rc;
-        // Threshold pass list depth.  Round 3: ONE entry per lane (its running maximum) wherever that still leaves 4 x ncand
-        // lane maxima per query: the ncand-th largest of nwgA * 4 group maxima is reached by ncand distinct rows (all a
-        // threshold has to guarantee), and with ~30 rows per group it sits within a few places of the exact ncand-th best of
-        // the sample -- the top ncand rows fall into distinct groups almost surely -- while the pass drops from an
-        // insert-bound 2.2 TB/s (depth-4 lists filling from empty) to streaming speed and its merge reads a quarter of the
-        // entries.  Few workgroups per query block (row-sharded search of many query blocks) keep depth 4.
-        const int depthA = g_thr_depth ? g_thr_depth : ((long)nwgA * 4 >= 4L * ncand ? 1 : 4);
-        auto scan_thr = [&]() -> int {                             // shallow lists, no threshold
-            if (depthA == 1) {
-                switch (dim) {
-                    case 128: return launch_scan<128, 1>(packed, 0, stagesA, w.qb, nullptr, w.lpairs, w.lmeta, nwgA, nqb, st);
-                    case 256: return launch_scan<256, 1>(packed, 0, stagesA, w.qb, nullptr, w.lpairs, w.lmeta, nwgA, nqb, st);
-                    case 512: return launch_scan<512, 1>(packed, 0, stagesA, w.qb, nullptr, w.lpairs, w.lmeta, nwgA, nqb, st);
-                    case 768: return launch_scan<768, 1>(packed, 0, stagesA, w.qb, nullptr, w.lpairs, w.lmeta, nwgA, nqb, st);
-                    default: return launch_scan<1024, 1>(packed, 0, stagesA, w.qb, nullptr, w.lpairs, w.lmeta, nwgA, nqb, st);
-                }
-            }
-            switch (dim) {
-                case 128: return launch_scan<128, 4>(packed, 0, stagesA, w.qb, nullptr, w.lpairs, w.lmeta, nwgA, nqb, st);
-                case 256: return launch_scan<256, 4>(packed, 0, stagesA, w.qb, nullptr, w.lpairs, w.lmeta, nwgA, nqb, st);
-                case 512: return launch_scan<512, 4>(packed, 0, stagesA, w.qb, nullptr, w.lpairs, w.lmeta, nwgA, nqb, st);
-                case 768: return launch_scan<768, 4>(packed, 0, stagesA, w.qb, nullptr, w.lpairs, w.lmeta, nwgA, nqb, st);
-                default: return launch_scan<1024, 4>(packed, 0, stagesA, w.qb, nullptr, w.lpairs, w.lmeta, nwgA, nqb, st);
-            }
-        };
-        auto scan_all = [&](const float* thr) -> int {            // depth-16 lists over every stage
-            switch (dim) {
-                case 128: return launch_scan<128, LISTK>(packed, 0, total_stages, w.qb, thr, w.lpairs, w.lmeta, nwgB, nqb, st);
-                case 256: return launch_scan<256, LISTK>(packed, 0, total_stages, w.qb, thr, w.lpairs, w.lmeta, nwgB, nqb, st);
-                case 512: return launch_scan<512, LISTK>(packed, 0, total_stages, w.qb, thr, w.lpairs, w.lmeta, nwgB, nqb, st);
-                case 768: return launch_scan<768, LISTK>(packed, 0, total_stages, w.qb, thr, w.lpairs, w.lmeta, nwgB, nqb, st);
-                default: return launch_scan<1024, LISTK>(packed, 0, total_stages, w.qb, thr, w.lpairs, w.lmeta, nwgB, nqb, st);
-            }
-        };
+        if ((rc = launch_qprep(queries + (size_t)q0 * dim, nb, dim, normalize_q, qn, w.qb, w.qstat, w.counters, st))) return rc;
         if (two_phase) {
             // Threshold pass: every lane keeps the best 4 scores of its share of the first 1/16 of the rows; the
             // ncand-th best of their union is a score that ncand real rows reach, so the final candidates all beat or
             // equal it.  The candidate pass then rescans everything, inserting only above that threshold, so list
             // inserts are rare for ANY data.
-            if ((rc = scan_thr())) return rc;
+            if ((rc = scan_dispatch(dim, p.depthA, packed, p.stagesA, w.qb, nullptr, w.lpairs, w.lmeta, p.nwgA, p.nqb, st))) return rc;
             KedsProfScope prof(KEDS_PROF_OTHER, st);
-            merge_pairs_kernel<false><<<nb, MERGE_THREADS, 0, st>>>(w.lpairs, w.lmeta, nwgA, 4 * depthA, w.aidx, w.aval, w.thr, ncand,
+            merge_pairs_kernel<false><<<nb, MERGE_THREADS, 0, st>>>(w.lpairs, w.lmeta, p.nwgA, 4 * p.depthA, w.aidx, w.aval, w.thr, ncand,
                                                                     nullptr, nullptr, TailArgs{});
             if ((rc = keds_check_launch("merge_pairs_kernel(thr)"))) return rc;
         }
-        if ((rc = scan_all(two_phase ? w.thr : nullptr))) return rc;
+        if ((rc = scan_dispatch(dim, LISTK, packed, total_stages, w.qb, two_phase ? w.thr : nullptr, w.lpairs, w.lmeta, p.nwgB, p.nqb, st)))
+            return rc;
         {
             KedsProfScope prof(KEDS_PROF_OTHER, st);
+            const int nwgB = p.nwgB;
             float* Dq = D + (size_t)q0 * k;
             long long* Iq = (long long*)I + (size_t)q0 * k;
 #ifdef KEDS_EXPERIMENTS
@@ -1452,15 +1503,13 @@ extern "C" int keds_index_search_packed_ex(const void* packed, const float* db, 
                 if ((rc = keds_check_launch("rerank_kernel"))) return rc;
                 certify_select_kernel<<<nb, ncand, 0, st>>>(w.cidx, w.cdist, ncand, metric, k, (long long)id_base, Dq, Iq, w.qstat,
                                                             w.sbound, bounds, w.counters, w.fail_ids, w.fslot, w.dk, status,
-                                                            g_force_exact);
+                                                            g_force_exact, dim);
                 if ((rc = keds_check_launch("certify_select_kernel"))) return rc;
             }
-            // exact fallback for the queries whose certificate failed (both kernels return at once when none did)
-            const size_t lds = (size_t)dim * 4 + (size_t)w.chunk_rows * 8;
-            if ((rc = keds_func_lds_once((const void*)exact_chunk_kernel, (int)lds, "exact_chunk_kernel"))) return rc;
-            exact_chunk_kernel<<<4 * cus, 256, lds, st>>>(db, n, dim, metric, qn, w.counters, w.fail_ids, w.dk, w.chunk_rows,
-                                                         w.nchunks, k, w.plist, w.pcnt, w.counters + 8, (long long)id_base, Dq, Iq);
-            if ((rc = keds_check_launch("exact_chunk_kernel"))) return rc;
+            // exact fallback for the queries whose certificate failed (the kernel returns at once when none did)
+            if ((rc = launch_exact(db, n, dim, metric, qn, w.counters, w.fail_ids, w.dk, w.chunk_rows, w.nchunks, k, w.plist, w.pcnt,
+                                   w.counters + 8, (long long)id_base, Dq, Iq, p.cus, st)))
+                return rc;
         }
     }
     if (rows_out) {
@@ -1478,6 +1527,111 @@ extern "C" int keds_index_search_packed(const void* packed, const float* db, int
                                  void* stream) {
     return keds_index_search_packed_ex(packed, db, n, dim, metric, queries, nq, normalize_q, k, id_base, D, I, rows_out,
                                        workspace, workspace_bytes, nullptr, stream);
+}
+
+// ---- the stages of the search one at a time, on caller-owned buffers (tests/test_gpu_search_kernels_edges.py): the same kernels
+// through the same launch helpers as keds_index_search_packed_ex.  Every argument is checked before anything is launched.
+extern "C" int keds_index_search_plan_query(int nq_set, int dim, int64_t n, int k, int cus, int32_t* out) {
+    KEDS_REQUIRE(out, "keds_index_search_plan_query: null pointer");
+    KEDS_REQUIRE(nq_set >= 1 && nq_set <= MAXQB * QBLOCK, "keds_index_search_plan_query: nq_set must be in [1,%d]", MAXQB * QBLOCK);
+    KEDS_REQUIRE(dim_supported(dim), "keds_index_search_plan_query: dim %d unsupported", dim);
+    KEDS_REQUIRE(n > 0 && n <= 2048LL * 16384, "keds_index_search_plan_query: n must be in [1, 2048 * 16384]");
+    KEDS_REQUIRE(k >= 1 && k <= MAXK && cus >= 1, "keds_index_search_plan_query: k must be in [1,%d], cus >= 1", MAXK);
+    const SearchPlan p = search_plan(nq_set, dim, n, k, cus);
+    KEDS_REQUIRE(p.chunk_rows > 0, "keds_index_search_plan_query: %lld rows x %d queries x k=%d exceed the exact-fallback budget",
+                 (long long)n, nq_set, k);
+    KEDS_REQUIRE(p.span_ok, "keds_index_search_plan_query: a workgroup's key stream would span 2 GiB or more");
+    const int v[KEDS_SEARCH_PLAN_FIELDS] = {p.two_phase, p.stagesA, p.nqb, p.nwgA, p.nwgB, p.depthA, p.ncand, p.chunk_rows,
+                                            p.nchunks, p.total_stages};
+    for (int i = 0; i < KEDS_SEARCH_PLAN_FIELDS; ++i) out[i] = v[i];
+    return KEDS_OK;
+}
+
+extern "C" int keds_search_qprep(const float* queries, int nq, int dim, int normalize, float* qn, void* qb, float* qstat,
+                                 int32_t* counters, void* stream) {
+    KEDS_REQUIRE(queries && qn && qb && qstat && counters, "keds_search_qprep: null pointer");
+    KEDS_REQUIRE(dim_supported(dim), "keds_search_qprep: dim %d unsupported", dim);
+    KEDS_REQUIRE(nq >= 1 && nq <= MAXQB * QBLOCK, "keds_search_qprep: nq must be in [1,%d] (got %d)", MAXQB * QBLOCK, nq);
+    return launch_qprep(queries, nq, dim, normalize, qn, (bf16_t*)qb, (f32x4*)qstat, counters, (hipStream_t)stream);
+}
+
+extern "C" int keds_search_scan(const void* packed, int64_t n, int dim, int stages, const void* qb, int nqb, const float* thr,
+                                int depth, int nwg, uint64_t* pairs, uint32_t* meta, void* stream) {
+    KEDS_REQUIRE(packed && qb && pairs && meta, "keds_search_scan: null pointer");
+    KEDS_REQUIRE(dim_supported(dim), "keds_search_scan: dim %d unsupported", dim);
+    KEDS_REQUIRE(n > 0 && n <= 2048LL * 16384, "keds_search_scan: n must be in [1, 2048 * 16384]");
+    const int total_stages = (int)((n + STAGE_KEYS - 1) / STAGE_KEYS);
+    KEDS_REQUIRE(stages >= 1 && stages <= total_stages, "keds_search_scan: stages must be in [1,%d] (got %d)", total_stages, stages);
+    KEDS_REQUIRE(nqb >= 1 && nqb <= MAXQB, "keds_search_scan: query blocks must be in [1,%d] (got %d)", MAXQB, nqb);
+    KEDS_REQUIRE(depth == 1 || depth == 4 || depth == LISTK, "keds_search_scan: list depth must be 1, 4 or %d (got %d)", LISTK, depth);
+    KEDS_REQUIRE(nwg >= 1 && nwg <= 256 && nwg <= stages, "keds_search_scan: nwg must be in [1, min(stages, 256)] (got %d)", nwg);
+    KEDS_REQUIRE(scan_span_ok(stages, nwg, dim), "keds_search_scan: %d stages over %d workgroups: a workgroup's key stream would "
+                 "span 2 GiB or more", stages, nwg);
+    return scan_dispatch(dim, depth, packed, stages, (const bf16_t*)qb, thr, (unsigned long long*)pairs, (uint2*)meta, nwg, nqb,
+                         (hipStream_t)stream);
+}
+
+extern "C" int keds_search_merge(const uint64_t* pairs, const uint32_t* meta, int nq, int nwg, int slots, int ncand,
+                                 const float* thr_in, int32_t* cand_idx, float* cand_val, float* thr_out, float* sbound,
+                                 void* stream) {
+    KEDS_REQUIRE(pairs && meta && cand_idx && cand_val, "keds_search_merge: null pointer");
+    KEDS_REQUIRE(nq >= 1 && nq <= MAXQB * QBLOCK, "keds_search_merge: nq must be in [1,%d] (got %d)", MAXQB * QBLOCK, nq);
+    KEDS_REQUIRE(nwg >= 1 && nwg <= MERGE_THREADS, "keds_search_merge: nwg must be in [1,%d] (got %d)", MERGE_THREADS, nwg);
+    KEDS_REQUIRE(slots == 4 || slots == 16 || slots == MERGE_SLOTS, "keds_search_merge: slots must be 4, 16 or 64 (got %d)", slots);
+    KEDS_REQUIRE(ncand == NCAND || ncand == NCAND_WIDE, "keds_search_merge: ncand must be 64 or 256 (got %d)", ncand);
+    hipStream_t st = (hipStream_t)stream;
+    KedsProfScope prof(KEDS_PROF_OTHER, st);
+    merge_pairs_kernel<false><<<nq, MERGE_THREADS, 0, st>>>((const unsigned long long*)pairs, (const uint2*)meta, nwg, slots, cand_idx,
+                                                            cand_val, thr_out, ncand, thr_in, sbound, TailArgs{});
+    return keds_check_launch("merge_pairs_kernel");
+}
+
+extern "C" int keds_search_rerank(const float* db, int dim, int metric, const float* qn, const int32_t* cand_idx, int nq, int ncand,
+                                  float* cand_d, void* stream) {
+    KEDS_REQUIRE(db && qn && cand_idx && cand_d, "keds_search_rerank: null pointer");
+    KEDS_REQUIRE(dim_supported(dim), "keds_search_rerank: dim %d unsupported", dim);
+    KEDS_REQUIRE(metric == KEDS_METRIC_L2 || metric == KEDS_METRIC_IP, "keds_search_rerank: bad metric");
+    KEDS_REQUIRE(nq >= 1 && nq <= MAXQB * QBLOCK, "keds_search_rerank: nq must be in [1,%d] (got %d)", MAXQB * QBLOCK, nq);
+    KEDS_REQUIRE(ncand == NCAND || ncand == NCAND_WIDE, "keds_search_rerank: ncand must be 64 or 256 (got %d)", ncand);
+    rerank_kernel<<<(nq * ncand + 3) / 4, 256, 0, (hipStream_t)stream>>>(db, dim, metric, qn, cand_idx, cand_d, nq * ncand, ncand);
+    return keds_check_launch("rerank_kernel");
+}
+
+extern "C" int keds_search_certify(const void* packed, int64_t n, int dim, const int32_t* cand_idx, const float* cand_d, int nq,
+                                   int ncand, int metric, int k, int64_t id_base, const float* qstat, const float* sbound, float* D,
+                                   int64_t* I, int32_t* counters, int32_t* fail_ids, int32_t* fslot, float* dk, int32_t* status,
+                                   int force_fail, void* stream) {
+    KEDS_REQUIRE(packed && cand_idx && cand_d && qstat && sbound && D && I && counters && fail_ids && fslot && dk,
+                 "keds_search_certify: null pointer");
+    KEDS_REQUIRE(dim_supported(dim), "keds_search_certify: dim %d unsupported", dim);
+    KEDS_REQUIRE(n > 0 && n <= 2048LL * 16384, "keds_search_certify: n must be in [1, 2048 * 16384]");
+    KEDS_REQUIRE(metric == KEDS_METRIC_L2 || metric == KEDS_METRIC_IP, "keds_search_certify: bad metric");
+    KEDS_REQUIRE(nq >= 1 && nq <= MAXQB * QBLOCK, "keds_search_certify: nq must be in [1,%d] (got %d)", MAXQB * QBLOCK, nq);
+    KEDS_REQUIRE(ncand == NCAND || ncand == NCAND_WIDE, "keds_search_certify: ncand must be 64 or 256 (got %d)", ncand);
+    KEDS_REQUIRE(k >= 1 && k <= MAXK && k <= ncand, "keds_search_certify: k must be in [1, min(%d, ncand)] (got %d)", MAXK, k);
+    const int64_t stages = (n + STAGE_KEYS - 1) / STAGE_KEYS;
+    const DbBounds* bounds = (const DbBounds*)((const char*)packed + (size_t)stages * stage_bytes(dim));
+    certify_select_kernel<<<nq, ncand, 0, (hipStream_t)stream>>>(cand_idx, cand_d, ncand, metric, k, (long long)id_base, D, (long long*)I,
+                                                                 (const f32x4*)qstat, sbound, bounds, counters, fail_ids, fslot, dk,
+                                                                 status, force_fail ? 1 : 0, dim);
+    return keds_check_launch("certify_select_kernel");
+}
+
+extern "C" int keds_search_exact(const float* db, int64_t n, int dim, int metric, const float* qn, int32_t* counters,
+                                 const int32_t* fail_ids, const float* dk, int chunk_rows, int k, int64_t id_base, uint64_t* plist,
+                                 int32_t* pcnt, float* D, int64_t* I, void* stream) {
+    KEDS_REQUIRE(db && qn && counters && fail_ids && dk && plist && pcnt && D && I, "keds_search_exact: null pointer");
+    KEDS_REQUIRE(dim_supported(dim), "keds_search_exact: dim %d unsupported", dim);
+    KEDS_REQUIRE(n > 0 && n <= 2048LL * 16384, "keds_search_exact: n must be in [1, 2048 * 16384]");
+    KEDS_REQUIRE(metric == KEDS_METRIC_L2 || metric == KEDS_METRIC_IP, "keds_search_exact: bad metric");
+    KEDS_REQUIRE(k >= 1 && k <= MAXK, "keds_search_exact: k must be in [1,%d] (got %d)", MAXK, k);
+    KEDS_REQUIRE(chunk_rows >= 1 && chunk_rows <= 16384, "keds_search_exact: chunk_rows must be in [1,16384] (got %d)", chunk_rows);
+    const int64_t nchunks = (n + chunk_rows - 1) / chunk_rows;
+    KEDS_REQUIRE(nchunks <= 2048, "keds_search_exact: %lld chunks of %d rows: at most 2048", (long long)nchunks, chunk_rows);
+    int cus = device_cus();
+    if (cus > 256) cus = 256;
+    return launch_exact(db, n, dim, metric, qn, counters, fail_ids, dk, chunk_rows, (int)nchunks, k, (unsigned long long*)plist, pcnt,
+                        counters + 8, (long long)id_base, D, (long long*)I, cus, (hipStream_t)stream);
 }
 
 extern "C" int keds_topk_merge_parts(const float* D_parts, const int64_t* I_parts, int parts, int nq, int k,
