@@ -30,14 +30,16 @@ extern "C" {
 #define KEDS_E_LAUNCH (-2)   /* HIP launch or runtime error */
 #define KEDS_E_WORKSPACE (-3)/* workspace too small */
 
-#define KEDS_ABI_VERSION 10       /* 10: keds_block_source, keds_block_pack_bytes, keds_block_pack (one weight-packing routine for both loaders);
+#define KEDS_ABI_VERSION 11       /* 11: keds_merge_stamp_buffer, keds_attention_stamp_buffer and keds_tower_fill_enable left the library; the debug
+                                     hooks refuse the timing-only variants they no longer offer (last at 14f64ac);
+                                     10: keds_block_source, keds_block_pack_bytes, keds_block_pack (one weight-packing routine for both loaders);
                                      9: the "fp16" operating point -- keds_tower_params.f16, KEDS_EPI_*_F16_H / *_F32_H epilogues, keds_attention_h /
                                      keds_attention_packed_h, keds_im2col_ex, keds_layernorm_ex, keds_cast_f16;
                                      8 (round 6): keds_gemm_x3 takes w_exp, keds_split_f16_weight, keds_block_params.x3_exp, keds_text_run_packed / keds_attention_packed; keds_gemm_duo_enable left the product */
 
 int keds_abi_version(void);
 /* compiler flags of this build beyond the Makefile's defaults ("" for the product build; `make EXTRA="-D..."` variants of the
- * A/B and timing-only scripts record theirs here, and the evidence digest of keds_amd/_lib.py includes it) */
+ * A/B scripts record theirs here, and the evidence digest of keds_amd/_lib.py includes it) */
 const char* keds_build_flags(void);
 const char* keds_last_error(void);
 
@@ -80,11 +82,10 @@ int keds_prof_read_work(int klass, double* units);
 #define KEDS_SCAN_CAND 64           /* candidates re-ranked in fp32 per query for k <= 16 (256 for larger k) */
 #define KEDS_SCAN_MAX_K 128         /* largest k of keds_index_search_packed */
 
-/* timing-only ablation hook of the D=768 scan kernel (0 = product path) */
+/* test / A/B hook of the search, process-wide (0 = product path); every form it selects is exact: bit 4 single-phase scan,
+ * bit 5 every query through the exact pass, bit 6 default-policy key stream, bits 7-9 threshold-pass list depth 1 or 4.
+ * Bits 0-3 (timing-only scan ablations) and bit 10 (the fused search tail) last existed at 14f64ac: KEDS_E_ARG, state unchanged. */
 int keds_scan_debug(int variant);
-/* diagnostic: device buffer (>= 8 uint64 per query) that merge_pairs_kernel fills with s_memtime stamps of its phases
- * (tools/stamp_merge.py); nullptr switches them off */
-int keds_merge_stamp_buffer(void* buf);
 
 /* bytes of the packed bf16 scan image for n rows of dimension dim (dim % 128 == 0); the image ends with a 128-byte
  * trailer holding max ||bf16(x)||, max ||x - bf16(x)||, max ||x|| over the rows (the search certificate's bounds) */
@@ -293,7 +294,8 @@ int keds_rowstats_cast_ex(const float* x, void* xb, int out_f16, float* stats, i
  * multiplied by v_mfma_scale_f32_16x16x128_f8f6f4 (block scales applied in hardware, 2x the bf16 MFMA rate).
  * Scales are stored as [K/128][rows_pad] dwords: byte b of dword (t, r) scales elements 128 t + 32 b .. + 31 of row r. */
 size_t keds_mxfp8_scale_bytes(int rows_pad, int K);
-int keds_mxfp8_debug(int variant);          /* timing-only ablation hook of the MXFP8 GEMM (0 = product path) */
+int keds_mxfp8_debug(int variant);          /* test hook: 16 = every shape on the 8-wave kernel, 0 = product path; any other value
+                                               (the timing-only ablations 1-4, last at 14f64ac) is KEDS_E_ARG, state unchanged */
 /* x fp32 or bf16 [rows, K] dense -> q fp8 [rows, K], scales as above.  K % 128 == 0. */
 int keds_quantize_mxfp8(const void* x, int x_is_bf16, int rows, int K, int rows_pad, void* q, void* scales, void* stream);
 /* out bf16 [M,N] = A . W^T + bias with A [M,K], W [N,K] in MXFP8 (m_pad / n_pad: row counts of the scale arrays).
@@ -346,10 +348,10 @@ int keds_split_f16_weight(const float* w, int64_t n, int k, void* out, int64_t p
  * docs/kernels.md: the table of forms).  The three entries below steer it, report what it led to, and ask it without a GPU.
  *
  * test/bench hook, process-wide, `on` replaces the previous call's bits: bit 0 routes every GEMM through the 128x128 kernel,
- * bit 8 skips the remainder-row launch (timing only), bit 9 disables split-K; A/B switches of the 256x256 kernels: bit 10
- * residual tile as the accumulators' initial value, bits 11-12 kernel form (1 = 4 waves, 2 = 4 waves persistent, 3 = 8 waves;
- * 0 = by shape), bits 13-15 stamped diagnostic build (launched outside the plan: nothing is recorded for it), bit 16 no
- * three-deep A ring, bit 17 no deferred epilogue stores in the persistent kernel */
+ * bit 9 disables split-K; A/B switches of the 256x256 kernels: bit 10 residual tile as the accumulators' initial value,
+ * bits 11-12 kernel form (1 = 4 waves, 2 = 4 waves persistent, 3 = 8 waves; 0 = by shape), bit 16 no three-deep A ring,
+ * bit 17 no deferred epilogue stores in the persistent kernel.  Every form computes the same GEMM.  Bit 8 (no remainder-row
+ * launch) and bits 13-15 (stamped builds) were timing-only and last existed at 14f64ac: KEDS_E_ARG, previous bits kept. */
 int keds_gemm_force_small(int on);
 /* test hook: what the last keds_gemm_bt* / keds_gemm_x3 call of the calling thread launched -- written where each kernel is
  * launched, not copied from the plan; a call whose launches differ from its plan fails with KEDS_E_LAUNCH.  info[8] (host ints, written):
@@ -366,7 +368,7 @@ int keds_gemm_force_small(int on);
 #define KEDS_GEMM_FLAG_RESID_PROLOGUE 2  /* residual tile + bias as the accumulators' initial value (bit 10 of the hook above) */
 int keds_gemm_last_launch(int* info);
 /* The plan of the call keds_gemm_bt_ex2 / keds_gemm_x3 (epilogue, M, N, K, lda, ldc) on a device of `cus` compute units, with
- * `splitk_bytes` of split-K scratch registered (0: none) and, small_lds != 0, inside a composite that asked for the 64 KiB-LDS
+ * `splitk_bytes` of split-K scratch registered (0: none) and, small_lds != 0, with the 64 KiB-LDS
  * form of the 128 x 128 kernel; under the switches keds_gemm_force_small set.  info[8] as keds_gemm_last_launch.  Touches no
  * device.  The shape rules of keds_gemm_bt_ex2 apply (N % 128, K % 64, row strides, a dense EPI_PATCH output). */
 int keds_gemm_plan_query(int epilogue, int M, int N, int K, int64_t lda, int64_t ldc, int cus, size_t splitk_bytes, int small_lds,
@@ -408,11 +410,9 @@ int keds_gather_token_rows(const void* src, void* dst, const int32_t* row, int S
 /* x[b * S, :] = cls + pos[0]: the class-token rows of a [B, S, d] stream; every other row is left alone */
 int keds_cls_rows(float* x, const float* cls, const float* pos, int B, int S, int d, void* stream);
 
-/* timing-only ablation hook of the S > 96 attention kernel (0 = product path) */
+/* test / A/B hook of the S = 257 attention, process-wide (0 = product path): bit 4 the generic (padded) kernel, bit 5 the 4-wave
+ * tail kernel.  Bits 0-3 and 6 (timing-only ablations) last existed at 14f64ac: KEDS_E_ARG, state unchanged. */
 int keds_attention_debug(int variant);
-/* diagnostic: device buffer of B * heads * 64 uint64 that the stamped build (keds_attention_debug(64 + 8)) of the S = 257
- * kernel fills with per-wave phase durations in shader cycles (tools/stamp_attn.py) */
-int keds_attention_stamp_buffer(void* buf);
 
 /* multi-head self attention core on a packed qkv buffer (nn.MultiheadAttention,
  * model.py:309,319-321): qkv bf16 [B*S, 3*d] (q | k | v, head h at columns h*64),
@@ -567,7 +567,6 @@ size_t keds_tower_workspace_bytes_ex(const keds_tower_params* p, int B);   /* kn
  * full-tile launches only (bench.py scales the flops to match). */
 int keds_tower_side_rows(int width, int seq, int B, int fp8);
 int keds_side_lane_enable(int on);            /* run-time override of KEDS_SIDE_STREAM (default: on); results are identical */
-int keds_tower_fill_enable(int on);           /* run-time override of KEDS_TOWER_FILL (default: off): ragged last row tile on filler rows */
 
 /* x fp32 [B*seq (padded to 128), width] in place through all residual blocks (model.py:372-373); workspace: rows padded to 256 */
 int keds_tower_forward(const keds_tower_params* p, float* x, int B,

@@ -17,7 +17,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "csrc", "libkeds_hip.so")
 
 # ---- constants mirrored from keds_hip.h ------------------------------------------------------
-ABI_VERSION = 10
+ABI_VERSION = 11
 METRIC_L2, METRIC_IP = 0, 1
 EPI_BIAS_BF16, EPI_BIAS_QGELU_BF16, EPI_BIAS_RELU_BF16, EPI_BIAS_RESID_F32, EPI_BIAS_F32, EPI_PATCH_F32 = range(6)
 EPI_LN_BIAS_BF16, EPI_LN_QGELU_BF16, EPI_RESID_STATS_F32, EPI_RESID_STATS_F16 = 6, 7, 8, 9
@@ -156,7 +156,6 @@ SIGNATURES = {
     "keds_prof_read": (i32, [i32, C.POINTER(C.c_double), C.POINTER(i64)]),
     "keds_prof_read_work": (i32, [i32, C.POINTER(C.c_double)]),
     "keds_scan_debug": (i32, [i32]),
-    "keds_merge_stamp_buffer": (i32, [vp]),
     "keds_index_packed_bytes": (sz, [i64, i32]),
     "keds_index_pack": (i32, [vp, i64, i32, i32, vp, vp]),
     "keds_index_pack_append": (i32, [vp, i64, i64, i32, i32, vp, vp]),
@@ -204,7 +203,6 @@ SIGNATURES = {
     "keds_gemm_bt_ex": (i32, [vp, i64, vp, vp, vp, i64, i32, i32, i32, i32, vp, i32, vp]),
     "keds_layernorm": (i32, [vp, i64, vp, vp, vp, i32, i32, i32, vp]),
     "keds_attention_debug": (i32, [i32]),
-    "keds_attention_stamp_buffer": (i32, [vp]),
     "keds_attention_ex": (i32, [vp, vp, i32, i32, i32, i32, i32, vp]),
     "keds_attention_mx": (i32, [vp, vp, i32, i32, i32, i32, i32, vp, vp, i32, vp]),
     "keds_attention": (i32, [vp, vp, i32, i32, i32, i32, vp]),
@@ -218,7 +216,6 @@ SIGNATURES = {
     "keds_l2_normalize": (i32, [vp, vp, i32, i32, vp]),
     "keds_mix_normalize": (i32, [vp, vp, f32, f32, vp, vp, vp, i32, i32, vp]),
     "keds_cast_bf16": (i32, [vp, vp, i64, vp]),
-    "keds_tower_fill_enable": (i32, [i32]),
     "keds_tower_workspace_bytes": (sz, [i32, i32, i32]),
     "keds_tower_workspace_bytes_ex": (sz, [C.POINTER(TowerParams), i32]),
     "keds_gemm_f32": (i32, [vp, i64, vp, vp, vp, i64, i32, i32, i32, i32, vp, i32, vp]),
@@ -334,7 +331,7 @@ def source_digest() -> str:
 
 
 def build_flags() -> str:
-    """The EXTRA flags the loaded library was built with ("" for the product build; "-DKEDS_EXPERIMENTS ..." for the A/B tools')."""
+    """The EXTRA flags the loaded library was built with ("" for the product build; "-DKEDS_ST_LN=1 ..." for an A/B variant)."""
     return (load().keds_build_flags() or b"").decode().strip()
 
 

@@ -72,7 +72,7 @@ struct AttnCtx {
 // TAIL: the sequence is 16*NKT + 1 keys; the MFMA tiles cover the first 16*NKT and the last key is a rank-1 VALU update
 // (its score from the lane's 16 query dims + a reduction over the four lanes of the query, its P.V term 16 FMAs per tile)
 // instead of two more key tiles of which 31 of 32 columns would be padding.
-template <typename T, int NKT, bool CAUSAL, int NFULL, int DBG, int NQ, bool TAIL = false>
+template <typename T, int NKT, bool CAUSAL, int NFULL, int NQ, bool TAIL = false>
 __device__ __forceinline__ void attn_tiles(const AttnCtx<T>& cx, int qt0) {
     using C = AttnCfg<NKT>;
     using V8 = typename Ev<T>::v8;
@@ -101,12 +101,8 @@ __device__ __forceinline__ void attn_tiles(const AttnCtx<T>& cx, int qt0) {
 #pragma unroll
         for (int t = 0; t < NQ; ++t) {
             f32x4 acc = f32x4{0.f, 0.f, 0.f, 0.f};
-            if constexpr (DBG != 2) {
-                acc = mfma16(a0, qf[t][0], acc, 0, 0, 0);
-                acc = mfma16(a1, qf[t][1], acc, 0, 0, 0);
-            } else {
-                acc[0] = (float)qf[t][0][kt & 7];
-            }
+            acc = mfma16(a0, qf[t][0], acc, 0, 0, 0);
+            acc = mfma16(a1, qf[t][1], acc, 0, 0, 0);
             sc[t][kt] = acc;
         }
         if (kt % 3 == 2) __builtin_amdgcn_sched_barrier(0);   // bound how far LDS reads are hoisted (VGPR pressure)
@@ -154,11 +150,9 @@ __device__ __forceinline__ void attn_tiles(const AttnCtx<T>& cx, int qt0) {
 #pragma unroll
             for (int hh = 0; hh < 2; ++hh) {
                 f32x2 e = f32x2{sc[t][kt][2 * hh], sc[t][kt][2 * hh + 1]};
-                if constexpr (DBG != 3) {
-                    e = pk_fma(e, vs, vn);
-                    e[0] = __builtin_amdgcn_exp2f(e[0]);   // exp2(-inf) = 0
-                    e[1] = __builtin_amdgcn_exp2f(e[1]);
-                }
+                e = pk_fma(e, vs, vn);
+                e[0] = __builtin_amdgcn_exp2f(e[0]);   // exp2(-inf) = 0
+                e[1] = __builtin_amdgcn_exp2f(e[1]);
                 sc[t][kt][2 * hh] = e[0];
                 sc[t][kt][2 * hh + 1] = e[1];
                 vsum += e;
@@ -190,15 +184,9 @@ __device__ __forceinline__ void attn_tiles(const AttnCtx<T>& cx, int qt0) {
         }
 #pragma unroll
         for (int dt = 0; dt < 4; ++dt) {
-            if constexpr (DBG != 4) {
-                const V8 a =
-                    *reinterpret_cast<const V8*>(cx.vt_lds + (dt * 16 + c) * C::VT_ROW + (4 * u + g) * 16);
+            const V8 a = *reinterpret_cast<const V8*>(cx.vt_lds + (dt * 16 + c) * C::VT_ROW + (4 * u + g) * 16);
 #pragma unroll
-                for (int t = 0; t < NQ; ++t) o[t][dt] = mfma16(a, pf[t], o[t][dt], 0, 0, 0);
-            } else {
-#pragma unroll
-                for (int t = 0; t < NQ; ++t) o[t][dt][0] += (float)pf[t][dt];
-            }
+            for (int t = 0; t < NQ; ++t) o[t][dt] = mfma16(a, pf[t], o[t][dt], 0, 0, 0);
         }
         if (u % 3 == 2) __builtin_amdgcn_sched_barrier(0);
     }
@@ -245,10 +233,9 @@ __device__ __forceinline__ void attn_tiles(const AttnCtx<T>& cx, int qt0) {
     }
 }
 
-// DBG (timing-only ablations): 1 = no K/V staging, 2 = no QK^T MFMA/reads, 3 = no softmax math, 4 = no PV, 5 = no q loop
 // CAUSAL: text tower mask.  NFULL: key tiles [0, NFULL) are known at compile time to lie entirely below S and
 // need no mask (non-causal only) -- evaluating the mask for all 72 score registers cost half the loop's instructions.
-template <int NKT, bool CAUSAL, int NFULL, int DBG = 0, bool NQ2 = (NKT == 18 && !CAUSAL), typename T = bf16_t>
+template <int NKT, bool CAUSAL, int NFULL, bool NQ2 = (NKT == 18 && !CAUSAL), typename T = bf16_t>
 __global__ __launch_bounds__(256, 2) void attention_kernel(const T* __restrict__ qkv, T* __restrict__ out, int S,
                                                         int heads, int q_limit, unsigned char* __restrict__ q8,
                                                         unsigned char* __restrict__ s8, int q8_rows,
@@ -278,7 +265,7 @@ __global__ __launch_bounds__(256, 2) void attention_kernel(const T* __restrict__
     // Work item = (4 consecutive keys, one 8-wide dh chunk): all global loads of a thread are issued before the
     // first LDS write (one HBM round trip instead of one per item), K goes in with ds_write_b128, and the four
     // keys of an item are adjacent in the permuted V^T row, so V^T goes in with 8-byte stores.
-    if constexpr (DBG != 1) {
+    {
         constexpr int ITEMS = (C::KEYS / 4) * 8;
         constexpr int PER = (ITEMS + 255) / 256;
         V8 kreg[PER][4], vreg[PER][4];
@@ -322,14 +309,14 @@ __global__ __launch_bounds__(256, 2) void attention_kernel(const T* __restrict__
 
     // ---- queries: NQ = 2 tiles (32 queries) per step share every K / V^T fragment read from LDS (the loop is
     // LDS-bandwidth bound: 72 ds_read_b128 per 16-query tile); an odd last tile runs alone on a rotating wave.
-    const int nqt = DBG == 5 ? 0 : (q_limit + 15) >> 4;      // only the first q_limit query rows are computed and stored
+    const int nqt = (q_limit + 15) >> 4;      // only the first q_limit query rows are computed and stored
     AttnCtx<T> cx{base, out + (size_t)row0 * d + h * DH, k_lds, vt_lds, S, q_limit, ld, d, g, c, q8, s8, q8_rows, row0, h * DH};
     if constexpr (NQ2) {
         const int npair = nqt >> 1;
-        for (int qp = wave; qp < npair; qp += 4) attn_tiles<T, NKT, CAUSAL, NFULL, DBG, 2>(cx, 2 * qp);
-        if ((nqt & 1) && wave == ((blockIdx.x + npair) & 3)) attn_tiles<T, NKT, CAUSAL, NFULL, DBG, 1>(cx, nqt - 1);
+        for (int qp = wave; qp < npair; qp += 4) attn_tiles<T, NKT, CAUSAL, NFULL, 2>(cx, 2 * qp);
+        if ((nqt & 1) && wave == ((blockIdx.x + npair) & 3)) attn_tiles<T, NKT, CAUSAL, NFULL, 1>(cx, nqt - 1);
     } else {
-        for (int qt = wave; qt < nqt; qt += 4) attn_tiles<T, NKT, CAUSAL, NFULL, DBG, 1>(cx, qt);
+        for (int qt = wave; qt < nqt; qt += 4) attn_tiles<T, NKT, CAUSAL, NFULL, 1>(cx, qt);
     }
 }
 
@@ -342,7 +329,7 @@ __global__ __launch_bounds__(256, 2) void attention_kernel(const T* __restrict__
 // accumulates output dims [16 w, 16 w + 16) (lane = dim x key quarter, reduced over the quarters with permlane swaps).
 constexpr int TAIL_LDS = 256 + 2 * 1056;      // last key's K and V rows | scores [257+] | probabilities [257+]
 
-template <int NKT, int DBG = 0, typename T = bf16_t>
+template <int NKT, typename T = bf16_t>
 __global__ __launch_bounds__(256, 2) void attention_tail1_kernel(const T* __restrict__ qkv, T* __restrict__ out,
                                                                  int heads, int q_limit) {
     using C = AttnCfg<NKT>;
@@ -403,11 +390,11 @@ __global__ __launch_bounds__(256, 2) void attention_tail1_kernel(const T* __rest
     __syncthreads();
 
     const int ql = q_limit < LAST ? q_limit : LAST;               // query rows covered by the MFMA tiles
-    const int nqt = DBG == 5 ? 0 : (ql + 15) >> 4;
+    const int nqt = (ql + 15) >> 4;
     AttnCtx<T> cx{base, out + (size_t)b * S * d + h * DH, k_lds, vt_lds, S, q_limit, ld, d, g, c, nullptr, nullptr, 0, b * S, h * DH, tail};
     const int npair = nqt >> 1;
-    for (int qp = wave; qp < npair; qp += 4) attn_tiles<T, NKT, false, NKT, DBG, 2, true>(cx, 2 * qp);
-    if ((nqt & 1) && wave == ((blockIdx.x + npair) & 3)) attn_tiles<T, NKT, false, NKT, DBG, 1, true>(cx, nqt - 1);
+    for (int qp = wave; qp < npair; qp += 4) attn_tiles<T, NKT, false, NKT, 2, true>(cx, 2 * qp);
+    if ((nqt & 1) && wave == ((blockIdx.x + npair) & 3)) attn_tiles<T, NKT, false, NKT, 1, true>(cx, nqt - 1);
     if (q_limit <= LAST) return;                                   // kernel-uniform: nobody waits at the barriers below
 
     // ---- the last query row: scores of this wave's 64 keys (lane = key)
@@ -492,8 +479,7 @@ constexpr int K_OFF = 0, V_OFF = 32768, TAIL_OFF = 65536;    // tail: row 256's 
 constexpr int SC_OFF = TAIL_OFF + 384;                        // last query: f32 scores [264]
 constexpr int PART_OFF = SC_OFF + 264 * 4;                    // last query: per wave {max, sum, -, ..., partial output [64]}: 72 floats
 constexpr int CNT_OFF = PART_OFF + 8 * 72 * 4;                // last query: arrival counter
-constexpr int DUMP_OFF = CNT_OFF + 16;                        // 256 B nobody reads: target of the L2 prefetch (KEDS_ATTN_PREFETCH)
-constexpr int LDS = DUMP_OFF + 256;                           // 69,552 B -> two workgroups per CU
+constexpr int LDS = CNT_OFF + 16 + 256;                       // 69,552 B -> two workgroups per CU (the last 256 B are unused)
 }  // namespace s257
 
 __device__ __forceinline__ float halves_max(float x) {
@@ -546,10 +532,9 @@ __device__ __forceinline__ float wave_max_v(float x) {
 
 // Q8 (fp8 towers): rows < q8_rows of the [B*S, d] output go out as MXFP8 (e4m3 + one e8m0 scale per 32 columns: q8 / s8
 // as in attention_kernel) INSTEAD of bf16; a 32-dim output tile of a query is exactly one MX block, held by two lanes.
-template <int DBG = 0, bool Q8 = false, typename T = bf16_t>
+template <bool Q8 = false, typename T = bf16_t>
 __global__ __launch_bounds__(512, 4) void attention_s257_kernel(const T* __restrict__ qkv, T* __restrict__ out,
                                                                 int heads, int q_limit,
-                                                                unsigned long long* __restrict__ stamp,
                                                                 unsigned char* __restrict__ q8 = nullptr,
                                                                 unsigned char* __restrict__ s8 = nullptr, int q8_rows = 0) {
     using namespace s257;
@@ -557,15 +542,6 @@ __global__ __launch_bounds__(512, 4) void attention_s257_kernel(const T* __restr
     using V4 = typename Ev<T>::v4;
     constexpr int S = 257, LAST = 256;
     extern __shared__ __attribute__((aligned(16))) char smem[];
-    [[maybe_unused]] unsigned long long t_in = 0, t_staged = 0, t_lastq = 0, t_loop = 0;
-    if constexpr (DBG == 8) t_in = __builtin_amdgcn_s_memtime();
-    if constexpr (DBG == 6 || DBG == 7) {     // phase-shift experiment: half of the first-round workgroups start ~half a lifetime late
-        const bool late = DBG == 6 ? (blockIdx.x & 1) : ((blockIdx.x >> 8) & 1);
-        if (blockIdx.x < 512 && late) {
-            const unsigned long long t0 = __builtin_amdgcn_s_memtime();
-            while (__builtin_amdgcn_s_memtime() - t0 < 12000ull) __builtin_amdgcn_s_sleep(16);
-        }
-    }
     const int b = blockIdx.x / heads, h = blockIdx.x % heads;
     const int d = heads * DH;
     const int ld = 3 * d;
@@ -587,7 +563,7 @@ __global__ __launch_bounds__(512, 4) void attention_s257_kernel(const T* __restr
 #pragma unroll
         for (int ks = 0; ks < 4; ++ks) qf[ks] = *reinterpret_cast<const V8*>(qp + 16 * ks);
     }
-    if constexpr (DBG != 1) {
+    {
         const int prow = lane >> 3, slot = lane & 7;
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
@@ -604,9 +580,8 @@ __global__ __launch_bounds__(512, 4) void attention_s257_kernel(const T* __restr
     // tail image: [q row 256 | k row 256 | v row 256], 128 B each, unswizzled; the last-query arrival counter
     if (tid < 24) *reinterpret_cast<V8*>(smem + TAIL_OFF + tid * 16) = trow;
     if (tid == 24) *reinterpret_cast<int*>(smem + CNT_OFF) = 0;
-    if constexpr (DBG != 1) asm volatile("s_waitcnt vmcnt(4)" ::: "memory");   // everything older than the last four DMA pieces
+    asm volatile("s_waitcnt vmcnt(4)" ::: "memory");   // everything older than the last four DMA pieces
     __syncthreads();
-    if constexpr (DBG == 8) t_staged = __builtin_amdgcn_s_memtime();
     const char* tq = smem + TAIL_OFF;
     const char* tk = smem + TAIL_OFF + 128;
     const char* tv = smem + TAIL_OFF + 256;
@@ -710,8 +685,8 @@ __global__ __launch_bounds__(512, 4) void attention_s257_kernel(const T* __restr
     };
 
     const int ql = q_limit < LAST ? q_limit : LAST;
-    const int nblk = DBG == 5 ? 0 : (ql + 31) >> 5;
-    const bool do_last = q_limit > LAST && DBG != 9;
+    const int nblk = (ql + 31) >> 5;
+    const bool do_last = q_limit > LAST;
     if (wave < nblk) {
         // lane-constant LDS offsets: K fragment of k-step ks (row r of the tile), V^T blocks of d-tile 0 / 1
         const int fk = (r >> 1) & 7;
@@ -750,29 +725,6 @@ __global__ __launch_bounds__(512, 4) void attention_s257_kernel(const T* __restr
                 if (half == 1 && attempt == 0) {                           // keys 128-255 (kernel-uniform count of barriers:
                     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");       // a recomputing wave does not come here again)
                     __syncthreads();
-                    if constexpr (DBG == 8) t_lastq = __builtin_amdgcn_s_memtime();
-#if KEDS_ATTN_PREFETCH
-                    {
-                        // L2 prefetch for the workgroup that follows this one on the XCD (block id + KEDS_ATTN_PREFETCH: a multiple
-                        // of 8 keeps the XCD): its 771 lines (257 rows x {q, k, v} x 128 B) as 4-byte LDS-DMA requests, one line per
-                        // lane, into a dump area -- no register, nothing waits for them but this workgroup's last vmcnt(0).  A
-                        // workgroup spends ~4.5 of its ~16 us waiting for the first byte of its rows.
-                        const int nb = (int)blockIdx.x + KEDS_ATTN_PREFETCH;
-                        if (nb < (int)gridDim.x) {
-                            const int b2 = nb / heads, h2 = nb - b2 * heads;
-                            const T* base2 = qkv + (size_t)b2 * S * ld + h2 * DH;
-#pragma unroll
-                            for (int i = 0; i < 2; ++i) {
-                                const int line = 64 * (2 * wave + i) + lane;
-                                if (line < 3 * S) {
-                                    const int row = line / 3, part = line - 3 * row;
-                                    __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(base2 + (size_t)row * ld + part * d),
-                                                                     (__attribute__((address_space(3))) void*)(smem + DUMP_OFF), 4, 0, 0);
-                                }
-                            }
-                        }
-                    }
-#endif
                     if (do_last) last_query_partial();
                 }
                 const char* kb = smem + half * 16384;
@@ -785,12 +737,8 @@ __global__ __launch_bounds__(512, 4) void attention_s257_kernel(const T* __restr
                     f32x16 sc;
 #pragma unroll
                     for (int i = 0; i < 16; ++i) sc[i] = 0.f;
-                    if constexpr (DBG != 2) {
 #pragma unroll
-                        for (int ks = 0; ks < 4; ++ks) sc = mfma32(a[ks], qf[ks], sc, 0, 0, 0);
-                    } else {
-                        sc[0] = (float)qf[k4][0] + (float)a[k4][0];
-                    }
+                    for (int ks = 0; ks < 4; ++ks) sc = mfma32(a[ks], qf[ks], sc, 0, 0, 0);
                     if (k4 == 0 && half == 0) {                            // the reference: first tile's row maximum
                         float t = fmaxf(fmaxf(sc[0], sc[1]), sc[2]);
 #pragma unroll
@@ -799,13 +747,11 @@ __global__ __launch_bounds__(512, 4) void attention_s257_kernel(const T* __restr
                         mref = have ? mgiven : halves_max(t);
                         nm = -mref * sl2;
                     }
-                    if constexpr (DBG != 3) {
 #pragma unroll
-                        for (int i = 0; i < 16; ++i) {
-                            const float e = __builtin_amdgcn_exp2f(__builtin_fmaf(sc[i], sl2, nm));
-                            lsum += e;
-                            sc[i] = e;
-                        }
+                    for (int i = 0; i < 16; ++i) {
+                        const float e = __builtin_amdgcn_exp2f(__builtin_fmaf(sc[i], sl2, nm));
+                        lsum += e;
+                        sc[i] = e;
                     }
                     const V8 p0 = V8{(T)sc[0], (T)sc[1], (T)sc[2], (T)sc[3],
                                              (T)sc[4], (T)sc[5], (T)sc[6], (T)sc[7]};
@@ -815,20 +761,15 @@ __global__ __launch_bounds__(512, 4) void attention_s257_kernel(const T* __restr
 #pragma unroll
                         for (int ks = 0; ks < 4; ++ks) a[ks] = *reinterpret_cast<const V8*>(kb + ka[ks] + (k4 + 1) * 4096);
                     }
-                    if constexpr (DBG != 4) {
-                        const char* v0 = kb + vb0 + k4 * 4096;
-                        const char* v1 = kb + vb1 + k4 * 4096;
-                        o0 = mfma32(tr_pair<V8>(v0, v0 + 1024), p0, o0, 0, 0, 0);
-                        o1 = mfma32(tr_pair<V8>(v1, v1 + 1024), p0, o1, 0, 0, 0);
-                        o0 = mfma32(tr_pair<V8>(v0 + 2048, v0 + 3072), p1, o0, 0, 0, 0);
-                        o1 = mfma32(tr_pair<V8>(v1 + 2048, v1 + 3072), p1, o1, 0, 0, 0);
-                    } else {
-                        o0[0] += (float)p0[0] + (float)p1[0];
-                    }
+                    const char* v0 = kb + vb0 + k4 * 4096;
+                    const char* v1 = kb + vb1 + k4 * 4096;
+                    o0 = mfma32(tr_pair<V8>(v0, v0 + 1024), p0, o0, 0, 0, 0);
+                    o1 = mfma32(tr_pair<V8>(v1, v1 + 1024), p0, o1, 0, 0, 0);
+                    o0 = mfma32(tr_pair<V8>(v0 + 2048, v0 + 3072), p1, o0, 0, 0, 0);
+                    o1 = mfma32(tr_pair<V8>(v1 + 2048, v1 + 3072), p1, o1, 0, 0, 0);
                     __builtin_amdgcn_sched_barrier(0);                     // keep the tiles apart: hoisted reads spill at 128 VGPRs
                 }
             }
-            if constexpr (DBG == 8) t_loop = __builtin_amdgcn_s_memtime();
             // ---- the last key: score from this lane's 32 query dims, combined over the two halves
             float ts = 0.f;
 #pragma unroll
@@ -929,23 +870,6 @@ __global__ __launch_bounds__(512, 4) void attention_s257_kernel(const T* __restr
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         __syncthreads();                                               // the barrier in front of keys 128-255
     }
-    if constexpr (DBG == 8) {
-        const unsigned long long t_issued = __builtin_amdgcn_s_memtime();
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        const unsigned long long t_end = __builtin_amdgcn_s_memtime();
-        if (lane == 0 && stamp) {
-            unsigned long long* o = stamp + ((size_t)blockIdx.x * 8 + wave) * 8;
-            o[0] = t_staged - t_in;     // row 256 + Q loads issued, K / V DMA landed, barrier
-            o[1] = t_lastq - t_staged;  // key tiles 0-3, wait for keys 128-255, barrier
-            o[2] = t_loop - t_lastq;    // last query partial + key tiles 4-7
-            o[3] = t_issued - t_loop;   // last key, normalisation, stores issued
-            o[4] = t_in;
-            o[5] = t_end;
-            o[6] = (unsigned long long)__builtin_amdgcn_s_getreg(63492) |                 // HW_ID: where the wave ran
-                   ((unsigned long long)__builtin_amdgcn_s_getreg(63508) << 32);          // XCC_ID
-            o[7] = t_end - t_issued;    // store drain
-        }
-    }
 }
 
 // NOTE (measured, round 2): a PERSISTENT form of the kernel above was built (two workgroups per CU walking the (batch, head)
@@ -981,7 +905,7 @@ __global__ __launch_bounds__(512, 4) void attention_s257_kernel(const T* __restr
 //      bit-identical, the tile loop itself free of scratch, but 48 spilled registers around it (item top, last-query share,
 //      epilogue) -- 122 us against 62.  A scratch reload is a vmcnt wait behind the DMA in flight; the compiler cannot be
 //      told.  The item loop needs hand-allocated registers.
-// In-kernel stamps with XCC_ID: every CU runs exactly 8 workgroups, 1.84 of 2 resident on average, the next workgroup enters
+// In-kernel stamps with XCC_ID (stamped build, last at 14f64ac): every CU runs exactly 8 workgroups, 1.84 of 2 resident on average, the next workgroup enters
 // 700-900 cycles after an exit, per-CU span 114.6 k cycles mean / 127 k max: a tenth of the launch is the spread between CUs.
 // NOTE (measured, round 2): the "keys 0-127 first" wait of the kernel above is not what the hardware executes: __syncthreads()
 // is a workgroup-scope fence and drains vmcnt in front of the barrier, the compiler puts s_waitcnt vmcnt(0) in front of the
@@ -991,30 +915,19 @@ __global__ __launch_bounds__(512, 4) void attention_s257_kernel(const T* __restr
 // correct and SLOWER, 92 us against 70: the asm statements pin the schedule and spill 15 registers, and the wait for keys
 // 0-127 alone is as long as the wait for all 256 (10 k cycles: first-byte latency, not volume).  Not kept.
 
-int g_attn_debug = 0;   // timing-only ablations (ViT kernel)
 int g_attn_tail = 1;    // A/B hook: 0 routes S = 257 through the generic (padded) kernel
 
 template <typename T = bf16_t>
 int launch_attn_tail1(const void* qkv, void* out, int B, int heads, int q_limit, hipStream_t st) {
     using C = AttnCfg<16>;
     constexpr int LDS = C::LDS + TAIL_LDS;
-    if (int rc = keds_func_lds_once((const void*)attention_tail1_kernel<16, 0, T>, LDS, "attention_tail1_kernel")) return rc;
+    if (int rc = keds_func_lds_once((const void*)attention_tail1_kernel<16, T>, LDS, "attention_tail1_kernel")) return rc;
     KedsProfScope prof(KEDS_PROF_ATTN, st);
-    attention_tail1_kernel<16, 0, T><<<B * heads, 256, LDS, st>>>((const T*)qkv, (T*)out, heads, q_limit);
+    attention_tail1_kernel<16, T><<<B * heads, 256, LDS, st>>>((const T*)qkv, (T*)out, heads, q_limit);
     return keds_check_launch("attention_tail1_kernel");
 }
 
 int g_attn_s257 = 1;    // A/B hook: 0 routes S = 257 through the 4-wave tail kernel
-
-unsigned long long* g_attn_stamp = nullptr;   // stamped build (code 8): 8 counters per wave, keds_attention_stamp_buffer
-int g_attn_s257_dbg = 0;   // timing-only ablations of the 8-wave kernel (keds_attention_debug bit 6 + code)
-
-template <int V>
-int launch_attn_s257_dbg(const void* qkv, void* out, int B, int heads, int q_limit, hipStream_t st) {
-    (void)hipFuncSetAttribute((const void*)attention_s257_kernel<V>, hipFuncAttributeMaxDynamicSharedMemorySize, s257::LDS);
-    attention_s257_kernel<V><<<B * heads, 512, s257::LDS, st>>>((const bf16_t*)qkv, (bf16_t*)out, heads, q_limit, g_attn_stamp);
-    return keds_check_launch("attention_s257_kernel<dbg>");
-}
 
 // The towers fork their remainder-row chain behind this launch.  An event RECORDED on the launching stream is a marker packet of
 // its own between two kernels (a kernel trace shows 7.9 us between the attention's end and the next GEMM's start with it, 1.4
@@ -1037,38 +950,25 @@ void launch_s257(K kernel, int grid, hipStream_t st, A... args) {
 
 int launch_attn_s257_q8(const void* qkv, void* out, int B, int heads, int q_limit, void* q8, void* s8, int q8_rows,
                         hipStream_t st) {
-    if (int rc = keds_func_lds_once((const void*)attention_s257_kernel<0, true>, s257::LDS, "attention_s257_kernel<q8>")) return rc;
+    if (int rc = keds_func_lds_once((const void*)attention_s257_kernel<true>, s257::LDS, "attention_s257_kernel<q8>")) return rc;
     KedsProfScope prof(KEDS_PROF_ATTN, st);
-    launch_s257(attention_s257_kernel<0, true>, B * heads, st, (const bf16_t*)qkv, (bf16_t*)out, heads, q_limit,
-                (unsigned long long*)nullptr, (unsigned char*)q8, (unsigned char*)s8, q8_rows);
+    launch_s257(attention_s257_kernel<true>, B * heads, st, (const bf16_t*)qkv, (bf16_t*)out, heads, q_limit, (unsigned char*)q8, (unsigned char*)s8, q8_rows);
     return keds_check_launch("attention_s257_kernel<q8>");
 }
 
 template <typename T = bf16_t>
 int launch_attn_s257(const void* qkv, void* out, int B, int heads, int q_limit, hipStream_t st) {
-    if constexpr (__is_same(T, f16_t)) {                          // the fp16 form: product kernel only (no ablation builds)
-        if (int rc = keds_func_lds_once((const void*)attention_s257_kernel<0, false, f16_t>, s257::LDS, "attention_s257_kernel<f16>")) return rc;
+    if constexpr (__is_same(T, f16_t)) {                          // the fp16 form
+        if (int rc = keds_func_lds_once((const void*)attention_s257_kernel<false, f16_t>, s257::LDS, "attention_s257_kernel<f16>")) return rc;
         KedsProfScope prof(KEDS_PROF_ATTN, st);
-        launch_s257(attention_s257_kernel<0, false, f16_t>, B * heads, st, (const f16_t*)qkv, (f16_t*)out, heads, q_limit,
-                    (unsigned long long*)nullptr, (unsigned char*)nullptr, (unsigned char*)nullptr, 0);
+        launch_s257(attention_s257_kernel<false, f16_t>, B * heads, st, (const f16_t*)qkv, (f16_t*)out, heads, q_limit,
+                    (unsigned char*)nullptr, (unsigned char*)nullptr, 0);
         return keds_check_launch("attention_s257_kernel<f16>");
     }
-    switch (g_attn_s257_dbg) {
-        case 1: return launch_attn_s257_dbg<1>(qkv, out, B, heads, q_limit, st);
-        case 2: return launch_attn_s257_dbg<2>(qkv, out, B, heads, q_limit, st);
-        case 3: return launch_attn_s257_dbg<3>(qkv, out, B, heads, q_limit, st);
-        case 4: return launch_attn_s257_dbg<4>(qkv, out, B, heads, q_limit, st);
-        case 5: return launch_attn_s257_dbg<5>(qkv, out, B, heads, q_limit, st);
-        case 6: return launch_attn_s257_dbg<6>(qkv, out, B, heads, q_limit, st);
-        case 7: return launch_attn_s257_dbg<7>(qkv, out, B, heads, q_limit, st);
-        case 8: return launch_attn_s257_dbg<8>(qkv, out, B, heads, q_limit, st);
-        case 9: return launch_attn_s257_dbg<9>(qkv, out, B, heads, q_limit, st);
-        default: break;
-    }
-    if (int rc = keds_func_lds_once((const void*)attention_s257_kernel<0>, s257::LDS, "attention_s257_kernel")) return rc;
+    if (int rc = keds_func_lds_once((const void*)attention_s257_kernel<>, s257::LDS, "attention_s257_kernel")) return rc;
     KedsProfScope prof(KEDS_PROF_ATTN, st);
-    launch_s257(attention_s257_kernel<0>, B * heads, st, (const bf16_t*)qkv, (bf16_t*)out, heads, q_limit, (unsigned long long*)nullptr,
-                (unsigned char*)nullptr, (unsigned char*)nullptr, 0);
+    launch_s257(attention_s257_kernel<>, B * heads, st, (const bf16_t*)qkv, (bf16_t*)out, heads, q_limit, (unsigned char*)nullptr,
+                (unsigned char*)nullptr, 0);
     return keds_check_launch("attention_s257_kernel");
 }
 
@@ -1076,36 +976,17 @@ template <int NKT, bool CAUSAL, int NFULL, typename T = bf16_t>
 int launch_attn(const void* qkv, void* out, int B, int S, int heads, int q_limit, void* q8, void* s8, int q8_rows,
                 hipStream_t st, const int* seq_off = nullptr) {
     using C = AttnCfg<NKT>;
-    if constexpr (__is_same(T, f16_t)) {                          // the fp16 form: product kernels only
+    if constexpr (__is_same(T, f16_t)) {                          // the fp16 form
         constexpr bool NQ2 = NKT == 18 && !CAUSAL;
-        if (int rc = keds_func_lds_once((const void*)attention_kernel<NKT, CAUSAL, NFULL, 0, NQ2, f16_t>, C::LDS, "attention_kernel<f16>"))
+        if (int rc = keds_func_lds_once((const void*)attention_kernel<NKT, CAUSAL, NFULL, NQ2, f16_t>, C::LDS, "attention_kernel<f16>"))
             return rc;
         KedsProfScope prof(KEDS_PROF_ATTN, st);
-        attention_kernel<NKT, CAUSAL, NFULL, 0, NQ2, f16_t><<<B * heads, 256, C::LDS, st>>>((const f16_t*)qkv, (f16_t*)out, S, heads, q_limit,
+        attention_kernel<NKT, CAUSAL, NFULL, NQ2, f16_t><<<B * heads, 256, C::LDS, st>>>((const f16_t*)qkv, (f16_t*)out, S, heads, q_limit,
                                                                                              nullptr, nullptr, 0, seq_off);
         return keds_check_launch("attention_kernel<f16>");
     }
     if (int rc = keds_func_lds_once((const void*)attention_kernel<NKT, CAUSAL, NFULL>, C::LDS, "attention_kernel")) return rc;
     KedsProfScope prof(KEDS_PROF_ATTN, st);
-    if constexpr (NKT == 18 && !CAUSAL && NFULL == 16) {
-        if (g_attn_debug) {
-#define KEDS_ATTN_DBG(V)                                                                                          \
-    {                                                                                                            \
-        (void)hipFuncSetAttribute((const void*)attention_kernel<NKT, CAUSAL, NFULL, V>,                          \
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, C::LDS);                           \
-        attention_kernel<NKT, CAUSAL, NFULL, V><<<B * heads, 256, C::LDS, st>>>((const bf16_t*)qkv, (bf16_t*)out, S, heads, q_limit, (unsigned char*)q8, (unsigned char*)s8, q8_rows, seq_off); \
-    }
-            switch (g_attn_debug) {
-                case 1: KEDS_ATTN_DBG(1) break;
-                case 2: KEDS_ATTN_DBG(2) break;
-                case 3: KEDS_ATTN_DBG(3) break;
-                case 4: KEDS_ATTN_DBG(4) break;
-                default: KEDS_ATTN_DBG(5) break;
-            }
-#undef KEDS_ATTN_DBG
-            return keds_check_launch("attention_kernel<dbg>");
-        }
-    }
     attention_kernel<NKT, CAUSAL, NFULL><<<B * heads, 256, C::LDS, st>>>((const bf16_t*)qkv, (bf16_t*)out, S, heads, q_limit,
                                                                          (unsigned char*)q8, (unsigned char*)s8, q8_rows, seq_off);
     return keds_check_launch("attention_kernel");
@@ -1122,14 +1003,10 @@ bool keds_attention_stop_event_taken() {
     return tl_attn_stop_taken;
 }
 
-extern "C" int keds_attention_stamp_buffer(void* buf) {      // diagnostic: B * heads * 64 uint64 for keds_attention_debug(64 + 8)
-    g_attn_stamp = (unsigned long long*)buf;
-    return KEDS_OK;
-}
-
 extern "C" int keds_attention_debug(int variant) {
-    g_attn_s257_dbg = (variant >> 6) & 1 ? (variant & 15) : 0;   // bit 6: the code applies to the 8-wave S = 257 kernel
-    g_attn_debug = (variant >> 6) & 1 ? 0 : (variant & 15);
+    // bits 0-3 and 6 selected timing-only ablations that last existed at 14f64ac
+    for (const int bit : {0, 1, 2, 3, 6})
+        KEDS_REQUIRE(!((variant >> bit) & 1), "keds_attention_debug: bit %d is no longer offered", bit);
     g_attn_tail = (variant >> 4) & 1 ? 0 : 1;      // bit 4: S = 257 through the generic kernel (A/B)
     g_attn_s257 = (variant >> 5) & 1 ? 0 : 1;      // bit 5: S = 257 through the 4-wave tail kernel (A/B)
     return KEDS_OK;
@@ -1155,10 +1032,10 @@ extern "C" int keds_attention_mx(const void* qkv, void* out, int B, int S, int h
     }
     if (S <= 32) return launch_attn<2, false, 0>(qkv, out, B, S, heads, q_limit, q8, s8, q8_rows, st);
     if (S <= 96) return launch_attn<6, false, 0>(qkv, out, B, S, heads, q_limit, q8, s8, q8_rows, st);
-    if (S == 257 && !q8 && g_attn_tail && g_attn_s257 && !g_attn_debug) return launch_attn_s257(qkv, out, B, heads, q_limit, st);
-    if (S == 257 && q8 && g_attn_tail && g_attn_s257 && !g_attn_debug && !g_attn_s257_dbg)
+    if (S == 257 && !q8 && g_attn_tail && g_attn_s257) return launch_attn_s257(qkv, out, B, heads, q_limit, st);
+    if (S == 257 && q8 && g_attn_tail && g_attn_s257)
         return launch_attn_s257_q8(qkv, out, B, heads, q_limit, q8, s8, q8_rows, st);
-    if (S == 257 && !q8 && g_attn_tail && !g_attn_debug) return launch_attn_tail1(qkv, out, B, heads, q_limit, st);
+    if (S == 257 && !q8 && g_attn_tail) return launch_attn_tail1(qkv, out, B, heads, q_limit, st);
     if (S >= 256) return launch_attn<18, false, 16>(qkv, out, B, S, heads, q_limit, q8, s8, q8_rows, st);   // ViT-L/14: 257 tokens
     return launch_attn<18, false, 0>(qkv, out, B, S, heads, q_limit, q8, s8, q8_rows, st);
 }

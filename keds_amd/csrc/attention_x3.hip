@@ -23,13 +23,6 @@
 #include "keds_common.h"
 #include <math.h>
 
-#ifndef KEDS_AX_PHASE
-#define KEDS_AX_PHASE 0
-#endif
-#ifndef KEDS_AX_DBG
-#define KEDS_AX_DBG 0      // timing only: 1 = staging alone, 2 = no staging, 8 = no MFMAs, 16 = phase stamps (s_memtime) of wave 0 into the fp32 output of the first 256 workgroups
-#endif
-
 namespace {
 
 constexpr int AX_WAVES = 8;
@@ -51,10 +44,6 @@ __device__ __forceinline__ float ax_halves_sum(float x) {
     return __uint_as_float(b[0]) + __uint_as_float(b[1]);
 }
 __device__ __forceinline__ f32x16 ax_mfma(f16x8 a, f16x8 b, f32x16 c) {
-    if (KEDS_AX_DBG & 8) {
-        c[0] += (float)a[0] * (float)b[0];
-        return c;
-    }
     return __builtin_amdgcn_mfma_f32_32x32x16_f16(a, b, c, 0, 0, 0);
 }
 __device__ __forceinline__ void ax_split(float v, f16_t& hi, f16_t& lo) {
@@ -83,17 +72,6 @@ __global__ __launch_bounds__(64 * AX_WAVES) void attention_x3_kernel(const float
     const int d = heads * 64, ld = 3 * d;
     const float* base = qkv + (size_t)row_base * ld + hd * 64;
     bool bad = false;
-    [[maybe_unused]] unsigned long long ts[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-#define AX_STAMP(i) do { if (KEDS_AX_DBG & 16) ts[i] = __builtin_amdgcn_s_memtime(); } while (0)
-#if KEDS_AX_PHASE
-    // the first round's workgroups start staggered (quarters of ~KEDS_AX_PHASE us): every CU stages K / V from HBM and then computes
-    // with the memory idle -- in lock step the chip alternates between the two; staggered, one CU's staging runs under another's MFMAs
-    if (blockIdx.x < 256 && (blockIdx.x & 3)) {
-        const unsigned long long t0 = __builtin_amdgcn_s_memtime(), wait = (unsigned long long)(blockIdx.x & 3) * (KEDS_AX_PHASE * 450ull);
-        while (__builtin_amdgcn_s_memtime() - t0 < wait) __builtin_amdgcn_s_sleep(32);
-    }
-#endif
-    AX_STAMP(0);
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
     const int j = lane & 31, hh = lane >> 5;
     const int nq = q_limit < S ? q_limit : S;
@@ -128,7 +106,7 @@ __global__ __launch_bounds__(64 * AX_WAVES) void attention_x3_kernel(const float
     if (KEDS_AX_QPF & 2) q_lone = fetch_q(nq - 1);
     // ---- staging: one item = two adjacent keys x four dims (adjacent keys are adjacent in the V^T row).  (All of a thread's
     // loads in flight before its first conversion -- 80 registers -- is SLOWER: 22 k instead of 15 k cycles, r05_x3_attention_stamps.)
-    for (int idx = threadIdx.x; idx < ((KEDS_AX_DBG & 2) ? 0 : (SP >> 1) * 16); idx += 64 * AX_WAVES) {
+    for (int idx = threadIdx.x; idx < (SP >> 1) * 16; idx += 64 * AX_WAVES) {
         const int c4 = idx & 15, row = 2 * (idx >> 4);
         f32x4 k0 = f32x4{0.f, 0.f, 0.f, 0.f}, k1 = k0, v0 = k0, v1 = k0;
         if (row < S) {
@@ -163,10 +141,7 @@ __global__ __launch_bounds__(64 * AX_WAVES) void attention_x3_kernel(const float
             *reinterpret_cast<f16x2*>(Vl + (size_t)(4 * c4 + e) * VP + vp) = f16x2{c0, c1};
         }
     }
-    AX_STAMP(1);
     __syncthreads();
-    AX_STAMP(2);
-    if (KEDS_AX_DBG & 1) return;
     // (half a key tile of start skew between the two waves of a SIMD, s_sleep 6 .. 40 for waves 4-7: no difference, 273-278 us)
     f16x8 qh[4], ql[4];
     float m, l;
@@ -269,7 +244,7 @@ __global__ __launch_bounds__(64 * AX_WAVES) void attention_x3_kernel(const float
             for (int g = 0; g < 4; ++g) {
                 const f32x16& o = blk ? a1 : a0;
                 const f32x4 v = f32x4{o[4 * g], o[4 * g + 1], o[4 * g + 2], o[4 * g + 3]};
-                if (out && !(KEDS_AX_DBG & 16)) *reinterpret_cast<f32x4*>(out + off + 32 * blk + 8 * g) = v;
+                if (out) *reinterpret_cast<f32x4*>(out + off + 32 * blk + 8 * g) = v;
                 if (pair) {
                     f16x4 vh, vl;
 #pragma unroll
@@ -289,20 +264,17 @@ __global__ __launch_bounds__(64 * AX_WAVES) void attention_x3_kernel(const float
     for (int qt = wave; qt < nqt_own; qt += AX_WAVES) {
         const int q = qt * 32 + j;
         split_q((qt == wave && (KEDS_AX_QPF & 1)) ? q_own : fetch_q(q));
-        AX_STAMP(3);
         int kt_end = nkt;
         if (causal) {                                                            // key tiles that hold a key <= the tile's last query
             const int lastq = qt * 32 + 31;
             kt_end = (lastq >> 5) + 1 < nkt ? (lastq >> 5) + 1 : nkt;
         }
         for (int kt = 0; kt < kt_end; ++kt) key_tile(kt, q);
-        AX_STAMP(4);
         const float inv = 1.0f / ax_halves_sum(l);
 #pragma unroll
         for (int e = 0; e < 16; ++e) r0[e] = o0[e] * inv, r1[e] = o1[e] * inv;
         if (!lone) store_tile(q, r0, r1);          // (with a shared query: no store in flight at its barrier -- a barrier waits for them)
     }
-    AX_STAMP(5);
     if (lone) {                                                                  // (uniform over the workgroup)
         const int q = nq - 1;
         split_q((KEDS_AX_QPF & 2) ? q_lone : fetch_q(q));                        // every lane of the tile holds the one query
@@ -317,7 +289,6 @@ __global__ __launch_bounds__(64 * AX_WAVES) void attention_x3_kernel(const float
                 pw[2 + 32 + (r & 3) + 8 * (r >> 2) + 4 * hh] = o1[r];
             }
         }
-        AX_STAMP(6);
         __syncthreads();
         if (wave < nqt_own) {
             if (pair && !out) {
@@ -369,7 +340,7 @@ __global__ __launch_bounds__(64 * AX_WAVES) void attention_x3_kernel(const float
             }
             const float v = acc / lsum;
             const size_t off = ((size_t)row_base + q) * d + hd * 64 + lane;
-            if (out && !(KEDS_AX_DBG & 16)) out[off] = v;
+            if (out) out[off] = v;
             if (pair) {
                 f16_t x, y;
                 ax_split(v, x, y);
@@ -377,9 +348,6 @@ __global__ __launch_bounds__(64 * AX_WAVES) void attention_x3_kernel(const float
             }
         }
     }
-    AX_STAMP(7);
-    if ((KEDS_AX_DBG & 16) && out && blockIdx.x < 256 && threadIdx.x == 0)
-        for (int i = 0; i < 8; ++i) reinterpret_cast<unsigned long long*>(out)[blockIdx.x * 8 + i] = ts[i];
     if (bad && overflow) *overflow = 1;                   // |q / 8|, |k| or |v| >= 65504: no fp16 hi plane (the caller falls back)
 }
 

@@ -593,14 +593,6 @@ __global__ __launch_bounds__(256) void layernorm_pair_stream_kernel(const float*
         for (int j = 0; j < NJ; ++j) cur[j][0] = nxt[j][0], cur[j][1] = nxt[j][1];
     }
 }
-static bool ln_stream_env() {          // KEDS_LN_STREAM=0 in the environment: the one-row-per-wave form (A/B)
-    static int v = -1;
-    if (v < 0) {
-        const char* e = keds_exp_env("KEDS_LN_STREAM");
-        v = !(e && e[0] == '0');
-    }
-    return v != 0;
-}
 
 // what the last keds_layernorm_pair_impl call of this thread launched (keds_layernorm_pair_last_form): 0 one row per wave, 1 stream
 static thread_local int tl_ln_pair_form = -1;
@@ -610,7 +602,7 @@ static thread_local int tl_ln_pair_form = -1;
 int keds_layernorm_pair_impl(const float* x, long long x_stride, const float* gamma, const float* beta, void* out, long long plane,
                              int rows, int dim, hipStream_t st, int form = 0) {
     KedsProfScope prof(KEDS_PROF_LN, st);
-    if (form != 1 && (dim == 1024 || dim == 512) && rows >= 2048 && x_stride % 4 == 0 && plane % 8 == 0 && ln_stream_env()) {
+    if (form != 1 && (dim == 1024 || dim == 512) && rows >= 2048 && x_stride % 4 == 0 && plane % 8 == 0) {
         // every wave resident at once (82 VGPRs: five per SIMD, five blocks per CU); at 32,768 rows a wave walks six or seven
         const int cus = keds_device_cus();
         int grid = cus * 5;
@@ -939,7 +931,7 @@ extern "C" int keds_tap_store_nt(int on) {
 int keds_tap_rows(const KedsTaps* tp, int l, int layers, const void* src, int src_type, size_t r0, long long n, int w,
                   hipStream_t st) {
     if (!tp || n <= 0 || r0 >= tp->rows) return KEDS_OK;
-    if ((long long)(tp->rows - r0) < n) n = (long long)(tp->rows - r0);      // (filler rows behind the last token are no output)
+    if ((long long)(tp->rows - r0) < n) n = (long long)(tp->rows - r0);      // (rows behind the last token are no output)
     const size_t es = tp->type == 1 ? 4 : 2;
     const char* s = (const char*)src + r0 * w * (src_type == 1 ? 4 : 2);
     int rc;

@@ -11,13 +11,9 @@
 // bank-conflict free, and W rows are permuted at staging time so a lane's two n-tiles are adjacent.
 #include "keds_common.h"
 #include <math.h>
-#include <cstdlib>
 #include "gemm_shared.h"
 #include "gemm_quad_gen.h"
 
-#ifndef KEDS_QUAD_NOEPI
-#define KEDS_QUAD_NOEPI 0
-#endif
 // cache policy of the persistent 4-wave kernel's LDS-DMA pieces per operand (aux bits of the buffer load: 1 = sc0, 2 = nt, 16 = sc1).
 // Per supertile (8 row panels x 4 column tiles on one XCD's 32 CUs) the A panels are 4 MB that nobody on this XCD reads again
 // and the W panels 2 MB that the XCD's NEXT supertile reads again (same column group): round 5 A/B, tools/rounds/r05_quad_policy.sh
@@ -26,9 +22,6 @@
 #endif
 #ifndef KEDS_QUAD_AUX_W
 #define KEDS_QUAD_AUX_W 0
-#endif
-#ifndef KEDS_QUAD_TIDDMA
-#define KEDS_QUAD_TIDDMA 0
 #endif
 
 namespace {
@@ -140,7 +133,7 @@ __device__ __forceinline__ float sum8(f32x4 a, f32x4 b) { return ((a[0] + a[1]) 
 
 // Epilogue of one wave's accumulator tile, shared by the 128^2 and 256^2 kernels: lane (g, c) owns rows
 // m_lane + 16*mi (mi < MI) and columns n_lane + 32*p + 0..7 (p = 0, 1) held in acc[2p][mi], acc[2p+1][mi].
-template <int EPI, int MI, int DBG = 0>   // DBG (stamped diagnostic build only): 2 = no statistics loads, 3 = no stores
+template <int EPI, int MI>
 __device__ __forceinline__ void tile_epilogue(f32x4 (&acc)[4][MI], const float* __restrict__ bias, void* __restrict__ out,
                                               int m_lane, int M, int n_lane, int N, int K, const float* __restrict__ aux,
                                               int aux_i, void* __restrict__ aux2, long long ldc, bool zero_lane,
@@ -152,11 +145,7 @@ __device__ __forceinline__ void tile_epilogue(f32x4 (&acc)[4][MI], const float* 
 #pragma unroll
         for (int mi = 0; mi < MI; ++mi) {
             const int m = m_lane + 16 * mi;
-            if constexpr (DBG == 2) {
-                rstd[mi] = 1.0f + invk;
-                nmr[mi] = invk;
-            } else
-                ln_row_coeff(aux, m < M ? m : M - 1, invk, rstd[mi], nmr[mi], zero_lane ? guard : nullptr);
+            ln_row_coeff(aux, m < M ? m : M - 1, invk, rstd[mi], nmr[mi], zero_lane ? guard : nullptr);
             if (zero && zero_lane && m < M) keds_stat_zero(zero + 2 * (size_t)m);
         }
 #pragma unroll
@@ -168,18 +157,6 @@ __device__ __forceinline__ void tile_epilogue(f32x4 (&acc)[4][MI], const float* 
             for (int mi = 0; mi < MI; ++mi) {
                 const int m = m_lane + 16 * mi;
                 if (m >= M) continue;
-                if constexpr (DBG == 1) {      // TIMING ONLY (wrong placement): every store instruction covers 8 rows x 128 B
-                    const int c_ = m & 15, row = m - c_ + (c_ & 7) + 8 * p;
-                    const int col = (n - 32 * p) - (n & 31) + ((n & 31) >> 3) * 8 + 32 * (c_ >> 3);
-                    epilogue_store<epi_base(EPI)>(acc[2 * p][mi] * rstd[mi] + (c0 * nmr[mi] + b0),
-                                                  acc[2 * p + 1][mi] * rstd[mi] + (c1 * nmr[mi] + b1), out, row, col, N, nullptr, 0, ldc);
-                    continue;
-                }
-                if constexpr (DBG == 3) {      // keep the math alive, store (almost) nothing
-                    const f32x4 v = acc[2 * p][mi] * rstd[mi] + (c0 * nmr[mi] + b0) + acc[2 * p + 1][mi] * rstd[mi] + (c1 * nmr[mi] + b1);
-                    if (v[0] + v[1] + v[2] + v[3] == 12345.678f) reinterpret_cast<float*>(out)[0] = v[0];
-                    continue;
-                }
                 epilogue_store<epi_base(EPI)>(acc[2 * p][mi] * rstd[mi] + (c0 * nmr[mi] + b0),
                                               acc[2 * p + 1][mi] * rstd[mi] + (c1 * nmr[mi] + b1), out, m, n, N, nullptr, 0, ldc,
                                               guard);
@@ -286,14 +263,14 @@ __device__ __forceinline__ void tile_epilogue(f32x4 (&acc)[4][MI], const float* 
 // LN epilogues of the 256^2 kernel.  The row coefficients {rstd, -mean rstd} and the tile's bias' / column-sum slices were
 // computed once per workgroup in the prologue (their loads and the 64-bit fixed-point -> float conversions hide behind the
 // wait for the first K-tile) and sit in the LDS side area; every row of the tile is valid (M % 256 == 0), and a lane's store
-// address is a uniform tile base + a 32-bit offset.  DBG 3 (stamped diagnostic build): no stores.
+// address is a uniform tile base + a 32-bit offset.
 // ND > 0 (persistent 4-wave kernel; H = the wave's 64-column half this call covers, PSEL = its 32-column quarter, -1: both):
 // a lane's 32 stores of a tile are numbered s = 16 H + 8 p + mi; with `defer` the last ND of them are NOT issued but handed
 // back in `pend` (pend[s - (32 - ND)]); the caller issues them between the first K-steps of its next tile
 // (quad_flush_pending), where nothing competes with them -- see the note at the persistent kernel.
 template <int EPI>
 constexpr int quad_nd() { return 18; }       // (measured on qkv, same-process A/B: 12 stores -7.7 us, 18 -8.7, 22 -9.3 of 179)
-template <int EPI, int DBG, int ND = 0, int H = 0, int PSEL = -1>
+template <int EPI, int ND = 0, int H = 0, int PSEL = -1>
 __device__ __forceinline__ void pair_ln_epilogue(f32x4 (&acc)[4][8], const char* __restrict__ side, void* __restrict__ out,
                                                  int m0, int n0, int N, int wm, int wn, int g, int c,
                                                  void* __restrict__ aux2, u32x4* __restrict__ pend = nullptr, bool defer = false,
@@ -345,11 +322,6 @@ __device__ __forceinline__ void pair_ln_epilogue(f32x4 (&acc)[4][8], const char*
                 v0 = v0 * z0;
                 v1 = v1 * z1;
             }
-            if constexpr (DBG == 3) {
-                const f32x4 v = v0 + v1;
-                if (v[0] + v[1] + v[2] + v[3] == 12345.678f) reinterpret_cast<float*>(out)[0] = v[0];
-                continue;
-            }
             const unsigned off = ((unsigned)(r0 + 16 * mi) * (unsigned)N + (unsigned)nl) * 2u;
             u32x4 ov;
             if constexpr (epi_out_f16(EPI)) {
@@ -395,7 +367,7 @@ __device__ __forceinline__ void quad_flush_pending(const u32x4* __restrict__ pen
 // offsets for the read-modify-write of the fp16 stream, bias slice from the LDS side area), all 16 loads of the lane issued
 // before the first is used.
 // REDUCE = false (4-wave kernel: a wave runs this once per 64-column half): leave the partial sums in `red`, the caller adds them
-template <int DBG = 0, bool REDUCE = true>   // DBG, stamped diagnostic build only: 3 = no stores, 4 = no statistics atomics, 5 = neither (and no loads)
+template <bool REDUCE = true>
 __device__ __forceinline__ void pair_resid_epilogue(f32x4 (&acc)[4][8], const char* __restrict__ side, void* __restrict__ out,
                                                     int m0, int n0, int N, int wm, int wn, int g, int c,
                                                     keds_stat_t* __restrict__ stats, char* __restrict__ red) {
@@ -417,8 +389,7 @@ __device__ __forceinline__ void pair_resid_epilogue(f32x4 (&acc)[4][8], const ch
             r[p][mi] = __builtin_bit_cast(f16x8, __builtin_amdgcn_raw_buffer_load_b128(
                            trs, (int)(((unsigned)(r0 + 16 * mi) * (unsigned)N + (unsigned)(nl + 32 * p)) * 2u), 0, KEDS_LD_RESID_AUX));
 #else
-            r[p][mi] = DBG == 5 ? f16x8{0, 0, 0, 0, 0, 0, 0, 0}
-                                : *reinterpret_cast<const f16x8*>(tile + ((unsigned)(r0 + 16 * mi) * (unsigned)N + (unsigned)(nl + 32 * p)) * 2u);
+            r[p][mi] = *reinterpret_cast<const f16x8*>(tile + ((unsigned)(r0 + 16 * mi) * (unsigned)N + (unsigned)(nl + 32 * p)) * 2u);
 #endif
         }
     f32x4 b[2][2];
@@ -438,26 +409,18 @@ __device__ __forceinline__ void pair_resid_epilogue(f32x4 (&acc)[4][8], const ch
             const f16x8 q = r[p][mi];
             const f32x4 v0 = f32x4{(float)q[0], (float)q[1], (float)q[2], (float)q[3]} + (acc[2 * p][mi] + b[p][0]);
             const f32x4 v1 = f32x4{(float)q[4], (float)q[5], (float)q[6], (float)q[7]} + (acc[2 * p + 1][mi] + b[p][1]);
-            if constexpr (DBG == 3 || DBG == 5) {
-                const f32x4 v = v0 + v1;
-                if (v[0] + v[1] + v[2] + v[3] == 12345.678f) reinterpret_cast<float*>(out)[0] = v[0];
-            } else {
-                const f16x8 ov = f16x8{(f16_t)v0[0], (f16_t)v0[1], (f16_t)v0[2], (f16_t)v0[3], (f16_t)v1[0], (f16_t)v1[1], (f16_t)v1[2], (f16_t)v1[3]};
-                // (a non-temporal store here is neutral: the stream is re-read by the very next GEMM)
-                keds_store16<KEDS_ST_RESID>(ov, tile, ((unsigned)(r0 + 16 * mi) * (unsigned)N + (unsigned)(nl + 32 * p)) * 2u);
-            }
+            const f16x8 ov = f16x8{(f16_t)v0[0], (f16_t)v0[1], (f16_t)v0[2], (f16_t)v0[3], (f16_t)v1[0], (f16_t)v1[1], (f16_t)v1[2], (f16_t)v1[3]};
+            // (a non-temporal store here is neutral: the stream is re-read by the very next GEMM)
+            keds_store16<KEDS_ST_RESID>(ov, tile, ((unsigned)(r0 + 16 * mi) * (unsigned)N + (unsigned)(nl + 32 * p)) * 2u);
             sv = sv + (v0 + v1);
             qv = qv + (v0 * v0 + v1 * v1);
         }
         float s = (sv[0] + sv[1]) + (sv[2] + sv[3]), ss = (qv[0] + qv[1]) + (qv[2] + qv[3]);
         s = rows_sum(s);                 // the four lanes (g = 0..3) that share the row hold this wave's 64 columns of it
         ss = rows_sum(ss);
-        if constexpr (DBG == 4 || DBG == 5) {
-            if (s + ss == 12345.678f) reinterpret_cast<float*>(out)[1] = s;
-        } else if (stats && g == 0)
-            rw[16 * mi] = f32x2{s, ss};
+        if (stats && g == 0) rw[16 * mi] = f32x2{s, ss};
     }
-    if constexpr (DBG != 4 && DBG != 5 && REDUCE) {
+    if constexpr (REDUCE) {
         if (stats) {                                                    // kernel-uniform
             __syncthreads();
             const int t = threadIdx.x;
@@ -789,10 +752,9 @@ constexpr int LDS_BYTES = SIDE_OFF + 4096;      // 132 KiB
 // before the first MFMA group, or two per group in the first half of the step (so the last piece has 1.5 K-steps to land
 // instead of one), against one piece per group: qkv 190 / 195 / 200 us, out 71 / 73 / 75, fc 264 / 268 / 275, proj
 // 229 / 228 / 234 (spread / early pairs / all first).  The K-loop does not wait for the last DMA piece.
-// STAMP (diagnostic build of one instantiation, tools/stamp_gemm.py): s_memtime stamps around the prologue, every
-// K-tile's wait and barrier, the loop and the epilogue; aux2 then receives 8 counters per wave instead of its usual role.
+// (The in-kernel cycle figures quoted in this file come from stamped diagnostic builds that last existed at 14f64ac.)
 // RP (KEDS_EPI_RESID_STATS_F16 only): residual tile + bias as the accumulators' initial value (pair_resid_epilogue_acc)
-template <int EPI, int STAMP = 0, int RP = 0>
+template <int EPI, int RP = 0>
 __global__ __launch_bounds__(512, 2) void gemm_bt_pair_kernel(const bf16_t* __restrict__ X, const bf16_t* __restrict__ W,
                                                               const float* __restrict__ bias, void* __restrict__ out,
                                                               int M, int N, int K, int n_tiles,
@@ -802,16 +764,6 @@ __global__ __launch_bounds__(512, 2) void gemm_bt_pair_kernel(const bf16_t* __re
     // (a_plane / w_plane: KEDS_EPI_X3_* only, as in gemm_bt_kernel)
     using namespace pr;
     extern __shared__ __attribute__((aligned(16))) char smem[];
-    unsigned long long t_entry = 0, vm_wait = 0, bar_wait = 0;
-    if constexpr (STAMP) {
-        // desynchronisation experiment (stamped build only): every other group of 8 first-round workgroups starts
-        // `aux_i` cycles late, so half of the CUs run half a tile out of phase with the other half
-        if (aux_i > 0 && blockIdx.x < 256 && (blockIdx.x & 8)) {
-            const unsigned long long t0 = __builtin_amdgcn_s_memtime();
-            while (__builtin_amdgcn_s_memtime() - t0 < (unsigned long long)aux_i) __builtin_amdgcn_s_sleep(8);
-        }
-        t_entry = __builtin_amdgcn_s_memtime();
-    }
     const int bid = xcd_remap(blockIdx.x, gridDim.x);
     // The 32 workgroups that run together on one XCD take consecutive logical ids.  Map each run of 32 ids to a
     // block of 8 m-tiles x 4 n-tiles (12 distinct operand panels per K-tile in that XCD's L2 instead of up to 18
@@ -876,7 +828,7 @@ __global__ __launch_bounds__(512, 2) void gemm_bt_pair_kernel(const bf16_t* __re
     const int wrow = OP_BYTES + (64 * wn + c) * 128;               // + ni * 2048
 
     f32x4 acc[4][8];
-    constexpr bool RESID_IN = RP != 0 && epi_resid16(EPI) && STAMP == 0;
+    constexpr bool RESID_IN = RP != 0 && epi_resid16(EPI);
     if constexpr (!RESID_IN) {
 #pragma unroll
         for (int ni = 0; ni < 4; ++ni)
@@ -966,14 +918,9 @@ __global__ __launch_bounds__(512, 2) void gemm_bt_pair_kernel(const bf16_t* __re
         asm volatile("s_waitcnt vmcnt(16)" : "+v"(st_raw), "+v"(pb), "+v"(pc)::"memory");
         if (tid < 256) {
             float rs, nm;
-            if constexpr (STAMP == 2) {
-                rs = 1.0f + 1.0f / (float)K;
-                nm = 1.0f / (float)K;
-            } else {
-                ln_coeff_from((keds_stat_t)(((unsigned long long)st_raw[1] << 32) | st_raw[0]),
-                              (keds_stat_t)(((unsigned long long)st_raw[3] << 32) | st_raw[2]), 1.0f / (float)K, rs, nm,
-                              n0 == 0 ? guard : nullptr);
-            }
+            ln_coeff_from((keds_stat_t)(((unsigned long long)st_raw[1] << 32) | st_raw[0]),
+                          (keds_stat_t)(((unsigned long long)st_raw[3] << 32) | st_raw[2]), 1.0f / (float)K, rs, nm,
+                          n0 == 0 ? guard : nullptr);
             *reinterpret_cast<f32x2*>(smem + SIDE_OFF + tid * 8) = f32x2{rs, nm};
         } else {
             *reinterpret_cast<float*>(smem + SIDE_OFF + 2048 + (tid - 256) * 4) = pb;
@@ -985,8 +932,6 @@ __global__ __launch_bounds__(512, 2) void gemm_bt_pair_kernel(const bf16_t* __re
     }
     if constexpr (RESID_IN) __builtin_amdgcn_sched_barrier(0);    // the conversions above stay in front of the wait for K-tile 0
     asm volatile("s_waitcnt vmcnt(8) lgkmcnt(0)\n\ts_barrier" ::: "memory");
-    unsigned long long t_loop0 = 0;
-    if constexpr (STAMP) t_loop0 = __builtin_amdgcn_s_memtime();
     bf16x8 xf[8], wa[4], wb[4];
 #pragma unroll
     for (int ni = 0; ni < 4; ++ni) wa[ni] = *reinterpret_cast<const bf16x8*>(smem + wrow + slot0 + ni * 2048);
@@ -1001,17 +946,7 @@ __global__ __launch_bounds__(512, 2) void gemm_bt_pair_kernel(const bf16_t* __re
 #define KEDS_PAIR_STEP(wc, wn_, nb, nslot, SYNC, ISSUE, ip, PREFETCH)                                          \
     {                                                                                                          \
         __builtin_amdgcn_sched_barrier(0);                                                                     \
-        if constexpr (SYNC && STAMP != 0) {                                                                    \
-            const unsigned long long ta = __builtin_amdgcn_s_memtime();                                        \
-            asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");                                        \
-            const unsigned long long tb = __builtin_amdgcn_s_memtime();                                        \
-            asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");                                    \
-            const unsigned long long tc = __builtin_amdgcn_s_memtime();                                        \
-            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");                                                 \
-            vm_wait += tb - ta;                                                                                \
-            bar_wait += tc - tb;                                                                               \
-        }                                                                                                      \
-        if constexpr (SYNC && STAMP == 0) asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)\n\ts_barrier" ::: "memory"); \
+        if constexpr (SYNC) asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)\n\ts_barrier" ::: "memory");           \
         __builtin_amdgcn_sched_barrier(0);                                                                     \
         _Pragma("unroll") for (int mi = 0; mi < 8; ++mi) {                                                     \
             _Pragma("unroll") for (int ni = 0; ni < 4; ++ni)                                                   \
@@ -1058,35 +993,8 @@ __global__ __launch_bounds__(512, 2) void gemm_bt_pair_kernel(const bf16_t* __re
 
     // ---- epilogue (same ownership pattern as the 128^2 kernel)
     const bool zl = epi_is_ln(EPI) ? (n0 == 0 && wn == 0 && g == 0) : (g == 0);
-    if constexpr (STAMP) {
-        const unsigned long long t_loop1 = __builtin_amdgcn_s_memtime();
-        if constexpr (epi_is_ln(EPI))
-            pair_ln_epilogue<EPI, STAMP>(acc, smem + SIDE_OFF, out, m0, n0, N, wm, wn, g, c, nullptr);
-        else if constexpr (epi_resid16(EPI))
-            pair_resid_epilogue<STAMP>(acc, smem + SIDE_OFF, out, m0, n0, N, wm, wn, g, c,
-                                       reinterpret_cast<keds_stat_t*>(const_cast<float*>(aux)), smem + (np & 1) * PBUF_BYTES);
-        else
-            tile_epilogue<EPI, 8, STAMP>(acc, bias, out, m0 + 128 * wm + c, M, n0 + 64 * wn + 8 * g, N, K, aux, aux_i, nullptr, N, zl);
-        const unsigned long long t_issued = __builtin_amdgcn_s_memtime();
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        const unsigned long long t_end = __builtin_amdgcn_s_memtime();
-        if (lane == 0) {
-            unsigned long long* o = reinterpret_cast<unsigned long long*>(aux2) + ((size_t)blockIdx.x * 8 + wave) * 8;
-            o[0] = t_loop0 - t_entry;   // prologue (address set-up, 16 DMA pieces, first K-tile landed)
-            o[1] = t_loop1 - t_loop0;   // K-loop
-            o[2] = t_issued - t_loop1;  // epilogue until the last store is issued
-            o[3] = vm_wait;             // summed over the K-tiles: s_waitcnt vmcnt(0) lgkmcnt(0)
-            o[4] = bar_wait;            // summed: s_barrier
-            o[5] = t_end - t_issued;    // store drain after the last issue
-            o[6] = t_entry;             // raw stamps + where the wave ran: gaps between consecutive workgroups of a CU
-            o[7] = t_end;
-            unsigned long long* o2 = reinterpret_cast<unsigned long long*>(aux2) + (size_t)gridDim.x * 64 + (size_t)blockIdx.x * 8 + wave;
-            *o2 = ((unsigned long long)__builtin_amdgcn_s_getreg(63508) << 32) | (unsigned)__builtin_amdgcn_s_getreg(63492);
-        }
-        return;
-    }
     if constexpr (epi_is_ln(EPI))
-        pair_ln_epilogue<EPI, 0>(acc, smem + SIDE_OFF, out, m0, n0, N, wm, wn, g, c, aux2, nullptr, false, guard);
+        pair_ln_epilogue<EPI>(acc, smem + SIDE_OFF, out, m0, n0, N, wm, wn, g, c, aux2, nullptr, false, guard);
     else if constexpr (RESID_IN)
         pair_resid_epilogue_acc(acc, out, m0, n0, N, wm, wn, g, c, reinterpret_cast<keds_stat_t*>(const_cast<float*>(aux)),
                                 smem + (np & 1) * PBUF_BYTES);
@@ -1121,7 +1029,7 @@ __global__ __launch_bounds__(512, 2) void gemm_bt_pair_kernel(const bf16_t* __re
 //
 // A K-step is 32 gaps (one behind every pair of MFMAs), each carrying at most ONE memory instruction: a 16x16x32 MFMA holds
 // the SIMD's vector issue for 8 of its 16 cycles and issue costs add (MI355X_MICROARCH.md, cycle constants), so a gap with
-// two LDS reads and a DMA piece overruns by their sum.  Measured with the stamped ablation builds (tools/stamp_quad.py,
+// two LDS reads and a DMA piece overruns by their sum.  Measured with the stamped ablation builds (last at 14f64ac;
 // cycles per K-tile; 2,099 for the MFMAs alone): 16 reads in 16 consecutive gaps +53; a DMA piece wants MORE room -- 16
 // pieces in 16 consecutive gaps +400, in every other gap (one per four MFMAs) +140; everything in clusters of two reads
 // + one piece per four MFMAs (the first build) +313.  So:
@@ -1133,21 +1041,6 @@ __global__ __launch_bounds__(512, 2) void gemm_bt_pair_kernel(const bf16_t* __re
 // cycling); 1: W fragment g against the eight X fragments (SrcA constant over eight MFMAs, the vendor kernel's order)
 #ifndef KEDS_QUAD_ORDER
 #define KEDS_QUAD_ORDER 1
-#endif
-// TIMING ONLY (tools/rounds/r05_noepi_bound.sh): KEDS_QUAD_FILL plain + KEDS_QUAD_FILLX transcendental vector instructions in EVERY gap
-// of the K-loop -- how much epilogue arithmetic the gaps between the MFMA pairs can carry before the K-tile grows
-#ifndef KEDS_QUAD_FILL
-#define KEDS_QUAD_FILL 0
-#endif
-#ifndef KEDS_QUAD_FILLX
-#define KEDS_QUAD_FILLX 0
-#endif
-#if KEDS_QUAD_FILL || KEDS_QUAD_FILLX
-#define KEDS_QUAD_FILLER                                                                                       \
-    _Pragma("unroll") for (int f_ = 0; f_ < KEDS_QUAD_FILL; ++f_) asm volatile("v_fma_f32 %0, %0, %0, %0" : "+v"(fill_v[f_ & 3])); \
-    _Pragma("unroll") for (int f_ = 0; f_ < KEDS_QUAD_FILLX; ++f_) asm volatile("v_exp_f32 %0, %0" : "+v"(fill_v[4 + (f_ & 1)]));
-#else
-#define KEDS_QUAD_FILLER
 #endif
 #define KEDS_QMFMA(FIRST, j, mi, wc, xc)                                                                       \
     if constexpr (FIRST) {                                                                                     \
@@ -1171,14 +1064,13 @@ __global__ __launch_bounds__(512, 2) void gemm_bt_pair_kernel(const bf16_t* __re
 #define KEDS_QGAP(n_, xn, wn_, nb, nslot, ISSUE, ip, PREFETCH)                                                 \
     if constexpr (ISSUE) {                                                                                     \
         if constexpr (((n_) & 1) == 0) {                                                                       \
-            if constexpr (!(DBG & 1) && ((int)(ISSUE) == 1 || (n_) < 16)) issue((ip), (n_) >> 1);              \
-        } else if constexpr (PREFETCH && !(DBG & 2)) {                                                         \
+            if constexpr ((int)(ISSUE) == 1 || (n_) < 16) issue((ip), (n_) >> 1);                              \
+        } else if constexpr (PREFETCH) {                                                                       \
             KEDS_QRD((n_) >> 1, xn, wn_, nb, nslot)                                                            \
         }                                                                                                      \
-    } else if constexpr (PREFETCH && (n_) < 16 && !(DBG & 2)) {                                                \
+    } else if constexpr (PREFETCH && (n_) < 16) {                                                              \
         KEDS_QRD(n_, xn, wn_, nb, nslot)                                                                       \
     }                                                                                                          \
-    KEDS_QUAD_FILLER                                                                                           \
     __builtin_amdgcn_sched_barrier(0);
 #define KEDS_QUAD_GROUP(FIRST, mi, xc, wc, xn, wn_, nb, nslot, ISSUE, ip, PREFETCH)                            \
     KEDS_QG2(FIRST, mi, 0, 1, wc, xc) KEDS_QGAP(4 * (mi), xn, wn_, nb, nslot, ISSUE, ip, PREFETCH)             \
@@ -1191,9 +1083,9 @@ __global__ __launch_bounds__(512, 2) void gemm_bt_pair_kernel(const bf16_t* __re
 #define KEDS_QUAD_STEP(FIRST, xc, wc, xn, wn_, nb, nslot, SYNC, ISSUE, ip, PREFETCH)                           \
     {                                                                                                          \
         __builtin_amdgcn_sched_barrier(0);                                                                     \
-        if constexpr ((int)(SYNC) >= 2 && !(DBG & 4))                                                          \
+        if constexpr ((int)(SYNC) >= 2)                                                                        \
             asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)\n\ts_barrier" ::"n"((int)(SYNC) >= 2 ? (int)(SYNC) : 0) : "memory"); \
-        else if constexpr (SYNC && !(DBG & 4)) asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)\n\ts_barrier" ::: "memory"); \
+        else if constexpr (SYNC) asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)\n\ts_barrier" ::: "memory");       \
         __builtin_amdgcn_sched_barrier(0);                                                                     \
         KEDS_QUAD_GROUP(FIRST, 0, xc, wc, xn, wn_, nb, nslot, ISSUE, ip, PREFETCH)                             \
         KEDS_QUAD_GROUP(FIRST, 1, xc, wc, xn, wn_, nb, nslot, ISSUE, ip, PREFETCH)                             \
@@ -1237,7 +1129,7 @@ constexpr int LDS_BYTES = RED_OFF + 8192;           // 144 KiB
 // stores younger than the DMA pieces stay in flight) -- with vmcnt(0) the trickle returns what it saved.  qkv 170 vs 179 us
 // (same process, medians of 7 x 20); not for the QuickGELU form (c_fc: its stores already leave under 512 transcendentals
 // per lane; deferring costs it 3 us).
-template <int EPI, int STAMP = 0, int PERSIST = 0>
+template <int EPI, int PERSIST = 0>
 __global__ __launch_bounds__(256, 1) void gemm_bt_quad_kernel(const bf16_t* __restrict__ X, const bf16_t* __restrict__ W,
                                                               const float* __restrict__ bias, void* __restrict__ out,
                                                               int M, int N, int K, int n_tiles,
@@ -1247,11 +1139,6 @@ __global__ __launch_bounds__(256, 1) void gemm_bt_quad_kernel(const bf16_t* __re
     // (a_plane / w_plane: KEDS_EPI_X3_* only, as in gemm_bt_pair_kernel: K-tile p of 3 K / 64 reads segment p / (K / 64))
     using namespace pr;
     extern __shared__ __attribute__((aligned(16))) char smem[];
-    [[maybe_unused]] unsigned long long t_entry = 0, t_loop0 = 0;
-    // stamped diagnostic builds 2..8 (timing only, results wrong): STAMP - 1 = bit mask of what the steady-state K-loop leaves
-    // out -- 1: the DMA pieces, 2: the fragment reads, 4: the per-K-tile wait + barrier
-    constexpr int DBG = STAMP > 1 ? STAMP - 1 : 0;
-    if constexpr (STAMP) t_entry = __builtin_amdgcn_s_memtime();
     const int m_tiles = ntiles / n_tiles;
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -1268,22 +1155,10 @@ __global__ __launch_bounds__(256, 1) void gemm_bt_quad_kernel(const bf16_t* __re
     // ONE loop-invariant VGPR per operand, the piece / K-tile part a scalar -- no vector add per piece
     // (a macro, not a lambda: a lambda RETURNING the descriptor type makes hipcc 7.2 drop the kernel's host-side stub without
     // a diagnostic -- every instantiation then links as an undefined symbol)
-#if KEDS_QUAD_TIDDMA   // TIMING ONLY (tools/rounds/r05_tid_dma.sh): what the K-loop would cost if a DMA piece needed NO address VGPR -- the
-    // descriptor adds the lane id itself (ADD_TID_ENABLE, stride 16: lane l reads base + offset + 16 l, a contiguous 1 KiB: the
-    // traffic shape of a tiled operand layout in which a piece is contiguous in memory).  Wrong operands, same bytes.
-#define make_rs_tid(base) __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(static_cast<const void*>(base)), 16, 0x7FFFFFFF, 0x00800000)
-#define make_rs_lin(base) __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(static_cast<const void*>(base)), 0, 0x7FFFFFFF, 0x00020000)
-#define make_rs(base) make_rs_lin(base)
-#define make_rsx(base) ((KEDS_QUAD_TIDDMA & 1) ? make_rs_tid(base) : make_rs_lin(base))
-#define make_rsw(base) ((KEDS_QUAD_TIDDMA & 2) ? make_rs_tid(base) : make_rs_lin(base))
-#else
 #define make_rs(base) __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(static_cast<const void*>(base)), 0, 0x7FFFFFFF, 0x00020000)
-#define make_rsx(base) make_rs(base)
-#define make_rsw(base) make_rs(base)
-#endif
     // (xrs / wrs: buffer descriptors of the CURRENT tile's operand panels; re-pointed at the next tile once this tile's last
     // piece has been requested)
-    auto xrs = make_rsx(X), wrs = make_rsw(W);
+    auto xrs = make_rs(X), wrs = make_rs(W);
     auto issue = [&](int p, int q) {                               // DMA piece q (0..15: X pieces 0..7, W pieces 0..7) of K-tile p
         const int i = q & 7;
         char* dst = smem + (p & 1) * PBUF_BYTES + (q < 8 ? 0 : OP_BYTES) + (wave + 4 * i) * 1024;
@@ -1292,24 +1167,10 @@ __global__ __launch_bounds__(256, 1) void gemm_bt_quad_kernel(const bf16_t* __re
             const X3Seg sg = x3_seg(p, K / TK);
             so = i * rstride + sg.koff + (q < 8 ? (sg.a_lo ? (unsigned)(a_plane * 2) : 0u) : (sg.w_lo ? (unsigned)(w_plane * 2) : 0u));
         }
-#if KEDS_QUAD_TIDDMA
-        if (q < 8) {
-            if (KEDS_QUAD_TIDDMA & 1)
-                __builtin_amdgcn_raw_ptr_buffer_load_lds(xrs, (__attribute__((address_space(3))) void*)dst, 16, 0, so + (unsigned)wave * 8u * (unsigned)K * 2u, 0, 0);
-            else
-                __builtin_amdgcn_raw_ptr_buffer_load_lds(xrs, (__attribute__((address_space(3))) void*)dst, 16, xoff, so, 0, 0);
-        } else {
-            if (KEDS_QUAD_TIDDMA & 2)
-                __builtin_amdgcn_raw_ptr_buffer_load_lds(wrs, (__attribute__((address_space(3))) void*)dst, 16, 0, so + (unsigned)wave * 8u * (unsigned)K * 2u, 0, 0);
-            else
-                __builtin_amdgcn_raw_ptr_buffer_load_lds(wrs, (__attribute__((address_space(3))) void*)dst, 16, woff, so, 0, 0);
-        }
-#else
         if (q < 8)
             __builtin_amdgcn_raw_ptr_buffer_load_lds(xrs, (__attribute__((address_space(3))) void*)dst, 16, xoff, so, 0, KEDS_QUAD_AUX_X);
         else
             __builtin_amdgcn_raw_ptr_buffer_load_lds(wrs, (__attribute__((address_space(3))) void*)dst, 16, woff, so, 0, KEDS_QUAD_AUX_W);
-#endif
     };
     const int f = (c >> 1) & 7;
     const int slot0 = ((0 + g) ^ f) << 4, slot1 = ((4 + g) ^ f) << 4;
@@ -1317,7 +1178,6 @@ __global__ __launch_bounds__(256, 1) void gemm_bt_quad_kernel(const bf16_t* __re
     const int wrow = OP_BYTES + (128 * wn2 + c) * 128;             // + j * 2048, j = 4 h + ni
     const int np = (epi_x3(EPI) ? 3 : 1) * (K / TK);               // >= 2
     const int step = PERSIST ? (int)gridDim.x : ntiles;            // (not persistent: one tile per workgroup)
-    [[maybe_unused]] float fill_v[6] = {1.f + K, 2.f, 3.f, 4.f, 0.5f, 0.25f};   // (KEDS_QUAD_FILLER)
 
     // side data of a tile: row t's LayerNorm statistics and column t's bias' / column sum (LN epilogues), column t's bias
     // (residual epilogue), one element per thread, requested with inline-asm loads (the compiler would wait vmcnt(0) for a
@@ -1357,8 +1217,8 @@ __global__ __launch_bounds__(256, 1) void gemm_bt_quad_kernel(const bf16_t* __re
     int tm, tn;
     quad_tile_coords(xcd_remap(id, ntiles), m_tiles, n_tiles, tm, tn);
     int m0 = tm * TM, n0 = tn * TN;
-    xrs = make_rsx(X + (size_t)m0 * K);
-    wrs = make_rsw(W + (size_t)n0 * K);
+    xrs = make_rs(X + (size_t)m0 * K);
+    wrs = make_rs(W + (size_t)n0 * K);
     side_request(m0, n0);
 #pragma unroll
     for (int q = 0; q < 16; ++q) issue(0, q);
@@ -1377,10 +1237,9 @@ __global__ __launch_bounds__(256, 1) void gemm_bt_quad_kernel(const bf16_t* __re
     [[maybe_unused]] bool have_pend = false;
     // (not the QuickGELU form: its epilogue is 2 x 256 transcendentals per lane long and its stores leave under them; deferring
     // 12 of them costs c_fc 3 us -- 242.8 vs 239.8 -- even with the quarter-wise read-back that keeps the registers free)
-    constexpr bool DEFER = PERSIST && epi_is_ln(EPI) && !epi_qgelu(EPI) && !STAMP;
+    constexpr bool DEFER = PERSIST && epi_is_ln(EPI) && !epi_qgelu(EPI);
     for (int it = 0;; ++it) {
         char* side = smem + qd::SIDE0 + (it & 1) * 4096;
-        if constexpr (STAMP) t_loop0 = __builtin_amdgcn_s_memtime();
         // next tile of this workgroup (PERSIST)
         const int nid = id + step;
         const bool more = PERSIST && nid < ntiles;
@@ -1435,8 +1294,6 @@ __global__ __launch_bounds__(256, 1) void gemm_bt_quad_kernel(const bf16_t* __re
             KEDS_QUAD_STEP(false, xb, wb, xa, wa, ob, slot0, false, false, 0, false)        // K-step (np-1, 1)
         }
 
-        [[maybe_unused]] unsigned long long t_loop1 = 0;
-        if constexpr (STAMP) t_loop1 = __builtin_amdgcn_s_memtime();
         if (more) {
             // every wave has its last fragments in registers: both operand buffers are free for the next tile's K-tiles 0, 1
             asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
@@ -1449,8 +1306,8 @@ __global__ __launch_bounds__(256, 1) void gemm_bt_quad_kernel(const bf16_t* __re
                 pc = bias[N + nn0 + tid];
             }
             if constexpr (epi_resid16(EPI)) pb = bias ? bias[nn0 + tid] : 0.f;
-            xrs = make_rsx(X + (size_t)nm0 * K);
-            wrs = make_rsw(W + (size_t)nn0 * K);
+            xrs = make_rs(X + (size_t)nm0 * K);
+            wrs = make_rs(W + (size_t)nn0 * K);
 #pragma unroll
             for (int q = 0; q < 16; ++q) issue(0, q);
 #pragma unroll
@@ -1460,30 +1317,23 @@ __global__ __launch_bounds__(256, 1) void gemm_bt_quad_kernel(const bf16_t* __re
         // ---- epilogues: the 8-wave kernel's, once per 64-column half (wave column 2 wn2 + h) read back from its AGPRs
         // (LayerNorm epilogues do not use aux_i: the A/B switch; the trickle needs the four peeled K-tiles + two more)
         [[maybe_unused]] const bool defer_now = more && aux_i != 0 && np >= 8;
-        [[maybe_unused]] void* stamp_out = aux2;
-        void* aux2e = STAMP ? nullptr : aux2;                             // (stamped build: aux2 carries the stamp buffer)
-#if KEDS_QUAD_NOEPI   // TIMING ONLY (-DKEDS_QUAD_NOEPI=1, tools/rounds/r05_noepi_bound.sh): no read-back, no epilogue arithmetic, no stores
-        if (more) { id = nid; m0 = nm0; n0 = nn0; side_write(smem + qd::SIDE0 + ((it + 1) & 1) * 4096, n0);
-                    asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)\n\ts_barrier" ::: "memory"); continue; }
-        break;
-#endif
         KEDS_QUAD_DRAIN
         f32x4 av[4][8];
         [[maybe_unused]] keds_stat_t* stats = reinterpret_cast<keds_stat_t*>(const_cast<float*>(aux));
         [[maybe_unused]] char* red = smem + qd::RED_OFF;
 #define KEDS_QUAD_EPI(h)                                                                                               \
     if constexpr (epi_is_ln(EPI))                                                                                      \
-        pair_ln_epilogue<EPI, 0>(av, side, out, m0, n0, N, wm, 2 * wn2 + h, g, c, aux2e, nullptr, false, guard);        \
+        pair_ln_epilogue<EPI>(av, side, out, m0, n0, N, wm, 2 * wn2 + h, g, c, aux2, nullptr, false, guard);        \
     else if constexpr (epi_resid16(EPI))                                                                \
-        pair_resid_epilogue<0, false>(av, side, out, m0, n0, N, wm, 2 * wn2 + h, g, c, stats, red);                    \
+        pair_resid_epilogue<false>(av, side, out, m0, n0, N, wm, 2 * wn2 + h, g, c, stats, red);                    \
     else                                                                                                               \
-        tile_epilogue<EPI, 8>(av, bias, out, m0 + 128 * wm + c, M, n0 + 64 * (2 * wn2 + h) + 8 * g, N, K, aux, aux_i, aux2e, N, g == 0, guard, \
+        tile_epilogue<EPI, 8>(av, bias, out, m0 + 128 * wm + c, M, n0 + 64 * (2 * wn2 + h) + 8 * g, N, K, aux, aux_i, aux2, N, g == 0, guard, \
                               epi_x3(EPI) ? x3_wscale(w_plane) : 1.0f);
         if constexpr (DEFER) {
             // one 32-column quarter at a time: 64 read-back registers live instead of 128 leave room for the deferred stores
 #define KEDS_QUAD_EPQ(h, p)                                                                                             \
     KEDS_QUAD_READ_Q##h##p(av)                                                                                          \
-    pair_ln_epilogue<EPI, 0, QUAD_ND, h, p>(av, side, out, m0, n0, N, wm, 2 * wn2 + h, g, c, aux2e, pend, defer_now, guard); \
+    pair_ln_epilogue<EPI, QUAD_ND, h, p>(av, side, out, m0, n0, N, wm, 2 * wn2 + h, g, c, aux2, pend, defer_now, guard); \
     __builtin_amdgcn_sched_barrier(0);
             KEDS_QUAD_EPQ(0, 0)
             KEDS_QUAD_EPQ(0, 1)
@@ -1508,24 +1358,6 @@ __global__ __launch_bounds__(256, 1) void gemm_bt_quad_kernel(const bf16_t* __re
                 const f32x2* rr = reinterpret_cast<const f32x2*>(red) + tid;
                 const f32x2 a = rr[0], b = rr[256], c2 = rr[512], d = rr[768];
                 keds_stat_add(stats + 2 * (size_t)(m0 + tid), (a[0] + b[0]) + (c2[0] + d[0]), (a[1] + b[1]) + (c2[1] + d[1]));
-            }
-        }
-        if constexpr (STAMP) {                                           // same record layout as the 8-wave kernel's stamped build
-            const unsigned long long t_issued = __builtin_amdgcn_s_memtime();
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            const unsigned long long t_end = __builtin_amdgcn_s_memtime();
-            if (lane == 0) {
-                unsigned long long* o = reinterpret_cast<unsigned long long*>(stamp_out) + ((size_t)blockIdx.x * 8 + wave) * 8;
-                o[0] = t_loop0 - t_entry;
-                o[1] = t_loop1 - t_loop0;
-                o[2] = t_issued - t_loop1;
-                o[3] = 0;
-                o[4] = 0;
-                o[5] = t_end - t_issued;
-                o[6] = t_entry;
-                o[7] = t_end;
-                unsigned long long* o2 = reinterpret_cast<unsigned long long*>(stamp_out) + (size_t)ntiles * 64 + (size_t)blockIdx.x * 8 + wave;
-                *o2 = ((unsigned long long)__builtin_amdgcn_s_getreg(63508) << 32) | (unsigned)__builtin_amdgcn_s_getreg(63492);
             }
         }
         if (!more) break;
@@ -1556,7 +1388,6 @@ __global__ __launch_bounds__(256, 1) void gemm_bt_quad3_kernel(const bf16_t* __r
     static_assert(epi_resid16(EPI), "three-deep A ring: residual epilogue only");
     using namespace pr;
     extern __shared__ __attribute__((aligned(16))) char smem[];
-    constexpr int DBG = 0;
     constexpr int WRING = 3 * OP_BYTES;                               // A buffers at 0, 32, 64 KiB; W buffers at 96, 128 KiB
     const int m_tiles = ntiles / n_tiles;
     const int tid = threadIdx.x, lane = tid & 63;
@@ -1595,7 +1426,6 @@ __global__ __launch_bounds__(256, 1) void gemm_bt_quad3_kernel(const bf16_t* __r
     const int xrow = (128 * wm + c) * 128;                              // relative to an A buffer
     const int wrow0 = (128 * wn2 + c) * 128;                            // relative to a W buffer
     const int np = K / TK;                                              // >= 4 (the launcher checks)
-    [[maybe_unused]] float fill_v[6] = {1.f + K, 2.f, 3.f, 4.f, 0.5f, 0.25f};   // (KEDS_QUAD_FILLER)
     float pb = 0.f;
     if (bias) {
         const float* bp = bias + n0 + tid;
@@ -1663,9 +1493,6 @@ __global__ __launch_bounds__(256, 1) void gemm_bt_quad3_kernel(const bf16_t* __r
     }
     // every wave has read its last fragments: the W ring becomes bias slice (side + 2048) and statistics scratch
     asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
-#if KEDS_QUAD_NOEPI   // TIMING ONLY: see gemm_bt_quad_kernel
-    if (np > 0) return;
-#endif
     char* side = smem + WRING;
     char* red = smem + WRING + 8192;
     *reinterpret_cast<float*>(side + 2048 + tid * 4) = pb;
@@ -1674,10 +1501,10 @@ __global__ __launch_bounds__(256, 1) void gemm_bt_quad3_kernel(const bf16_t* __r
     f32x4 av[4][8];
     keds_stat_t* stats = reinterpret_cast<keds_stat_t*>(const_cast<float*>(aux));
     KEDS_QUAD_READ_HALF0(av)
-    pair_resid_epilogue<0, false>(av, side, out, m0, n0, N, wm, 2 * wn2 + 0, g, c, stats, red);
+    pair_resid_epilogue<false>(av, side, out, m0, n0, N, wm, 2 * wn2 + 0, g, c, stats, red);
     __builtin_amdgcn_sched_barrier(0);
     KEDS_QUAD_READ_HALF1(av)
-    pair_resid_epilogue<0, false>(av, side, out, m0, n0, N, wm, 2 * wn2 + 1, g, c, stats, red);
+    pair_resid_epilogue<false>(av, side, out, m0, n0, N, wm, 2 * wn2 + 1, g, c, stats, red);
     if (stats) {                                                        // kernel-uniform
         __syncthreads();
         const f32x2* rr = reinterpret_cast<const f32x2*>(red) + tid;
@@ -1693,7 +1520,6 @@ __global__ __launch_bounds__(256, 1) void gemm_bt_quad3_kernel(const bf16_t* __r
 #undef KEDS_QGAP
 #undef KEDS_QRD
 #undef KEDS_QMFMA
-#undef KEDS_QUAD_FILLER
 
 // NOTE (measured twice in round 1): a PERSISTENT form of this kernel does not pay.  Second attempt, with the fp16 residual
 // stream and the LDS-staged LN epilogue in place: one workgroup per CU walks its tiles; before the LAST K-step of a tile
@@ -1708,7 +1534,7 @@ __global__ __launch_bounds__(256, 1) void gemm_bt_quad3_kernel(const bf16_t* __r
 // costs the same ~1-1.5k cycles of vector issue wherever it sits, the extra barrier, the drain before the side-area staging
 // and the static tile -> CU assignment take the rest.  Not kept.
 
-// NOTE (measured, round 2, tools/stamp_gemm.py with SHAPE=out / proj): the fp16-residual epilogue cost 21-25 k cycles per
+// NOTE (measured, round 2, stamped build of the out / proj shapes): the fp16-residual epilogue cost 21-25 k cycles per
 // tile against 7 k for the same epilogue without residual traffic: ~9 k the 16 dependent residual loads per lane, 5-7 k
 // the 64-bit statistics atomics (2,048 per tile), stores ~0.  Kept: the four waves that share a row reduce their partial
 // {sum, sum sq} through LDS and threads 0-255 add ONE pair per row (512 atomics per tile: epilogue 20.8 k -> 14.8 k cycles).
@@ -1742,36 +1568,11 @@ __global__ __launch_bounds__(256, 1) void gemm_bt_quad3_kernel(const bf16_t* __r
 
 // ---- host: every launch is planned by gemm_plan() (gemm_plan.h), one launch_* per kernel form runs the plan ----------------------
 
-// the library's switches (gemm_plan.h): the defaults -- in an experiment build what the KEDS_* environment said, read once --
-// under the bits of the last keds_gemm_force_small call
-const GemmSwitches& gemm_env_switches() {
-    static const GemmSwitches env = [] {
-        const auto is = [](const char* name, char c) {
-            const char* e = keds_exp_env(name);
-            return e && e[0] == c;
-        };
-        const auto num = [](const char* name, int dflt) {
-            const char* e = keds_exp_env(name);
-            return e && e[0] ? atoi(e) : dflt;
-        };
-        GemmSwitches s;
-        s.no_split = is("KEDS_NO_SPLITK", '1');
-        s.small_lds = is("KEDS_SMALL_NST", '2');
-        s.quad_defer = !is("KEDS_QUAD_DEFER", '0');
-        s.quad = num("KEDS_GEMM_QUAD", s.quad);
-        s.resid_quad_min_k = num("KEDS_RESID_QUAD_K", s.resid_quad_min_k);
-        s.x3_quad = !is("KEDS_X3_QUAD", '0');
-        s.big_tiles_pct = num("KEDS_BIG_TILES_PCT", s.big_tiles_pct);
-        return s;
-    }();
-    return env;
-}
+// the library's switches (gemm_plan.h): the defaults under the bits of the last keds_gemm_force_small call
 GemmSwitches& gemm_switches() {
-    static GemmSwitches sw = gemm_env_switches();
+    static GemmSwitches sw;
     return sw;
 }
-// request of the calling composite (towers.hip, keds_gemm_small_lds): 128^2 launches of this thread take the 64 KiB-LDS kernel form
-thread_local int tl_small_lds = 0;
 
 // What the last keds_gemm_bt* / keds_gemm_x3 call of this thread launched (keds_gemm_last_launch, keds_hip.h): slot 0 = the main
 // launch, slot 1 = the remainder-row launch behind a 256^2 main launch.  A few stores to a thread-local per call; written at each
@@ -1845,9 +1646,9 @@ int launch_pair(const GemmArgs& a, const GemmPlan::Part& p) {
     const int m_tiles = a.M / pr::TM, n_tiles = a.N / pr::TN;         // M is a multiple of 256 here
     if constexpr (epi_resid16(EPI)) {
         if (p.flags & KEDS_GEMM_FLAG_RESID_PROLOGUE) {
-            if (int rc = keds_func_lds_once((const void*)gemm_bt_pair_kernel<EPI, 0, 1>, pr::LDS_BYTES, "gemm_bt_pair_kernel")) return rc;
+            if (int rc = keds_func_lds_once((const void*)gemm_bt_pair_kernel<EPI, 1>, pr::LDS_BYTES, "gemm_bt_pair_kernel")) return rc;
             rec_launch(KEDS_GEMM_FORM_PAIR, 2, 1, 0, KEDS_GEMM_FLAG_RESID_PROLOGUE);
-            KEDS_LAUNCH((gemm_bt_pair_kernel<EPI, 0, 1>), m_tiles * n_tiles, 512, pr::LDS_BYTES, a.st, (const bf16_t*)a.A, (const bf16_t*)a.W,
+            KEDS_LAUNCH((gemm_bt_pair_kernel<EPI, 1>), m_tiles * n_tiles, 512, pr::LDS_BYTES, a.st, (const bf16_t*)a.A, (const bf16_t*)a.W,
                         a.bias, a.out, a.M, a.N, a.K, n_tiles, a.aux, a.aux_i, a.aux2, keds_numerics_guard(), 0LL, 0LL);
             return keds_check_launch("gemm_bt_pair_kernel");
         }
@@ -1875,10 +1676,10 @@ int launch_quad(const GemmArgs& a, const GemmPlan::Part&) {
 template <int EPI>
 int launch_quad_persistent(const GemmArgs& a, const GemmPlan::Part& p) {
     const int n_tiles = a.N / pr::TN, ntiles = (a.M / pr::TM) * n_tiles;
-    if (int rc = keds_func_lds_once((const void*)gemm_bt_quad_kernel<EPI, 0, 1>, qd::LDS_BYTES, "gemm_bt_quad_kernel")) return rc;
+    if (int rc = keds_func_lds_once((const void*)gemm_bt_quad_kernel<EPI, 1>, qd::LDS_BYTES, "gemm_bt_quad_kernel")) return rc;
     const int aux_i = epi_is_ln(EPI) ? p.defer : a.aux_i;
     rec_launch(KEDS_GEMM_FORM_QUAD, 2, 1, 1, epi_is_ln(EPI) && !epi_qgelu(EPI) && aux_i && a.K / pr::TK >= 8 ? KEDS_GEMM_FLAG_DEFER : 0);
-    KEDS_LAUNCH((gemm_bt_quad_kernel<EPI, 0, 1>), p.workgroups, 256, qd::LDS_BYTES, a.st, (const bf16_t*)a.A, (const bf16_t*)a.W, a.bias, a.out,
+    KEDS_LAUNCH((gemm_bt_quad_kernel<EPI, 1>), p.workgroups, 256, qd::LDS_BYTES, a.st, (const bf16_t*)a.A, (const bf16_t*)a.W, a.bias, a.out,
                 a.M, a.N, a.K, n_tiles, a.aux, aux_i, a.aux2, keds_numerics_guard(), ntiles, a.a_plane, a.w_plane);
     return keds_check_launch("gemm_bt_quad_kernel<persistent>");
 }
@@ -1911,65 +1712,6 @@ int launch_part(const GemmArgs& a, const GemmPlan::Part& p) {
     return KEDS_E_LAUNCH;
 }
 
-// The two main launches the planner does not model, in place of the planned launch on full 256-row tiles: the stamped diagnostic
-// builds of the qkv / residual GEMMs (bits 13-15 of keds_gemm_force_small: aux2 = stamp buffer; they record nothing) and, in an
-// experiment build, the two-accumulator-set kernel.  False: neither applies, the planned launch runs.
-template <int EPI>
-bool launch_unplanned(const GemmArgs& a, const GemmSwitches& sw, int* rc) {
-#ifdef KEDS_EXPERIMENTS
-    if constexpr (EPI == KEDS_EPI_LN_BIAS_BF16_H || EPI == KEDS_EPI_LN_QGELU_BF16_H) {
-        // (a forced kernel form -- keds_gemm_force_small bits 11-15, KEDS_GEMM_QUAD -- keeps the round-4 kernels: A/B tools)
-        if (sw.quad < 0 && !sw.stamp && keds_gemm_duo_ok(EPI, a.M, a.N, a.K)) {
-            *rc = keds_gemm_duo_launch(EPI, a.A, a.W, a.bias, a.out, a.M, a.N, a.K, a.aux, a.aux2, a.st);
-            return true;
-        }
-    }
-#endif
-    if constexpr (EPI == KEDS_EPI_LN_BIAS_BF16_H || EPI == KEDS_EPI_RESID_STATS_F16) {
-        const int n_tiles = a.N / pr::TN, ntiles = (a.M / pr::TM) * n_tiles;
-        if (sw.stamp && sw.quad > 0) {                               // stamped build of the 4-wave kernel
-#define KEDS_QSTAMP(V)                                                                                              \
-    {                                                                                                              \
-        (void)keds_func_lds_once((const void*)gemm_bt_quad_kernel<EPI, V>, qd::LDS_BYTES, "gemm_bt_quad_kernel<stamp>"); \
-        gemm_bt_quad_kernel<EPI, V><<<ntiles, 256, qd::LDS_BYTES, a.st>>>((const bf16_t*)a.A, (const bf16_t*)a.W, a.bias, a.out, a.M, a.N, \
-                                                                          a.K, n_tiles, a.aux, a.aux_i, a.aux2, nullptr, ntiles); \
-    }
-            switch (sw.stamp) {
-                case 2: KEDS_QSTAMP(2) break;
-                case 3: KEDS_QSTAMP(3) break;
-                case 4: KEDS_QSTAMP(4) break;
-                case 5: KEDS_QSTAMP(5) break;
-                case 6: KEDS_QSTAMP(6) break;
-                case 7: KEDS_QSTAMP(8) break;
-                default: KEDS_QSTAMP(1) break;
-            }
-#undef KEDS_QSTAMP
-            *rc = keds_check_launch("gemm_bt_quad_kernel<stamp>");
-            return true;
-        }
-        if (sw.stamp) {
-            const dim3 grid(ntiles);
-#define KEDS_STAMP_LAUNCH(V)                                                                                       \
-    {                                                                                                             \
-        (void)keds_func_lds_once((const void*)gemm_bt_pair_kernel<EPI, V>, pr::LDS_BYTES, "gemm_bt_pair_kernel<stamp>"); \
-        gemm_bt_pair_kernel<EPI, V><<<grid, 512, pr::LDS_BYTES, a.st>>>((const bf16_t*)a.A, (const bf16_t*)a.W, a.bias, a.out, a.M, a.N, \
-                                                                         a.K, n_tiles, a.aux, a.aux_i, a.aux2, nullptr);  \
-    }
-            switch (sw.stamp) {
-                case 2: KEDS_STAMP_LAUNCH(2) break;
-                case 3: KEDS_STAMP_LAUNCH(3) break;
-                case 4: KEDS_STAMP_LAUNCH(4) break;
-                case 5: KEDS_STAMP_LAUNCH(5) break;
-                default: KEDS_STAMP_LAUNCH(1) break;
-            }
-#undef KEDS_STAMP_LAUNCH
-            *rc = keds_check_launch("gemm_bt_pair_kernel<stamp>");
-            return true;
-        }
-    }
-    return false;
-}
-
 template <int EPI>
 int launch_gemm(GemmArgs a) {
     const int M = a.M, N = a.N, K = a.K;
@@ -1983,13 +1725,10 @@ int launch_gemm(GemmArgs a) {
     size_t splitk_bytes = 0;
     if (needs.splitk) keds_splitk_scratch(&a.splitk, &splitk_bytes);
     if (!a.splitk) splitk_bytes = 0;
-    const GemmPlan plan = gemm_plan(EPI, M, N, K, a.lda, a.ldc, needs.cus ? keds_device_cus() : 0, splitk_bytes, tl_small_lds != 0, sw);
+    const GemmPlan plan = gemm_plan(EPI, M, N, K, a.lda, a.ldc, needs.cus ? keds_device_cus() : 0, splitk_bytes, false, sw);
 
     a.M = plan.main.rows;
-    int rc = KEDS_OK;
-    const bool planned = plan.main.form == KEDS_GEMM_FORM_SMALL || !launch_unplanned<EPI>(a, sw, &rc);
-    if (planned) rc = launch_part<EPI>(a, plan.main);
-    if (rc) return rc;
+    if (int rc = launch_part<EPI>(a, plan.main)) return rc;
     if (plan.tail.form != KEDS_GEMM_FORM_NONE) {
         tl_rec_slot = 1;
         const size_t m_main = plan.main.rows;
@@ -2008,13 +1747,13 @@ int launch_gemm(GemmArgs a) {
         a.A = (const char*)a.A + m_main * K * 2;
         a.out = (char*)a.out + m_main * N * esz;
         a.M = plan.tail.rows;
-        if ((rc = launch_part<EPI>(a, plan.tail))) return rc;
+        if (int rc = launch_part<EPI>(a, plan.tail)) return rc;
     }
     // keds_gemm_last_launch reports what the launch sites recorded, not the plan: the two must agree
     int want[8], got[8];
     plan.info(want);
     tl_rec.info(got);
-    for (int i = 0; planned && i < 8; ++i) {
+    for (int i = 0; i < 8; ++i) {
         if (got[i] != want[i]) {
             keds_set_error("keds_gemm_bt: launched form differs from the plan at [%d]: %d, planned %d (epilogue %d, %d x %d x %d)", i, got[i],
                            want[i], EPI, M, N, K);
@@ -2028,7 +1767,6 @@ int launch_gemm(GemmArgs a) {
 
 // (keds_common.h) any epilogue, dense strides: what bf16_rows_split (towers.hip) asks per GEMM shape of a block
 bool keds_gemm_splits_rows(int M, int N, int K) { return gemm_big_tiles_fill(M, N, K, gemm_switches()) && M % 256 != 0; }
-void keds_gemm_small_lds(int on) { tl_small_lds = on; }
 
 extern "C" int keds_gemm_last_launch(int* info) {
     KEDS_REQUIRE(info, "keds_gemm_last_launch: null pointer");
@@ -2037,7 +1775,10 @@ extern "C" int keds_gemm_last_launch(int* info) {
 }
 
 extern "C" int keds_gemm_force_small(int on) {
-    gemm_switches() = gemm_switches_decode(on, gemm_env_switches());
+    // bit 8 (no remainder-row launch) and bits 13-15 (stamped builds) selected timing-only forms that last existed at 14f64ac
+    for (const int bit : {8, 13, 14, 15})
+        KEDS_REQUIRE(!((on >> bit) & 1), "keds_gemm_force_small: bit %d is no longer offered", bit);
+    gemm_switches() = gemm_switches_decode(on, GemmSwitches{});
     return KEDS_OK;
 }
 

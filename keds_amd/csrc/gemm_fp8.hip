@@ -114,14 +114,6 @@ __global__ __launch_bounds__(256) void fold_quantize_mxfp8_kernel(const float* _
 }
 
 // ---- the epilogues of one wave's 128 x 64 block of accumulators (both tile kernels): wave row wm (0..1), wave column wn (0..3)
-// timing-only ablations of the 4-wave kernel (tools/fp8_ablate.sh rebuilds with -DKEDS_FQ_ABL=n; results are wrong), bits:
-// 1: no epilogue (read-back only)   2: the K-loop runs its first two and last two K-tiles only
-// residual epilogues:  4: no statistics atomics   8: no MXFP8 copy / scale stores   16: no residual store   32: no residual load
-// K-loop (tools/fp8_kloop_ab.sh, with -DKEDS_FQ_STAMP):  64: no DMA pieces   128: no fragment / scale reads   256: no wait +
-//          barrier per K-tile   512: the wait without the barrier   1024: the barrier without the vmcnt wait   2048: the barrier alone
-#ifndef KEDS_FQ_ABL
-#define KEDS_FQ_ABL 0
-#endif
 // ---- the epilogues, one ROW GROUP at a time: the 16 rows 16 mi + c of one wave's 128 x 64 block, lane (g, c) owning row c and
 // the columns 64 wn + 32 pp + 8 g + 0..7 (a[2 pp], a[2 pp + 1]) of both 32-column MX blocks pp.  The four lanes g = 0..3 of a row
 // hold exactly one MX block per pp, so block amax / row sums are two xor-shuffles.  (Row groups outermost since round 4: the
@@ -215,15 +207,13 @@ __device__ __forceinline__ void mx_epilogue_rows(const f32x4 (&a)[4], int mi, co
             } else {                                          // fp16 residual stream (cf. KEDS_EPI_RESID_STATS_F16)
                 f16x8* o = reinterpret_cast<f16x8*>(reinterpret_cast<f16_t*>(out) + (size_t)m * N + n);
                 f16x8 r;
-                if constexpr (PRE && !(KEDS_FQ_ABL & 32)) r = pre[pp];
-                else if constexpr ((KEDS_FQ_ABL & 32) != 0) r = f16x8{(f16_t)1.f, (f16_t)2.f, (f16_t)-1.f, (f16_t)0.5f, (f16_t)1.f, (f16_t)2.f, (f16_t)-1.f, (f16_t)0.5f};
+                if constexpr (PRE) r = pre[pp];
                 else r = *o;
                 v0 += f32x4{(float)r[0], (float)r[1], (float)r[2], (float)r[3]};
                 v1 += f32x4{(float)r[4], (float)r[5], (float)r[6], (float)r[7]};
                 const f16x8 nr = f16x8{(f16_t)v0[0], (f16_t)v0[1], (f16_t)v0[2], (f16_t)v0[3],
                                        (f16_t)v1[0], (f16_t)v1[1], (f16_t)v1[2], (f16_t)v1[3]};
-                if constexpr ((KEDS_FQ_ABL & 16) != 0) { if (nr[0] == (f16_t)123.25f) *o = nr; }
-                else if constexpr (PRE)
+                if constexpr (PRE)
                     keds_store16<8>(nr, reinterpret_cast<f16_t*>(out) + (size_t)m0 * N + n0, (unsigned)(((size_t)(m - m0) * N + (n - n0)) * 2));
                 else
                     *o = nr;
@@ -257,13 +247,11 @@ __device__ __forceinline__ void mx_epilogue_rows(const f32x4 (&a)[4], int mi, co
                 const auto s1 = __builtin_amdgcn_permlane16_swap(mxk.y, pk.y, false, false);
                 const int blk = g & 1, half = g >> 1;          // after the swap: this lane's block and 16-column half
                 const unsigned qoff = (unsigned)((size_t)(m - m0) * N + (64 * wn + 32 * blk + 16 * half));
-                if constexpr ((KEDS_FQ_ABL & 8) != 0) {
-                    if (s0[0] == 0x12345678u) qout[0] = 1;
-                } else if constexpr (EPI == 2)       // MLP hidden (MXFP8): read once by c_proj
+                if constexpr (EPI == 2)              // MLP hidden (MXFP8): read once by c_proj
                     keds_store16<KEDS_ST_FP8_MX>(u32x4{s0[0], s1[0], s0[1], s1[1]}, qout + (size_t)m0 * N + n0, qoff);
                 else                           // MXFP8 copy of the residual stream: the next GEMM's A operand
                     keds_store16<(PRE && KEDS_ST_FP8_MXR == 0) ? 8 : KEDS_ST_FP8_MXR>(u32x4{s0[0], s1[0], s0[1], s1[1]}, qout + (size_t)m0 * N + n0, qoff);
-                if (g == 0 && !(KEDS_FQ_ABL & 8))
+                if (g == 0)
                     *reinterpret_cast<unsigned short*>(qscale + mx_scale_index((n0 + 64 * wn) >> 5, m, q_pad)) =
                         (unsigned short)((mxe + 127) | ((e + 127) << 8));
             }
@@ -275,7 +263,7 @@ __device__ __forceinline__ void mx_epilogue_rows(const f32x4 (&a)[4], int mi, co
         if constexpr (STAT == 4) {
             if (g == 0) *reinterpret_cast<f32x2*>(red + (wn * 256 + 128 * wm + 16 * mi + c) * 2) = f32x2{rs, rss};
         } else {
-            if (g == 0 && !(KEDS_FQ_ABL & 4)) keds_stat_add(reinterpret_cast<keds_stat_t*>(aux) + 2 * (size_t)m, rs, rss);
+            if (g == 0) keds_stat_add(reinterpret_cast<keds_stat_t*>(aux) + 2 * (size_t)m, rs, rss);
         }
     }
 }
@@ -302,7 +290,7 @@ __device__ __forceinline__ void mx_epilogue(f32x4 (&acc)[4][8], const char* side
 //          buffer to clear; out bf16
 //      2 = the same + QuickGELU, emitted as MXFP8: qout / qscale (rows padded to q_pad) instead of `out`
 //      3 = out fp32 += acc + bias (residual stream), its MXFP8 copy to qout / qscale and row {sum, sum sq} atomically to aux
-template <int EPI, int DBG>
+template <int EPI>
 __global__ __launch_bounds__(512, 2) void gemm_mxfp8_kernel(const unsigned char* __restrict__ X, const unsigned char* __restrict__ sX,
                                                             const unsigned char* __restrict__ W, const unsigned char* __restrict__ sW,
                                                             const float* __restrict__ bias, void* __restrict__ out, int M, int N,
@@ -435,77 +423,46 @@ __global__ __launch_bounds__(512, 2) void gemm_mxfp8_kernel(const unsigned char*
 #define KEDS_FP8_MFMA(NI, OB)                                                                                         \
     acc[NI][mi] = __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(wf[NI], xf[mi], acc[NI][mi], 0, 0, NI, swp, OB, sxp[mi >> 2]);
 #define KEDS_FP8_ROW(OB) KEDS_FP8_MFMA(0, OB) KEDS_FP8_MFMA(1, OB) KEDS_FP8_MFMA(2, OB) KEDS_FP8_MFMA(3, OB)
-            if constexpr (DBG == 2) {
-#pragma unroll
-                for (int ni = 0; ni < 4; ++ni) acc[ni][mi][0] += __int_as_float(wf[ni][0] ^ xf[mi][3] ^ swp ^ sxp[mi >> 2]);
-            } else {
-                switch (mi & 3) {                      // op_sel is an immediate: the unrolled mi makes this a constant
-                    case 0: KEDS_FP8_ROW(0) break;
-                    case 1: KEDS_FP8_ROW(1) break;
-                    case 2: KEDS_FP8_ROW(2) break;
-                    default: KEDS_FP8_ROW(3) break;
-                }
+            switch (mi & 3) {                      // op_sel is an immediate: the unrolled mi makes this a constant
+                case 0: KEDS_FP8_ROW(0) break;
+                case 1: KEDS_FP8_ROW(1) break;
+                case 2: KEDS_FP8_ROW(2) break;
+                default: KEDS_FP8_ROW(3) break;
             }
 #undef KEDS_FP8_ROW
 #undef KEDS_FP8_MFMA
         }
     };
-    unsigned long long t0 = 0, r0 = 0;
-    if constexpr (DBG == 3) {                                      // diagnostic build only
-        t0 = __builtin_amdgcn_s_memtime();
-        r0 = __builtin_amdgcn_s_memrealtime();
-    }
     for (int p = 0; p < np; ++p) {
         const char* cb = smem + (p & 1) * PBUF_BYTES;
         // tile p has landed (own pieces) and, past the barrier, everybody is done with the other buffer
         asm volatile("s_waitcnt vmcnt(0)\n\ts_barrier" ::: "memory");
-        if (p + 1 < np && DBG != 4) {
+        if (p + 1 < np) {
 #pragma unroll
             for (int q = 0; q < 8; ++q) issue(p + 1, q);
             issue_scales(p + 1);
         }
         __builtin_amdgcn_sched_barrier(0);
-        if (grp == 1 && p > 0 && DBG != 1) multiply();
+        if (grp == 1 && p > 0) multiply();
         __builtin_amdgcn_sched_barrier(0);
-        if constexpr (DBG != 1 && DBG != 4) {
-            swp = 0;
-            sxp[0] = sxp[1] = 0;
+        swp = 0;
+        sxp[0] = sxp[1] = 0;
 #pragma unroll
-            for (int ni = 0; ni < 4; ++ni) {
-                wf[ni] = load_frag(cb, wrow + ni * 2048);
-                swp |= ((*reinterpret_cast<const unsigned*>(cb + sw_base + (32 * ((ni >> 1) & 1) + 4 * (ni & 1)) * 4) >> (8 * g)) & 0xFFu) << (8 * ni);
-            }
+        for (int ni = 0; ni < 4; ++ni) {
+            wf[ni] = load_frag(cb, wrow + ni * 2048);
+            swp |= ((*reinterpret_cast<const unsigned*>(cb + sw_base + (32 * ((ni >> 1) & 1) + 4 * (ni & 1)) * 4) >> (8 * g)) & 0xFFu) << (8 * ni);
+        }
 #pragma unroll
-            for (int mi = 0; mi < 8; ++mi) {
-                xf[mi] = load_frag(cb, xrow + mi * 2048);
-                sxp[mi >> 2] |= ((*reinterpret_cast<const unsigned*>(cb + sx_off + mi * 64) >> (8 * g)) & 0xFFu) << (8 * (mi & 3));
-            }
-        } else if (p == 0) {
-#pragma unroll
-            for (int mi = 0; mi < 8; ++mi) {
-#pragma unroll
-                for (int j = 0; j < 8; ++j) xf[mi][j] = lane * 0x01010101 + j + mi;
-            }
-#pragma unroll
-            for (int ni = 0; ni < 4; ++ni) wf[ni] = xf[ni] + ni;
-            swp = 0x7F7F7F7F;
-            sxp[0] = sxp[1] = 0x7F7F7F7F + (lane & 1);
+        for (int mi = 0; mi < 8; ++mi) {
+            xf[mi] = load_frag(cb, xrow + mi * 2048);
+            sxp[mi >> 2] |= ((*reinterpret_cast<const unsigned*>(cb + sx_off + mi * 64) >> (8 * g)) & 0xFFu) << (8 * (mi & 3));
         }
         __builtin_amdgcn_sched_barrier(0);
-        if (grp == 0 && DBG != 1) multiply();
+        if (grp == 0) multiply();
         __builtin_amdgcn_sched_barrier(0);
     }
-    if (grp == 1 && DBG != 1) multiply();
+    if (grp == 1) multiply();
 
-    if constexpr (DBG == 3) {   // (core-clock ticks, 100 MHz ticks) of the K-loop into the first words of this tile's output
-        const unsigned long long t1 = __builtin_amdgcn_s_memtime(), r1 = __builtin_amdgcn_s_memrealtime();
-        if (tid == 0) {
-            unsigned long long* dbg = reinterpret_cast<unsigned long long*>(reinterpret_cast<bf16_t*>(out) + (size_t)m0 * N + n0);
-            dbg[0] = t1 - t0;
-            dbg[1] = r1 - r0;
-        }
-        return;
-    }
     mx_epilogue<EPI>(acc, smem + SIDE_OFF, bias, out, m0, n0, N, wm, wn, g, c, aux, aux2, qout, qscale, q_pad);
 }
 
@@ -626,14 +583,11 @@ constexpr int LDS_BYTES = RAW + 6144;            // 146 KiB
 // buffer is free (wait + barrier), 2: the buffer is free (every wave's fragment reads of it are done; no wait for pieces)
 #define KEDS_FQ_STEP(FIRST, xc, sxc, swc, xn, sxn, swn, nb, SYNC_, ISSUE_, ip, PF_)                              \
     {                                                                                                            \
-        constexpr int SYNCM = (KEDS_FQ_ABL & 256) ? 0 : (int)(SYNC_);                                            \
-        constexpr bool SYNC = SYNCM == 1, ISSUE = (ISSUE_) && !(KEDS_FQ_ABL & 64),                               \
-                       PF = (PF_) && !(KEDS_FQ_ABL & 128);                                                       \
+        constexpr int SYNCM = (int)(SYNC_);                                                                      \
+        constexpr bool ISSUE = (ISSUE_), PF = (PF_);                                                             \
         __builtin_amdgcn_sched_barrier(0);                                                                       \
-        if constexpr (SYNC && (KEDS_FQ_ABL & 512)) asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");     \
-        else if constexpr ((SYNC && (KEDS_FQ_ABL & 1024)) || SYNCM == 2) asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); \
-        else if constexpr (SYNC && (KEDS_FQ_ABL & 2048)) asm volatile("s_barrier" ::: "memory");                  \
-        else if constexpr (SYNC) asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)\n\ts_barrier" ::: "memory");        \
+        if constexpr (SYNCM == 2) asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");                 \
+        else if constexpr (SYNCM == 1) asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)\n\ts_barrier" ::: "memory");   \
         __builtin_amdgcn_sched_barrier(0);                                                                       \
         KEDS_FQ_ROW(FIRST, 0, xc, sxc, swc, xn, sxn, swn, nb, ISSUE, ip, PF)                                     \
         KEDS_FQ_ROW(FIRST, 1, xc, sxc, swc, xn, sxn, swn, nb, ISSUE, ip, PF)                                     \
@@ -739,17 +693,7 @@ __global__ __launch_bounds__(256, 1) void gemm_mxfp8_quad_kernel(const unsigned 
     for (int q = 0; q < 16; ++q) issue(1, q);
     issue_scales(1);
 
-#ifdef KEDS_FQ_STAMP
-    // diagnostic build (tools/fp8_stamp.py; EPI 1 only: qout carries a buffer of 8 x 64-bit words per (workgroup, wave)): core-clock
-    // ticks of the phases of the workgroup's SECOND tile -- wait for its K-tiles | fragment reads of K-tile 0 | K-loop | requests of the
-    // next tile | epilogue
-    unsigned long long ts[6] = {0, 0, 0, 0, 0, 0};
-#define KEDS_FQ_TS(i) if (it == 1) ts[i] = __builtin_amdgcn_s_memtime();
-#else
-#define KEDS_FQ_TS(i)
-#endif
     for (int it = 0;; ++it) {
-        KEDS_FQ_TS(0)
         // this tile's K-tiles 0 and 1 and its raw side data have landed.  They were requested in the last two K-steps of the previous
         // tile, AHEAD of its epilogue's stores; vmcnt retires in order (loads and stores alike on this family), so the wait leaves
         // the epilogue's last NST stores in flight instead of sitting out their write latency (~1 k cycles per tile, round 4 stamps)
@@ -757,7 +701,6 @@ __global__ __launch_bounds__(256, 1) void gemm_mxfp8_quad_kernel(const unsigned 
         // retire, so the youngest dozen are the ones still in flight here)
         if (it == 0) asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)\n\ts_barrier" ::: "memory");
         else asm volatile("s_waitcnt vmcnt(12) lgkmcnt(0)\n\ts_barrier" ::: "memory");
-        KEDS_FQ_TS(1)
         char* side = smem + fq::SIDE0 + (it & 1) * 4096;
         const int nid = id + step;
         const bool more = nid < ntiles;
@@ -821,15 +764,11 @@ __global__ __launch_bounds__(256, 1) void gemm_mxfp8_quad_kernel(const unsigned 
             }
         }
         // K-tiles 0 | 1 | [2j, 2j + 1] | np - 2 | np - 1
-#ifdef KEDS_FQ_STAMP
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-#endif
-        KEDS_FQ_TS(2)
         // (step 0 syncs in mode 2: K-tile 1 landed behind the wait that opened the tile; what the step needs is buffer 0 free of
         // every wave's K-tile-0 reads -- and a vmcnt(0) here would sit out the previous epilogue's stores after all)
         KEDS_FQ_STEP(true, xa, sxa, swa, xb, sxb, swb, 1, 2, true, 2, true)
         KEDS_FQ_STEP(false, xb, sxb, swb, xa, sxa, swa, 0, 1, true, 3, true)
-        for (int p = 2; p + 2 < np && !(KEDS_FQ_ABL & 2); p += 2) {
+        for (int p = 2; p + 2 < np; p += 2) {
             KEDS_FQ_STEP(false, xa, sxa, swa, xb, sxb, swb, 1, 1, true, p + 2, true)
             KEDS_FQ_STEP(false, xb, sxb, swb, xa, sxa, swa, 0, 1, true, p + 3, true)
         }
@@ -853,7 +792,6 @@ __global__ __launch_bounds__(256, 1) void gemm_mxfp8_quad_kernel(const unsigned 
             KEDS_FQ_STEP(false, xb, sxb, swb, xa, sxa, swa, 0, 0, false, 0, false)
         }
 
-        KEDS_FQ_TS(3)
         // (the lane coordinates through an opaque move: everything the epilogue derives from them is otherwise loop invariant, and
         // hoisted out of the tile loop it is ~60 registers the K-loop does not have)
         const int le = lane_now();
@@ -892,7 +830,6 @@ __global__ __launch_bounds__(256, 1) void gemm_mxfp8_quad_kernel(const unsigned 
             }
         }
         if constexpr (EPI == 4) resid_request(1);
-        KEDS_FQ_TS(4)
         // ---- epilogue: the 8-wave kernel's (its wave column 2 wn2 + h), one row group of 16 accumulator registers at a time
         KEDS_QUAD_DRAIN
         constexpr bool RES = EPI == 3 || EPI == 4;      // (their row partials meet the other three wave columns' in LDS)
@@ -902,9 +839,8 @@ __global__ __launch_bounds__(256, 1) void gemm_mxfp8_quad_kernel(const unsigned 
     {                                                                                                                    \
         f32x4 av[4];                                                                                                     \
         KEDS_QUAD_READ_G##h##mi(av)                                                                                      \
-        if constexpr (!(KEDS_FQ_ABL & 1))                                                                                \
-            mx_epilogue_rows<EPI, EPI == 4, RES ? 4 : 2>(av, mi, sd, side, out, m0, n0, N, wm, 2 * wn2 + h, ge, ce, aux, aux2, qout,   \
-                                                         qscale, q_pad, rpre[h][mi], red);                               \
+        mx_epilogue_rows<EPI, EPI == 4, RES ? 4 : 2>(av, mi, sd, side, out, m0, n0, N, wm, 2 * wn2 + h, ge, ce, aux, aux2, qout, \
+                                                     qscale, q_pad, rpre[h][mi], red);                                   \
     }
 #define KEDS_FQ_EPH(h)                                                                                                   \
     mx_side<EPI>(sd, side, bias, n0, 2 * wn2 + h, ge);                                                                   \
@@ -914,39 +850,28 @@ __global__ __launch_bounds__(256, 1) void gemm_mxfp8_quad_kernel(const unsigned 
         KEDS_FQ_EPH(1)
 #undef KEDS_FQ_EPH
 #undef KEDS_FQ_EPG
-        if constexpr (RES && !(KEDS_FQ_ABL & 1)) {      // row t: the four wave columns' partials (the side areas: unused by these epilogues)
+        if constexpr (RES) {      // row t: the four wave columns' partials (the side areas: unused by these epilogues)
             __syncthreads();
             const f32x2* rr = reinterpret_cast<const f32x2*>(red) + tid;
             const f32x2 p0 = rr[0], p1 = rr[256], p2 = rr[512], p3 = rr[768];
-            if (!(KEDS_FQ_ABL & 4))
-                keds_stat_add(reinterpret_cast<keds_stat_t*>(aux) + 2 * (size_t)(m0 + tid), (p0[0] + p1[0]) + (p2[0] + p3[0]),
-                              (p0[1] + p1[1]) + (p2[1] + p3[1]));
+            keds_stat_add(reinterpret_cast<keds_stat_t*>(aux) + 2 * (size_t)(m0 + tid), (p0[0] + p1[0]) + (p2[0] + p3[0]),
+                          (p0[1] + p1[1]) + (p2[1] + p3[1]));
         }
-#ifdef KEDS_FQ_STAMP
-        if constexpr (EPI == 1) {
-            if (it == 1) {
-                const unsigned long long t5 = __builtin_amdgcn_s_memtime();
-                if (lane == 0 && qout) {
-                    unsigned long long* o = reinterpret_cast<unsigned long long*>(qout) + ((size_t)blockIdx.x * 4 + wave) * 8;
-                    o[0] = ts[1] - ts[0]; o[1] = ts[2] - ts[1]; o[2] = ts[3] - ts[2]; o[3] = ts[4] - ts[3]; o[4] = t5 - ts[4]; o[5] = ts[0]; o[6] = t5;
-                }
-            }
-        }
-#endif
         if (!more) break;
         id = nid;
         m0 = nm0;
         n0 = nn0;
     }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");    // (the last tile's re-requested K-tiles: no LDS-DMA write may outlive the workgroup)
-#undef KEDS_FQ_TS
 #undef make_rs
 }
 
 }  // namespace
 
-int g_fp8_debug = 0;   // timing-only ablations of gemm_mxfp8_kernel
+int g_fp8_debug = 0;   // 16: every shape on the 8-wave kernel (the bit-identity test's reference)
 extern "C" int keds_mxfp8_debug(int variant) {
+    // values 1-4 selected timing-only ablations of gemm_mxfp8_kernel that last existed at 14f64ac
+    KEDS_REQUIRE(variant == 0 || variant == 16, "keds_mxfp8_debug: value %d is no longer offered (0 or 16)", variant);
     g_fp8_debug = variant;
     return KEDS_OK;
 }
@@ -976,27 +901,19 @@ struct Fp8LaunchRecord {
 };
 thread_local Fp8LaunchRecord tl_fp8_rec = {};
 
-template <int EPI, int DBG>
+template <int EPI>
 int launch_mxfp8(const void* Aq, const void* As, int m_pad, const void* Wq, const void* Ws, int n_pad, const float* bias,
                  void* out, int M, int N, int K, float* aux, float* aux2, void* qout, void* qscale, int q_pad, hipStream_t st) {
-    if (int rc = keds_func_lds_once((const void*)gemm_mxfp8_kernel<EPI, DBG>, LDS_BYTES, "gemm_mxfp8_kernel")) return rc;
+    if (int rc = keds_func_lds_once((const void*)gemm_mxfp8_kernel<EPI>, LDS_BYTES, "gemm_mxfp8_kernel")) return rc;
     const int m_tiles = M / TM, n_tiles = N / TN;
     tl_fp8_rec = Fp8LaunchRecord{KEDS_FP8_FORM_PAIR, m_tiles * n_tiles, m_tiles * n_tiles};
-    KEDS_LAUNCH((gemm_mxfp8_kernel<EPI, DBG>), m_tiles * n_tiles, 512, LDS_BYTES, st,
+    KEDS_LAUNCH((gemm_mxfp8_kernel<EPI>), m_tiles * n_tiles, 512, LDS_BYTES, st,
                 (const unsigned char*)Aq, (const unsigned char*)As, (const unsigned char*)Wq, (const unsigned char*)Ws, bias, out, M, N, K,
                 n_tiles, m_pad, n_pad, aux, aux2, (unsigned char*)qout, (unsigned char*)qscale, q_pad);
     return keds_check_launch("gemm_mxfp8_kernel");
 }
 
 // the 4-wave persistent kernel: K-tiles in pairs (K % 256 == 0), at least four
-bool fp8_quad_enabled() {
-    static int on = -1;
-    if (on < 0) {
-        const char* e = keds_exp_env("KEDS_FP8_QUAD");
-        on = !(e && e[0] == '0');
-    }
-    return on != 0;
-}
 template <int EPI>
 int launch_mxfp8_quad(const void* Aq, const void* As, int m_pad, const void* Wq, const void* Ws, int n_pad, const float* bias,
                       void* out, int M, int N, int K, float* aux, float* aux2, void* qout, void* qscale, int q_pad, hipStream_t st) {
@@ -1031,33 +948,29 @@ extern "C" int keds_gemm_mxfp8_ex(const void* Aq, const void* As, int m_pad, con
     // keds_mxfp8_debug(16): the 8-wave kernel whatever the shape (the bit-identity test's reference).  The fp32-residual epilogue
     // (3: API only, the towers keep their stream in fp16) stays on the 8-wave kernel: beside its 256-bit residual chunks the
     // 4-wave K-loop has no registers left
-    const bool quad = g_fp8_debug == 0 && fp8_quad_enabled() && K % (2 * TKB) == 0 && K >= 4 * TKB;
-#define KEDS_FP8_GO(E, D)                                                                                                         \
+    const bool quad = g_fp8_debug == 0 && K % (2 * TKB) == 0 && K >= 4 * TKB;
+#define KEDS_FP8_GO(E)                                                                                                            \
     {                                                                                                                             \
-        if constexpr ((D) == 0 && (E) != 3)                                                                                        \
+        if constexpr ((E) != 3)                                                                                                   \
             if (quad) return launch_mxfp8_quad<E>(Aq, As, m_pad, Wq, Ws, n_pad, bias, out, M, N, K, aux, aux2, qout, qscale, q_pad, st); \
-        return launch_mxfp8<E, D>(Aq, As, m_pad, Wq, Ws, n_pad, bias, out, M, N, K, aux, aux2, qout, qscale, q_pad, st);              \
+        return launch_mxfp8<E>(Aq, As, m_pad, Wq, Ws, n_pad, bias, out, M, N, K, aux, aux2, qout, qscale, q_pad, st);              \
     }
     switch (epilogue) {
         case KEDS_FP8_EPI_BIAS_BF16:
             KEDS_REQUIRE(out != nullptr, "keds_gemm_mxfp8: null output");
-            if (g_fp8_debug == 1) KEDS_FP8_GO(0, 1)
-            if (g_fp8_debug == 2) KEDS_FP8_GO(0, 2)
-            if (g_fp8_debug == 3) KEDS_FP8_GO(0, 3)
-            if (g_fp8_debug == 4) KEDS_FP8_GO(0, 4)
-            KEDS_FP8_GO(0, 0)
+            KEDS_FP8_GO(0)
         case KEDS_FP8_EPI_LN_BIAS_BF16:
             KEDS_REQUIRE(out && bias && aux, "keds_gemm_mxfp8: LN epilogue needs out, bias = [bias' | csum] and row statistics");
-            KEDS_FP8_GO(1, 0)
+            KEDS_FP8_GO(1)
         case KEDS_FP8_EPI_LN_QGELU_MX:
             KEDS_REQUIRE(bias && aux && qout && qscale && q_pad >= M, "keds_gemm_mxfp8: LN+QuickGELU MX epilogue arguments");
-            KEDS_FP8_GO(2, 0)
+            KEDS_FP8_GO(2)
         case KEDS_FP8_EPI_RESID_STATS_MX:
             KEDS_REQUIRE(out && aux && qout && qscale && q_pad >= M, "keds_gemm_mxfp8: residual MX epilogue arguments");
-            KEDS_FP8_GO(3, 0)
+            KEDS_FP8_GO(3)
         case KEDS_FP8_EPI_RESID_STATS_MX_H:
             KEDS_REQUIRE(out && aux && qout && qscale && q_pad >= M, "keds_gemm_mxfp8: residual MX epilogue arguments");
-            KEDS_FP8_GO(4, 0)
+            KEDS_FP8_GO(4)
         default: keds_set_error("keds_gemm_mxfp8: unknown epilogue %d", epilogue); return KEDS_E_ARG;
     }
 #undef KEDS_FP8_GO

@@ -42,37 +42,33 @@ constexpr bool epi_out_f16(int e) { return epi_base(e) == EPI_INT_BIAS_F16 || ep
 
 // ---- switches ------------------------------------------------------------------------------------------------------------
 // Everything that steers the decision besides the call's own arguments.  The defaults are the product's; keds_gemm_force_small
-// (tests, A/B tools) and, in a KEDS_EXPERIMENTS build, the KEDS_* environment switches change them (gemm.hip keeps the instance).
+// (tests, A/B tools) changes them (gemm.hip keeps the instance).
 struct GemmSwitches {
     bool force_small = false;       // bit 0: everything on the 128^2 kernel
-    bool skip_tail = false;         // bit 8: timing-only, no remainder-row launch
-    bool no_split = false;          // bit 9, KEDS_NO_SPLITK=1: no split-K anywhere
+    bool no_split = false;          // bit 9: no split-K anywhere
     bool resid_prologue = false;    // bit 10: 8-wave kernel, fp16-residual epilogues: residual + bias as the accumulators' initial value
                                     // (built, bit-compatible within the fp32 addition order and SLOWER: out-proj 75.5 vs 73.0 us, c_proj
                                     // 232.4 vs 229.0 -- tools/ab_resid_prologue.py; off)
-    int quad = -1;                  // bits 11-12, KEDS_GEMM_QUAD: 256^2 tiles on the 4-wave kernel: -1 by shape, 0 never, 1 always with
+    int quad = -1;                  // bits 11-12: 256^2 tiles on the 4-wave kernel: -1 by shape, 0 never, 1 always with
                                     // one tile per workgroup, 2 always, persistent where the launch allows it
-    int stamp = 0;                  // bits 13-15: stamped diagnostic build of the qkv / residual GEMMs (not planned: gemm.hip)
     bool quad3 = true;              // bit 16 clears it: 4-wave kernel, fp16-residual epilogues: three-deep A ring
-    bool quad_defer = true;         // bit 17, KEDS_QUAD_DEFER=0 clear it: persistent 4-wave kernel, LayerNorm epilogues: 12 of a tile's
+    bool quad_defer = true;         // bit 17 clears it: persistent 4-wave kernel, LayerNorm epilogues: 12 of a tile's
                                     // 32 stores per lane wait for the next K-loop
-    int resid_quad_min_k = 1024;    // KEDS_RESID_QUAD_K: fp16-residual GEMMs go to the 4-wave kernel from this K on (round 4: out-proj too,
+    int resid_quad_min_k = 1024;    // fp16-residual GEMMs go to the 4-wave kernel from this K on (round 4: out-proj too,
                                     // +0.35 % on the headline: its A operand is cold in the step and the three-deep ring tolerates that)
-    bool x3_quad = true;            // KEDS_X3_QUAD=0 clears it: the split-operand GEMMs on the 4-wave kernel
-    int big_tiles_pct = 85;         // KEDS_BIG_TILES_PCT: the fill of its CU-rounds a 256^2 launch needs
-    bool small_lds = false;         // KEDS_SMALL_NST=2: every 128^2 launch takes the 64 KiB-LDS form
+    bool x3_quad = true;            // the split-operand GEMMs on the 4-wave kernel
+    int big_tiles_pct = 85;         // the fill of its CU-rounds a 256^2 launch needs
+    bool small_lds = false;         // every 128^2 launch takes the 64 KiB-LDS form
 };
 
-// the argument of keds_gemm_force_small over `base` (the defaults, or what the environment of an experiment build said)
+// the argument of keds_gemm_force_small over `base` (the defaults); bits 8 and 13-15 are refused before this is called
 inline GemmSwitches gemm_switches_decode(int bits, const GemmSwitches& base) {
     GemmSwitches s = base;
     s.force_small = bits & 1;
-    s.skip_tail = (bits >> 8) & 1;
     s.no_split = base.no_split || ((bits >> 9) & 1);
     s.resid_prologue = (bits >> 10) & 1;
-    const int q = (bits >> 11) & 3;                       // 0 = by shape (or the environment's form), 3 = never
+    const int q = (bits >> 11) & 3;                       // 0 = by shape, 3 = never
     if (q) s.quad = q == 3 ? 0 : q;
-    s.stamp = (bits >> 13) & 7;
     s.quad3 = !((bits >> 16) & 1);
     s.quad_defer = base.quad_defer && !((bits >> 17) & 1);
     return s;
@@ -173,12 +169,12 @@ struct GemmPlanNeeds {
 };
 inline GemmPlanNeeds gemm_plan_needs(int epi, int M, int N, int K, long long lda, long long ldc, const GemmSwitches& sw) {
     const bool big = gemm_big_tiles(epi, M, N, K, lda, ldc, sw);
-    const int small_rows = big ? (sw.skip_tail ? 0 : M % 256) : M;
+    const int small_rows = big ? M % 256 : M;
     return GemmPlanNeeds{big && gemm_quad_mode(epi, K, sw) == 2, small_rows > 0 && gemm_may_split(epi, small_rows, N, K, sw)};
 }
 
 // cus: compute units of the device; splitk_bytes: the split-K scratch this call may use (0: none); small_lds: the calling
-// composite wants the 64 KiB-LDS form of the 128^2 kernel (keds_gemm_small_lds)
+// composite wants the 64 KiB-LDS form of the 128^2 kernel
 inline GemmPlan gemm_plan(int epi, int M, int N, int K, long long lda, long long ldc, int cus, size_t splitk_bytes, bool small_lds,
                           const GemmSwitches& sw) {
     GemmPlan plan;
@@ -215,7 +211,7 @@ inline GemmPlan gemm_plan(int epi, int M, int N, int K, long long lda, long long
         p.form = KEDS_GEMM_FORM_PAIR;
         if (epi_resid16(epi) && sw.resid_prologue) p.flags = KEDS_GEMM_FLAG_RESID_PROLOGUE;
     }
-    if (p.rows != M && !sw.skip_tail) plan.tail = gemm_plan_small(epi, M - p.rows, N, K, splitk_bytes, small_lds, sw);
+    if (p.rows != M) plan.tail = gemm_plan_small(epi, M - p.rows, N, K, splitk_bytes, small_lds, sw);
     return plan;
 }
 

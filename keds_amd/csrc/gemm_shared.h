@@ -1,17 +1,9 @@
-// Pieces shared by the GEMM translation units (gemm.hip, gemm_duo.hip): the LDS image's swizzle and W-row permutation, the
+// Pieces shared by the GEMM translation units: the LDS image's swizzle and W-row permutation, the
 // epilogue classes, the LayerNorm row coefficients and the numerics guard.  Everything here is internal to the library.
 #pragma once
 #include "keds_common.h"
 #include <math.h>
 #include "gemm_plan.h"      // the epilogue classes (epi_*), shared with the host-only planner
-
-#ifdef KEDS_EXPERIMENTS
-// tools/experiments/gemm_duo.hip (round 5, a measured negative: docs/findings_r05.md section 1): the two-accumulator-set kernel
-// (LayerNorm-folded epilogues under the next unit's MFMAs); only the experiment build links it
-bool keds_gemm_duo_ok(int epi, int M, int N, int K);
-int keds_gemm_duo_launch(int epi, const void* A, const void* W, const float* bias, void* out, int M, int N, int K, const float* aux,
-                         void* aux2, hipStream_t st);
-#endif
 
 namespace {
 

@@ -19,17 +19,9 @@ typedef __attribute__((ext_vector_type(2))) unsigned int u32x2;
 
 #define KEDS_WAVE 64
 
-// ---- switches of the EXPERIMENT build (host) -------------------------------------------------
-// The product library reads four environment variables, all documented in INTEGRATION.md: KEDS_DETERMINISTIC, KEDS_SIDE_STREAM,
-// KEDS_TEXT_TRIM (and, in Python, KEDS_PRECISION / the tokenizer's KEDS_BPE_VOCAB).  Every other KEDS_* switch selects a kernel form
-// or a schedule that lost a measured A/B; they exist only in a library built with `make EXTRA=-DKEDS_EXPERIMENTS` (what the A/B
-// tools under tools/ build), so that the product has one dispatch path per shape.
+// The library reads three environment variables, all documented in INTEGRATION.md: KEDS_DETERMINISTIC, KEDS_SIDE_STREAM,
+// KEDS_TEXT_TRIM (and, in Python, KEDS_PRECISION / the tokenizer's KEDS_BPE_VOCAB): one dispatch path per shape.
 #include <cstdlib>
-#ifdef KEDS_EXPERIMENTS
-inline const char* keds_exp_env(const char* name) { return getenv(name); }
-#else
-inline const char* keds_exp_env(const char*) { return nullptr; }
-#endif
 
 // Packed rows of a causal tower (round 6, keds_text_run_packed): sample b owns rows [off[b], off[b + 1]) of every activation buffer
 // instead of [b S, (b + 1) S).  The GEMMs and LayerNorm statistics are row-wise and do not care; the attention kernels and the
@@ -152,8 +144,6 @@ int* keds_numerics_guard();
 // true when a dense [M,K] x [N,K]^T problem sends its full 256-row tiles to a 256^2 kernel and its M % 256 rows to a second, small
 // launch: the towers then run those remainder rows as their own chain on the side lane
 bool keds_gemm_splits_rows(int M, int N, int K);
-// 128^2 GEMM launches of the calling thread take the 64 KiB-LDS kernel form while `on`
-void keds_gemm_small_lds(int on);
 
 // ---- output-tile stores (device) -----------------------------------------------------------------------------------
 // 16-byte store of an output tile that ANOTHER kernel reads next.  Policy per site class, compile-time (same-box A/B:
@@ -198,11 +188,7 @@ void keds_gemm_small_lds(int on);
 #ifndef KEDS_LD_RESID_AUX
 #define KEDS_LD_RESID_AUX 0 /* the residual tile the fp16-residual epilogue reads, modifies and writes back */
 #endif
-#ifndef KEDS_ATTN_PREFETCH
-#define KEDS_ATTN_PREFETCH 0 /* S = 257 attention: block distance of an L2 prefetch of a later workgroup's rows (0 = off).  Measured,
-                                round 4 (profiles/r04_attn_prefetch_ab.txt): 256 / 512 / 1024 all cost the kernel 27 % (1.74 -> 2.2 ms
-                                per step): 771 four-byte requests per workgroup are dearer than the first-byte latency they hide */
-#endif
+// (An L2 prefetch of a later attention workgroup's rows, round 4, cost the kernel 27 %: profiles/r04_attn_prefetch_ab.txt; last at 14f64ac.)
 // `base` is wave-uniform (the tile's first byte), `off` the lane's 32-bit byte offset inside it: policies other than 0 go out
 // as a buffer store whose `aux` operand carries the cache-policy bits -- a builtin, so the compiler counts the store and pads
 // its data-register hazard (an inline-asm global_store_dwordx4 gets neither: cdna_hip_programming.md section 5.7).

@@ -73,8 +73,6 @@ __device__ __forceinline__ void wait_stage_and_barrier(int ahead) {
 }
 
 // ------------------------------------------------------------------------------------------
-// DBG (timing-only ablations; results wrong unless 0): 1 = no list update, 2 = no MFMA (and no list update),
-// 3 = no LDS fragment reads
 // L = per-lane list depth: LISTK (16) for the candidate pass, 4 for the threshold pass
 // order-preserving integer image of a score: a > b  <=>  ord_key(a) > ord_key(b); 0 is below every real score's key
 __device__ __forceinline__ unsigned ord_key(float f) {
@@ -100,7 +98,7 @@ __device__ __forceinline__ float key_float(unsigned k) { return __uint_as_float(
 // out_meta[query * nwg + wg] = {entries written, largest key sitting in the LAST slot of a full list (0: none)}.
 // With insert thresholds almost every list slot stays empty: the merge then reads a handful of pairs per segment instead
 // of all 4L slots of it.
-template <int D, int L = LISTK, int DBG = 0, int NT = 0>
+template <int D, int L = LISTK, int NT = 0>
 __global__ __launch_bounds__(SCAN_THREADS, 2) void scan_topk_kernel(
     const char* __restrict__ packed, int stage_begin, int total_stages, const bf16_t* __restrict__ qb,
     const float* __restrict__ thr, unsigned long long* __restrict__ out_pairs, uint2* __restrict__ out_meta) {
@@ -189,17 +187,10 @@ __global__ __launch_bounds__(SCAN_THREADS, 2) void scan_topk_kernel(
 #pragma unroll
         for (int s = 0; s < C::KSTEPS; ++s) {
             const int ch = swz_chunk(4 * s + g, c);
-            bf16x8 a0 = qf[s], a1 = qf[s];
-            if constexpr (DBG != 3) {
-                a0 = *reinterpret_cast<const bf16x8*>(sb + row_off + ch * 16);
-                a1 = *reinterpret_cast<const bf16x8*>(sb + row_off + 16 * C::ROWB + ch * 16);
-            }
-            if constexpr (DBG != 2) {
-                acc0 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a0, qf[s], acc0, 0, 0, 0);
-                acc1 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a1, qf[s], acc1, 0, 0, 0);
-            } else {
-                asm volatile("" ::"v"(a0), "v"(a1));
-            }
+            const bf16x8 a0 = *reinterpret_cast<const bf16x8*>(sb + row_off + ch * 16);
+            const bf16x8 a1 = *reinterpret_cast<const bf16x8*>(sb + row_off + 16 * C::ROWB + ch * 16);
+            acc0 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a0, qf[s], acc0, 0, 0, 0);
+            acc1 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a1, qf[s], acc1, 0, 0, 0);
         }
         // D layout: lane (g,c) holds query c, keys 4g..4g+3 of each 16-key tile
         const int kbase = t * STAGE_KEYS + g * 4;
@@ -208,8 +199,7 @@ __global__ __launch_bounds__(SCAN_THREADS, 2) void scan_topk_kernel(
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
                 const float sc = tt == 0 ? acc0[r] : acc1[r];
-                if constexpr (DBG == 1 || DBG == 2) asm volatile("" ::"v"(sc));
-                if ((DBG == 0 || DBG == 3) && sc > lmin) {
+                if (sc > lmin) {
                     // branch-free sorted insert with no serial chain: every slot looks only at the OLD list.
                     // new v[j] = med3(v[j-1], v[j], x); id follows the same three cases (x > v[j] strict, so an
                     // equal score stays behind the earlier key).
@@ -425,58 +415,27 @@ __device__ __forceinline__ unsigned wave_reduce_u32(unsigned x, Op op) {       /
     return op(b[0], b[1]);
 }
 
-__device__ unsigned long long* g_merge_stamp = nullptr;     // diagnostic (keds_merge_stamp_buffer): 8 stamps per block
-#define KEDS_MSTAMP(i)                                                                   \
-    if (mst && threadIdx.x == 0) mst[(size_t)blockIdx.x * 8 + (i)] = __builtin_amdgcn_s_memtime();
-
 constexpr int MERGE_THREADS = 256;
 constexpr int MERGE_WAVES = MERGE_THREADS / 64;
 constexpr int MERGE_SLOTS = 4 * LISTK;    // pairs per segment at most (64)
 constexpr int MERGE_LDS_PAIRS = 4096;
 constexpr int MERGE_SPEC = 16;            // segment slots loaded before the segment's count is known
 
-// FUSED (round 4: the final merge of a search): the block that has merged a query's lists also re-ranks its `ncand` candidates
-// with the exact fp32 distance (its four waves take the candidates in turn, four rows in flight each) and runs the selection
-// + certificate on them -- what rerank_kernel and certify_select_kernel did as two more launches (6.4 + 10 us, each a grid
-// of short dependent round trips, + two kernel boundaries): one launch less to wait for, and the candidate ids / scores never
-// leave the CU.  Same arithmetic in the same order as the two kernels.  Measured neutral (see search_tail_fused): an A/B form.
-struct TailArgs {
-    const float* db;
-    const float* qn;
-    const f32x4* qstat;
-    const DbBounds* bounds;
-    float* D;
-    long long* I;
-    int* counters;
-    int* fail_ids;
-    int* fslot;
-    float* dk;
-    int* status;
-    long long id_base;
-    int dim, metric, k, force_fail;
-};
-
-template <bool FUSED>
+// (A fused form -- the merging block also re-ranks and certifies its candidates, round 4, measured neutral -- last existed at
+// 14f64ac: docs/findings_r06.md.)
 __global__ __launch_bounds__(MERGE_THREADS) void merge_pairs_kernel(const unsigned long long* __restrict__ pairs,
                                                                     const uint2* __restrict__ meta, int nwg, int slots,
                                                                     int* __restrict__ cand_idx, float* __restrict__ cand_val,
                                                                     float* __restrict__ thr_out, int ncand,
                                                                     const float* __restrict__ thr_in,
-                                                                    float* __restrict__ sbound_out, TailArgs ta) {
+                                                                    float* __restrict__ sbound_out) {
     __shared__ unsigned long long lp[MERGE_LDS_PAIRS];
-    [[maybe_unused]] __shared__ int s_cid[FUSED ? NCAND_WIDE : 1];
-    [[maybe_unused]] __shared__ float s_cd[FUSED ? NCAND_WIDE : 1];
-    [[maybe_unused]] __shared__ float s_sb;
-    [[maybe_unused]] __shared__ int s_nvalid;
-    [[maybe_unused]] __shared__ float s_dk;
     __shared__ unsigned s_red[4][MERGE_WAVES];
     __shared__ unsigned s_T, s_rem, s_out, s_eq;
     __shared__ __attribute__((aligned(16))) unsigned hist[256];
     __shared__ int eq_idx[256];
     __shared__ float eq_val[256];
     const int q = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-    unsigned long long* mst = g_merge_stamp;
-    KEDS_MSTAMP(0)
     auto umax = [](unsigned a, unsigned b) { return a > b ? a : b; };
     auto umin = [](unsigned a, unsigned b) { return a < b ? a : b; };
     auto uadd = [](unsigned a, unsigned b) { return a + b; };
@@ -528,9 +487,7 @@ __global__ __launch_bounds__(MERGE_THREADS) void merge_pairs_kernel(const unsign
         s_red[2][wv] = kmin;
         s_red[3][wv] = lastkey;
     }
-    KEDS_MSTAMP(1)
     __syncthreads();
-    KEDS_MSTAMP(2)
     unsigned V = 0, wbase = 0;
 #pragma unroll
     for (int w = 0; w < MERGE_WAVES; ++w) {
@@ -552,11 +509,8 @@ __global__ __launch_bounds__(MERGE_THREADS) void merge_pairs_kernel(const unsign
         const int id = (int)(unsigned)(p2 & 0xFFFFFFFFu);
         if (V <= (unsigned)ncand || k > Tc) {
             const unsigned o = atomicAdd(&s_out, 1u);
-            if constexpr (FUSED) s_cid[o] = id;
-            else {
-                cand_idx[q * ncand + o] = id;
-                cand_val[q * ncand + o] = key_float(k);
-            }
+            cand_idx[q * ncand + o] = id;
+            cand_val[q * ncand + o] = key_float(k);
         } else if (k == Tc) {
             const unsigned o = atomicAdd(&s_eq, 1u);
             if (o < 256) {
@@ -571,7 +525,6 @@ __global__ __launch_bounds__(MERGE_THREADS) void merge_pairs_kernel(const unsign
         for (int j = 0; j < MERGE_SLOTS; ++j)
             if ((unsigned)j < cnt) lp[off + j] = pr[j];
         __syncthreads();
-        KEDS_MSTAMP(3)
         if (V > (unsigned)ncand) {
             // T = the want-th largest key by MSB-first radix selection, 8 bits per pass over the bits in which keys differ
             // (scores of one query share their high bits: usually three passes): LDS histogram of the digit among the keys
@@ -618,9 +571,7 @@ __global__ __launch_bounds__(MERGE_THREADS) void merge_pairs_kernel(const unsign
             T = pfx;                                                   // all 32 bits decided: the want-th largest key
             rem = rem_l;                                               // of the keys == T, this many are taken
         }
-        KEDS_MSTAMP(4)
         for (unsigned p2 = tid; p2 < V; p2 += MERGE_THREADS) take(lp[p2], T);
-        KEDS_MSTAMP(5)
     } else {
         // dense lists: block-wide bisection over the registers (two barriers per bit)
         auto block_sum = [&](unsigned x) -> unsigned {
@@ -658,126 +609,21 @@ __global__ __launch_bounds__(MERGE_THREADS) void merge_pairs_kernel(const unsign
             unsigned rank = 0;
             for (unsigned j = 0; j < neq; ++j) rank += eq_idx[j] < my ? 1u : 0u;
             if (rank < rem) {
-                if constexpr (FUSED) s_cid[base + rank] = my;
-                else {
-                    cand_idx[q * ncand + base + rank] = my;
-                    cand_val[q * ncand + base + rank] = eq_val[tid];
-                }
+                cand_idx[q * ncand + base + rank] = my;
+                cand_val[q * ncand + base + rank] = eq_val[tid];
             }
         }
     }
     for (int o = (int)want + tid; o < ncand; o += MERGE_THREADS) {       // fillers when fewer than ncand valid entries
-        if constexpr (FUSED) s_cid[o] = -1;
-        else {
-            cand_idx[q * ncand + o] = -1;
-            cand_val[q * ncand + o] = -INFINITY;
-        }
+        cand_idx[q * ncand + o] = -1;
+        cand_val[q * ncand + o] = -INFINITY;
     }
-    KEDS_MSTAMP(6)
-    if (mst && tid == 0) mst[(size_t)blockIdx.x * 8 + 7] = V;
     if (tid == 0) {
         if (thr_out) thr_out[q] = V > (unsigned)ncand ? key_float(T) : -INFINITY;
-        if (sbound_out || FUSED) {
+        if (sbound_out) {
             float b2 = V > (unsigned)ncand ? key_float(T) : (thr_in ? thr_in[q] : -INFINITY);
             if (lastkey) b2 = fmaxf(b2, key_float(lastkey));
-            if (sbound_out) sbound_out[q] = b2;
-            if constexpr (FUSED) s_sb = b2;
-        }
-        if constexpr (FUSED) {
-            s_nvalid = 0;
-            s_dk = ta.metric == KEDS_METRIC_L2 ? INFINITY : -INFINITY;
-        }
-    }
-    if constexpr (FUSED) {
-        __syncthreads();
-        // ---- rerank_kernel's arithmetic: exact fp32 distance of every candidate, one wave each, four rows requested at a time
-        const int dim = ta.dim, metric = ta.metric;
-        const float* qq = ta.qn + (size_t)q * dim;
-        for (int c0 = 4 * wv; c0 < ncand; c0 += 4 * MERGE_WAVES) {
-            float acc[4];
-            int ids[4];
-#pragma unroll
-            for (int u = 0; u < 4; ++u) {
-                ids[u] = c0 + u < ncand ? s_cid[c0 + u] : -1;
-                acc[u] = 0.f;
-            }
-            for (int i = lane * 4; i < dim; i += 256) {
-                const f32x4 a = *reinterpret_cast<const f32x4*>(qq + i);
-                f32x4 b[4];
-#pragma unroll
-                for (int u = 0; u < 4; ++u)
-                    b[u] = ids[u] >= 0 ? *reinterpret_cast<const f32x4*>(ta.db + (size_t)ids[u] * dim + i) : a;
-#pragma unroll
-                for (int u = 0; u < 4; ++u) {
-                    if (metric == KEDS_METRIC_L2) {
-                        const f32x4 d = a - b[u];
-                        acc[u] += d[0] * d[0] + d[1] * d[1] + d[2] * d[2] + d[3] * d[3];
-                    } else {
-                        acc[u] += a[0] * b[u][0] + a[1] * b[u][1] + a[2] * b[u][2] + a[3] * b[u][3];
-                    }
-                }
-            }
-#pragma unroll
-            for (int u = 0; u < 4; ++u) {
-                const float sum = wave_sum(acc[u]);
-                if (lane == 0 && c0 + u < ncand)
-                    s_cd[c0 + u] = ids[u] >= 0 ? sum : (metric == KEDS_METRIC_L2 ? INFINITY : -INFINITY);
-            }
-        }
-        __syncthreads();
-        // ---- certify_select_kernel's body on the block's own candidates (threads 0 .. ncand-1)
-        const int k = ta.k;
-        const int t = tid;
-        const bool act = t < ncand;
-        const float d = act ? s_cd[t] : 0.f;
-        const int id = act ? s_cid[t] : -1;
-        const f32x4 qs = ta.qstat[q];
-        const float xt = ta.bounds->xt, rm = ta.bounds->r, xm = ta.bounds->x;
-        const float key = metric == KEDS_METRIC_L2 ? d : -d;           // smaller is better
-        int rank = 0;
-        if (act) {
-            for (int j = 0; j < ncand; ++j) {
-                const float dj = s_cd[j];
-                const float kj = metric == KEDS_METRIC_L2 ? dj : -dj;
-                const int ij = s_cid[j];
-                const bool before = ij >= 0 && (id < 0 || kj < key || (kj == key && ij < id));
-                rank += (before && j != t) ? 1 : 0;
-            }
-            if (id >= 0) atomicAdd(&s_nvalid, 1);
-            if (id < 0) rank = ncand + t;                              // never selected before a valid one
-            if (rank < k) {
-                ta.D[(size_t)q * k + rank] = d;
-                ta.I[(size_t)q * k + rank] = id + ta.id_base;
-            }
-            if (id >= 0 && rank == k - 1) s_dk = d;
-        }
-        __syncthreads();
-        const int nvalid = s_nvalid;
-        if (t >= nvalid && t < k) {                                    // fewer than k valid candidates: fillers like faiss
-            ta.D[(size_t)q * k + t] = metric == KEDS_METRIC_L2 ? INFINITY : -INFINITY;
-            ta.I[(size_t)q * k + t] = -1;
-        }
-        if (t == 0) {
-            const float sb = s_sb;
-            bool ok = sb == -INFINITY;                                 // nothing was ever left out of the candidate set
-            if (ta.force_fail) ok = false;
-            else if (!ok && nvalid >= k) {
-                const float tk = metric == KEDS_METRIC_L2 ? 0.5f * (qs[0] - s_dk) : s_dk;
-                const float eps = (qs[1] * xt + qs[2] * rm + qs[1] * rm + 2e-4f * qs[2] * xt + bias_err(dim, metric, xm)) * 1.01f +
-                                  1e-6f * (fabsf(tk) + qs[0] + 1.0f);
-                ok = tk - eps > sb;
-            }
-            if (ok) {
-                ta.fslot[q] = -1;
-                if (ta.status) atomicAdd(ta.status + 0, 1);
-            } else {
-                const int f = atomicAdd(ta.counters, 1);
-                ta.fail_ids[f] = q;
-                ta.fslot[q] = f;
-                ta.counters[8 + f] = 0;                                // chunks of this query the exact pass has finished
-                ta.dk[q] = nvalid >= k ? s_dk : (metric == KEDS_METRIC_L2 ? INFINITY : -INFINITY);
-                if (ta.status) atomicAdd(ta.status + 1, 1);
-            }
+            sbound_out[q] = b2;
         }
     }
 }
@@ -1189,26 +1035,10 @@ SearchWs carve(void* ws, int nq, int dim, int64_t n, int k) {
     return w;
 }
 
-int g_scan_debug = 0;   // timing-only ablations of the D=768 scan kernel
 int g_scan_phases = 0;  // test hook: 1 forces the single-phase scan (no thresholds)
 int g_force_exact = 0;  // test hook: 1 sends every query through the exact fallback
 int g_scan_nt = 1;      // non-temporal LDS-DMA for the D = 768 candidate pass (A/B hook: keds_scan_debug bit 6 turns it off)
 int g_thr_depth = 0;    // threshold-pass list depth: 0 = by launch shape, 1 / 4 forced (A/B hook: keds_scan_debug bits 7-9)
-int g_tail_fused = 0; // keds_scan_debug bit 10: merge + re-rank + certificate in ONE launch (A/B, tests; see search_tail_fused)
-// (Measured, round 4, same box, tools/search_profile.py: fused 234-242 us per search, three launches 237 -- one block per
-// query re-ranks its 64 candidates on four waves where rerank_kernel spreads 8,192 waves over the chip; the two kernel
-// boundaries it saves cost less than that.  OFF by default; KEDS_SEARCH_FUSED=1 / keds_scan_debug bit 10 select it.)
-#ifdef KEDS_EXPERIMENTS
-bool search_tail_fused() {
-    static int env = -1;
-    if (env < 0) {
-        const char* e = keds_exp_env("KEDS_SEARCH_FUSED");
-        env = e && e[0] == '1';
-    }
-    return env || g_tail_fused;
-}
-#endif
-
 template <int D, int L>
 int launch_scan(const void* packed, int stage_begin, int total_stages, const bf16_t* qb, const float* thr,
                 unsigned long long* lval, uint2* lidx, int nwg, int nqb, hipStream_t st) {
@@ -1220,29 +1050,11 @@ int launch_scan(const void* packed, int stage_begin, int total_stages, const bf1
                  "keds_index_search: %d stages over %d workgroups: a workgroup's key stream would span 2 GiB or more "
                  "(search the index in row ranges)", total_stages, nwg);
     if (int rc = keds_func_lds_once((const void*)scan_topk_kernel<D, L>, (int)lds, "scan_topk_kernel")) return rc;
-    KedsProfScope prof(KEDS_PROF_SCAN, st, /*lazy*/ !g_scan_debug);
-    if constexpr (D == 768 && L == LISTK) {
-        if (g_scan_debug) {
-#define KEDS_SCAN_DBG(V)                                                                                            \
-    {                                                                                                              \
-        (void)hipFuncSetAttribute((const void*)scan_topk_kernel<D, L, V>, hipFuncAttributeMaxDynamicSharedMemorySize, \
-                                  (int)lds);                                                                       \
-        scan_topk_kernel<D, L, V><<<dim3(nwg, nqb), SCAN_THREADS, lds, st>>>((const char*)packed, stage_begin, total_stages, qb, thr, \
-                                                               lval, lidx);                                        \
-    }
-            switch (g_scan_debug) {
-                case 1: KEDS_SCAN_DBG(1) break;
-                case 2: KEDS_SCAN_DBG(2) break;
-                default: KEDS_SCAN_DBG(3) break;
-            }
-#undef KEDS_SCAN_DBG
-            return keds_check_launch("scan_topk_kernel<dbg>");
-        }
-    }
+    KedsProfScope prof(KEDS_PROF_SCAN, st, /*lazy*/ true);
     if constexpr (D == 768 && L == LISTK) {
         if (g_scan_nt) {
-            if (int rc = keds_func_lds_once((const void*)scan_topk_kernel<D, L, 0, 1>, (int)lds, "scan_topk_kernel<nt>")) return rc;
-            KEDS_LAUNCH((scan_topk_kernel<D, L, 0, 1>), dim3(nwg, nqb), SCAN_THREADS, lds, st, (const char*)packed, stage_begin, total_stages, qb,
+            if (int rc = keds_func_lds_once((const void*)scan_topk_kernel<D, L, 1>, (int)lds, "scan_topk_kernel<nt>")) return rc;
+            KEDS_LAUNCH((scan_topk_kernel<D, L, 1>), dim3(nwg, nqb), SCAN_THREADS, lds, st, (const char*)packed, stage_begin, total_stages, qb,
                         thr, lval, lidx);
             return keds_check_launch("scan_topk_kernel<nt>");
         }
@@ -1327,15 +1139,6 @@ struct SearchPlan {
     bool span_ok;
 };
 
-int scan_sample_div() {                     // KEDS_SCAN_SAMPLE_DIV=<d> forces a 1/d sample (A/B; experiments build only)
-    static int sample_div = -1;
-    if (sample_div < 0) {
-        const char* e = keds_exp_env("KEDS_SCAN_SAMPLE_DIV");
-        sample_div = e && atoi(e) >= 2 ? atoi(e) : 0;
-    }
-    return sample_div;
-}
-
 SearchPlan search_plan(int nq_set, int dim, int64_t n, int k, int cus) {
     SearchPlan p;
     p.total_stages = (int)((n + STAGE_KEYS - 1) / STAGE_KEYS);
@@ -1352,13 +1155,11 @@ SearchPlan search_plan(int nq_set, int dim, int64_t n, int k, int cus) {
     // The sample: 1/16 of the rows, but at least 16 k rows (512 stages) where a quarter of the database allows it.  Round 4: at the
     // 8-GPU shard shape (1,024 queries x 62.5 k rows) a 1/16 sample is 3.9 k rows, the accept rate 64 / 3.9 k = 1.6 % instead of
     // the 0.2 % of the 0.5 M-row search, and with eight query blocks per launch set nothing hides the inserts: the candidate
-    // pass took 236 us of which 125 were list updates (keds_scan_debug ablations under rocprofv3).  Whole search at that shape with
+    // pass took 236 us of which 125 were list updates (scan ablations under rocprofv3; last at 14f64ac).  Whole search at that shape with
     // 1/16, 1/8, 1/6, 1/4, 1/3 of the rows sampled: 342, 301, 294, 292, 299 us; the 0.5 M-row search is unchanged (its 1/16 is 31 k
     // rows).
-    const int sample_div = scan_sample_div();
     p.stagesA = p.total_stages / 16;
-    if (sample_div) p.stagesA = p.total_stages / sample_div;
-    else if (p.stagesA < 512) p.stagesA = p.total_stages / 4 < 512 ? p.total_stages / 4 : 512;
+    if (p.stagesA < 512) p.stagesA = p.total_stages / 4 < 512 ? p.total_stages / 4 : 512;
     // Up to MAXQB query blocks (1024 queries) share one set of launches: grid.y = query block, and the `cus`
     // workgroups are divided between the blocks, each block's workgroups splitting the stage range.  A row-sharded
     // multi-GPU search (every rank scans its small shard for ALL ranks' queries) then costs one launch set, and the
@@ -1383,19 +1184,15 @@ SearchPlan search_plan(int nq_set, int dim, int64_t n, int k, int cus) {
 
 }  // namespace
 
-extern "C" int keds_merge_stamp_buffer(void* buf) {     // diagnostic: >= 8 uint64 per query; nullptr switches the stamps off
-    unsigned long long* p = (unsigned long long*)buf;
-    return hipMemcpyToSymbol(HIP_SYMBOL(g_merge_stamp), &p, sizeof(p)) == hipSuccess ? KEDS_OK : KEDS_E_LAUNCH;
-}
-
 extern "C" int keds_scan_debug(int variant) {
-    g_scan_debug = variant & 15;          // bits 0-3: timing-only ablation
+    // bits 0-3 (timing-only ablations of the scan) and bit 10 (the fused search tail) selected forms that last existed at 14f64ac
+    for (const int bit : {0, 1, 2, 3, 10})
+        KEDS_REQUIRE(!((variant >> bit) & 1), "keds_scan_debug: bit %d is no longer offered", bit);
     g_scan_phases = (variant >> 4) & 1;   // bit 4: force the single-phase scan (exact as well; for A/B tests)
     g_force_exact = (variant >> 5) & 1;   // bit 5: fail every certificate (tests of the exact fallback)
     g_scan_nt = (variant >> 6) & 1 ? 0 : 1;   // bit 6: default-policy key stream instead of non-temporal (A/B)
     g_thr_depth = (variant >> 7) & 7;         // bits 7-9: threshold-pass list depth 1 or 4 forced (0: by launch shape)
     if (g_thr_depth != 1 && g_thr_depth != 4) g_thr_depth = 0;
-    g_tail_fused = (variant >> 10) & 1;     // bit 10: merge + re-rank + certificate in one launch (A/B, tests)
     return KEDS_OK;
 }
 
@@ -1475,8 +1272,8 @@ extern "C" int keds_index_search_packed_ex(const void* packed, const float* db, 
             // inserts are rare for ANY data.
             if ((rc = scan_dispatch(dim, p.depthA, packed, p.stagesA, w.qb, nullptr, w.lpairs, w.lmeta, p.nwgA, p.nqb, st))) return rc;
             KedsProfScope prof(KEDS_PROF_OTHER, st);
-            merge_pairs_kernel<false><<<nb, MERGE_THREADS, 0, st>>>(w.lpairs, w.lmeta, p.nwgA, 4 * p.depthA, w.aidx, w.aval, w.thr, ncand,
-                                                                    nullptr, nullptr, TailArgs{});
+            merge_pairs_kernel<<<nb, MERGE_THREADS, 0, st>>>(w.lpairs, w.lmeta, p.nwgA, 4 * p.depthA, w.aidx, w.aval, w.thr, ncand,
+                                                             nullptr, nullptr);
             if ((rc = keds_check_launch("merge_pairs_kernel(thr)"))) return rc;
         }
         if ((rc = scan_dispatch(dim, LISTK, packed, total_stages, w.qb, two_phase ? w.thr : nullptr, w.lpairs, w.lmeta, p.nwgB, p.nqb, st)))
@@ -1486,18 +1283,9 @@ extern "C" int keds_index_search_packed_ex(const void* packed, const float* db, 
             const int nwgB = p.nwgB;
             float* Dq = D + (size_t)q0 * k;
             long long* Iq = (long long*)I + (size_t)q0 * k;
-#ifdef KEDS_EXPERIMENTS
-            if (search_tail_fused()) {       // merge + exact re-rank + selection + certificate: one launch
-                const TailArgs ta{db, qn, w.qstat, bounds, Dq, Iq, w.counters, w.fail_ids, w.fslot, w.dk, status, (long long)id_base,
-                                  dim, metric, k, g_force_exact};
-                merge_pairs_kernel<true><<<nb, MERGE_THREADS, 0, st>>>(w.lpairs, w.lmeta, nwgB, 4 * LISTK, w.cidx, w.cval, nullptr, ncand,
-                                                                       two_phase ? w.thr : nullptr, w.sbound, ta);
-                if ((rc = keds_check_launch("merge_pairs_kernel<fused>"))) return rc;
-            } else
-#endif
             {
-                merge_pairs_kernel<false><<<nb, MERGE_THREADS, 0, st>>>(w.lpairs, w.lmeta, nwgB, 4 * LISTK, w.cidx, w.cval, nullptr, ncand,
-                                                                        two_phase ? w.thr : nullptr, w.sbound, TailArgs{});
+                merge_pairs_kernel<<<nb, MERGE_THREADS, 0, st>>>(w.lpairs, w.lmeta, nwgB, 4 * LISTK, w.cidx, w.cval, nullptr, ncand,
+                                                                        two_phase ? w.thr : nullptr, w.sbound);
                 if ((rc = keds_check_launch("merge_pairs_kernel"))) return rc;
                 rerank_kernel<<<(nb * ncand + 3) / 4, 256, 0, st>>>(db, dim, metric, qn, w.cidx, w.cdist, nb * ncand, ncand);
                 if ((rc = keds_check_launch("rerank_kernel"))) return rc;
@@ -1581,8 +1369,8 @@ extern "C" int keds_search_merge(const uint64_t* pairs, const uint32_t* meta, in
     KEDS_REQUIRE(ncand == NCAND || ncand == NCAND_WIDE, "keds_search_merge: ncand must be 64 or 256 (got %d)", ncand);
     hipStream_t st = (hipStream_t)stream;
     KedsProfScope prof(KEDS_PROF_OTHER, st);
-    merge_pairs_kernel<false><<<nq, MERGE_THREADS, 0, st>>>((const unsigned long long*)pairs, (const uint2*)meta, nwg, slots, cand_idx,
-                                                            cand_val, thr_out, ncand, thr_in, sbound, TailArgs{});
+    merge_pairs_kernel<<<nq, MERGE_THREADS, 0, st>>>((const unsigned long long*)pairs, (const uint2*)meta, nwg, slots, cand_idx,
+                                                            cand_val, thr_out, ncand, thr_in, sbound);
     return keds_check_launch("merge_pairs_kernel");
 }
 

@@ -31,7 +31,7 @@ int keds_readout_impl(const float* x, int S, const int32_t* row, const float* ga
 
 namespace {
 
-size_t pad_rows(size_t m) { return keds_align_up(m, 256); }     // (256: a tower may run its ragged last row tile as a full one)
+size_t pad_rows(size_t m) { return keds_align_up(m, 256); }     // (256: whole row tiles; packed rows run up to the next one)
 
 // scratch of one tower: h [Mp,w] (the fp16 residual stream of the folded flow; the bf16 LayerNorm output of the unfolded
 // one) | qkv [Mp,3w] | attn [Mp,w] | MLP hidden [Mp,4w] (bf16) |
@@ -102,14 +102,10 @@ struct RowLanes {
     }
     int to_side() { return split ? keds_stream_order(main, fork, side) : KEDS_OK; }
     // the fork behind an attention launch: the launch records the event itself (its stop event: no marker packet between it and
-    // the next GEMM on the main stream); kernel forms that do not take it get the recorded event.  KEDS_FORK_EXT=0: always recorded (A/B)
+    // the next GEMM on the main stream); kernel forms that do not take it get the recorded event.
     template <typename F>
     int attention_then_side(F launch) {
-        static const bool ext = [] {
-            const char* e = keds_exp_env("KEDS_FORK_EXT");
-            return !(e && e[0] == '0');
-        }();
-        if (!split || !ext) {
+        if (!split) {
             const int rc = launch();
             return rc ? rc : to_side();
         }
@@ -219,47 +215,13 @@ int rows_tail(const keds_tower_params* p, const keds_block_params& k, const Towe
     return KEDS_OK;
 }
 
-// KEDS_TAIL_ATTN=1 in the environment: the tail samples' attention on the side lane (round-4 experiment, OFF by default:
-// bit-identical and neutral -- 6,759-6,770 vs 6,770-6,776 img/s in four same-box pairs, profiles/r04_tail_attention_ab.txt)
-#ifdef KEDS_EXPERIMENTS
-bool tail_attention_on_side() {
-    static int v = -1;
-    if (v < 0) {
-        const char* e = keds_exp_env("KEDS_TAIL_ATTN");
-        v = e && e[0] == '1';
-    }
-    return v != 0;
-}
-#else
-constexpr bool tail_attention_on_side() { return false; }
-#endif
-
 bool bf16_rows_split(int M, int w) {
     return keds_gemm_splits_rows(M, 3 * w, w) && keds_gemm_splits_rows(M, w, w) && keds_gemm_splits_rows(M, 4 * w, w) &&
            keds_gemm_splits_rows(M, w, 4 * w);
 }
 
-// Round 3 experiment, OFF by default: the ragged last row tile as a FULL tile.  At B = 128 a ViT-L/14 tower has 32,896 rows =
-// 128 x 256 + 128; the 128 remainder rows run as their own chain of four small GEMMs per block on the side lane (0.39 ms per
-// step).  Rows only meet in the attention, so the GEMMs can just as well run on 129 full tiles: 128 filler rows behind the
-// last token (a copy of the first rows; never read by the attention -- their attention output stays zero -- or by the
-// read-out), 0.39 % more GEMM work, one lane.  Correct (test_ragged_row_tile_on_filler_rows_matches_the_two_lane_tower) and
-// 4 ms per step SLOWER (23.9 vs 19.85 ms, same-box A/B): 129 row tiles x 4..16 column tiles is no longer a whole number of
-// 256-workgroup rounds, and every one of the 94 GEMM launches of a step pays a nearly empty extra round (12..16 tiles on 256
-// CUs) that the side lane's small launches used to fill.  KEDS_TOWER_FILL=1 / keds_tower_fill_enable(1) turn it on.
-#ifdef KEDS_EXPERIMENTS
-int g_tower_fill = -1;                          // -1: take KEDS_TOWER_FILL (default off)
-int tower_fill_rows(int M, int w) {
-    if (g_tower_fill < 0) {
-        const char* e = keds_exp_env("KEDS_TOWER_FILL");
-        g_tower_fill = e && e[0] == '1';
-    }
-    const int fill = (256 - M % 256) % 256;
-    return g_tower_fill && fill && bf16_rows_split(M, w) && (long)fill * 64 <= M ? fill : 0;
-}
-#else
-constexpr int tower_fill_rows(int, int) { return 0; }      // (the product library: remainder rows always take the side lane)
-#endif
+// (The ragged last row tile as a full tile on filler rows -- round 3, 4 ms per step slower: docs/findings_r03.md -- and the tail
+// samples' attention on the side lane -- round 4, neutral: profiles/r04_tail_attention_ab.txt -- last existed at 14f64ac.)
 
 // BASELINE config 5: the four GEMMs of every block on MXFP8 operands (gemm_fp8.hip).  The residual stream stays fp32;
 // its MXFP8 copy (xq, xs), the attention output (aq) and the MLP hidden (hq) are e4m3 + one e8m0 scale per 32 columns,
@@ -308,13 +270,11 @@ int tower_forward_fp8(const keds_tower_params* p, float* x, int B, const TowerWs
     return keds_cast_rows_f16_f32_impl(t.h, x, M, w, w, st);       // the caller reads x in fp32
 }
 
-// allow_fill: the caller's x holds pad_rows(B * seq) rows (keds_vit_run / keds_text_run carve it so); the public
-// keds_tower_forward promises only a multiple of 128 and keeps the two-lane scheme
 // last_rows (device int32 [B], nullable): the one row of every sample that is read after the last block (rows_tail): on
 // return x[b] (row b of the first B rows) holds that row of sample b; without it x holds every row as before
 // pk (nullable): packed rows -- M = pk->rows <= B * seq, the workspace is carved for B * seq
 // tp (nullable): per-block taps (KedsTaps, keds_vit_run_tokens); the caller clears last_cls_only for such a pass
-int tower_forward(const keds_tower_params* p, float* x, int B, void* ws, hipStream_t st, bool allow_fill,
+int tower_forward(const keds_tower_params* p, float* x, int B, void* ws, hipStream_t st,
                   const int32_t* last_rows = nullptr, const PackedRows* pk = nullptr, const KedsTaps* tp = nullptr) {
     const int w = p->width, S = p->seq;
     const int M = pk ? pk->rows : B * S;
@@ -359,40 +319,12 @@ int tower_forward(const keds_tower_params* p, float* x, int B, void* ws, hipStre
     if (folded) {
         // When every GEMM of the block would split into full 256-row tiles + a remainder launch anyway, the remainder
         // rows become their own chain on the side lane; otherwise one span covers all rows.
-        const int fill = allow_fill ? tower_fill_rows(M, w) : 0;
-        const bool two = !fill && bf16_rows_split(M, w);
         RowLanes lanes;
-        if ((rc = lanes.init(st, two))) return rc;
-        const RowSpan body{0, lanes.split ? Mm : M + fill, st};
+        if ((rc = lanes.init(st, bf16_rows_split(M, w)))) return rc;
+        const RowSpan body{0, lanes.split ? Mm : M, st};
         const RowSpan rem{(size_t)Mm, lanes.split ? M - Mm : 0, lanes.side};
-        if (fill) {       // filler rows: a copy of the first rows of the stream; their attention output is zero in every block
-            if (hipMemcpyAsync(x + (size_t)M * w, x, (size_t)fill * w * sizeof(float), hipMemcpyDeviceToDevice, st) != hipSuccess ||
-                hipMemsetAsync(t.att + (size_t)M * w, 0, (size_t)fill * w * sizeof(bf16_t), st) != hipSuccess) {
-                keds_set_error("keds_tower_forward: filler rows: %s", hipGetErrorString(hipGetLastError()));
-                return KEDS_E_LAUNCH;
-            }
-        }
-        if ((rc = keds_rowstats_cast_ex(x, t.h, 1, (float*)t.st1, M + fill, w, st))) return rc;
+        if ((rc = keds_rowstats_cast_ex(x, t.h, 1, (float*)t.st1, M, w, st))) return rc;
         if ((rc = lanes.to_side())) return rc;
-        // Round-4 experiment (KEDS_TAIL_ATTN=1; off): the samples whose rows reach into the remainder ("tail" samples: b >= Mm / S;
-        // one of 128 at ViT-L/14) get their attention ON THE SIDE LANE.  A kernel trace shows the main lane waiting 9 us per block
-        // on average at its join in front of the attention launch (profiles/r04_trace_gaps.txt): the side chain's last launch
-        // (the remainder rows' in_proj) cannot get a CU while the main lane's PERSISTENT in_proj holds all of them, so it runs
-        // behind it.  Here the main lane's attention covers the samples that live in full tiles only and needs no join; the side
-        // lane waits for the main in_proj, runs the tail samples' attention beside the main attention launch, and the main lane
-        // waits for THAT in front of out-proj.  Bit-identical -- and neutral: the side launches (128 KiB of LDS each) do not fit
-        // beside an attention workgroup either, so the wait only moves.
-        const int b_tail = lanes.split && !pk && tail_attention_on_side() ? Mm / S : B;      // first tail sample (B: none)
-        const bool tail_side = b_tail > 0 && b_tail < B;
-        // Round 5: with the tail samples' attention on the side lane the WHOLE remainder chain of a block (out-proj, c_fc, c_proj,
-        // the next in_proj of the remainder rows) starts beside the main ATTENTION launch instead of beside the main GEMMs, whose
-        // one-wave-per-SIMD workgroups own every register of their CU -- provided its workgroups fit next to a resident attention
-        // workgroup (74 KiB of LDS, half the CU's registers): the 64 KiB kernel form (keds_gemm_small_lds) instead of the 128 KiB one.
-        struct SmallLds {
-            bool on;
-            explicit SmallLds(bool o) : on(o) { if (on) keds_gemm_small_lds(1); }
-            ~SmallLds() { if (on) keds_gemm_small_lds(0); }
-        } small_lds(tail_side);
         for (int l = 0; l < p->layers; ++l) {
             const keds_block_params& k = p->blocks[l];
             const bool last = l == p->layers - 1;
@@ -402,17 +334,8 @@ int tower_forward(const keds_tower_params* p, float* x, int B, void* ws, hipStre
                 if ((rc = lanes.to_main())) return rc;
                 return last_rows ? rows_tail(p, k, t, x, t.h, B, last_rows, st, pk) : cls_rows_tail(p, k, t, x, t.h, B, st);
             }
-            if (tail_side) {
-                if ((rc = lanes.to_side())) return rc;               // side: behind the main in_proj
-                if ((rc = attention16(h, t.qkv, t.att, b_tail, S, p->heads, p->causal, S, st))) return rc;
-                if ((rc = attention16(h, t.qkv + (size_t)b_tail * S * 3 * w, t.att + (size_t)b_tail * S * w, B - b_tail, S, p->heads,
-                                      p->causal, S, lanes.side)))
-                    return rc;
-                if ((rc = lanes.to_main())) return rc;               // main: behind the tail samples' attention
-            } else {
-                if ((rc = lanes.to_main())) return rc;
-                if ((rc = lanes.attention_then_side([&] { return attention(st); }))) return rc;
-            }
+            if ((rc = lanes.to_main())) return rc;
+            if ((rc = lanes.attention_then_side([&] { return attention(st); }))) return rc;
             if ((rc = out_rows(t, k, w, body, h))) return rc;
             if (rem.n && (rc = out_rows(t, k, w, rem, h))) return rc;
             if ((rc = fc_rows(t, k, w, body, h))) return rc;
@@ -469,21 +392,9 @@ extern "C" size_t keds_tower_workspace_bytes(int width, int seq, int B) {
     return carve_tower(nullptr, width, seq, B).bytes;
 }
 
-extern "C" int keds_tower_fill_enable(int on) {       // run-time override of KEDS_TOWER_FILL (A/B, tests): experiment build only
-#ifdef KEDS_EXPERIMENTS
-    g_tower_fill = on ? 1 : 0;
-    return KEDS_OK;
-#else
-    if (!on) return KEDS_OK;
-    keds_set_error("keds_tower_fill_enable: the filler-row tower is an experiment (round 3, slower): build with make EXTRA=-DKEDS_EXPERIMENTS");
-    return KEDS_E_ARG;
-#endif
-}
-
 extern "C" int keds_tower_side_rows(int width, int seq, int B, int fp8) {
     if (width <= 0 || seq <= 0 || B <= 0) return 0;
     const int M = B * seq, Mt = M % 256;
-    if (!fp8 && tower_fill_rows(M, width)) return 0;       // the ragged tile runs as a full one on the caller's stream
     const bool split = fp8 ? (M >= 256 && Mt > 0) : bf16_rows_split(M, width);
     return split && keds_side_lane_enabled() ? Mt : 0;    // only a query: no stream is created here (no GPU needed)
 }
@@ -498,7 +409,7 @@ extern "C" int keds_tower_forward(const keds_tower_params* p, float* x, int B, v
         return KEDS_E_WORKSPACE;
     }
     if (p->f32) return keds_tower_forward_f32(p, x, B, workspace, (hipStream_t)stream);
-    return tower_forward(p, x, B, workspace, (hipStream_t)stream, false);
+    return tower_forward(p, x, B, workspace, (hipStream_t)stream);
 }
 
 extern "C" size_t keds_tower_workspace_bytes_ex(const keds_tower_params* p, int B) {
@@ -585,7 +496,7 @@ int vit_run(const keds_vit_params* p, const float* image, int B, float* out, int
     if ((rc = keds_cls_rows_impl(v.x, p->class_emb, p->pos_emb, B, S, w, st))) return rc;
     // ln_pre in place (each wave holds its whole row in registers before it stores)
     if ((rc = keds_layernorm_impl(v.x, w, nullptr, 1, p->ln_pre_g, p->ln_pre_b, v.x, 1, B * S, w, st))) return rc;
-    if ((rc = tower_forward(tw, v.x, B, v.tower, st, true, nullptr, nullptr, tp))) return rc;
+    if ((rc = tower_forward(tw, v.x, B, v.tower, st, nullptr, nullptr, tp))) return rc;
     if (!out) return KEDS_OK;
     return keds_readout_impl(v.x, S, nullptr, p->ln_post_g, p->ln_post_b, p->proj_t, out, B, w, p->embed_dim, normalize, v.ro,
                              keds_readout_workspace_bytes(B, w), stream, h);
@@ -699,7 +610,7 @@ extern "C" int keds_text_run_ex(const keds_text_params* p, const int32_t* tokens
         return keds_readout_f32(v.x, last_rows ? 1 : Lx, last_rows ? nullptr : readout_row, p->ln_final_g, p->ln_final_b,
                                 (const float*)p->proj_t, out, B, w, p->embed_dim, normalize, v.ro, (hipStream_t)stream);
     }
-    if ((rc = tower_forward(&tp, v.x, B, v.tower, (hipStream_t)stream, true, last_rows))) return rc;
+    if ((rc = tower_forward(&tp, v.x, B, v.tower, (hipStream_t)stream, last_rows))) return rc;
     return keds_readout_impl(v.x, last_rows ? 1 : Lx, last_rows ? nullptr : readout_row, p->ln_final_g, p->ln_final_b, p->proj_t, out,
                              B, w, p->embed_dim, normalize, v.ro, keds_readout_workspace_bytes(B, w), stream, tp.f16);
 }
@@ -752,7 +663,7 @@ extern "C" int keds_text_run_packed(const keds_text_params* p, const int32_t* to
         return keds_readout_f32(v.x, 1, nullptr, p->ln_final_g, p->ln_final_b, (const float*)p->proj_t, out, B, w, p->embed_dim, normalize,
                                 v.ro, (hipStream_t)stream);
     }
-    if ((rc = tower_forward(&tp, v.x, B, v.tower, (hipStream_t)stream, false, readout_global, &pk))) return rc;
+    if ((rc = tower_forward(&tp, v.x, B, v.tower, (hipStream_t)stream, readout_global, &pk))) return rc;
     return keds_readout_impl(v.x, 1, nullptr, p->ln_final_g, p->ln_final_b, p->proj_t, out, B, w, p->embed_dim, normalize, v.ro,
                              keds_readout_workspace_bytes(B, w), stream, tp.f16);
 }
@@ -780,7 +691,7 @@ extern "C" int keds_text_run_tokens(const keds_text_params* p, const int32_t* to
     tp.last_cls_only = 0;
     if ((rc = keds_embed_tokens_impl(tokens, p->token_emb, p->pos_emb, nullptr, 0, 0, v.x, B, L, L, w, stream))) return rc;
     if (tp.f32) rc = keds_tower_forward_f32(&tp, v.x, B, v.tower, st);
-    else rc = tower_forward(&tp, v.x, B, v.tower, st, true);
+    else rc = tower_forward(&tp, v.x, B, v.tower, st);
     if (rc) return rc;
     return keds_layernorm_impl(v.x, w, nullptr, 1, p->ln_final_g, p->ln_final_b, out, out_type, B * L, w, st);
 }

@@ -552,7 +552,7 @@ def test_gemm_quad_kernel_bit_identical_to_the_eight_wave_kernel(M, K):
     must as well -- including the LayerNorm epilogue's deferred stores (K >= 512: 18 of a lane's 32 stores of a tile are issued
     from inside the next tile's K-loop; K = 256 is too short for the trickle and stores everything in the epilogue).
     What the dispatcher picks by shape (`default`) must give the same bits too, with the other statistics buffer cleared for
-    exactly the rows of the launch.  (The two-accumulator-set kernel of round 5 is not in the product library: tools/experiments/.)"""
+    exactly the rows of the launch.  (The two-accumulator-set kernel of round 5 last existed at 14f64ac.)"""
     lib = _lib.load()
     N = 4096                                                     # >= 256 tiles of 256 x 256: the big-tile path
     g = torch.Generator(device="cuda").manual_seed(K)

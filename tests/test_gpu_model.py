@@ -195,7 +195,6 @@ def test_side_lane_for_remainder_rows_changes_no_bit(precision):
     del sd
     img = torch.from_numpy(O.synth_tensor("imgs", [128, 3, 224, 224], 1.0).numpy()).cuda()
     try:
-        lib.keds_tower_fill_enable(0)      # (the filler-row experiment of round 3, off by default: next test)
         lib.keds_side_lane_enable(1)
         assert lib.keds_tower_side_rows(1024, 257, 128, int(precision == "fp8")) == 128
         on = [m.encode_image(img).clone() for _ in range(3)]
@@ -209,37 +208,6 @@ def test_side_lane_for_remainder_rows_changes_no_bit(precision):
         assert torch.equal(o, off)
 
 
-def test_ragged_row_tile_on_filler_rows_matches_the_two_lane_tower():
-    """Round 3 experiment (KEDS_TOWER_FILL=1; off by default because every GEMM launch then pays a nearly empty extra round of
-    workgroups): at B = 128 the 128 remainder rows of a bf16 ViT-L/14 tower run as a 129th FULL row tile on 128 filler rows
-    (copies of the first rows; never read by the attention or the read-out) instead of as a chain of small GEMMs on the side
-    lane.  Rows are independent outside the attention, so every real row must come out as before -- the same MFMA chains in
-    another kernel: equal bits are expected and reported, closeness is asserted -- and run after run the same."""
-    from keds_amd import _lib
-    lib = _lib.load()
-    if "KEDS_EXPERIMENTS" not in _lib.build_flags():
-        assert lib.keds_tower_fill_enable(1) != 0            # the product library says so instead of silently ignoring the request
-        pytest.skip("the filler-row tower lost its A/B and is not in the product library (experiment build only)")
-    sd = O.synth_clip_state_dict(**VITL, seed=7)
-    m = keds_amd.build_model(sd, fp16=False).cuda()
-    del sd
-    base = torch.from_numpy(O.synth_tensor("imgs", [200, 3, 224, 224], 1.0).numpy()).cuda()
-    try:
-        for B in (128, 129, 200, 64):
-            lib.keds_tower_fill_enable(1)
-            filled = lib.keds_tower_side_rows(1024, 257, B, 0) == 0 and (B * 257) % 256 != 0
-            a = m.encode_image(base[:B]).clone()
-            a2 = m.encode_image(base[:B]).clone()
-            lib.keds_tower_fill_enable(0)
-            b = m.encode_image(base[:B]).clone()
-            assert torch.equal(a, a2) and torch.isfinite(a).all()
-            cos = float(torch.nn.functional.cosine_similarity(a, b).min().item())
-            report("tower_fill_vs_two_lanes", B=B, filler_rows_used=bool(filled), bit_equal=bool(torch.equal(a, b)), min_cosine=cos)
-            assert cos >= 0.99999, (B, cos)
-    finally:
-        lib.keds_tower_fill_enable(0)
-
-
 def test_batch_size_sweep_lane_split_and_dispatch_boundaries():
     """ViT-L/14 at batch sizes that land on every dispatch rule of the tower (128^2 / 256^2 tiles, rows split over the two
     lanes or not, fp8 main rows + fp16 remainder rows): lane on == lane off bit for bit, finite, and image 0's embedding
@@ -251,7 +219,6 @@ def test_batch_size_sweep_lane_split_and_dispatch_boundaries():
     del sd
     base = torch.from_numpy(O.synth_tensor("imgs", [200, 3, 224, 224], 1.0).numpy()).cuda()
     try:
-        lib.keds_tower_fill_enable(0)       # the two-lane dispatch rules are what this sweep is about
         for precision, cos_min in (("bf16", 0.9999), ("fp8", 0.995)):
             m.set_precision(precision)
             first, splits = None, set()

@@ -14,8 +14,9 @@ from tests.conftest import ROOT
 
 NONE, SMALL, PAIR, QUAD, QUAD3 = range(5)     # KEDS_GEMM_FORM_*
 DEFER, PROLOGUE = 1, 2                        # KEDS_GEMM_FLAG_*
-F_SMALL, F_SKIPTAIL, F_NOSPLIT, F_PROLOGUE, F_QUAD, F_PERSIST, F_PAIR, F_NOQUAD3, F_NODEFER = (
-    1, 1 << 8, 1 << 9, 1 << 10, 1 << 11, 2 << 11, 3 << 11, 1 << 16, 1 << 17)
+F_SMALL, F_NOSPLIT, F_PROLOGUE, F_QUAD, F_PERSIST, F_PAIR, F_NOQUAD3, F_NODEFER = (
+    1, 1 << 9, 1 << 10, 1 << 11, 2 << 11, 3 << 11, 1 << 16, 1 << 17)
+F_REFUSED = (1 << 8, 1 << 13, 1 << 14, 1 << 15)           # timing-only forms the library no longer has: keds_gemm_force_small refuses them
 PUBLIC = tuple(range(13)) + tuple(range(16, 23))          # the epilogue ids of keds_gemm_bt_ex2
 X3 = (13, 14, 15)                                         # ... and of keds_gemm_x3
 BIG = tuple(c for c in PUBLIC if c != 12)                 # BIAS_BF16_HEADF32 never takes 256^2 tiles
@@ -56,7 +57,7 @@ def model(epi, M, N, K, lda, ldc, cus, ws, small_lds, force):
     form = np.where(persistent | ((quad != 0) & ~ring3), QUAD, np.where(ring3, QUAD3, PAIR))
     flags = np.where(persistent & ln & ~ln_qgelu & (not bit(17)) & (K // 64 >= 8), DEFER,
                      np.where((form == PAIR) & resid16 & bit(10), PROLOGUE, 0))
-    tail = big & (M % 256 != 0) & (not bit(8))
+    tail = big & (M % 256 != 0)
     ring_all, splits_all = small(M)
     ring_tail, splits_tail = small(M % 256)
     z = np.zeros_like(K)
@@ -104,13 +105,13 @@ SWEEP_M = (1, 7, 127, 128, 129, 255, 256, 257, 1024, 1025, 2048, 2170, 3584, 358
            4096, 11008, 19712, 32768, 32896)
 SWEEP_N = (128, 256, 384, 768, 1024, 2048, 3072, 4096)
 SWEEP_K = (64, 128, 192, 448, 512, 576, 1024, 1088, 2048, 2176, 2304, 2560, 3072, 4096)
-SWEEP_FORCE = (0, F_SMALL, F_SKIPTAIL, F_NOSPLIT, F_PROLOGUE, F_NOQUAD3, F_NODEFER, F_QUAD, F_PERSIST, F_PAIR)
+SWEEP_FORCE = (0, F_SMALL, F_NOSPLIT, F_PROLOGUE, F_NOQUAD3, F_NODEFER, F_QUAD, F_PERSIST, F_PAIR)
 SWEEP_CUS = (8, 64, 256, 304)
 SWEEP_WS = (0, MIB, 32 * MIB)
 
 
 def test_library_plans_what_the_model_plans_over_the_full_product(lib):
-    """M x N x K x epilogue x force x cus x scratch x small-LDS x {dense, padded strides}: 28.4 M plans, all eight ints equal.
+    """M x N x K x epilogue x force x cus x scratch x small-LDS x {dense, padded strides}: 25.6 M plans, all eight ints equal.
     (The PATCH epilogues want a dense output, as in keds_gemm_bt_ex2: their padded case pads lda only.)"""
     M, N, K, cus, ws, small_lds, padded = (a.ravel() for a in np.meshgrid(SWEEP_M, SWEEP_N, SWEEP_K, SWEEP_CUS, SWEEP_WS, (0, 1), (0, 1),
                                                                           indexing="ij"))
@@ -126,7 +127,26 @@ def test_library_plans_what_the_model_plans_over_the_full_product(lib):
                                    f"lda {lda[bad[0]]} ldc {ldc[bad[0]]} cus {cus[bad[0]]} ws {ws[bad[0]]} small_lds {small_lds[bad[0]]}: "
                                    f"library {got[bad[0]].tolist()}, model {want[bad[0]].tolist()}")
             n += len(got)
-    assert n == 23 * 8 * 14 * 23 * 10 * 4 * 3 * 2 * 2
+    assert n == 23 * 8 * 14 * 23 * len(SWEEP_FORCE) * 4 * 3 * 2 * 2 and len(SWEEP_FORCE) == 9
+
+
+def test_refused_force_bits_leave_the_switches_as_they_were(lib):
+    """Bit 8 and bits 13-15 selected timing-only launches that are gone: the hook says so, names the bit, and the plans stay those
+    of the bits set before -- here F_PAIR, then none."""
+    cases = [(code, M, 1024, K) for code in (6, 9, 10) for M in (2048, 32896) for K in (1024, 4096)]
+    info = (ctypes.c_int * 8)()
+    try:
+        for base in (F_PAIR, 0):
+            for bad in F_REFUSED + (F_PAIR | 1 << 8, 7 << 13):
+                assert lib.keds_gemm_force_small(base) == 0
+                assert lib.keds_gemm_force_small(bad) == -1                               # KEDS_E_ARG
+                err = _lib.last_error()
+                assert err.startswith("keds_gemm_force_small: bit ") and re.search(r"bit (8|13|14|15)\b", err), err
+                for epi, M, N, K in cases:
+                    _lib.check(lib.keds_gemm_plan_query(epi, M, N, K, K, N, 256, 32 * MIB, 0, info), "keds_gemm_plan_query")
+                    assert list(info) == [int(v) for v in model(epi, M, N, K, K, N, 256, 32 * MIB, 0, base)], (base, bad, epi, M, K)
+    finally:
+        lib.keds_gemm_force_small(0)
 
 
 def test_query_applies_the_shape_rules_of_the_gemm_entry(lib):
@@ -235,7 +255,6 @@ def test_row_remainder_launch_behind_big_tiles(lib):
             main = QUAD if code in LN and K >= 512 else QUAD3 if code in RESID16 and K >= 1024 else PAIR
             _has(got, main=main, tail=SMALL, tail_ring=4, splits=1, persistent=0)
             assert (got["tail_splits"] > 1) == (K == 2048), got
-            _has(query(lib, code, M, N, K, force=F_SKIPTAIL), main=main, tail=NONE, tail_ring=0, tail_splits=0)
         for code in PATCH:
             _has(query(lib, code, M, N, K), main=SMALL, tail=NONE, ring=2, splits=1)
 
