@@ -30,7 +30,9 @@ extern "C" {
 #define KEDS_E_LAUNCH (-2)   /* HIP launch or runtime error */
 #define KEDS_E_WORKSPACE (-3)/* workspace too small */
 
-#define KEDS_ABI_VERSION 11       /* 11: keds_merge_stamp_buffer, keds_attention_stamp_buffer and keds_tower_fill_enable left the library; the debug
+#define KEDS_ABI_VERSION 12       /* 12: keds_attention_plan_query, keds_attention_last_launch and keds_gemm_mxfp8_plan_query (every 16-bit attention and
+                                     MXFP8 GEMM launch is planned by one pure host function, as the bf16 GEMMs are);
+                                     11: keds_merge_stamp_buffer, keds_attention_stamp_buffer and keds_tower_fill_enable left the library; the debug
                                      hooks refuse the timing-only variants they no longer offer (last at 14f64ac);
                                      10: keds_block_source, keds_block_pack_bytes, keds_block_pack (one weight-packing routine for both loaders);
                                      9: the "fp16" operating point -- keds_tower_params.f16, KEDS_EPI_*_F16_H / *_F32_H epilogues, keds_attention_h /
@@ -320,6 +322,10 @@ int keds_gemm_mxfp8_ex(const void* Aq, const void* As, int m_pad, const void* Wq
 #define KEDS_FP8_FORM_PAIR 1    /* gemm_mxfp8_kernel: 8 waves, one tile per workgroup */
 #define KEDS_FP8_FORM_QUAD 2    /* gemm_mxfp8_quad_kernel: 4 waves, one tile per workgroup or persistent */
 int keds_gemm_mxfp8_last_launch(int* info);
+/* The plan of that call on a device of `cus` compute units under keds_mxfp8_debug's value (mxfp8_plan, csrc/gemm_plan.h: the
+ * function the call launches from; a launch that differs from it fails with KEDS_E_LAUNCH): info[4] as above.  Touches no device;
+ * the shape rules of keds_gemm_mxfp8_ex apply. */
+int keds_gemm_mxfp8_plan_query(int epilogue, int M, int N, int K, int cus, int* info);
 /* Weight preparation for the fp8 tower: W fp32 [N,K] (times diag(gamma) when a LayerNorm is folded in) -> MXFP8 wq / wscale,
  * bias_csum fp32 [2N] = [bias + W beta | row sums of the dequantised weight].  gamma = beta = NULL: plain quantisation. */
 int keds_fold_layernorm_mxfp8(const float* W, const float* bias, const float* gamma, const float* beta, int N, int K,
@@ -432,6 +438,25 @@ int keds_attention_packed(const void* qkv, void* out, int B, int s_max, const in
  * matrix instruction, the probabilities rounded to fp16.  The output is a convex combination of V and cannot overflow. */
 int keds_attention_h(const void* qkv, void* out, int B, int S, int heads, int causal, int q_limit, void* stream);
 int keds_attention_packed_h(const void* qkv, void* out, int B, int s_max, const int32_t* seq_off, int heads, int causal, void* stream);
+/* Which kernel form the six entries above get is decided in one host function (csrc/attention_plan.h: the rules; docs/kernels.md: the
+ * table of forms) under keds_attention_debug's switches.  info[8] (host ints, written): [0] KEDS_ATTN_FORM_*, [1] 16-key tiles held
+ * (2, 6, 18; 16 + the rank-1 last key for the two S = 257 forms), [2] leading key tiles left unmasked (0 or 16), [3] KEDS_ATTN_FLAG_*,
+ * [4] grid, [5] block, [6] LDS bytes, [7] the effective q_limit. */
+#define KEDS_ATTN_FORM_NONE 0
+#define KEDS_ATTN_FORM_GENERIC 1    /* attention_kernel<nkt, causal, nfull>: 4 waves, keys padded to whole tiles */
+#define KEDS_ATTN_FORM_TAIL1 2      /* attention_tail1_kernel<16>: 4 waves, S = 257 as 16 tiles + one key / query */
+#define KEDS_ATTN_FORM_S257 3       /* attention_s257_kernel: 8 waves, S = 257 (the ViT-L/14 tower) */
+#define KEDS_ATTN_FLAG_CAUSAL 1
+#define KEDS_ATTN_FLAG_F16 2        /* fp16 qkv / out */
+#define KEDS_ATTN_FLAG_Q8 4         /* MXFP8 output rows */
+#define KEDS_ATTN_FLAG_PACKED 8     /* per-sample row offsets */
+#define KEDS_ATTN_FLAG_STOP_EVENT 16 /* the form whose launch can record a (library-internal) caller's event as its stop event */
+/* the plan of a call (packed != 0: S = s_max, q_limit ignored; q8 != 0: MXFP8 output rows); touches no device; B, heads > 0 and
+ * 1 <= S <= 288, else KEDS_E_ARG with info untouched */
+int keds_attention_plan_query(int B, int S, int heads, int causal, int q_limit, int f16, int q8, int packed, int* info);
+/* test hook: what the calling thread's last such call launched -- written where the kernel is launched, not copied from the plan; a
+ * call whose launch differs from its plan fails with KEDS_E_LAUNCH */
+int keds_attention_last_launch(int* info);
 
 /* patch im2col for conv1 (model.py:381,394-396): image fp32 [B,3,R,R] -> bf16 [B*G, Kpad],
  * column c*P*P + ky*P + kx, zero padded to Kpad (a multiple of 64). */

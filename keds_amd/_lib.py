@@ -17,7 +17,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "csrc", "libkeds_hip.so")
 
 # ---- constants mirrored from keds_hip.h ------------------------------------------------------
-ABI_VERSION = 11
+ABI_VERSION = 12
 METRIC_L2, METRIC_IP = 0, 1
 EPI_BIAS_BF16, EPI_BIAS_QGELU_BF16, EPI_BIAS_RELU_BF16, EPI_BIAS_RESID_F32, EPI_BIAS_F32, EPI_PATCH_F32 = range(6)
 EPI_LN_BIAS_BF16, EPI_LN_QGELU_BF16, EPI_RESID_STATS_F32, EPI_RESID_STATS_F16 = 6, 7, 8, 9
@@ -199,10 +199,13 @@ SIGNATURES = {
     "keds_gemm_mxfp8": (i32, [vp, vp, i32, vp, vp, i32, vp, vp, i32, i32, i32, vp]),
     "keds_gemm_mxfp8_ex": (i32, [vp, vp, i32, vp, vp, i32, vp, vp, i32, i32, i32, i32, vp, vp, vp, vp, i32, vp]),
     "keds_gemm_mxfp8_last_launch": (i32, [vp]),
+    "keds_gemm_mxfp8_plan_query": (i32, [i32, i32, i32, i32, i32, vp]),
     "keds_fold_layernorm_mxfp8": (i32, [vp, vp, vp, vp, i32, i32, i32, vp, vp, vp, vp]),
     "keds_gemm_bt_ex": (i32, [vp, i64, vp, vp, vp, i64, i32, i32, i32, i32, vp, i32, vp]),
     "keds_layernorm": (i32, [vp, i64, vp, vp, vp, i32, i32, i32, vp]),
     "keds_attention_debug": (i32, [i32]),
+    "keds_attention_plan_query": (i32, [i32, i32, i32, i32, i32, i32, i32, i32, vp]),
+    "keds_attention_last_launch": (i32, [vp]),
     "keds_attention_ex": (i32, [vp, vp, i32, i32, i32, i32, i32, vp]),
     "keds_attention_mx": (i32, [vp, vp, i32, i32, i32, i32, i32, vp, vp, i32, vp]),
     "keds_attention": (i32, [vp, vp, i32, i32, i32, i32, vp]),

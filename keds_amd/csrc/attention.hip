@@ -11,23 +11,14 @@
 // are in-lane reductions plus two xor-shuffles, and the probabilities, packed to bf16 in
 // registers, are already the B operand of O^T = V^T . P^T (the MFMA k-slot order is permuted to
 // match: k-slot (g, j) of step u is key 32u + 16*(j>>2) + 4g + (j&3); V^T is staged in that order).
+// Which of the kernels below a call gets, with which template arguments, grid and LDS, is decided in attention_plan.h and
+// nowhere else; the host section at the end of this file launches the plan.
 #include "keds_common.h"
+#include "attention_plan.h"      // DH, AttnCfg, TAIL_LDS, s257::* (the LDS layouts) and attention_plan()
 #include <math.h>
 #include <hip/hip_ext.h>
 
 namespace {
-
-constexpr int DH = 64;
-
-template <int NKT>
-struct AttnCfg {
-    static constexpr int KEYS = NKT * 16;
-    static constexpr int K_BYTES = KEYS * DH * 2;          // [key][64] bf16, 128-byte rows, swizzled
-    static constexpr int VT_ROW = KEYS * 2 + 16;           // bytes per dh row of V^T (+16: odd chunk stride)
-    static constexpr int VT_BYTES = DH * VT_ROW;
-    static constexpr int LDS = K_BYTES + VT_BYTES;
-    static_assert(NKT % 2 == 0, "PV consumes key tiles in pairs");
-};
 
 typedef float f32x2 __attribute__((ext_vector_type(2)));
 __device__ __forceinline__ f32x2 pk_fma(f32x2 a, f32x2 b, f32x2 c) {
@@ -327,8 +318,6 @@ __global__ __launch_bounds__(256, 2) void attention_kernel(const T* __restrict__
 // and the last QUERY is one row of plain VALU work split over the four waves after their tile loops: wave w scores keys
 // [64 w, 64 w + 64) (one per lane), the scores and then the probabilities cross waves through 2 KB of LDS, and wave w
 // accumulates output dims [16 w, 16 w + 16) (lane = dim x key quarter, reduced over the quarters with permlane swaps).
-constexpr int TAIL_LDS = 256 + 2 * 1056;      // last key's K and V rows | scores [257+] | probabilities [257+]
-
 template <int NKT, typename T = bf16_t>
 __global__ __launch_bounds__(256, 2) void attention_tail1_kernel(const T* __restrict__ qkv, T* __restrict__ out,
                                                                  int heads, int q_limit) {
@@ -474,14 +463,6 @@ __global__ __launch_bounds__(256, 2) void attention_tail1_kernel(const T* __rest
 //     row-major [key][64] with a chunk swizzle applied on the SOURCE side; V^T fragments are read with ds_read_b64_tr_b16
 //     (hardware transpose), so no V^T image is built (the 8-byte V^T writes of the 4-wave kernels were 8-way bank conflicted).
 //   * key 256 is a rank-1 VALU update per block, query 256 one VALU row split over the eight waves after their blocks.
-namespace s257 {
-constexpr int K_OFF = 0, V_OFF = 32768, TAIL_OFF = 65536;    // tail: row 256's q | k | v (128 B each)
-constexpr int SC_OFF = TAIL_OFF + 384;                        // last query: f32 scores [264]
-constexpr int PART_OFF = SC_OFF + 264 * 4;                    // last query: per wave {max, sum, -, ..., partial output [64]}: 72 floats
-constexpr int CNT_OFF = PART_OFF + 8 * 72 * 4;                // last query: arrival counter
-constexpr int LDS = CNT_OFF + 16 + 256;                       // 69,552 B -> two workgroups per CU (the last 256 B are unused)
-}  // namespace s257
-
 __device__ __forceinline__ float halves_max(float x) {
     auto b = __builtin_amdgcn_permlane32_swap(__float_as_uint(x), __float_as_uint(x), false, false);
     return fmaxf(__uint_as_float(b[0]), __uint_as_float(b[1]));
@@ -915,183 +896,148 @@ __global__ __launch_bounds__(512, 4) void attention_s257_kernel(const T* __restr
 // correct and SLOWER, 92 us against 70: the asm statements pin the schedule and spill 15 registers, and the wait for keys
 // 0-127 alone is as long as the wait for all 256 (10 k cycles: first-byte latency, not volume).  Not kept.
 
-int g_attn_tail = 1;    // A/B hook: 0 routes S = 257 through the generic (padded) kernel
+// ---- host: every launch is planned by attention_plan() (attention_plan.h); launch_plan() runs the plan -------------------------------
 
-template <typename T = bf16_t>
-int launch_attn_tail1(const void* qkv, void* out, int B, int heads, int q_limit, hipStream_t st) {
-    using C = AttnCfg<16>;
-    constexpr int LDS = C::LDS + TAIL_LDS;
-    if (int rc = keds_func_lds_once((const void*)attention_tail1_kernel<16, T>, LDS, "attention_tail1_kernel")) return rc;
-    KedsProfScope prof(KEDS_PROF_ATTN, st);
-    attention_tail1_kernel<16, T><<<B * heads, 256, LDS, st>>>((const T*)qkv, (T*)out, heads, q_limit);
-    return keds_check_launch("attention_tail1_kernel");
-}
+AttnSwitches g_attn_sw;     // the defaults under the bits of the last keds_attention_debug call
 
-int g_attn_s257 = 1;    // A/B hook: 0 routes S = 257 through the 4-wave tail kernel
+// What the last 16-bit attention call of this thread launched (keds_attention_last_launch, keds_hip.h): written at each launch site
+// with the literal form and template arguments of the kernel launched there, and compared with the plan afterwards (attention16)
+thread_local AttnPlan tl_attn_rec = {};
 
-// The towers fork their remainder-row chain behind this launch.  An event RECORDED on the launching stream is a marker packet of
-// its own between two kernels (a kernel trace shows 7.9 us between the attention's end and the next GEMM's start with it, 1.4
-// without: profiles/r05_trace_block.txt); as the launch's STOP event it is the kernel's completion signal and costs nothing.
-thread_local hipEvent_t tl_attn_stop = nullptr;
-thread_local bool tl_attn_stop_taken = false;
+// One launch, as `rec` describes it.  The towers fork their remainder-row chain behind the S = 257 launch: an event RECORDED on the
+// launching stream is a marker packet of its own between two kernels (a kernel trace shows 7.9 us between the attention's end and the
+// next GEMM's start with it, 1.4 without: profiles/r05_trace_block.txt); as the launch's STOP event it is the kernel's completion
+// signal and costs nothing.
 template <typename K, typename... A>
-void launch_s257(K kernel, int grid, hipStream_t st, A... args) {
-    hipEvent_t stop = tl_attn_stop;
-    tl_attn_stop = nullptr;
+int launch(const AttnArgs& a, const AttnPlan& rec, K kernel, const char* name, bool* stop_taken, A... args) {
+    if (int rc = keds_func_lds_once((const void*)kernel, rec.lds, name)) return rc;
+    KedsProfScope prof(KEDS_PROF_ATTN, a.stream);
+    tl_attn_rec = rec;
+    hipEvent_t stop = rec.takes_stop_event && stop_taken ? a.stop : nullptr;
     hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-    if (stop && (hipStreamIsCapturing(st, &cap) != hipSuccess || cap != hipStreamCaptureStatusNone)) stop = nullptr;   // (a graph capture records it itself)
+    if (stop && (hipStreamIsCapturing(a.stream, &cap) != hipSuccess || cap != hipStreamCaptureStatusNone)) stop = nullptr;   // (a graph capture records it itself)
     if (stop) {
-        hipExtLaunchKernelGGL(kernel, dim3(grid), dim3(512), s257::LDS, st, nullptr, stop, 0, args...);
-        tl_attn_stop_taken = true;
+        hipExtLaunchKernelGGL(kernel, dim3(rec.grid), dim3(rec.block), rec.lds, a.stream, nullptr, stop, 0, args...);
+        *stop_taken = true;
     } else {
-        kernel<<<grid, 512, s257::LDS, st>>>(args...);
+        kernel<<<rec.grid, rec.block, rec.lds, a.stream>>>(args...);
     }
+    return keds_check_launch(name);
 }
 
-int launch_attn_s257_q8(const void* qkv, void* out, int B, int heads, int q_limit, void* q8, void* s8, int q8_rows,
-                        hipStream_t st) {
-    if (int rc = keds_func_lds_once((const void*)attention_s257_kernel<true>, s257::LDS, "attention_s257_kernel<q8>")) return rc;
-    KedsProfScope prof(KEDS_PROF_ATTN, st);
-    launch_s257(attention_s257_kernel<true>, B * heads, st, (const bf16_t*)qkv, (bf16_t*)out, heads, q_limit, (unsigned char*)q8, (unsigned char*)s8, q8_rows);
-    return keds_check_launch("attention_s257_kernel<q8>");
+template <typename T, int NKT, bool CAUSAL, int NFULL>
+int launch_generic(const AttnArgs& a, int q_limit) {
+    constexpr bool H = __is_same(T, f16_t);
+    const AttnPlan rec{KEDS_ATTN_FORM_GENERIC, NKT, NFULL, CAUSAL, H, a.q8 != nullptr, a.seq_off != nullptr, false, a.B * a.heads, 256, AttnCfg<NKT>::LDS, q_limit};
+    return launch(a, rec, attention_kernel<NKT, CAUSAL, NFULL, NKT == 18 && !CAUSAL, T>, H ? "attention_kernel<f16>" : "attention_kernel", nullptr,
+                  (const T*)a.qkv, (T*)a.out, a.S, a.heads, q_limit, (unsigned char*)a.q8, (unsigned char*)a.s8, a.q8_rows, a.seq_off);
 }
 
-template <typename T = bf16_t>
-int launch_attn_s257(const void* qkv, void* out, int B, int heads, int q_limit, hipStream_t st) {
-    if constexpr (__is_same(T, f16_t)) {                          // the fp16 form
-        if (int rc = keds_func_lds_once((const void*)attention_s257_kernel<false, f16_t>, s257::LDS, "attention_s257_kernel<f16>")) return rc;
-        KedsProfScope prof(KEDS_PROF_ATTN, st);
-        launch_s257(attention_s257_kernel<false, f16_t>, B * heads, st, (const f16_t*)qkv, (f16_t*)out, heads, q_limit,
-                    (unsigned char*)nullptr, (unsigned char*)nullptr, 0);
-        return keds_check_launch("attention_s257_kernel<f16>");
+// (form, nkt, causal, nfull, q8) -> the template instantiation, for one element type: the only place that names them
+template <typename T>
+int launch_plan(const AttnArgs& a, const AttnPlan& p, bool* stop_taken) {
+    constexpr bool H = __is_same(T, f16_t);
+    const int grid = a.B * a.heads, q = p.q_limit;
+    if (p.form == KEDS_ATTN_FORM_S257) {
+        if constexpr (!H)
+            if (p.q8)
+                return launch(a, AttnPlan{KEDS_ATTN_FORM_S257, 16, 16, false, H, true, false, true, grid, 512, s257::LDS, q}, attention_s257_kernel<true, T>,
+                              "attention_s257_kernel<q8>", stop_taken, (const T*)a.qkv, (T*)a.out, a.heads, q, (unsigned char*)a.q8, (unsigned char*)a.s8, a.q8_rows);
+        return launch(a, AttnPlan{KEDS_ATTN_FORM_S257, 16, 16, false, H, false, false, true, grid, 512, s257::LDS, q}, attention_s257_kernel<false, T>,
+                      H ? "attention_s257_kernel<f16>" : "attention_s257_kernel", stop_taken, (const T*)a.qkv, (T*)a.out, a.heads, q, (unsigned char*)nullptr,
+                      (unsigned char*)nullptr, 0);
     }
-    if (int rc = keds_func_lds_once((const void*)attention_s257_kernel<>, s257::LDS, "attention_s257_kernel")) return rc;
-    KedsProfScope prof(KEDS_PROF_ATTN, st);
-    launch_s257(attention_s257_kernel<>, B * heads, st, (const bf16_t*)qkv, (bf16_t*)out, heads, q_limit, (unsigned char*)nullptr,
-                (unsigned char*)nullptr, 0);
-    return keds_check_launch("attention_s257_kernel");
+    if (p.form == KEDS_ATTN_FORM_TAIL1)
+        return launch(a, AttnPlan{KEDS_ATTN_FORM_TAIL1, 16, 16, false, H, false, false, false, grid, 256, AttnCfg<16>::LDS + TAIL_LDS, q},
+                      attention_tail1_kernel<16, T>, "attention_tail1_kernel", nullptr, (const T*)a.qkv, (T*)a.out, a.heads, q);
+    if (p.form == KEDS_ATTN_FORM_GENERIC && p.nfull) return launch_generic<T, 18, false, 16>(a, q);     // ViT-L/14: 257 tokens
+    if (p.form == KEDS_ATTN_FORM_GENERIC && p.nkt == 2) return p.causal ? launch_generic<T, 2, true, 0>(a, q) : launch_generic<T, 2, false, 0>(a, q);
+    if (p.form == KEDS_ATTN_FORM_GENERIC && p.nkt == 6) return p.causal ? launch_generic<T, 6, true, 0>(a, q) : launch_generic<T, 6, false, 0>(a, q);
+    if (p.form == KEDS_ATTN_FORM_GENERIC) return p.causal ? launch_generic<T, 18, true, 0>(a, q) : launch_generic<T, 18, false, 0>(a, q);
+    keds_set_error("keds_attention: no kernel of form %d", p.form);
+    return KEDS_E_LAUNCH;
 }
 
-template <int NKT, bool CAUSAL, int NFULL, typename T = bf16_t>
-int launch_attn(const void* qkv, void* out, int B, int S, int heads, int q_limit, void* q8, void* s8, int q8_rows,
-                hipStream_t st, const int* seq_off = nullptr) {
-    using C = AttnCfg<NKT>;
-    if constexpr (__is_same(T, f16_t)) {                          // the fp16 form
-        constexpr bool NQ2 = NKT == 18 && !CAUSAL;
-        if (int rc = keds_func_lds_once((const void*)attention_kernel<NKT, CAUSAL, NFULL, NQ2, f16_t>, C::LDS, "attention_kernel<f16>"))
-            return rc;
-        KedsProfScope prof(KEDS_PROF_ATTN, st);
-        attention_kernel<NKT, CAUSAL, NFULL, NQ2, f16_t><<<B * heads, 256, C::LDS, st>>>((const f16_t*)qkv, (f16_t*)out, S, heads, q_limit,
-                                                                                             nullptr, nullptr, 0, seq_off);
-        return keds_check_launch("attention_kernel<f16>");
+int attention16(const AttnArgs& a, const AttnPlan& p, bool* stop_taken) {
+    tl_attn_rec = AttnPlan{};
+    if (int rc = p.f16 ? launch_plan<f16_t>(a, p, stop_taken) : launch_plan<bf16_t>(a, p, stop_taken)) return rc;
+    // keds_attention_last_launch reports what the launch site recorded, not the plan: the two must agree
+    int want[8], got[8];
+    p.info(want);
+    tl_attn_rec.info(got);
+    for (int i = 0; i < 8; ++i) {
+        if (got[i] != want[i]) {
+            keds_set_error("keds_attention: launched form differs from the plan at [%d]: %d, planned %d (B %d, S %d, heads %d)", i, got[i], want[i],
+                           a.B, a.S, a.heads);
+            return KEDS_E_LAUNCH;
+        }
     }
-    if (int rc = keds_func_lds_once((const void*)attention_kernel<NKT, CAUSAL, NFULL>, C::LDS, "attention_kernel")) return rc;
-    KedsProfScope prof(KEDS_PROF_ATTN, st);
-    attention_kernel<NKT, CAUSAL, NFULL><<<B * heads, 256, C::LDS, st>>>((const bf16_t*)qkv, (bf16_t*)out, S, heads, q_limit,
-                                                                         (unsigned char*)q8, (unsigned char*)s8, q8_rows, seq_off);
-    return keds_check_launch("attention_kernel");
+    return KEDS_OK;
 }
 
 }  // namespace
 
-void keds_attention_stop_event(hipEvent_t ev) {
-    tl_attn_stop = ev;
-    tl_attn_stop_taken = false;
-}
-bool keds_attention_stop_event_taken() {
-    tl_attn_stop = nullptr;                 // (a kernel form that does not take it: the caller records the event itself)
-    return tl_attn_stop_taken;
+// (keds_common.h) the public entries below after their argument checks, and the towers, whose parameters check_tower has checked
+int keds_attention16(const AttnArgs& a, bool f16, int causal, int q_limit, bool* stop_taken) {
+    if (stop_taken) *stop_taken = false;
+    KEDS_REQUIRE(a.qkv && a.out && a.B > 0 && a.heads > 0 && a.S >= 1 && a.S <= 288 && !(a.q8 && (f16 || a.seq_off)), "keds_attention16: bad argument");
+    return attention16(a, attention_plan(a.B, a.S, a.heads, causal != 0, q_limit, f16, a.q8 != nullptr, a.seq_off != nullptr, g_attn_sw), stop_taken);
 }
 
 extern "C" int keds_attention_debug(int variant) {
     // bits 0-3 and 6 selected timing-only ablations that last existed at 14f64ac
     for (const int bit : {0, 1, 2, 3, 6})
         KEDS_REQUIRE(!((variant >> bit) & 1), "keds_attention_debug: bit %d is no longer offered", bit);
-    g_attn_tail = (variant >> 4) & 1 ? 0 : 1;      // bit 4: S = 257 through the generic kernel (A/B)
-    g_attn_s257 = (variant >> 5) & 1 ? 0 : 1;      // bit 5: S = 257 through the 4-wave tail kernel (A/B)
+    g_attn_sw = attn_switches_decode(variant);     // bits 4 and 5: S = 257 through the generic / the 4-wave tail kernel (A/B)
     return KEDS_OK;
 }
 
-extern "C" int keds_attention_ex(const void* qkv, void* out, int B, int S, int heads, int causal, int q_limit,
-                                 void* stream) {
+extern "C" int keds_attention_plan_query(int B, int S, int heads, int causal, int q_limit, int f16, int q8, int packed, int* info) {
+    KEDS_REQUIRE(info && B > 0 && heads > 0 && S >= 1 && S <= 288, "keds_attention_plan_query: bad argument (B, heads > 0, 1 <= S <= 288)");
+    attention_plan(B, S, heads, causal != 0, q_limit, f16 != 0, q8 != 0, packed != 0, g_attn_sw).info(info);
+    return KEDS_OK;
+}
+
+extern "C" int keds_attention_last_launch(int* info) {
+    KEDS_REQUIRE(info, "keds_attention_last_launch: null pointer");
+    tl_attn_rec.info(info);
+    return KEDS_OK;
+}
+
+extern "C" int keds_attention_ex(const void* qkv, void* out, int B, int S, int heads, int causal, int q_limit, void* stream) {
     return keds_attention_mx(qkv, out, B, S, heads, causal, q_limit, nullptr, nullptr, 0, stream);
 }
 
-extern "C" int keds_attention_mx(const void* qkv, void* out, int B, int S, int heads, int causal, int q_limit, void* q8,
-                                 void* s8, int q8_rows, void* stream) {
+extern "C" int keds_attention_mx(const void* qkv, void* out, int B, int S, int heads, int causal, int q_limit, void* q8, void* s8, int q8_rows,
+                                 void* stream) {
     KEDS_REQUIRE(qkv && out && B > 0 && heads > 0, "keds_attention: bad argument");
     KEDS_REQUIRE((q8 == nullptr) == (s8 == nullptr) && (q8 == nullptr || (q8_rows > 0 && (heads * 64) % 128 == 0)),
                  "keds_attention_mx: q8, s8 and q8_rows come together; width must be a multiple of 128");
     KEDS_REQUIRE(S >= 1 && S <= 288, "keds_attention: S=%d unsupported (1..288)", S);
-    if (q_limit <= 0 || q_limit > S) q_limit = S;
-    hipStream_t st = (hipStream_t)stream;
-    if (causal) {
-        if (S <= 32) return launch_attn<2, true, 0>(qkv, out, B, S, heads, q_limit, q8, s8, q8_rows, st);
-        if (S <= 96) return launch_attn<6, true, 0>(qkv, out, B, S, heads, q_limit, q8, s8, q8_rows, st);
-        return launch_attn<18, true, 0>(qkv, out, B, S, heads, q_limit, q8, s8, q8_rows, st);
-    }
-    if (S <= 32) return launch_attn<2, false, 0>(qkv, out, B, S, heads, q_limit, q8, s8, q8_rows, st);
-    if (S <= 96) return launch_attn<6, false, 0>(qkv, out, B, S, heads, q_limit, q8, s8, q8_rows, st);
-    if (S == 257 && !q8 && g_attn_tail && g_attn_s257) return launch_attn_s257(qkv, out, B, heads, q_limit, st);
-    if (S == 257 && q8 && g_attn_tail && g_attn_s257)
-        return launch_attn_s257_q8(qkv, out, B, heads, q_limit, q8, s8, q8_rows, st);
-    if (S == 257 && !q8 && g_attn_tail) return launch_attn_tail1(qkv, out, B, heads, q_limit, st);
-    if (S >= 256) return launch_attn<18, false, 16>(qkv, out, B, S, heads, q_limit, q8, s8, q8_rows, st);   // ViT-L/14: 257 tokens
-    return launch_attn<18, false, 0>(qkv, out, B, S, heads, q_limit, q8, s8, q8_rows, st);
+    return keds_attention16(AttnArgs{qkv, out, B, S, heads, q8, s8, q8_rows, nullptr, (hipStream_t)stream, nullptr}, false, causal, q_limit);
 }
 
-// fp16 forms (the "fp16" operating point): the same dispatch on fp16 qkv / out
+// fp16 forms (the "fp16" operating point): the same plan on fp16 qkv / out
 extern "C" int keds_attention_h(const void* qkv, void* out, int B, int S, int heads, int causal, int q_limit, void* stream) {
     KEDS_REQUIRE(qkv && out && B > 0 && heads > 0, "keds_attention_h: bad argument");
     KEDS_REQUIRE(S >= 1 && S <= 288, "keds_attention_h: S=%d unsupported (1..288)", S);
-    if (q_limit <= 0 || q_limit > S) q_limit = S;
-    hipStream_t st = (hipStream_t)stream;
-    if (causal) {
-        if (S <= 32) return launch_attn<2, true, 0, f16_t>(qkv, out, B, S, heads, q_limit, nullptr, nullptr, 0, st);
-        if (S <= 96) return launch_attn<6, true, 0, f16_t>(qkv, out, B, S, heads, q_limit, nullptr, nullptr, 0, st);
-        return launch_attn<18, true, 0, f16_t>(qkv, out, B, S, heads, q_limit, nullptr, nullptr, 0, st);
-    }
-    if (S <= 32) return launch_attn<2, false, 0, f16_t>(qkv, out, B, S, heads, q_limit, nullptr, nullptr, 0, st);
-    if (S <= 96) return launch_attn<6, false, 0, f16_t>(qkv, out, B, S, heads, q_limit, nullptr, nullptr, 0, st);
-    if (S == 257 && g_attn_tail && g_attn_s257) return launch_attn_s257<f16_t>(qkv, out, B, heads, q_limit, st);
-    if (S == 257 && g_attn_tail) return launch_attn_tail1<f16_t>(qkv, out, B, heads, q_limit, st);
-    if (S >= 256) return launch_attn<18, false, 16, f16_t>(qkv, out, B, S, heads, q_limit, nullptr, nullptr, 0, st);
-    return launch_attn<18, false, 0, f16_t>(qkv, out, B, S, heads, q_limit, nullptr, nullptr, 0, st);
+    return keds_attention16(AttnArgs{qkv, out, B, S, heads, nullptr, nullptr, 0, nullptr, (hipStream_t)stream, nullptr}, true, causal, q_limit);
 }
 
-extern "C" int keds_attention_packed_h(const void* qkv, void* out, int B, int s_max, const int32_t* seq_off, int heads, int causal,
-                                       void* stream) {
+extern "C" int keds_attention_packed_h(const void* qkv, void* out, int B, int s_max, const int32_t* seq_off, int heads, int causal, void* stream) {
     KEDS_REQUIRE(qkv && out && seq_off && B > 0 && heads > 0, "keds_attention_packed_h: bad argument");
     KEDS_REQUIRE(s_max >= 1 && s_max <= 288, "keds_attention_packed_h: s_max=%d unsupported (1..288)", s_max);
-    hipStream_t st = (hipStream_t)stream;
-    if (causal) {
-        if (s_max <= 32) return launch_attn<2, true, 0, f16_t>(qkv, out, B, s_max, heads, s_max, nullptr, nullptr, 0, st, seq_off);
-        if (s_max <= 96) return launch_attn<6, true, 0, f16_t>(qkv, out, B, s_max, heads, s_max, nullptr, nullptr, 0, st, seq_off);
-        return launch_attn<18, true, 0, f16_t>(qkv, out, B, s_max, heads, s_max, nullptr, nullptr, 0, st, seq_off);
-    }
-    if (s_max <= 32) return launch_attn<2, false, 0, f16_t>(qkv, out, B, s_max, heads, s_max, nullptr, nullptr, 0, st, seq_off);
-    if (s_max <= 96) return launch_attn<6, false, 0, f16_t>(qkv, out, B, s_max, heads, s_max, nullptr, nullptr, 0, st, seq_off);
-    return launch_attn<18, false, 0, f16_t>(qkv, out, B, s_max, heads, s_max, nullptr, nullptr, 0, st, seq_off);
+    return keds_attention16(AttnArgs{qkv, out, B, s_max, heads, nullptr, nullptr, 0, seq_off, (hipStream_t)stream, nullptr}, true, causal, s_max);
 }
 
-// Packed rows: sample b is rows [seq_off[b], seq_off[b + 1]) of qkv / out (device int32 [B + 1], lengths 1 .. s_max).  The text
-// tower's captions end at different columns and the mask is causal: rows behind a caption's read-out column reach nothing that is
-// read (model.py:543-549), so the tower computes none of them (keds_text_run_packed).
-extern "C" int keds_attention_packed(const void* qkv, void* out, int B, int s_max, const int32_t* seq_off, int heads, int causal,
-                                     void* stream) {
+// packed rows (attention_kernel's seq_off; keds_hip.h): the text tower's captions end at different columns (keds_text_run_packed)
+extern "C" int keds_attention_packed(const void* qkv, void* out, int B, int s_max, const int32_t* seq_off, int heads, int causal, void* stream) {
     KEDS_REQUIRE(qkv && out && seq_off && B > 0 && heads > 0, "keds_attention_packed: bad argument");
     KEDS_REQUIRE(s_max >= 1 && s_max <= 288, "keds_attention_packed: s_max=%d unsupported (1..288)", s_max);
-    hipStream_t st = (hipStream_t)stream;
-    if (causal) {
-        if (s_max <= 32) return launch_attn<2, true, 0>(qkv, out, B, s_max, heads, s_max, nullptr, nullptr, 0, st, seq_off);
-        if (s_max <= 96) return launch_attn<6, true, 0>(qkv, out, B, s_max, heads, s_max, nullptr, nullptr, 0, st, seq_off);
-        return launch_attn<18, true, 0>(qkv, out, B, s_max, heads, s_max, nullptr, nullptr, 0, st, seq_off);
-    }
-    if (s_max <= 32) return launch_attn<2, false, 0>(qkv, out, B, s_max, heads, s_max, nullptr, nullptr, 0, st, seq_off);
-    if (s_max <= 96) return launch_attn<6, false, 0>(qkv, out, B, s_max, heads, s_max, nullptr, nullptr, 0, st, seq_off);
-    return launch_attn<18, false, 0>(qkv, out, B, s_max, heads, s_max, nullptr, nullptr, 0, st, seq_off);
+    return keds_attention16(AttnArgs{qkv, out, B, s_max, heads, nullptr, nullptr, 0, seq_off, (hipStream_t)stream, nullptr}, false, causal, s_max);
 }
 
 extern "C" int keds_attention(const void* qkv, void* out, int B, int S, int heads, int causal, void* stream) {
     return keds_attention_ex(qkv, out, B, S, heads, causal, S, stream);
 }
+

@@ -15,6 +15,7 @@
 #include "keds_common.h"
 #include "gemm_quad_gen.h"       // accumulator read-back / drain of the 4-wave kernels
 #include "gemm_fp8_quad_gen.h"
+#include "gemm_plan.h"           // mxfp8_plan(): which of the two kernels, and its grid
 #include <cstdlib>
 
 namespace {
@@ -895,85 +896,96 @@ extern "C" int keds_quantize_mxfp8(const void* x, int x_is_bf16, int rows, int K
 
 namespace {
 // What the last keds_gemm_mxfp8* call of this thread launched (keds_gemm_mxfp8_last_launch, keds_hip.h): written at the two launch
-// sites with the literal form of the kernel launched there, in the spirit of gemm.hip's record
-struct Fp8LaunchRecord {
-    int form, grid, tiles;
+// sites with the literal form of the kernel launched there and compared with the plan afterwards, as gemm.hip's record is
+thread_local Mxfp8Plan tl_fp8_rec = {};
+
+struct Fp8Args {      // keds_gemm_mxfp8_ex's
+    const void *Aq, *As, *Wq, *Ws; int m_pad, n_pad; const float* bias; void* out; int M, N, K;
+    float *aux, *aux2; void *qout, *qscale; int q_pad; hipStream_t st;
 };
-thread_local Fp8LaunchRecord tl_fp8_rec = {};
 
 template <int EPI>
-int launch_mxfp8(const void* Aq, const void* As, int m_pad, const void* Wq, const void* Ws, int n_pad, const float* bias,
-                 void* out, int M, int N, int K, float* aux, float* aux2, void* qout, void* qscale, int q_pad, hipStream_t st) {
+int launch_mxfp8(const Fp8Args& a) {
     if (int rc = keds_func_lds_once((const void*)gemm_mxfp8_kernel<EPI>, LDS_BYTES, "gemm_mxfp8_kernel")) return rc;
-    const int m_tiles = M / TM, n_tiles = N / TN;
-    tl_fp8_rec = Fp8LaunchRecord{KEDS_FP8_FORM_PAIR, m_tiles * n_tiles, m_tiles * n_tiles};
-    KEDS_LAUNCH((gemm_mxfp8_kernel<EPI>), m_tiles * n_tiles, 512, LDS_BYTES, st,
-                (const unsigned char*)Aq, (const unsigned char*)As, (const unsigned char*)Wq, (const unsigned char*)Ws, bias, out, M, N, K,
-                n_tiles, m_pad, n_pad, aux, aux2, (unsigned char*)qout, (unsigned char*)qscale, q_pad);
+    const int m_tiles = a.M / TM, n_tiles = a.N / TN;
+    tl_fp8_rec = Mxfp8Plan{KEDS_FP8_FORM_PAIR, m_tiles * n_tiles, m_tiles * n_tiles};
+    KEDS_LAUNCH((gemm_mxfp8_kernel<EPI>), m_tiles * n_tiles, 512, LDS_BYTES, a.st,
+                (const unsigned char*)a.Aq, (const unsigned char*)a.As, (const unsigned char*)a.Wq, (const unsigned char*)a.Ws, a.bias, a.out, a.M, a.N,
+                a.K, n_tiles, a.m_pad, a.n_pad, a.aux, a.aux2, (unsigned char*)a.qout, (unsigned char*)a.qscale, a.q_pad);
     return keds_check_launch("gemm_mxfp8_kernel");
 }
 
-// the 4-wave persistent kernel: K-tiles in pairs (K % 256 == 0), at least four
+// the 4-wave kernel, one tile per workgroup or (plan.grid < tiles) persistent
 template <int EPI>
-int launch_mxfp8_quad(const void* Aq, const void* As, int m_pad, const void* Wq, const void* Ws, int n_pad, const float* bias,
-                      void* out, int M, int N, int K, float* aux, float* aux2, void* qout, void* qscale, int q_pad, hipStream_t st) {
+int launch_mxfp8_quad(const Fp8Args& a, const Mxfp8Plan& p) {
     if (int rc = keds_func_lds_once((const void*)gemm_mxfp8_quad_kernel<EPI>, fq::LDS_BYTES, "gemm_mxfp8_quad_kernel")) return rc;
-    const int m_tiles = M / TM, n_tiles = N / TN, ntiles = m_tiles * n_tiles;
-    int cus = keds_device_cus();
-    if (cus > 256) cus = 256;
-    cus &= ~7;                                    // whole XCD groups: workgroup b and its tile ids b, b + grid, ... share an XCD label
-    // (A/B, round 4: the residual epilogues with one tile per workgroup, so that the hardware deals the tiles and the side lane's
-    // small launches slot in between them: the GEMM class takes 0.5 ms more per step, the gaps in front of the attention launches
-    // shrink by as much -- 14.87-15.06 against 14.92-15.00 ms per step, four alternating runs on one box)
-    const int grid = (cus >= 8 && ntiles > cus) ? cus : ntiles;
-    tl_fp8_rec = Fp8LaunchRecord{KEDS_FP8_FORM_QUAD, grid, ntiles};
-    KEDS_LAUNCH((gemm_mxfp8_quad_kernel<EPI>), grid, 256, fq::LDS_BYTES, st,
-                (const unsigned char*)Aq, (const unsigned char*)As, (const unsigned char*)Wq, (const unsigned char*)Ws, bias, out, M, N, K,
-                n_tiles, m_pad, n_pad, aux, aux2, (unsigned char*)qout, (unsigned char*)qscale, q_pad, ntiles);
+    const int m_tiles = a.M / TM, n_tiles = a.N / TN, ntiles = m_tiles * n_tiles;
+    tl_fp8_rec = Mxfp8Plan{KEDS_FP8_FORM_QUAD, p.grid, ntiles};
+    KEDS_LAUNCH((gemm_mxfp8_quad_kernel<EPI>), p.grid, 256, fq::LDS_BYTES, a.st,
+                (const unsigned char*)a.Aq, (const unsigned char*)a.As, (const unsigned char*)a.Wq, (const unsigned char*)a.Ws, a.bias, a.out, a.M, a.N,
+                a.K, n_tiles, a.m_pad, a.n_pad, a.aux, a.aux2, (unsigned char*)a.qout, (unsigned char*)a.qscale, a.q_pad, ntiles);
     return keds_check_launch("gemm_mxfp8_quad_kernel");
 }
+
+template <int EPI>
+int launch_mxfp8_plan(const Fp8Args& a) {
+    const Mxfp8Plan p = mxfp8_plan(EPI, a.M, a.N, a.K, mxfp8_quad(EPI, a.K, g_fp8_debug) ? keds_device_cus() : 0, g_fp8_debug);
+    int rc;
+    if constexpr (EPI != KEDS_FP8_EPI_RESID_STATS_MX) rc = p.form == KEDS_FP8_FORM_QUAD ? launch_mxfp8_quad<EPI>(a, p) : launch_mxfp8<EPI>(a);
+    else rc = launch_mxfp8<EPI>(a);
+    if (rc) return rc;
+    if (tl_fp8_rec.form != p.form || tl_fp8_rec.grid != p.grid || tl_fp8_rec.tiles != p.tiles) {
+        keds_set_error("keds_gemm_mxfp8: launched (form, grid, tiles) (%d, %d, %d) differs from the plan (%d, %d, %d)", tl_fp8_rec.form,
+                       tl_fp8_rec.grid, tl_fp8_rec.tiles, p.form, p.grid, p.tiles);
+        return KEDS_E_LAUNCH;
+    }
+    return KEDS_OK;
+}
 }  // namespace
+
+// the shape rules of keds_gemm_mxfp8_ex (what the kernels and the planner rely on)
+static int mxfp8_check_shape(const char* who, int M, int N, int K) {
+    KEDS_REQUIRE(M > 0 && M % TM == 0 && N > 0 && N % TN == 0, "%s: M and N must be multiples of 256 (M=%d N=%d)", who, M, N);
+    KEDS_REQUIRE(K % TKB == 0 && K >= 2 * TKB, "%s: K=%d must be a multiple of 128, >= 256", who, K);
+    return KEDS_OK;
+}
 
 extern "C" int keds_gemm_mxfp8_ex(const void* Aq, const void* As, int m_pad, const void* Wq, const void* Ws, int n_pad,
                                   const float* bias, void* out, int M, int N, int K, int epilogue, float* aux, float* aux2,
                                   void* qout, void* qscale, int q_pad, void* stream) {
-    tl_fp8_rec = Fp8LaunchRecord{};               // a call that launches nothing records nothing
+    tl_fp8_rec = Mxfp8Plan{};               // a call that launches nothing records nothing
     KEDS_REQUIRE(Aq && As && Wq && Ws, "keds_gemm_mxfp8: null pointer");
-    KEDS_REQUIRE(M > 0 && M % TM == 0 && N > 0 && N % TN == 0, "keds_gemm_mxfp8: M and N must be multiples of 256 (M=%d N=%d)", M, N);
-    KEDS_REQUIRE(K % TKB == 0 && K >= 2 * TKB, "keds_gemm_mxfp8: K=%d must be a multiple of 128, >= 256", K);
+    if (int rc = mxfp8_check_shape("keds_gemm_mxfp8", M, N, K)) return rc;
     KEDS_REQUIRE(m_pad >= M && n_pad >= N && m_pad % 4 == 0 && n_pad % 4 == 0, "keds_gemm_mxfp8: bad scale row padding");
-    hipStream_t st = (hipStream_t)stream;
-    KedsProfScope prof(KEDS_PROF_GEMM, st, /*lazy: KEDS_LAUNCH binds the pair*/ true);
+    const Fp8Args a{Aq, As, Wq, Ws, m_pad, n_pad, bias, out, M, N, K, aux, aux2, qout, qscale, q_pad, (hipStream_t)stream};
+    KedsProfScope prof(KEDS_PROF_GEMM, a.st, /*lazy: KEDS_LAUNCH binds the pair*/ true);
     prof.work(2.0 * M * N * K);
-    // keds_mxfp8_debug(16): the 8-wave kernel whatever the shape (the bit-identity test's reference).  The fp32-residual epilogue
-    // (3: API only, the towers keep their stream in fp16) stays on the 8-wave kernel: beside its 256-bit residual chunks the
-    // 4-wave K-loop has no registers left
-    const bool quad = g_fp8_debug == 0 && K % (2 * TKB) == 0 && K >= 4 * TKB;
-#define KEDS_FP8_GO(E)                                                                                                            \
-    {                                                                                                                             \
-        if constexpr ((E) != 3)                                                                                                   \
-            if (quad) return launch_mxfp8_quad<E>(Aq, As, m_pad, Wq, Ws, n_pad, bias, out, M, N, K, aux, aux2, qout, qscale, q_pad, st); \
-        return launch_mxfp8<E>(Aq, As, m_pad, Wq, Ws, n_pad, bias, out, M, N, K, aux, aux2, qout, qscale, q_pad, st);              \
-    }
     switch (epilogue) {
         case KEDS_FP8_EPI_BIAS_BF16:
             KEDS_REQUIRE(out != nullptr, "keds_gemm_mxfp8: null output");
-            KEDS_FP8_GO(0)
+            return launch_mxfp8_plan<KEDS_FP8_EPI_BIAS_BF16>(a);
         case KEDS_FP8_EPI_LN_BIAS_BF16:
             KEDS_REQUIRE(out && bias && aux, "keds_gemm_mxfp8: LN epilogue needs out, bias = [bias' | csum] and row statistics");
-            KEDS_FP8_GO(1)
+            return launch_mxfp8_plan<KEDS_FP8_EPI_LN_BIAS_BF16>(a);
         case KEDS_FP8_EPI_LN_QGELU_MX:
             KEDS_REQUIRE(bias && aux && qout && qscale && q_pad >= M, "keds_gemm_mxfp8: LN+QuickGELU MX epilogue arguments");
-            KEDS_FP8_GO(2)
+            return launch_mxfp8_plan<KEDS_FP8_EPI_LN_QGELU_MX>(a);
         case KEDS_FP8_EPI_RESID_STATS_MX:
             KEDS_REQUIRE(out && aux && qout && qscale && q_pad >= M, "keds_gemm_mxfp8: residual MX epilogue arguments");
-            KEDS_FP8_GO(3)
+            return launch_mxfp8_plan<KEDS_FP8_EPI_RESID_STATS_MX>(a);
         case KEDS_FP8_EPI_RESID_STATS_MX_H:
             KEDS_REQUIRE(out && aux && qout && qscale && q_pad >= M, "keds_gemm_mxfp8: residual MX epilogue arguments");
-            KEDS_FP8_GO(4)
+            return launch_mxfp8_plan<KEDS_FP8_EPI_RESID_STATS_MX_H>(a);
         default: keds_set_error("keds_gemm_mxfp8: unknown epilogue %d", epilogue); return KEDS_E_ARG;
     }
-#undef KEDS_FP8_GO
+}
+
+extern "C" int keds_gemm_mxfp8_plan_query(int epilogue, int M, int N, int K, int cus, int* info) {
+    KEDS_REQUIRE(info && epilogue >= 0 && epilogue <= KEDS_FP8_EPI_RESID_STATS_MX_H, "keds_gemm_mxfp8_plan_query: null pointer or unknown epilogue %d", epilogue);
+    if (int rc = mxfp8_check_shape("keds_gemm_mxfp8_plan_query", M, N, K)) return rc;
+    const Mxfp8Plan p = mxfp8_plan(epilogue, M, N, K, cus, g_fp8_debug);
+    info[0] = p.form, info[1] = p.grid, info[2] = p.tiles, info[3] = p.grid < p.tiles;
+    return KEDS_OK;
 }
 
 extern "C" int keds_gemm_mxfp8_last_launch(int* info) {

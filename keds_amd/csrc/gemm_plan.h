@@ -215,4 +215,25 @@ inline GemmPlan gemm_plan(int epi, int M, int N, int K, long long lda, long long
     return plan;
 }
 
+// ---- the MXFP8 GEMMs (gemm_fp8.hip: keds_gemm_mxfp8_ex launches from this, keds_gemm_mxfp8_plan_query answers from it) ---------------
+// The 4-wave kernel walks K-tiles of 128 in pairs and needs at least four.  debug (keds_mxfp8_debug) 16: the 8-wave kernel whatever
+// the shape (the bit-identity test's reference).  The fp32-residual epilogue (API only, the towers keep their stream in fp16) stays on
+// the 8-wave kernel: beside its 256-bit residual chunks the 4-wave K-loop has no registers left.
+inline bool mxfp8_quad(int epilogue, int K, int debug) {
+    return debug == 0 && K % 256 == 0 && K >= 512 && epilogue != KEDS_FP8_EPI_RESID_STATS_MX;
+}
+struct Mxfp8Plan {
+    int form, grid, tiles;      // the layout of keds_gemm_mxfp8_last_launch (+ [3] = grid < tiles: persistent)
+};
+// cus: compute units of the device (read for the 4-wave form only)
+inline Mxfp8Plan mxfp8_plan(int epilogue, int M, int N, int K, int cus, int debug) {
+    const int tiles = (M / 256) * (N / 256);
+    if (!mxfp8_quad(epilogue, K, debug)) return Mxfp8Plan{KEDS_FP8_FORM_PAIR, tiles, tiles};
+    const int T = (cus > 256 ? 256 : cus) & ~7;       // whole XCD groups: workgroup b and its tile ids b, b + grid, ... share an XCD label
+    // (A/B, round 4: the residual epilogues with one tile per workgroup, so that the hardware deals the tiles and the side lane's
+    // small launches slot in between them: the GEMM class takes 0.5 ms more per step, the gaps in front of the attention launches
+    // shrink by as much -- 14.87-15.06 against 14.92-15.00 ms per step, four alternating runs on one box)
+    return Mxfp8Plan{KEDS_FP8_FORM_QUAD, T >= 8 && tiles > T ? T : tiles, tiles};
+}
+
 }  // namespace

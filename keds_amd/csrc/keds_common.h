@@ -104,10 +104,15 @@ int keds_stream_order(hipStream_t from, hipEvent_t ev, hipStream_t to);
 void keds_order_lock();
 void keds_order_unlock();
 int keds_stream_wait_locked(hipEvent_t ev, hipStream_t to);
-// (attention.hip) the next S = 257 attention launch of this thread records `ev` as its stop event; returns through
-// keds_attention_stop_event_taken() whether a launch consumed it (other kernel forms do not: the caller records it itself then)
-void keds_attention_stop_event(hipEvent_t ev);
-bool keds_attention_stop_event_taken();
+// (attention.hip) what the six public 16-bit attention entries and the towers launch through.  q8 / s8 / q8_rows: MXFP8 output rows
+// (keds_attention_mx) or null; seq_off: packed rows (S = s_max) or null; stop (nullable): an event the launch records as its stop
+// event if its kernel form takes one and the stream is not capturing -- *stop_taken says whether it did (else the caller records it)
+struct AttnArgs {
+    const void* qkv; void* out; int B, S, heads;
+    void *q8, *s8; int q8_rows; const int32_t* seq_off;
+    hipStream_t stream; hipEvent_t stop;
+};
+int keds_attention16(const AttnArgs& a, bool f16, int causal, int q_limit, bool* stop_taken = nullptr);
 
 static inline size_t keds_align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
 

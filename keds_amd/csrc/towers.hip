@@ -104,15 +104,14 @@ struct RowLanes {
     // the fork behind an attention launch: the launch records the event itself (its stop event: no marker packet between it and
     // the next GEMM on the main stream); kernel forms that do not take it get the recorded event.
     template <typename F>
-    int attention_then_side(F launch) {
+    int attention_then_side(F launch) {      // launch(stop event or null, &taken)
+        bool taken = false;
         if (!split) {
-            const int rc = launch();
+            const int rc = launch(nullptr, &taken);
             return rc ? rc : to_side();
         }
         keds_order_lock();
-        keds_attention_stop_event(fork);
-        int rc = launch();
-        const bool taken = keds_attention_stop_event_taken();
+        int rc = launch(fork, &taken);
         if (!rc && taken) rc = keds_stream_wait_locked(fork, side);
         keds_order_unlock();
         if (!rc && !taken) rc = to_side();
@@ -152,13 +151,12 @@ int proj_rows(const TowerWs& t, const keds_block_params& k, int w, bool last, Ro
                             h ? KEDS_EPI_RESID_STATS_F16_H : KEDS_EPI_RESID_STATS_F16, last ? nullptr : (const float*)(t.st1 + 2 * s.r0),
                             0, nullptr, s.st);
 }
-// the attention of the 16-bit flows: bf16 or (h) fp16 qkv / output
-int attention16(bool h, const void* qkv, void* out, int B, int S, int heads, int causal, int q_limit, hipStream_t st) {
-    return h ? keds_attention_h(qkv, out, B, S, heads, causal, q_limit, st) : keds_attention_ex(qkv, out, B, S, heads, causal, q_limit, st);
-}
-int attention16_packed(bool h, const void* qkv, void* out, int B, int s_max, const int32_t* off, int heads, int causal, hipStream_t st) {
-    return h ? keds_attention_packed_h(qkv, out, B, s_max, off, heads, causal, st)
-             : keds_attention_packed(qkv, out, B, s_max, off, heads, causal, st);
+// the attention of the 16-bit flows, t.qkv -> t.att: bf16 or (p->f16) fp16, rectangular or (pk) packed rows, and for the fp8 tower
+// rows < q8_rows as MXFP8 into t.aq / t.as.  stop / taken: RowLanes::attention_then_side
+int tower_attention(const keds_tower_params* p, const TowerWs& t, int B, int q_limit, const PackedRows* pk, int q8_rows, hipStream_t st,
+                    hipEvent_t stop = nullptr, bool* taken = nullptr) {
+    const AttnArgs a{t.qkv, t.att, B, p->seq, p->heads, q8_rows ? t.aq : nullptr, q8_rows ? t.as : nullptr, q8_rows, pk ? pk->off : nullptr, st, stop};
+    return keds_attention16(a, p->f16, p->causal, q_limit, taken);
 }
 
 // After the last block only token 0 of every sample is read (ln_post(x[:,0,:]), model.py:412), so the attention
@@ -172,7 +170,7 @@ int cls_rows_tail(const keds_tower_params* p, const keds_block_params& k, const 
     const int resid = h ? KEDS_EPI_BIAS_RESID_F32_H : KEDS_EPI_BIAS_RESID_F32;
     int rc;
     if (x16 && (rc = keds_cast_rows_f16_f32_impl(x16, x, B, w, ld, st))) return rc;
-    if ((rc = attention16(h, t.qkv, t.att, B, S, p->heads, p->causal, 1, st))) return rc;
+    if ((rc = tower_attention(p, t, B, 1, nullptr, 0, st))) return rc;
     if ((rc = keds_gemm_bt_ex(t.att, ld, k.out_w, k.out_b, x, ld, B, w, w, resid, nullptr, 0, st))) return rc;
     if ((rc = keds_layernorm_impl(x, w, nullptr, S, k.ln2_g, k.ln2_b, t.h, h ? 2 : 0, B, w, st))) return rc;
     if ((rc = keds_gemm_bt(t.h, k.fc_w, k.fc_b, t.hid, B, 4 * w, w, h ? KEDS_EPI_BIAS_QGELU_F16_H : KEDS_EPI_BIAS_QGELU_BF16, nullptr, 0,
@@ -194,9 +192,7 @@ int rows_tail(const keds_tower_params* p, const keds_block_params& k, const Towe
     const bool h = p->f16;
     const int resid = h ? KEDS_EPI_BIAS_RESID_F32_H : KEDS_EPI_BIAS_RESID_F32;
     int rc;
-    if (pk) rc = attention16_packed(h, t.qkv, t.att, B, S, pk->off, p->heads, p->causal, st);
-    else rc = attention16(h, t.qkv, t.att, B, S, p->heads, p->causal, S, st);
-    if (rc) return rc;
+    if ((rc = tower_attention(p, t, B, S, pk, 0, st))) return rc;
     bf16_t* att_c = t.qkv;                                               // [B, w] 16-bit (2 w bytes per row: a multiple of 256)
     float* x_c = (float*)((char*)t.qkv + (size_t)B * w * 2);             // [B, w] fp32; 6 B w <= the buffer's 6 w pad256(B S)
     const int bound = pk ? pk->valid : S;
@@ -249,7 +245,7 @@ int tower_forward_fp8(const keds_tower_params* p, float* x, int B, const TowerWs
         if (last && last_rows) return rows_tail(p, k, t, x, t.h, B, last_rows, st);
         if (last && p->last_cls_only) return cls_rows_tail(p, k, t, x, t.h, B, st);
         // attention writes its output as MXFP8 for the full-tile rows and as bf16 for the remainder rows
-        if ((rc = lanes.attention_then_side([&] { return keds_attention_mx(t.qkv, t.att, B, S, p->heads, p->causal, S, t.aq, t.as, Mm, st); })))
+        if ((rc = lanes.attention_then_side([&](hipEvent_t stop, bool* taken) { return tower_attention(p, t, B, S, nullptr, Mm, st, stop, taken); })))
             return rc;
         if ((rc = keds_gemm_mxfp8_ex(t.aq, t.as, Mm, k.out_q8, k.out_s8, w, k.out_b, t.h, Mm, w, w,
                                      KEDS_FP8_EPI_RESID_STATS_MX_H, (float*)t.st2, nullptr, t.xq, t.xs, Mm, st)))
@@ -311,9 +307,8 @@ int tower_forward(const keds_tower_params* p, float* x, int B, void* ws, hipStre
         keds_set_error("keds_tower_forward: packed rows: %s", hipGetErrorString(hipGetLastError()));
         return KEDS_E_LAUNCH;
     }
-    auto attention = [&](hipStream_t s_) {           // the block's attention on all samples
-        return pk ? attention16_packed(h, t.qkv, t.att, B, S, pk->off, p->heads, p->causal, s_)
-                  : attention16(h, t.qkv, t.att, B, S, p->heads, p->causal, S, s_);
+    auto attention = [&](hipEvent_t stop, bool* taken) {           // the block's attention on all samples
+        return tower_attention(p, t, B, S, pk, 0, st, stop, taken);
     };
     if (fp8) return tower_forward_fp8(p, x, B, t, Mm, st, last_rows, tp);
     if (folded) {
@@ -335,7 +330,7 @@ int tower_forward(const keds_tower_params* p, float* x, int B, void* ws, hipStre
                 return last_rows ? rows_tail(p, k, t, x, t.h, B, last_rows, st, pk) : cls_rows_tail(p, k, t, x, t.h, B, st);
             }
             if ((rc = lanes.to_main())) return rc;
-            if ((rc = lanes.attention_then_side([&] { return attention(st); }))) return rc;
+            if ((rc = lanes.attention_then_side(attention))) return rc;
             if ((rc = out_rows(t, k, w, body, h))) return rc;
             if (rem.n && (rc = out_rows(t, k, w, rem, h))) return rc;
             if ((rc = fc_rows(t, k, w, body, h))) return rc;
@@ -356,7 +351,7 @@ int tower_forward(const keds_tower_params* p, float* x, int B, void* ws, hipStre
         if ((rc = keds_gemm_bt(t.h, k.qkv_w, k.qkv_b, t.qkv, M, 3 * w, w, KEDS_EPI_BIAS_BF16, nullptr, 0, st))) return rc;
         if (last && last_rows) return rows_tail(p, k, t, x, nullptr, B, last_rows, st, pk);
         if (last && p->last_cls_only) return cls_rows_tail(p, k, t, x, nullptr, B, st);
-        if ((rc = attention(st))) return rc;
+        if ((rc = attention(nullptr, nullptr))) return rc;
         if ((rc = keds_gemm_bt(t.att, k.out_w, k.out_b, x, M, w, w, KEDS_EPI_BIAS_RESID_F32, nullptr, 0, st))) return rc;
         if ((rc = keds_layernorm_impl(x, w, nullptr, 1, k.ln2_g, k.ln2_b, t.h, 0, M, w, st))) return rc;
         if ((rc = keds_gemm_bt(t.h, k.fc_w, k.fc_b, t.hid, M, 4 * w, w, KEDS_EPI_BIAS_QGELU_BF16, nullptr, 0, st))) return rc;

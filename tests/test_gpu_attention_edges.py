@@ -3,6 +3,7 @@ the bounds; tests/test_host_attention_check.py: proof that the bound catches one
 
 B = 3, H = 3 everywhere: nine workgroups hit every value of the odd-tile wave rotation, an odd head count catches a head-stride
 error.  Each test loops the sequence lengths and collects the failing rows of the whole loop before it asserts."""
+import ctypes
 import functools
 
 import pytest
@@ -22,6 +23,8 @@ DTYPE = {"bf16": torch.bfloat16, "fp16": torch.float16, "f32": torch.float32, "x
 ENTRIES = ("bf16", "fp16", "f32", "x3")      # keds_attention_ex, keds_attention_h, keds_attention_f32, keds_attention_x3
 MASKS = pytest.mark.parametrize("causal", [False, True], ids=["full", "causal"])
 X3_OUT_FLOOR, X3_PLANE_FLOOR = 2.0 ** -25, 2.0 ** -24     # attention_check.check_f32: what the split-fp16 format itself implies
+GENERIC, TAIL1, S257 = 1, 2, 3               # KEDS_ATTN_FORM_*
+F_CAUSAL, F_F16, F_Q8, F_PACKED, F_STOP = 1, 2, 4, 8, 16                       # KEDS_ATTN_FLAG_*
 
 
 @functools.lru_cache(maxsize=None)
@@ -44,6 +47,22 @@ def _untouched(t):
     return bool((t == torch.tensor(SENTINEL, dtype=t.dtype, device=t.device)).all())
 
 
+def _recorded(lib):
+    """keds_attention_last_launch -> [form, nkt, nfull, flags, grid, block, lds, q_limit]: what the launch site wrote"""
+    info = (ctypes.c_int * 8)()
+    _lib.check(lib.keds_attention_last_launch(info), "keds_attention_last_launch")
+    return list(info)
+
+
+def _recorded_is_planned(lib, Bn, S, heads, causal, q_limit, f16=0, q8=0, packed=0):
+    """the record of the launch just made equals keds_attention_plan_query under the hook in force, all eight ints -> the record"""
+    plan = (ctypes.c_int * 8)()
+    _lib.check(lib.keds_attention_plan_query(Bn, S, heads, int(causal), q_limit, f16, q8, packed, plan), "keds_attention_plan_query")
+    got = _recorded(lib)
+    assert got == list(plan), f"S{S} causal={causal} q_limit={q_limit} f16={f16} q8={q8} packed={packed}: recorded {got}, planned {list(plan)}"
+    return got
+
+
 def _run(entry, case, q_limit=0):
     """-> (out buffer with guard rows, planes [2, rows + GUARD, D] or None)"""
     lib = _lib.load()
@@ -52,8 +71,10 @@ def _run(entry, case, q_limit=0):
     P, st = _lib.ptr, _lib.stream()
     if entry == "bf16":
         _lib.check(lib.keds_attention_ex(P(case.qkv), P(out), B, S, H, c, q_limit, st), "keds_attention_ex")
+        _recorded_is_planned(lib, B, S, H, c, q_limit)
     elif entry == "fp16":
         _lib.check(lib.keds_attention_h(P(case.qkv), P(out), B, S, H, c, q_limit, st), "keds_attention_h")
+        _recorded_is_planned(lib, B, S, H, c, q_limit, f16=1)
     elif entry == "f32":
         _lib.check(lib.keds_attention_f32(P(case.qkv), P(out), B, S, H, c, q_limit, st), "keds_attention_f32")
     else:
@@ -110,7 +131,8 @@ def _verify(entry, case, regime, out, planes, q_limit=None, tag=""):
 def test_attention_rows_at_every_edge_length(entry, causal, regime):
     """S over every tile edge of every kernel form (1, 2, 16 k +- 1, the dispatch thresholds 32 | 33, 96 | 97, 255 .. 258, 288), all
     rows against float64 per element; 64 guard rows behind the output stay untouched.  At S = 257 the 4-wave tail kernel and the
-    generic kernel (keds_attention_debug 32 / 16) run on the same case."""
+    generic kernel (keds_attention_debug 32 / 16) run on the same case.  The 16-bit entries' launch record equals the plan at every
+    length (_run), and at S = 257 it names the form each hook asks for: a hook that stopped routing fails here, not only in the numerics."""
     lib = _lib.load()
     msgs, worst, worst_at = [], 0.0, None
     for S in ac.S_EDGES:
@@ -122,8 +144,13 @@ def test_attention_rows_at_every_edge_length(entry, causal, regime):
             try:
                 lib.keds_attention_debug(hook)
                 out, planes = _run(entry, case)
+                rec = _recorded(lib)
             finally:
                 lib.keds_attention_debug(0)
+            if S == 257 and not causal and entry in ("bf16", "fp16"):
+                want = {0: [S257, 16, 16], 32: [TAIL1, 16, 16], 16: [GENERIC, 18, 16]}[hook]
+                if rec[:3] != want:
+                    msgs.append(f"S257{tag}: hook {hook} recorded (form, nkt, nfull) {rec[:3]}, wanted {want}")
             m, w = _verify(entry, case, regime, out, planes, tag=tag)
             msgs += m
             if w > worst:
@@ -178,6 +205,8 @@ def test_attention_packed_rows(entry, causal, name, lens, s_max):
     out = _buffer(case.rows, DTYPE[entry])
     fn = lib.keds_attention_packed if entry == "bf16" else lib.keds_attention_packed_h
     _lib.check(fn(_lib.ptr(qkv), _lib.ptr(out), n, s_max, _lib.ptr(offs), H, int(causal), _lib.stream()), "keds_attention_packed")
+    rec = _recorded_is_planned(lib, n, s_max, H, causal, s_max, f16=int(entry == "fp16"), packed=1)
+    assert rec[:4] == [GENERIC, {32: 2, 97: 18, 288: 18}[s_max], 0, F_CAUSAL * causal | F_F16 * (entry == "fp16") | F_PACKED], rec
     f = ac.check(out, case)
     report(f"attention_edges.packed.{entry}.{'causal' if causal else 'full'}.{name}", worst_ratio=f.worst)
     assert not f, str(f)
@@ -204,6 +233,20 @@ def test_attention_mx_boundary_inside_a_sample_and_a_tile(S, causal, rows8):
     s8 = torch.full((d // 128, rows8, 4), 127, dtype=torch.uint8, device="cuda")
     _lib.check(lib.keds_attention_mx(_lib.ptr(qkv), _lib.ptr(out), B, S, Hm, int(causal), S, _lib.ptr(q8), _lib.ptr(s8), rows8,
                                      _lib.stream()), "keds_attention_mx")
+    rec = _recorded_is_planned(lib, B, S, Hm, causal, S, q8=1)
+    assert rec[3] & F_Q8 and rec[0] == (S257 if S == 257 else GENERIC), rec
+    if S == 257:                        # hook 32 with MXFP8 rows: no tail kernel for them, the generic kernel with 16 unmasked tiles
+        out32, q32, s32 = torch.full_like(out, SENTINEL), torch.zeros_like(q8), torch.full_like(s8, 127)
+        try:
+            lib.keds_attention_debug(32)
+            _lib.check(lib.keds_attention_mx(_lib.ptr(qkv), _lib.ptr(out32), B, S, Hm, int(causal), S, _lib.ptr(q32), _lib.ptr(s32), rows8,
+                                             _lib.stream()), "keds_attention_mx (hook 32)")
+            rec32 = _recorded_is_planned(lib, B, S, Hm, causal, S, q8=1)
+        finally:
+            lib.keds_attention_debug(0)
+        assert rec32[:4] == [GENERIC, 18, 16, F_Q8], rec32
+        assert _untouched(out32[:rows8]) and _untouched(out32[B * S:])
+        assert rel_l2(_dequantize(q32, s32), ref[:rows8].float()) <= 4e-2
     assert torch.equal(out[rows8:B * S], ref[rows8:])
     assert _untouched(out[:rows8]) and _untouched(out[B * S:])
     got = _dequantize(q8, s8)

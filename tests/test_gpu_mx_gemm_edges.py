@@ -3,8 +3,8 @@ bound and the MX-output checks; tests/test_host_mx_check.py: proof that they cat
 the neighbouring block or row, side data of the previous tile, two interchanged MX blocks, a block exponent one too small, ...).
 
 All calls go through keds_gemm_mxfp8_ex on operands built directly in the kernels' format; every case asserts the kernel form, grid
-and tile count that keds_gemm_mxfp8_last_launch recorded, so a shape the dispatcher sends elsewhere fails instead of testing the wrong
-kernel.  Outputs, the MX copy [q_pad = M + 256, N], its scale bytes, the statistics and the statistics buffer to clear sit in
+and tile count that keds_gemm_mxfp8_last_launch recorded (and that keds_gemm_mxfp8_plan_query plans the same for this device), so a shape
+the dispatcher sends elsewhere fails instead of testing the wrong kernel.  Outputs, the MX copy [q_pad = M + 256, N], its scale bytes, the statistics and the statistics buffer to clear sit in
 sentinel-filled buffers with 256 guard rows that must survive; the operands' scale slabs carry pad rows with a gross scale (every
 regime but `random`), the operands themselves NaN guard rows.  One reference per (shape, regime) is shared by all epilogues and
 forms.  Each test collects every failure before it asserts; the worst bound ratio per (form, epilogue, regime) goes to the metrics log."""
@@ -112,6 +112,9 @@ def _launch(case, epi, debug=0):
         rc = lib.keds_gemm_mxfp8_ex(P(aq), P(as_), m_pad, P(wq), P(ws), n_pad, P(bias), P(out), M, N, case.K, epi, P(aux), P(aux2), P(q), P(qs),
                                     q_pad, _lib.stream())
         _lib.check(lib.keds_gemm_mxfp8_last_launch(info), "keds_gemm_mxfp8_last_launch")
+        plan = (ctypes.c_int * 4)()            # ... and what the planner says of this call on this device, under the same debug value
+        _lib.check(lib.keds_gemm_mxfp8_plan_query(epi, M, N, case.K, torch.cuda.get_device_properties(0).multi_processor_count, plan),
+                   "keds_gemm_mxfp8_plan_query")
     finally:
         lib.keds_mxfp8_debug(0)
     try:
@@ -120,6 +123,8 @@ def _launch(case, epi, debug=0):
     except RuntimeError as e:             # a failed launch or a device fault: nothing more of this session may run on the card
         pytest.exit(f"{case.name} {mc.NAMES[epi]} debug={debug}: {e}", returncode=3)
     bad, res = [], {}
+    if tuple(info) != tuple(plan):
+        bad.append(f"recorded (form, grid, tiles, persistent) {tuple(info)} is not the plan {tuple(plan)}")
     if out is not None:
         if not _sent(out[M:], SENT):
             bad.append("output rows >= M written")

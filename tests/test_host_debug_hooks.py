@@ -101,3 +101,16 @@ def test_the_stamp_buffers_and_the_filler_switch_left_the_library(lib):
     for name in ("keds_merge_stamp_buffer", "keds_attention_stamp_buffer", "keds_tower_fill_enable"):
         assert not hasattr(raw, name), name
         assert name not in _lib.SIGNATURES
+
+
+def test_the_attention_stop_event_protocol_left_the_library_and_the_plan_entries_arrived(lib):
+    """keds_attention_stop_event / keds_attention_stop_event_taken were C++ symbols (mangled: no dlsym by their plain names), so the
+    library's bytes are searched: its symbol and string tables must not name them.  The event is an argument of keds_attention16 now."""
+    raw = ctypes.CDLL(_lib.LIB_PATH)
+    image = open(_lib.LIB_PATH, "rb").read()
+    assert b"keds_attention16" in image                          # (the probe finds what is there)
+    for gone in (b"keds_attention_stop_event_taken", b"keds_attention_stop_event"):
+        assert gone not in image, gone
+    for name in ("keds_attention_plan_query", "keds_attention_last_launch", "keds_gemm_mxfp8_plan_query"):
+        assert hasattr(raw, name), name
+        assert name in _lib.SIGNATURES
