@@ -30,7 +30,9 @@ extern "C" {
 #define KEDS_E_LAUNCH (-2)   /* HIP launch or runtime error */
 #define KEDS_E_WORKSPACE (-3)/* workspace too small */
 
-#define KEDS_ABI_VERSION 12       /* 12: keds_attention_plan_query, keds_attention_last_launch and keds_gemm_mxfp8_plan_query (every 16-bit attention and
+#define KEDS_ABI_VERSION 13       /* 13: keds_cross_attn_core, keds_cross_core_f32, keds_knowledge_pack_rows, keds_place_token (the knowledge stream's
+                                     kernels one at a time; the module paths launch through the same helpers);
+                                     12: keds_attention_plan_query, keds_attention_last_launch and keds_gemm_mxfp8_plan_query (every 16-bit attention and
                                      MXFP8 GEMM launch is planned by one pure host function, as the bf16 GEMMs are);
                                      11: keds_merge_stamp_buffer, keds_attention_stamp_buffer and keds_tower_fill_enable left the library; the debug
                                      hooks refuse the timing-only variants they no longer offer (last at 14f64ac);
@@ -192,7 +194,10 @@ int keds_gather_rows(const float* db, int dim, const int64_t* idx, int64_t count
 
 /* full gallery ranking for the recall metric (src/eval_utils.py:1040-1067):
  * order[q,:] = stable argsort of (1 - ref[q] . gallery[g]) ascending.  Up to 8192 gallery rows sort in LDS; larger
- * galleries (ImageNet domain-conversion targets) sort 8192-row chunks and merge the runs in global memory. */
+ * galleries (ImageNet domain-conversion targets) sort 8192-row chunks and merge the runs in global memory.
+ * The call leaves dist fp32 [nq, ng] (the distances it sorted) in the first nq * ng floats of `workspace`; order[q,:] is the
+ * ascending order of the 64-bit keys (orderable(bits of dist[q,g]) << 32 | g), orderable(u) = ~u for a set sign bit and
+ * u | 0x80000000 otherwise: -0 before +0, ties by the smaller g, a NaN where its sign bit puts it (beyond +-inf). */
 size_t keds_rank_gallery_workspace_bytes(int nq, int ng);
 int keds_rank_gallery(const float* ref, int nq, const float* gallery, int ng, int dim,
                       int32_t* order, void* workspace, size_t workspace_bytes, void* stream);
@@ -716,6 +721,17 @@ size_t keds_crossformer_fused_bytes(const keds_crossformer_params* p);
 int keds_crossformer_fuse(const keds_crossformer_params* p, void* buffer, size_t buffer_bytes, keds_crossformer_fused* out,
                           void* stream);
 
+/* The kernels of the stream one at a time (what keds_crossformer_forward and keds_knowledge_run launch, through the same
+ * helpers); bad arguments return KEDS_E_ARG before any launch.
+ * keds_cross_attn_core: single-query attention, dim_head 64: Q bf16 [B, 64 heads], Kp / Vp bf16 rows [B K] of stride kv_ld
+ *   elements (kv_ld >= 64 heads: the fused form keeps every layer's k | v side by side), out bf16 [B, 64 heads]; K in [1, 32].
+ * keds_knowledge_pack_rows: rows bf16 [B (1 + 2 K), dim] = [q; nbr_img; nbr_txt] (fp32, 16-byte aligned), dim % 8 == 0.
+ * keds_place_token: tokens[b, slot, :] = src[b, :] for tokens fp32 [B, nslots, dim], 0 <= slot < nslots. */
+int keds_cross_attn_core(const void* Q, const void* Kp, const void* Vp, void* out, int B, int K, int heads, int kv_ld, void* stream);
+int keds_knowledge_pack_rows(const float* q, const float* nbr_img, const float* nbr_txt, void* rows, int B, int K, int dim,
+                             void* stream);
+int keds_place_token(const float* src, float* tokens, int B, int dim, int slot, int nslots, void* stream);
+
 size_t keds_knowledge_workspace_bytes(const keds_knowledge_params* p, int B, int K);
 /* one stream of eval_utils.py:661-672: q [B,dim] fp32, nbr_img / nbr_txt [B,K,dim] fp32 ->
  * tokens_out [B,3,dim] fp32 = [retrieval_fuse(m, I, I), text_condition(m, T, T), m], m = img2text(q),
@@ -804,6 +820,10 @@ int keds_im2col_f32(const float* image, float* out, int B, int R, int P, int Kpa
 size_t keds_knowledge_f32_workspace_bytes(const keds_knowledge_params* p, int B, int K);
 int keds_knowledge_run_f32(const keds_knowledge_params* p, const float* q, const float* nbr_img, const float* nbr_txt, int B,
                            int K, float* tokens_out, void* workspace, size_t workspace_bytes, void* stream);
+
+/* the fp32 stream's single-query attention core alone: Q fp32 [B, 64 heads], Kp / Vp fp32 [B K, 64 heads] -> out fp32
+ * [B, 64 heads]; K in [1, 64] */
+int keds_cross_core_f32(const float* Q, const float* Kp, const float* Vp, float* out, int B, int K, int heads, void* stream);
 
 #ifdef __cplusplus
 }

@@ -17,7 +17,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "csrc", "libkeds_hip.so")
 
 # ---- constants mirrored from keds_hip.h ------------------------------------------------------
-ABI_VERSION = 12
+ABI_VERSION = 13
 METRIC_L2, METRIC_IP = 0, 1
 EPI_BIAS_BF16, EPI_BIAS_QGELU_BF16, EPI_BIAS_RELU_BF16, EPI_BIAS_RESID_F32, EPI_BIAS_F32, EPI_PATCH_F32 = range(6)
 EPI_LN_BIAS_BF16, EPI_LN_QGELU_BF16, EPI_RESID_STATS_F32, EPI_RESID_STATS_F16 = 6, 7, 8, 9
@@ -270,6 +270,11 @@ SIGNATURES = {
     "keds_crossformer_forward": (i32, [C.POINTER(CrossFormerParams), vp, vp, vp, i32, i32, vp, vp, sz, vp]),
     "keds_crossformer_fused_bytes": (sz, [C.POINTER(CrossFormerParams)]),
     "keds_crossformer_fuse": (i32, [C.POINTER(CrossFormerParams), vp, sz, C.POINTER(CrossFormerFused), vp]),
+    # the knowledge stream's kernels one at a time (tests/test_gpu_knowledge_metric_kernels_edges.py, ABI 13)
+    "keds_cross_attn_core": (i32, [vp, vp, vp, vp, i32, i32, i32, i32, vp]),
+    "keds_cross_core_f32": (i32, [vp, vp, vp, vp, i32, i32, i32, vp]),
+    "keds_knowledge_pack_rows": (i32, [vp, vp, vp, vp, i32, i32, i32, vp]),
+    "keds_place_token": (i32, [vp, vp, i32, i32, i32, i32, vp]),
     "keds_knowledge_workspace_bytes": (sz, [C.POINTER(KnowledgeParams), i32, i32]),
     "keds_knowledge_run": (i32, [C.POINTER(KnowledgeParams), vp, vp, vp, i32, i32, vp, vp, sz, vp]),
 }

@@ -562,6 +562,11 @@ __global__ __launch_bounds__(256) void cross_core_f32_kernel(const float* __rest
     out[(size_t)b * inner + h * 64 + lane] = o / sum;
 }
 
+int launch_core_f32(const float* Q, const float* Kp, const float* Vp, float* out, int B, int K, int heads, hipStream_t st) {
+    cross_core_f32_kernel<<<(B * heads + 3) / 4, 256, 0, st>>>(Q, Kp, Vp, out, B, K, heads);
+    return keds_check_launch("cross_core_f32_kernel");
+}
+
 struct KnowF32Ws {
     float *x, *h1, *h2, *y, *qp, *kp, *vp, *core, *qt;
     size_t bytes;
@@ -601,8 +606,7 @@ int crossformer_f32(const keds_crossformer_params* p, const float* q, long long 
         if ((rc = keds_gemm_f32(q, ldq, (const float*)c.wq, c.bq, w.qp, inner, B, inner, dim, F32_EPI_BIAS, nullptr, 0, st))) return rc;
         if ((rc = keds_gemm_f32(kv, dim, (const float*)c.wk, c.bk, w.kp, inner, B * K, inner, dim, F32_EPI_BIAS, nullptr, 0, st))) return rc;
         if ((rc = keds_gemm_f32(kv, dim, (const float*)c.wv, c.bv, w.vp, inner, B * K, inner, dim, F32_EPI_BIAS, nullptr, 0, st))) return rc;
-        cross_core_f32_kernel<<<(B * p->heads + 3) / 4, 256, 0, st>>>(w.qp, w.kp, w.vp, w.core, B, K, p->heads);
-        if ((rc = keds_check_launch("cross_core_f32_kernel"))) return rc;
+        if ((rc = launch_core_f32(w.qp, w.kp, w.vp, w.core, B, K, p->heads, st))) return rc;
         float* dst = last ? out : w.qt;
         const long long ldd = last ? ldo : dim;
         if ((rc = keds_gemm_f32(w.core, inner, (const float*)c.wo, c.bo, dst, ldd, B, dim, inner, F32_EPI_BIAS, nullptr, 0, st))) return rc;
@@ -612,6 +616,12 @@ int crossformer_f32(const keds_crossformer_params* p, const float* q, long long 
     return KEDS_OK;
 }
 }  // namespace
+
+extern "C" int keds_cross_core_f32(const float* Q, const float* Kp, const float* Vp, float* out, int B, int K, int heads, void* stream) {
+    KEDS_REQUIRE(Q && Kp && Vp && out && B > 0 && heads >= 1, "keds_cross_core_f32: bad argument");
+    KEDS_REQUIRE(K >= 1 && K <= 64, "keds_cross_core_f32: K=%d must be in [1,64]", K);
+    return launch_core_f32(Q, Kp, Vp, out, B, K, heads, (hipStream_t)stream);
+}
 
 extern "C" size_t keds_knowledge_f32_workspace_bytes(const keds_knowledge_params* p, int B, int K) {
     if (!p || B <= 0 || K <= 0) return 0;

@@ -97,6 +97,24 @@ __global__ __launch_bounds__(256) void fold_qo_kernel(const bf16_t* __restrict__
 
 size_t rpad(size_t r) { return keds_align_up(r, 128); }
 
+// the launches of the three kernels above: the module paths and the stand-alone entries share them
+int launch_core(const bf16_t* Q, const bf16_t* Kp, const bf16_t* Vp, bf16_t* out, int B, int K, int heads, int kv_ld,
+                hipStream_t st) {
+    KedsProfScope prof(KEDS_PROF_OTHER, st);
+    cross_attn_core_kernel<<<(B * heads + 3) / 4, 256, 0, st>>>(Q, Kp, Vp, out, B, K, heads, kv_ld);
+    return keds_check_launch("cross_attn_core_kernel");
+}
+int launch_place(const float* src, float* tokens, int B, int dim, int slot, int nslots, hipStream_t st) {
+    place_token_kernel<<<(B * dim + 255) / 256, 256, 0, st>>>(src, tokens, B, dim, slot, nslots);
+    return keds_check_launch("place_token_kernel");
+}
+int launch_pack(const float* q, const float* ni, const float* nt, bf16_t* rows, int B, int K, int dim, hipStream_t st) {
+    KedsProfScope prof(KEDS_PROF_OTHER, st);
+    const long long nq = (long long)B * dim, nn = (long long)B * K * dim;
+    pack_rows_kernel<<<(unsigned)(((nq + 2 * nn) / 8 + 255) / 256), 256, 0, st>>>(q, ni, nt, rows, nq, nn);
+    return keds_check_launch("pack_rows_kernel");
+}
+
 int check_i2t(const keds_im2text_params* p, const char* who) {
     if (!p || p->n_layer < 1 || p->n_layer > 4 || !p->out_w) {
         keds_set_error("%s: bad IM2TEXT parameters", who);
@@ -170,13 +188,8 @@ int xf_run(const keds_crossformer_params* p, const void* q_bf, const void* k_bf,
         if ((rc = keds_gemm_bt(qin, c.wq, c.bq, s.Qp, B, inner, dim, KEDS_EPI_BIAS_BF16, nullptr, 0, stream))) return rc;
         if ((rc = keds_gemm_bt(k_bf, c.wk, c.bk, s.Kp, BK, inner, dim, KEDS_EPI_BIAS_BF16, nullptr, 0, stream))) return rc;
         if ((rc = keds_gemm_bt(v_bf, c.wv, c.bv, s.Vp, BK, inner, dim, KEDS_EPI_BIAS_BF16, nullptr, 0, stream))) return rc;
-        {
-            KedsProfScope prof(KEDS_PROF_OTHER, st);
-            cross_attn_core_kernel<<<(B * p->heads + 3) / 4, 256, 0, st>>>((const bf16_t*)s.Qp, (const bf16_t*)s.Kp,
-                                                                           (const bf16_t*)s.Vp, (bf16_t*)s.att, B, K,
-                                                                           p->heads, inner);
-            if ((rc = keds_check_launch("cross_attn_core_kernel"))) return rc;
-        }
+        if ((rc = launch_core((const bf16_t*)s.Qp, (const bf16_t*)s.Kp, (const bf16_t*)s.Vp, (bf16_t*)s.att, B, K, p->heads, inner, st)))
+            return rc;
         if (l == p->layers - 1) {
             if ((rc = keds_gemm_bt(s.att, c.wo, c.bo, out_f, B, dim, inner, KEDS_EPI_BIAS_F32, nullptr, 0, stream))) return rc;
         } else {
@@ -224,13 +237,8 @@ int xf_run_fused(const keds_crossformer_params* p, const void* q_bf, const void*
                 return rc;
         } else if ((rc = keds_gemm_bt(s.att, f->wqn[l], f->bqn[l], s.Qp, B, inner, inner, KEDS_EPI_BIAS_BF16, nullptr, 0, st)))
             return rc;
-        {
-            KedsProfScope prof(KEDS_PROF_OTHER, st);
-            const bf16_t* kp = (const bf16_t*)s.KV + (size_t)l * 2 * inner;
-            cross_attn_core_kernel<<<(B * p->heads + 3) / 4, 256, 0, st>>>((const bf16_t*)s.Qp, kp, kp + inner, (bf16_t*)s.att, B, K,
-                                                                           p->heads, kv_ld);
-            if ((rc = keds_check_launch("cross_attn_core_kernel"))) return rc;
-        }
+        const bf16_t* kp = (const bf16_t*)s.KV + (size_t)l * 2 * inner;
+        if ((rc = launch_core((const bf16_t*)s.Qp, kp, kp + inner, (bf16_t*)s.att, B, K, p->heads, kv_ld, st))) return rc;
     }
     const keds_cross_layer_params& last = p->layer[p->layers - 1];
     return keds_gemm_bt_ex(s.att, inner, last.wo, last.bo, out_f, ld_out, B, dim, inner, KEDS_EPI_BIAS_F32, nullptr, 0, st);
@@ -283,6 +291,27 @@ extern "C" int keds_crossformer_fuse(const keds_crossformer_params* p, void* buf
         }
     }
     return keds_check_launch("keds_crossformer_fuse");
+}
+
+// ---- the stream's kernels one at a time (keds_hip.h) ---------------------------------------------
+extern "C" int keds_cross_attn_core(const void* Q, const void* Kp, const void* Vp, void* out, int B, int K, int heads, int kv_ld,
+                                    void* stream) {
+    KEDS_REQUIRE(Q && Kp && Vp && out && B > 0 && heads >= 1, "keds_cross_attn_core: bad argument");
+    KEDS_REQUIRE(K >= 1 && K <= 32, "keds_cross_attn_core: K=%d must be in [1,32]", K);
+    KEDS_REQUIRE(kv_ld >= 64 * heads, "keds_cross_attn_core: kv_ld=%d is less than 64 heads", kv_ld);
+    return launch_core((const bf16_t*)Q, (const bf16_t*)Kp, (const bf16_t*)Vp, (bf16_t*)out, B, K, heads, kv_ld, (hipStream_t)stream);
+}
+
+extern "C" int keds_knowledge_pack_rows(const float* q, const float* nbr_img, const float* nbr_txt, void* rows, int B, int K, int dim,
+                                        void* stream) {
+    KEDS_REQUIRE(q && nbr_img && nbr_txt && rows && B > 0 && K >= 1 && dim > 0, "keds_knowledge_pack_rows: bad argument");
+    KEDS_REQUIRE(dim % 8 == 0, "keds_knowledge_pack_rows: dim=%d must be a multiple of 8", dim);
+    return launch_pack(q, nbr_img, nbr_txt, (bf16_t*)rows, B, K, dim, (hipStream_t)stream);
+}
+
+extern "C" int keds_place_token(const float* src, float* tokens, int B, int dim, int slot, int nslots, void* stream) {
+    KEDS_REQUIRE(src && tokens && B > 0 && dim > 0 && nslots >= 1 && slot >= 0 && slot < nslots, "keds_place_token: bad argument");
+    return launch_place(src, tokens, B, dim, slot, nslots, (hipStream_t)stream);
 }
 
 // ---- standalone IM2TEXT ------------------------------------------------------------------------
@@ -411,12 +440,7 @@ extern "C" int keds_knowledge_run(const keds_knowledge_params* p, const float* q
         // inputs, three IM2TEXT GEMMs (the last one writes the bf16 rows AND token slot 2), and per CrossFormer one k/v
         // GEMM for all layers + (query GEMM, attention core) per layer + the output GEMM straight into its token slot.
         // The two CrossFormer chains are independent: text_condition runs on the side lane beside retrieval_fuse.
-        {
-            KedsProfScope prof(KEDS_PROF_OTHER, st);
-            const long long nq = (long long)B * dim, nn = (long long)BK * dim;
-            pack_rows_kernel<<<(unsigned)(((nq + 2 * nn) / 8 + 255) / 256), 256, 0, st>>>(q, nbr_img, nbr_txt, rows, nq, nn);
-            if ((rc = keds_check_launch("pack_rows_kernel"))) return rc;
-        }
+        if ((rc = launch_pack(q, nbr_img, nbr_txt, rows, B, K, dim, st))) return rc;
         char* hbuf[2] = {w.i2t, w.i2t + keds_align_up(rpad(R) * p->i2t.middle * 2, 256)};
         const void* cur = rows;
         int cur_dim = p->i2t.dim_in;
@@ -447,15 +471,13 @@ extern "C" int keds_knowledge_run(const keds_knowledge_params* p, const float* q
     if ((rc = keds_cast_bf16(nbr_txt, rows + (size_t)(B + BK) * dim, (int64_t)BK * dim, stream))) return rc;
     if ((rc = i2t_run(&p->i2t, rows, R, w.map_f, w.i2t, stream))) return rc;
     if ((rc = keds_cast_bf16(w.map_f, w.map_bf, (int64_t)R * dim, stream))) return rc;
-    place_token_kernel<<<(B * dim + 255) / 256, 256, 0, st>>>(w.map_f, tokens_out, B, dim, 2, 3);
-    if ((rc = keds_check_launch("place_token_kernel"))) return rc;
+    if ((rc = launch_place(w.map_f, tokens_out, B, dim, 2, 3, st))) return rc;
     const bf16_t* map_bf = (const bf16_t*)w.map_bf;
     for (int which = 0; which < 2; ++which) {
         const keds_crossformer_params* xf = which == 0 ? &p->fuse : &p->cond;
         const bf16_t* nb = map_bf + (size_t)(B + which * BK) * dim;
         if ((rc = xf_run(xf, map_bf, nb, nb, B, K, w.outf, w.xf, stream))) return rc;
-        place_token_kernel<<<(B * dim + 255) / 256, 256, 0, st>>>(w.outf, tokens_out, B, dim, which, 3);
-        if ((rc = keds_check_launch("place_token_kernel"))) return rc;
+        if ((rc = launch_place(w.outf, tokens_out, B, dim, which, 3, st))) return rc;
     }
     return KEDS_OK;
 }

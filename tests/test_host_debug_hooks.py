@@ -114,3 +114,10 @@ def test_the_attention_stop_event_protocol_left_the_library_and_the_plan_entries
     for name in ("keds_attention_plan_query", "keds_attention_last_launch", "keds_gemm_mxfp8_plan_query"):
         assert hasattr(raw, name), name
         assert name in _lib.SIGNATURES
+
+
+def test_the_knowledge_stream_kernels_have_entries_of_their_own(lib):
+    raw = ctypes.CDLL(_lib.LIB_PATH)
+    for name in ("keds_cross_attn_core", "keds_cross_core_f32", "keds_knowledge_pack_rows", "keds_place_token"):
+        assert hasattr(raw, name), name
+        assert name in _lib.SIGNATURES
