@@ -30,7 +30,9 @@ extern "C" {
 #define KEDS_E_LAUNCH (-2)   /* HIP launch or runtime error */
 #define KEDS_E_WORKSPACE (-3)/* workspace too small */
 
-#define KEDS_ABI_VERSION 13       /* 13: keds_cross_attn_core, keds_cross_core_f32, keds_knowledge_pack_rows, keds_place_token (the knowledge stream's
+#define KEDS_ABI_VERSION 14       /* 14: keds_attention_f32_packed, keds_attention_x3_packed (the fp32 and split-fp16 attention on packed rows, one call at a
+                                     time; the tower passes launch through the same helpers);
+                                     13: keds_cross_attn_core, keds_cross_core_f32, keds_knowledge_pack_rows, keds_place_token (the knowledge stream's
                                      kernels one at a time; the module paths launch through the same helpers);
                                      12: keds_attention_plan_query, keds_attention_last_launch and keds_gemm_mxfp8_plan_query (every 16-bit attention and
                                      MXFP8 GEMM launch is planned by one pure host function, as the bf16 GEMMs are);
@@ -813,6 +815,13 @@ int keds_attention_f32(const float* qkv, float* out, int B, int S, int heads, in
  * overflow (nullable int on the device): raised when |q / 8|, |k| or |v| >= 65504.  Reference: src/model/model.py:319-321 */
 int keds_attention_x3(const float* qkv, float* out, void* pair, int64_t plane, int B, int S, int heads, int causal, int q_limit,
                       int* overflow, void* stream);
+/* the two on PACKED rows (keds_attention_packed): sample b is rows [seq_off[b], seq_off[b + 1]) of qkv / out (device int32 [B + 1],
+ * lengths 1 .. s_max <= 288), every query row of every sample; what keds_text_run_packed launches in the fp32 and fp32x3 flows.
+ * x3: `plane` is the distance of the two planes in elements and must hold every packed row (the caller's to size: the row count
+ * lives on the device). */
+int keds_attention_f32_packed(const float* qkv, float* out, int B, int s_max, const int32_t* seq_off, int heads, int causal, void* stream);
+int keds_attention_x3_packed(const float* qkv, float* out, void* pair, int64_t plane, int B, int s_max, const int32_t* seq_off, int heads,
+                             int causal, int* overflow, void* stream);
 /* keds_im2col with an fp32 patch matrix [B*G, Kpad] (Kpad % 16 == 0) */
 int keds_im2col_f32(const float* image, float* out, int B, int R, int P, int Kpad, void* stream);
 /* keds_knowledge_run with EVERY weight pointer of the params an FP32 array (per-layer weights; `fused` unused): one stream

@@ -17,7 +17,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "csrc", "libkeds_hip.so")
 
 # ---- constants mirrored from keds_hip.h ------------------------------------------------------
-ABI_VERSION = 13
+ABI_VERSION = 14
 METRIC_L2, METRIC_IP = 0, 1
 EPI_BIAS_BF16, EPI_BIAS_QGELU_BF16, EPI_BIAS_RELU_BF16, EPI_BIAS_RESID_F32, EPI_BIAS_F32, EPI_PATCH_F32 = range(6)
 EPI_LN_BIAS_BF16, EPI_LN_QGELU_BF16, EPI_RESID_STATS_F32, EPI_RESID_STATS_F16 = 6, 7, 8, 9
@@ -224,6 +224,9 @@ SIGNATURES = {
     "keds_gemm_f32": (i32, [vp, i64, vp, vp, vp, i64, i32, i32, i32, i32, vp, i32, vp]),
     "keds_attention_f32": (i32, [vp, vp, i32, i32, i32, i32, i32, vp]),
     "keds_attention_x3": (i32, [vp, vp, vp, i64, i32, i32, i32, i32, i32, vp, vp]),
+    # packed rows of the fp32 / split-fp16 attention one call at a time (tests/test_gpu_tower_compositions.py, ABI 14)
+    "keds_attention_f32_packed": (i32, [vp, vp, i32, i32, vp, i32, i32, vp]),
+    "keds_attention_x3_packed": (i32, [vp, vp, vp, i64, i32, i32, vp, i32, i32, vp, vp]),
     "keds_im2col_f32": (i32, [vp, vp, i32, i32, i32, i32, vp]),
     "keds_knowledge_f32_workspace_bytes": (sz, [C.POINTER(KnowledgeParams), i32, i32]),
     "keds_knowledge_run_f32": (i32, [C.POINTER(KnowledgeParams), vp, vp, vp, i32, i32, vp, vp, sz, vp]),

@@ -373,6 +373,15 @@ int keds_attention_x3_impl(const float* qkv, float* out, void* pair, int64_t pla
     return keds_check_launch("attention_x3_kernel");
 }
 
+// packed rows one call at a time (tests/test_gpu_tower_compositions.py): what tower_forward_x3 launches under PackedRows
+extern "C" int keds_attention_x3_packed(const float* qkv, float* out, void* pair, int64_t plane, int B, int s_max, const int32_t* seq_off,
+                                        int heads, int causal, int* overflow, void* stream) {
+    KEDS_REQUIRE(qkv && (out || pair) && seq_off && B > 0 && heads > 0, "keds_attention_x3_packed: bad argument");
+    KEDS_REQUIRE(s_max >= 1 && s_max <= 288, "keds_attention_x3_packed: s_max=%d unsupported (1..288)", s_max);
+    KEDS_REQUIRE(!pair || plane > 0, "keds_attention_x3_packed: the planes need their stride");
+    return keds_attention_x3_impl(qkv, out, pair, plane, B, s_max, heads, causal, s_max, overflow, seq_off, stream);
+}
+
 extern "C" int keds_attention_x3(const float* qkv, float* out, void* pair, int64_t plane, int B, int S, int heads, int causal,
                                  int q_limit, int* overflow, void* stream) {
     return keds_attention_x3_impl(qkv, out, pair, plane, B, S, heads, causal, q_limit, overflow, nullptr, stream);

@@ -329,6 +329,14 @@ static int attention_f32_impl(const float* qkv, float* out, int B, int S, int he
     return keds_check_launch("attention_f32_kernel");
 }
 
+// packed rows one call at a time (tests/test_gpu_tower_compositions.py): the launch helper keds_tower_forward_f32 uses
+extern "C" int keds_attention_f32_packed(const float* qkv, float* out, int B, int s_max, const int32_t* seq_off, int heads, int causal,
+                                         void* stream) {
+    KEDS_REQUIRE(qkv && out && seq_off && B > 0 && heads > 0, "keds_attention_f32_packed: bad argument");
+    KEDS_REQUIRE(s_max >= 1 && s_max <= 288, "keds_attention_f32_packed: s_max=%d unsupported (1..288)", s_max);
+    return attention_f32_impl(qkv, out, B, s_max, heads, causal, s_max, seq_off, stream);
+}
+
 extern "C" int keds_im2col_f32(const float* image, float* out, int B, int R, int P, int Kpad, void* stream) {
     KEDS_REQUIRE(image && out && B > 0 && P > 0 && R % P == 0, "keds_im2col_f32: bad argument");
     KEDS_REQUIRE(Kpad >= 3 * P * P && Kpad % 16 == 0, "keds_im2col_f32: Kpad must cover 3*P*P and be a multiple of 16");

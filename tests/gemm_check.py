@@ -193,6 +193,33 @@ class Case:
         self.rstd = (self.var + LN_EPS).rsqrt()
         self._e_acc = None
 
+    @classmethod
+    def from_operands(cls, A, W, bias, resid=None, stats=None, csum=None):
+        """The case of GIVEN operands (a link of a tower pass, read back from its buffers): A [M, K], W [N, K] of one operand type, bias
+        fp32 [N] or None, resid [M, N] (what the output held before the launch), stats int64 [M, 2] (the fixed-point pairs the launch
+        read) and csum fp32 [N] for the LayerNorm-folded epilogues.  Never `exact`: every check is by the bound."""
+        c = cls.__new__(cls)
+        c.dtype, c.device, c.regime = A.dtype, A.device, "operands"
+        c.tile_k = 16 if c.dtype == F32 else TILE_K
+        (c.M, c.K), c.N = A.shape, W.shape[0]
+        c.name = f"{c.M}x{c.N}x{c.K}.operands"
+        c.A, c.W = A, W
+        c.bias = torch.zeros(c.N, device=A.device) if bias is None else bias.float()
+        c.resid = None if resid is None else resid.float()
+        c.pos = None
+        A64, W64 = A.double(), W.double()
+        c.acc = A64 @ W64.t()
+        c.S = A64.abs() @ W64.abs().t()
+        if stats is not None:
+            c.stats, c.csum = stats, csum.float()
+            sf = stats.double() / STAT_SCALE
+            c.mean = sf[:, :1] / c.K
+            c.q = sf[:, 1:] / c.K
+            c.var = (c.q - c.mean.square()).clamp_min(0.0)
+            c.rstd = (c.var + LN_EPS).rsqrt()
+        c._e_acc = None
+        return c
+
     @property
     def exact(self):
         return self.regime == "integer"
@@ -319,6 +346,24 @@ class X3Case:
             if self.extra is not None:
                 self._e_acc = self._e_acc + self.extra
         return self._e_acc
+
+    @classmethod
+    def from_operands(cls, ah, al, wh, wl, w_exp, bias, resid=None):
+        """The case of GIVEN planes (a link of a tower pass): A planes [M, K], W planes [N, K] of W 2^w_exp (fp16), bias fp32 [N] or None,
+        resid fp32 [M, N].  The reference is the three products of the planes themselves; never `exact`."""
+        c = cls.__new__(cls)
+        (c.M, c.K), c.N = ah.shape, wh.shape[0]
+        c.regime, c.device, c.dtype, c.extra, c.p, c.np1 = "operands", ah.device, HF, None, None, c.K // TILE_K
+        c.ah, c.al, c.wh, c.wl, c.w_exp = ah, al, wh, wl, int(w_exp)
+        c.bias = torch.zeros(c.N, device=ah.device) if bias is None else bias.float()
+        c.resid = None if resid is None else resid.float()
+        c.name = f"{c.M}x{c.N}x{c.K}.x3.operands.e{c.w_exp}"
+        sc = 2.0 ** -c.w_exp
+        AH, AL, WH, WL = ah.double(), al.double(), wh.double(), wl.double()
+        c.S = (AH.abs() @ (WH.abs() + WL.abs()).t() + AL.abs() @ WH.abs().t()) * sc
+        c.acc = (AH @ (WH + WL).t() + AL @ WH.t()) * sc
+        c._e_acc = None
+        return c
 
     def spike_share(self):
         """the share of S that K-tile p carries, averaged over the outputs"""

@@ -225,6 +225,32 @@ class MxCase(gc.Case):
         self.rstd = (self.var + gc.LN_EPS).rsqrt()
         self._e_acc = None
 
+    @classmethod
+    def from_operands(cls, aq, a_exp, wq, w_exp, bias, resid=None, stats=None, csum=None):
+        """The case of GIVEN MXFP8 operands (a link of a tower pass, decoded from its buffers): bytes aq [M, K] / wq [N, K] and block
+        exponents [rows, K / 32], bias fp32 [N] or None, resid [M, N] (what the output held), stats int64 [M, 2] (the pairs the launch
+        read) and csum fp32 [N] for the LayerNorm-folded epilogues.  Never `exact`."""
+        c = cls.__new__(cls)
+        (c.M, c.K), c.N = aq.shape, wq.shape[0]
+        c.regime, c.device, c.dtype = "operands", aq.device, BF
+        c.name = f"{c.M}x{c.N}x{c.K}.operands"
+        c.aq, c.a_exp, c.wq, c.w_exp = aq, a_exp, wq, w_exp
+        c.bias = torch.zeros(c.N, device=aq.device) if bias is None else bias.float()
+        c.resid = None if resid is None else resid.float()
+        c.pos = None
+        A64, W64 = dequantize(aq, a_exp), dequantize(wq, w_exp)
+        c.acc = A64 @ W64.t()
+        c.S = A64.abs() @ W64.abs().t()
+        if stats is not None:
+            c.stats, c.csum = stats, csum.float()
+            sf = stats.double() / STAT_SCALE
+            c.mean = sf[:, :1] / c.K
+            c.q = sf[:, 1:] / c.K
+            c.var = (c.q - c.mean.square()).clamp_min(0.0)
+            c.rstd = (c.var + gc.LN_EPS).rsqrt()
+        c._e_acc = None
+        return c
+
     @property
     def exact(self):
         return self.regime.startswith("integer")
