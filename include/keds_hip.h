@@ -30,7 +30,9 @@ extern "C" {
 #define KEDS_E_LAUNCH (-2)   /* HIP launch or runtime error */
 #define KEDS_E_WORKSPACE (-3)/* workspace too small */
 
-#define KEDS_ABI_VERSION 14       /* 14: keds_attention_f32_packed, keds_attention_x3_packed (the fp32 and split-fp16 attention on packed rows, one call at a
+#define KEDS_ABI_VERSION 15       /* 15: keds_tower_plan_query (every tower pass is planned by one pure host function and run from its steps, as the
+                                     GEMM and attention launches are);
+                                     14: keds_attention_f32_packed, keds_attention_x3_packed (the fp32 and split-fp16 attention on packed rows, one call at a
                                      time; the tower passes launch through the same helpers);
                                      13: keds_cross_attn_core, keds_cross_core_f32, keds_knowledge_pack_rows, keds_place_token (the knowledge stream's
                                      kernels one at a time; the module paths launch through the same helpers);
@@ -599,6 +601,65 @@ size_t keds_tower_workspace_bytes_ex(const keds_tower_params* p, int B);   /* kn
  * full-tile launches only (bench.py scales the flops to match). */
 int keds_tower_side_rows(int width, int seq, int B, int fp8);
 int keds_side_lane_enable(int on);            /* run-time override of KEDS_SIDE_STREAM (default: on); results are identical */
+
+/* What a tower pass launches, answered without a GPU from the function the passes themselves run from (csrc/tower_plan.h; ABI 15).
+ *   flow         KEDS_TOWER_FLOW_*; width, heads, seq, causal, layers, B as in keds_tower_params
+ *   tail         KEDS_TOWER_TAIL_*: what is read after the last block -- every row, the CLS rows (last_cls_only), or one read-out
+ *                row per sample (keds_text_run_ex's default flow, keds_text_run_packed)
+ *   packed_rows / packed_valid   packed rows (keds_text_run_packed): the rows the pass runs (rows_total rounded up to 256 where the
+ *                workspace allows) and rows_total; 0, 0: rectangular rows
+ *   taps         the per-block taps of keds_vit_run_tokens
+ *   split        -1: the library's own rule (what keds_tower_side_rows reports) decides whether the remainder rows behind the last
+ *                full 256-row tile are a span of their own; 0 / 1: as given (an MXFP8 tower splits by its row count alone)
+ *   lane         -1: keds_side_lane_enable's setting; 0 / 1: without / with the side lane.  A bf16 / fp16 / fp32x3 pass has a
+ *                remainder span only with the lane
+ * steps (nullable): int32 [max_steps][KEDS_TOWER_STEP_INTS], the first min(*n_steps, max_steps) steps in enqueue order; *n_steps:
+ * the count.  buffers (nullable): int64 [KEDS_TOWER_BUF_COUNT][4] = {id, byte offset in the tower scratch (-1: x, the caller's
+ * stream), bytes (0: not a buffer of this flow), alias-of id}; *workspace_bytes (nullable): keds_tower_workspace_bytes_ex.
+ * A step record: [0] op  [1] layer (-1: none)  [2] weight (0 none, 1 in_proj, 2 out_proj, 3 c_fc, 4 c_proj, 5 / 6 in_proj / c_fc with
+ * their LayerNorm folded in, 7 ln_1, 8 ln_2)  [3] epi: the public epilogue id of a GEMM (KEDS_EPI_* / KEDS_FP8_EPI_* / KEDS_F32_EPI_*),
+ * the output type of a LayerNorm / statistics cast (keds_layernorm_ex), the mode of a gather (0 16-bit rows, 1 fp16 -> fp32, 2 fp32
+ * rows), the source type of a tap (1 fp32, 2 fp16), 1 for a copy that is a 2-D copy  [4] in  [5] its first row  [6] its row step
+ * [7] out  [8] first row  [9] row step  [10] rows  [11] out2: the MXFP8 copy written beside out (its scale buffer: the next id)
+ * [12] fp32x3: rows of one fp16 plane of in / out  [13] statistics buffer read  [14] added into (statistics cast: written)
+ * [15] cleared  [16] their first row  [17] attention: q_limit  [18] rows written as MXFP8  [19] packed rows  [20] gather: rows
+ * outside [0, bound) give NaN  [21] global (packed) row indices  [22] lane (0 the caller's stream, 1 the side lane)  [23] 0.
+ * KEDS_E_ARG for an unknown flow, bad geometry, or packed rows on an MXFP8 / non-causal tower or without a read-out row. */
+#define KEDS_TOWER_FLOW_UNFOLDED 0   /* stand-alone LayerNorm launches (no folded weights) */
+#define KEDS_TOWER_FLOW_BF16 1
+#define KEDS_TOWER_FLOW_FP16 2       /* keds_tower_params.f16 */
+#define KEDS_TOWER_FLOW_FP8 3        /* keds_tower_params.fp8 */
+#define KEDS_TOWER_FLOW_F32 4        /* keds_tower_params.f32 == 1 */
+#define KEDS_TOWER_FLOW_X3 5         /* keds_tower_params.f32 == 2 */
+#define KEDS_TOWER_TAIL_ALL 0
+#define KEDS_TOWER_TAIL_CLS 1
+#define KEDS_TOWER_TAIL_READOUT 2
+#define KEDS_TOWER_OP_ZERO 1         /* memset of rows */
+#define KEDS_TOWER_OP_STATS_CAST 2   /* keds_rowstats_cast_ex */
+#define KEDS_TOWER_OP_QUANT 3        /* keds_quantize_mxfp8 */
+#define KEDS_TOWER_OP_CAST 4         /* fp16 rows -> fp32 rows */
+#define KEDS_TOWER_OP_COPY 5         /* strided rows, device to device */
+#define KEDS_TOWER_OP_SPLIT 6        /* keds_split_f16_pair */
+#define KEDS_TOWER_OP_GATHER 7       /* keds_gather_rows */
+#define KEDS_TOWER_OP_LN 8           /* keds_layernorm_ex */
+#define KEDS_TOWER_OP_LN_PAIR 9      /* keds_layernorm_pair */
+#define KEDS_TOWER_OP_ATTN 10        /* the flow's attention */
+#define KEDS_TOWER_OP_ATTN_FORK 11   /* the same with the side lane forked behind it (the launch's stop event where the form takes one) */
+#define KEDS_TOWER_OP_GEMM16 12      /* keds_gemm_bt_ex2 */
+#define KEDS_TOWER_OP_GEMM_MX 13     /* keds_gemm_mxfp8_ex */
+#define KEDS_TOWER_OP_GEMM_F32 14    /* keds_gemm_f32 */
+#define KEDS_TOWER_OP_GEMM_X3 15     /* keds_gemm_x3 */
+#define KEDS_TOWER_OP_TAP 16         /* a span of the stream written out (keds_vit_run_tokens) */
+#define KEDS_TOWER_OP_FORK 17        /* the side lane waits for the caller's stream */
+#define KEDS_TOWER_OP_JOIN 18        /* the caller's stream waits for the side lane */
+enum { KEDS_TOWER_BUF_NONE = 0, KEDS_TOWER_BUF_X, KEDS_TOWER_BUF_H, KEDS_TOWER_BUF_QKV, KEDS_TOWER_BUF_ATT, KEDS_TOWER_BUF_HID,
+       KEDS_TOWER_BUF_ST1, KEDS_TOWER_BUF_ST2, KEDS_TOWER_BUF_XQ, KEDS_TOWER_BUF_XS, KEDS_TOWER_BUF_AQ, KEDS_TOWER_BUF_AS,
+       KEDS_TOWER_BUF_HQ, KEDS_TOWER_BUF_HS, KEDS_TOWER_BUF_SPLITK, KEDS_TOWER_BUF_LN, KEDS_TOWER_BUF_ATT_C, KEDS_TOWER_BUF_X_C,
+       KEDS_TOWER_BUF_COUNT };
+#define KEDS_TOWER_STEP_INTS 24
+int keds_tower_plan_query(int flow, int width, int heads, int seq, int causal, int layers, int B, int tail, int packed_rows,
+                          int packed_valid, int taps, int split, int lane, int32_t* steps, int max_steps, int* n_steps,
+                          int64_t* buffers, size_t* workspace_bytes);
 
 /* x fp32 [B*seq (padded to 128), width] in place through all residual blocks (model.py:372-373); workspace: rows padded to 256 */
 int keds_tower_forward(const keds_tower_params* p, float* x, int B,

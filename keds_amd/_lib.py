@@ -17,7 +17,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "csrc", "libkeds_hip.so")
 
 # ---- constants mirrored from keds_hip.h ------------------------------------------------------
-ABI_VERSION = 14
+ABI_VERSION = 15
 METRIC_L2, METRIC_IP = 0, 1
 EPI_BIAS_BF16, EPI_BIAS_QGELU_BF16, EPI_BIAS_RELU_BF16, EPI_BIAS_RESID_F32, EPI_BIAS_F32, EPI_PATCH_F32 = range(6)
 EPI_LN_BIAS_BF16, EPI_LN_QGELU_BF16, EPI_RESID_STATS_F32, EPI_RESID_STATS_F16 = 6, 7, 8, 9
@@ -236,6 +236,7 @@ SIGNATURES = {
     "keds_tokenize": (i32, [vp, C.POINTER(C.c_char_p), i32, i32, i32, vp]),
     "keds_tower_side_rows": (i32, [i32, i32, i32, i32]),
     "keds_side_lane_enable": (i32, [i32]),
+    "keds_tower_plan_query": (i32, [i32] * 13 + [vp, i32, C.POINTER(i32), vp, C.POINTER(sz)]),
     "keds_tower_forward": (i32, [C.POINTER(TowerParams), vp, i32, vp, sz, vp]),
     "keds_vit_workspace_bytes": (sz, [C.POINTER(VitParams), i32]),
     "keds_vit_run": (i32, [C.POINTER(VitParams), vp, i32, vp, i32, vp, sz, vp]),

@@ -47,7 +47,7 @@ struct AttnPlan {                       // (an aggregate: the plan and the launc
     int nkt = 0;                        // 16-key tiles the kernel holds: 2, 6, 18; 16 (+ the rank-1 last key) for the two S = 257 forms
     int nfull = 0;                      // key tiles [0, nfull) are known to lie below S and are not masked: 0 or 16
     bool causal = false, f16 = false, q8 = false, packed = false;
-    bool takes_stop_event = false;      // the launch records the caller's event as its stop event (RowLanes, towers.hip)
+    bool takes_stop_event = false;      // the launch records the caller's event as its stop event (the fork behind the attention, towers.hip)
     int grid = 0, block = 0, lds = 0;
     int q_limit = 0;                    // the effective one: query rows computed and stored per sample
     // the layout of keds_attention_last_launch

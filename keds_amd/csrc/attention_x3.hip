@@ -373,7 +373,7 @@ int keds_attention_x3_impl(const float* qkv, float* out, void* pair, int64_t pla
     return keds_check_launch("attention_x3_kernel");
 }
 
-// packed rows one call at a time (tests/test_gpu_tower_compositions.py): what tower_forward_x3 launches under PackedRows
+// packed rows one call at a time (tests/test_gpu_tower_compositions.py): what the x3 tower pass launches under PackedRows
 extern "C" int keds_attention_x3_packed(const float* qkv, float* out, void* pair, int64_t plane, int B, int s_max, const int32_t* seq_off,
                                         int heads, int causal, int* overflow, void* stream) {
     KEDS_REQUIRE(qkv && (out || pair) && seq_off && B > 0 && heads > 0, "keds_attention_x3_packed: bad argument");

@@ -8,6 +8,7 @@
 // (v_mfma_f32_32x32x2_f32: exact fp32 products, fp32 accumulate = an fmaf chain, cdna_hip_programming.md section 3), the
 // residual stream, the LayerNorm output, q / k / v, the attention probabilities and the MLP hidden layer all stay fp32.
 // Throughput is secondary here (the f32 matrix rate is 1/16 of the bf16 one): simple tiles, no side lane, no fused LayerNorm.
+// The tower passes of this flow and of the fp32x3 one (f32 = 2) are planned in tower_plan.h and run by towers.hip like every other.
 //
 //   gemm_f32_kernel       out[M,N] = epilogue(X[M,K] . W[N,K]^T + bias)      model.py:309-326 (in/out projections, MLP), :381 (conv1)
 //   attention_f32_kernel  softmax(q k^T / 8 [+ causal mask]) v per (sample, head) model.py:319-321, nn.MultiheadAttention
@@ -17,11 +18,6 @@
 
 int keds_layernorm_impl(const float* x, long long x_stride, const int* row_map, int row_mul, const float* gamma,
                         const float* beta, void* out, int out_f32, int rows, int dim, hipStream_t st);
-
-int keds_attention_x3_impl(const float* qkv, float* out, void* pair, int64_t plane, int B, int S, int heads, int causal, int q_limit,
-                           int* overflow, const int32_t* seq_off, void* stream);
-extern "C" int keds_attention_x3(const float* qkv, float* out, void* pair, int64_t plane, int B, int S, int heads, int causal,
-                                 int q_limit, int* overflow, void* stream);
 
 namespace {
 
@@ -311,13 +307,12 @@ extern "C" int keds_gemm_f32(const float* A, int64_t lda, const float* W, const 
     return KEDS_E_ARG;
 }
 
-static int attention_f32_impl(const float* qkv, float* out, int B, int S, int heads, int causal, int q_limit, const int32_t* seq_off,
-                              void* stream);
+// (seq_off: packed rows or null; what the tower passes launch, towers.hip)
+int attention_f32_impl(const float* qkv, float* out, int B, int S, int heads, int causal, int q_limit, const int32_t* seq_off, void* stream);
 extern "C" int keds_attention_f32(const float* qkv, float* out, int B, int S, int heads, int causal, int q_limit, void* stream) {
     return attention_f32_impl(qkv, out, B, S, heads, causal, q_limit, nullptr, stream);
 }
-static int attention_f32_impl(const float* qkv, float* out, int B, int S, int heads, int causal, int q_limit, const int32_t* seq_off,
-                              void* stream) {
+int attention_f32_impl(const float* qkv, float* out, int B, int S, int heads, int causal, int q_limit, const int32_t* seq_off, void* stream) {
     KEDS_REQUIRE(qkv && out && B > 0 && heads > 0, "keds_attention_f32: bad argument");
     KEDS_REQUIRE(S >= 1 && S <= 288, "keds_attention_f32: S must be in [1, 288] (got %d)", S);
     const int lds = ((S + 31) / 32 * 32) * (65 + 64) * (int)sizeof(float);           // K and V padded to whole 32-key tiles
@@ -329,7 +324,7 @@ static int attention_f32_impl(const float* qkv, float* out, int B, int S, int he
     return keds_check_launch("attention_f32_kernel");
 }
 
-// packed rows one call at a time (tests/test_gpu_tower_compositions.py): the launch helper keds_tower_forward_f32 uses
+// packed rows one call at a time (tests/test_gpu_tower_compositions.py): the launch helper the fp32 tower pass uses
 extern "C" int keds_attention_f32_packed(const float* qkv, float* out, int B, int s_max, const int32_t* seq_off, int heads, int causal,
                                          void* stream) {
     KEDS_REQUIRE(qkv && out && seq_off && B > 0 && heads > 0, "keds_attention_f32_packed: bad argument");
@@ -346,187 +341,7 @@ extern "C" int keds_im2col_f32(const float* image, float* out, int B, int R, int
     return keds_check_launch("im2col_f32_kernel");
 }
 
-// ---- whole towers ----------------------------------------------------------------------------------------------------
-// scratch of one fp32 tower: ln [M,w] | qkv [M,3w] | att [M,w] | hid [M,4w], all fp32 (1.2 GB at B = 128, ViT-L/14)
-size_t keds_tower_f32_workspace_bytes(int width, int seq, int B) {
-    const size_t M = keds_align_up((size_t)B * seq, 256);
-    return keds_align_up(M * width * 4, 256) + keds_align_up(M * (size_t)width * 3 * 4, 256) + keds_align_up(M * (size_t)width * 4, 256) +
-           keds_align_up(M * (size_t)width * 4 * 4, 256);
-}
-
-int keds_gather_rows_impl(const void* src, void* dst, const int32_t* row, int S, int B, int dim, int mode, hipStream_t st,
-                          bool global_rows = false);
-
-int keds_layernorm_pair_impl(const float* x, long long x_stride, const float* gamma, const float* beta, void* out, long long plane,
-                             int rows, int dim, hipStream_t st, int form = 0);
-
-// keds_tower_params.f32 == 2: the "fp32x3" operating point (round 5).  The same fp32 flow -- fp32 residual stream, fp32
-// LayerNorm / attention / QuickGELU -- with the four block GEMMs on SPLIT fp16 operands (keds_gemm_x3: x = hi + lo to 22 bits,
-// products hi.hi + hi.lo + lo.hi on the fp16 MFMA, fp32 accumulate): fp32-grade results at about a third of the bf16 GEMMs'
-// rate instead of the f32-input MFMA's sixteenth.  The weights arrive as fp16 planes [2][N][K] (keds_split_f16_pair at packing
-// time); LayerNorm writes its output as planes, the attention output is split by a pass of its own, c_fc's epilogue writes the
-// MLP hidden layer as planes.  A value beyond the fp16 range raises the caller's numerics guard (the host falls back to f32 = 1).
-static int tower_forward_x3(const keds_tower_params* p, float* x, int B, void* ws, hipStream_t st, const int32_t* last_rows,
-                            const PackedRows* pk, const KedsTaps* tp) {
-    const int w = p->width, S = p->seq, M = pk ? pk->rows : B * S;
-    const size_t Mp = keds_align_up((size_t)B * S, 256);          // (the buffers are carved for the rectangular layout either way)
-    const int32_t* soff = pk ? pk->off : nullptr;
-    const int gbound = pk ? pk->valid : S;
-    char* base = (char*)ws;
-    _Float16* ln2 = (_Float16*)base;                              // planes [2][Mp][w] (the fp32 flow's ln buffer: same bytes)
-    float* qkv = (float*)(base + keds_align_up(Mp * w * 4, 256));
-    float* att = (float*)((char*)qkv + keds_align_up(Mp * (size_t)w * 3 * 4, 256));
-    _Float16* hid2 = (_Float16*)((char*)att + keds_align_up(Mp * (size_t)w * 4, 256));      // planes [2][Mp][4w]
-    const long long pl = (long long)Mp * w, plh = (long long)Mp * 4 * w;
-    int* guard = keds_numerics_guard();
-    int rc;
-    const long long wq = 3LL * w * w, wo = (long long)w * w, wf = 4LL * w * w;         // elements between a weight's planes
-    // Two lanes, as in the default flow (towers.hip, RowLanes): the rows beyond the last full 256-row tile (ViT-L/14 at B = 128:
-    // 128 of 32,896) are a handful of workgroups per GEMM whose time is pure latency -- 150 us per block when they run between
-    // the full-tile launches.  Rows only meet in the attention: the remainder rows' chain (out-proj, ln_2, MLP, next ln_1, next
-    // in_proj) runs on the side lane beside the same chain on the full tiles; fork behind the attention, join in front of the next.
-    struct Span {
-        size_t r0;
-        int n;
-        hipStream_t st;
-    };
-    const int m_main = M / 256 * 256;
-    KedsSideLane* lane = (m_main > 0 && m_main < M && keds_gemm_splits_rows(M, 3 * w, w)) ? keds_side_lane() : nullptr;
-    Span spans[2] = {{0, lane ? m_main : M, st}, {(size_t)m_main, M - m_main, lane ? lane->s : st}};
-    const int nspan = lane ? 2 : 1;
-    auto pre = [&](const keds_block_params& k, const Span& sp) -> int {               // ln_1 + in_proj
-        int r = keds_layernorm_pair_impl(x + sp.r0 * w, w, k.ln1_g, k.ln1_b, ln2 + sp.r0 * w, pl, sp.n, w, sp.st);
-        if (r) return r;
-        return keds_gemm_x3(ln2 + sp.r0 * w, pl, w, k.qkv_w, wq, k.qkv_b, qkv + sp.r0 * 3 * w, 3 * w, sp.n, 3 * w, w, KEDS_EPI_X3_BIAS_F32, 0, k.x3_exp[0], sp.st);
-    };
-    auto post = [&](const keds_block_params& k, const Span& sp) -> int {              // out-proj + ln_2 + MLP
-        int r;
-        if ((r = keds_gemm_x3(ln2 + sp.r0 * w, pl, w, k.out_w, wo, k.out_b, x + sp.r0 * w, w, sp.n, w, w, KEDS_EPI_X3_RESID_F32, 0, k.x3_exp[1], sp.st))) return r;
-        if ((r = keds_layernorm_pair_impl(x + sp.r0 * w, w, k.ln2_g, k.ln2_b, ln2 + sp.r0 * w, pl, sp.n, w, sp.st))) return r;
-        if ((r = keds_gemm_x3(ln2 + sp.r0 * w, pl, w, k.fc_w, wf, k.fc_b, hid2 + sp.r0 * 4 * w, 4 * w, sp.n, 4 * w, w, KEDS_EPI_X3_QGELU_PAIR, (int)plh, k.x3_exp[2], sp.st))) return r;
-        return keds_gemm_x3(hid2 + sp.r0 * 4 * w, plh, 4 * w, k.proj_w, wf, k.proj_b, x + sp.r0 * w, w, sp.n, w, 4 * w, KEDS_EPI_X3_RESID_F32, 0, k.x3_exp[3], sp.st);
-    };
-    if (lane && (rc = keds_stream_order(st, lane->fork, lane->s))) return rc;
-    for (int i = 0; i < nspan; ++i)
-        if ((rc = pre(p->blocks[0], spans[i]))) return rc;
-    for (int l = 0; l < p->layers; ++l) {
-        const keds_block_params& k = p->blocks[l];
-        const bool last = l == p->layers - 1;
-        if (lane && (rc = keds_stream_order(lane->s, lane->join, st))) return rc;      // every row's q, k, v before the attention
-        if (last && (last_rows || p->last_cls_only)) {
-            // after the last block one row per sample is read (model.py:412 the CLS row; :587-589, 847-849 the read-out row):
-            // attention (all rows for the text tower, the CLS query for the ViT), then the B rows in compact buffers
-            float* att_c = qkv;                                   // [B, w] fp32 each, in the qkv buffer (dead after the attention)
-            float* x_c = qkv + (size_t)B * w;
-            if (last_rows) {
-                if ((rc = keds_attention_x3_impl(qkv, att, nullptr, 0, B, S, p->heads, p->causal, S, guard, soff, st))) return rc;
-                if ((rc = keds_gather_rows_impl(att, att_c, last_rows, gbound, B, w, 2, st, pk != nullptr))) return rc;
-                if ((rc = keds_gather_rows_impl(x, x_c, last_rows, gbound, B, w, 2, st, pk != nullptr))) return rc;
-            } else {
-                if ((rc = keds_attention_x3(qkv, att, nullptr, 0, B, S, p->heads, p->causal, 1, guard, st))) return rc;
-                if (hipMemcpy2DAsync(att_c, (size_t)w * 4, att, (size_t)S * w * 4, (size_t)w * 4, B, hipMemcpyDeviceToDevice, st) != hipSuccess ||
-                    hipMemcpy2DAsync(x_c, (size_t)w * 4, x, (size_t)S * w * 4, (size_t)w * 4, B, hipMemcpyDeviceToDevice, st) != hipSuccess) {
-                    keds_set_error("keds_tower_forward_f32: CLS rows: %s", hipGetErrorString(hipGetLastError()));
-                    return KEDS_E_LAUNCH;
-                }
-            }
-            const long long pc = (long long)keds_align_up((size_t)B, 256) * w;
-            if ((rc = keds_split_f16_pair(att_c, w, B, w, ln2, pc, guard, st))) return rc;
-            if ((rc = keds_gemm_x3(ln2, pc, w, k.out_w, wo, k.out_b, x_c, w, B, w, w, KEDS_EPI_X3_RESID_F32, 0, k.x3_exp[1], st))) return rc;
-            if ((rc = keds_layernorm_pair_impl(x_c, w, k.ln2_g, k.ln2_b, ln2, pc, B, w, st))) return rc;
-            if ((rc = keds_gemm_x3(ln2, pc, w, k.fc_w, wf, k.fc_b, hid2, 4 * w, B, 4 * w, w, KEDS_EPI_X3_QGELU_PAIR, (int)(4 * pc), k.x3_exp[2], st))) return rc;
-            if ((rc = keds_gemm_x3(hid2, 4 * pc, 4 * w, k.proj_w, wf, k.proj_b, x_c, w, B, w, 4 * w, KEDS_EPI_X3_RESID_F32, 0, k.x3_exp[3], st))) return rc;
-            // the caller reads row b of a compact x (text tower) or row b * S (ViT: CLS rows in place)
-            if (hipMemcpy2DAsync(x, (size_t)(last_rows ? w : S * w) * 4, x_c, (size_t)w * 4, (size_t)w * 4, B, hipMemcpyDeviceToDevice, st) != hipSuccess) {
-                keds_set_error("keds_tower_forward_f32: read-out rows: %s", hipGetErrorString(hipGetLastError()));
-                return KEDS_E_LAUNCH;
-            }
-            return KEDS_OK;
-        }
-        // (the attention writes the out-projection's A operand planes itself: no fp32 copy of its output, no split pass)
-        if ((rc = keds_attention_x3_impl(qkv, nullptr, ln2, pl, B, S, p->heads, p->causal, S, guard, soff, st))) return rc;
-        if (lane && (rc = keds_stream_order(st, lane->fork, lane->s))) return rc;
-        for (int i = 0; i < nspan; ++i) {
-            if ((rc = post(k, spans[i]))) return rc;
-            if ((rc = keds_tap_rows(tp, l, p->layers, x, 1, spans[i].r0, spans[i].n, w, spans[i].st))) return rc;
-            if (!last && (rc = pre(p->blocks[l + 1], spans[i]))) return rc;
-        }
-    }
-    return lane ? keds_stream_order(lane->s, lane->join, st) : KEDS_OK;
-}
-
-// last_rows (device int32 [B], nullable): towers.hip, rows_tail -- the text tower's read-out rows; on return x[b] = that row
-// pk (nullable): packed rows of a causal tower with a read-out row per sample (keds_common.h) -- M = pk->rows, last_rows global
-// tp (nullable): per-block taps of the fp32 stream x (keds_vit_run_tokens; the caller clears last_cls_only)
-int keds_tower_forward_f32(const keds_tower_params* p, float* x, int B, void* ws, hipStream_t st, const int32_t* last_rows,
-                           const PackedRows* pk, const KedsTaps* tp) {
-    if (pk && (!p->causal || !last_rows)) {
-        keds_set_error("keds_tower_forward_f32: packed rows need a causal tower with a read-out row per sample");
-        return KEDS_E_ARG;
-    }
-    if (p->f32 == 2) return tower_forward_x3(p, x, B, ws, st, last_rows, pk, tp);
-    const int w = p->width, S = p->seq, M = pk ? pk->rows : B * S;
-    const size_t Mp = keds_align_up((size_t)B * S, 256);          // (the buffers are carved for the rectangular layout either way)
-    const int32_t* soff = pk ? pk->off : nullptr;
-    const int gbound = pk ? pk->valid : S;
-    char* base = (char*)ws;
-    float* ln = (float*)base;
-    float* qkv = (float*)(base + keds_align_up(Mp * w * 4, 256));
-    float* att = (float*)((char*)qkv + keds_align_up(Mp * (size_t)w * 3 * 4, 256));
-    float* hid = (float*)((char*)att + keds_align_up(Mp * (size_t)w * 4, 256));
-    int rc;
-    // packed rows: the zero rows behind the last sample are nobody's queries -- their attention output is cleared once so that they
-    // stay finite through the blocks
-    if (pk && pk->rows > pk->valid &&
-        hipMemsetAsync(att + (size_t)pk->valid * w, 0, (size_t)(pk->rows - pk->valid) * w * sizeof(float), st) != hipSuccess) {
-        keds_set_error("keds_tower_forward_f32: packed rows: %s", hipGetErrorString(hipGetLastError()));
-        return KEDS_E_LAUNCH;
-    }
-    for (int l = 0; l < p->layers; ++l) {
-        const keds_block_params& k = p->blocks[l];
-        const bool last = l == p->layers - 1;
-        const float *qkv_w = (const float*)k.qkv_w, *out_w = (const float*)k.out_w, *fc_w = (const float*)k.fc_w,
-                    *proj_w = (const float*)k.proj_w;
-        if ((rc = keds_layernorm_impl(x, w, nullptr, 1, k.ln1_g, k.ln1_b, ln, 1, M, w, st))) return rc;
-        if ((rc = keds_gemm_f32(ln, w, qkv_w, k.qkv_b, qkv, 3 * w, M, 3 * w, w, F32_EPI_BIAS, nullptr, 0, st))) return rc;
-        if (last && last_rows) {
-            // after the last block only the read-out row of every sample is read (model.py:587-589, 847-849): attention on all
-            // rows, then out-proj, ln_2 and the MLP on the B gathered rows (compact [B, w] buffers in the qkv buffer)
-            if ((rc = attention_f32_impl(qkv, att, B, S, p->heads, p->causal, S, soff, st))) return rc;
-            float* att_c = qkv;
-            float* x_c = qkv + (size_t)B * w;
-            if ((rc = keds_gather_rows_impl(att, att_c, last_rows, gbound, B, w, 2, st, pk != nullptr))) return rc;
-            if ((rc = keds_gather_rows_impl(x, x_c, last_rows, gbound, B, w, 2, st, pk != nullptr))) return rc;
-            if ((rc = keds_gemm_f32(att_c, w, out_w, k.out_b, x_c, w, B, w, w, F32_EPI_RESID, nullptr, 0, st))) return rc;
-            if ((rc = keds_layernorm_impl(x_c, w, nullptr, 1, k.ln2_g, k.ln2_b, ln, 1, B, w, st))) return rc;
-            if ((rc = keds_gemm_f32(ln, w, fc_w, k.fc_b, hid, 4 * w, B, 4 * w, w, F32_EPI_QGELU, nullptr, 0, st))) return rc;
-            if ((rc = keds_gemm_f32(hid, 4 * w, proj_w, k.proj_b, x_c, w, B, w, 4 * w, F32_EPI_RESID, nullptr, 0, st))) return rc;
-            if (hipMemcpyAsync(x, x_c, (size_t)B * w * sizeof(float), hipMemcpyDeviceToDevice, st) != hipSuccess) {
-                keds_set_error("keds_tower_forward_f32: read-out rows: %s", hipGetErrorString(hipGetLastError()));
-                return KEDS_E_LAUNCH;
-            }
-            return KEDS_OK;
-        }
-        if (last && p->last_cls_only) {
-            // after the last block only token 0 of every sample is read (model.py:412): its attention query, out-proj, ln_2
-            // and MLP run on those B rows (row stride S*w in x / att)
-            const long long ldr = (long long)S * w;
-            if ((rc = keds_attention_f32(qkv, att, B, S, p->heads, p->causal, 1, st))) return rc;
-            if ((rc = keds_gemm_f32(att, ldr, out_w, k.out_b, x, ldr, B, w, w, F32_EPI_RESID, nullptr, 0, st))) return rc;
-            if ((rc = keds_layernorm_impl(x, w, nullptr, S, k.ln2_g, k.ln2_b, ln, 1, B, w, st))) return rc;
-            if ((rc = keds_gemm_f32(ln, w, fc_w, k.fc_b, hid, 4 * w, B, 4 * w, w, F32_EPI_QGELU, nullptr, 0, st))) return rc;
-            return keds_gemm_f32(hid, 4 * w, proj_w, k.proj_b, x, ldr, B, w, 4 * w, F32_EPI_RESID, nullptr, 0, st);
-        }
-        if ((rc = attention_f32_impl(qkv, att, B, S, p->heads, p->causal, S, soff, st))) return rc;
-        if ((rc = keds_gemm_f32(att, w, out_w, k.out_b, x, w, M, w, w, F32_EPI_RESID, nullptr, 0, st))) return rc;
-        if ((rc = keds_layernorm_impl(x, w, nullptr, 1, k.ln2_g, k.ln2_b, ln, 1, M, w, st))) return rc;
-        if ((rc = keds_gemm_f32(ln, w, fc_w, k.fc_b, hid, 4 * w, M, 4 * w, w, F32_EPI_QGELU, nullptr, 0, st))) return rc;
-        if ((rc = keds_gemm_f32(hid, 4 * w, proj_w, k.proj_b, x, w, M, w, 4 * w, F32_EPI_RESID, nullptr, 0, st))) return rc;
-        if ((rc = keds_tap_rows(tp, l, p->layers, x, 1, 0, M, w, st))) return rc;
-    }
-    return KEDS_OK;
-}
-
+// ---- read-out (the tower passes themselves: tower_plan.h says what they launch, towers.hip runs it) -----------------------------
 // ln_post / ln_final on the read-out rows + projection (+ L2 normalisation), fp32 (model.py:412-414, 586-589, 841-849)
 size_t keds_readout_f32_workspace_bytes(int B, int d) { return keds_align_up((size_t)B, 128) * d * 4; }
 

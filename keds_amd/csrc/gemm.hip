@@ -1765,7 +1765,7 @@ int launch_gemm(GemmArgs a) {
 
 }  // namespace
 
-// (keds_common.h) any epilogue, dense strides: what bf16_rows_split (towers.hip) asks per GEMM shape of a block
+// (keds_common.h) any epilogue, dense strides: what tower_splits_rows (tower_plan.h) asks per GEMM shape of a block
 bool keds_gemm_splits_rows(int M, int N, int K) { return gemm_big_tiles_fill(M, N, K, gemm_switches()) && M % 256 != 0; }
 
 extern "C" int keds_gemm_last_launch(int* info) {

@@ -1,16 +1,23 @@
-// Whole-tower forward passes built from the kernels in gemm/attention/elementwise:
+// Whole-tower forward passes built from the kernels in gemm/attention/elementwise/f32path:
 //   keds_tower_forward : N pre-LN residual blocks        (src/model/model.py:305-326,372-373)
 //   keds_vit_run   : CLIP.encode_image, ViT branch   (src/model/model.py:569-575,393-415)
 //   keds_text_run  : CLIP.encode_text / encode_text_img_retrieval (src/model/model.py:577-590,808-851)
 //   keds_vit_run_tokens / keds_text_run_tokens : encode_image(mid_feature=True), VisualTransformer.get_tokens,
 //                    CLIP.get_text_tokens (model.py:337-342, 393-427, 592-605): per-block taps / all tokens of the same passes
+// What a pass launches, flow by flow, is decided in tower_plan.h; tower_step() below runs one step of it and is the only place a
+// tower pass calls a GEMM, attention or LayerNorm entry from.
 // Host code only: every launch is asynchronous on the caller's stream, the caller owns the
 // workspace, nothing is allocated or synchronised here.
 #include "keds_common.h"
+#include "tower_plan.h"
 #include <cstdlib>
+#include <cstring>
+#include <optional>
 
 int keds_layernorm_impl(const float* x, long long x_stride, const int* row_map, int row_mul, const float* gamma,
                         const float* beta, void* out, int out_f32, int rows, int dim, hipStream_t st);
+int keds_layernorm_pair_impl(const float* x, long long x_stride, const float* gamma, const float* beta, void* out, long long plane,
+                             int rows, int dim, hipStream_t st, int form = 0);
 int keds_cls_rows_impl(float* x, const float* cls, const float* pos, int B, int S, int d, hipStream_t st);
 int keds_cast_rows_f16_f32_impl(const void* x16, float* x32, int rows, int dim, long long stride, hipStream_t st);
 int keds_gather_rows_impl(const void* src, void* dst, const int32_t* row, int S, int B, int dim, int mode, hipStream_t st,
@@ -19,10 +26,11 @@ int keds_embed_tokens_impl(const int32_t* tokens, const float* table, const floa
                            int n_tok, int insert_col, float* x, int B, int L, int Lx, int d, void* stream,
                            const int32_t* seq_off = nullptr);
 
-// f32path.hip: the fp32-accurate flow (keds_tower_params.f32)
-size_t keds_tower_f32_workspace_bytes(int width, int seq, int B);
-int keds_tower_forward_f32(const keds_tower_params* p, float* x, int B, void* ws, hipStream_t st, const int32_t* last_rows = nullptr,
-                           const PackedRows* pk = nullptr, const KedsTaps* tp = nullptr);
+// f32path.hip / attention_x3.hip: the attention and the read-out of the fp32-accurate flows (keds_tower_params.f32)
+int attention_f32_impl(const float* qkv, float* out, int B, int S, int heads, int causal, int q_limit, const int32_t* seq_off,
+                       void* stream);
+int keds_attention_x3_impl(const float* qkv, float* out, void* pair, int64_t plane, int B, int S, int heads, int causal, int q_limit,
+                           int* overflow, const int32_t* seq_off, void* stream);
 size_t keds_readout_f32_workspace_bytes(int B, int d);
 int keds_readout_f32(const float* x, int S, const int32_t* row, const float* gamma, const float* beta, const float* proj_t,
                      float* out, int B, int d, int E, int normalize, void* workspace, hipStream_t st);
@@ -31,334 +39,199 @@ int keds_readout_impl(const float* x, int S, const int32_t* row, const float* ga
 
 namespace {
 
-size_t pad_rows(size_t m) { return keds_align_up(m, 256); }     // (256: whole row tiles; packed rows run up to the next one)
+static_assert(TOWER_SPLITK_BYTES == KEDS_SPLITK_BYTES, "tower_plan.h carves the split-K scratch");
 
-// scratch of one tower: h [Mp,w] (the fp16 residual stream of the folded flow; the bf16 LayerNorm output of the unfolded
-// one) | qkv [Mp,3w] | attn [Mp,w] | MLP hidden [Mp,4w] (bf16) |
-// two row-statistics buffers [Mp,2] of 64-bit fixed point (LayerNorm folded into the GEMMs: ln_1 / ln_2 statistics).
-// No buffer aliases another: the remainder-row chain runs beside the full-tile chain (see RowLanes) and the two touch
-// disjoint ROWS of every buffer, which only keeps them apart if the buffers themselves are distinct.
-struct TowerWs {
-    bf16_t *h, *qkv, *att, *hid;
-    keds_stat_t *st1, *st2;
-    // MXFP8 operands of the full 256-row tiles (fp8 towers): residual copy, attention output, MLP hidden (+ scale dwords)
-    unsigned char *xq, *xs, *aq, *as, *hq, *hs;
-    char* splitk;          // fp32 partial tiles of the split-K launches of THIS call (remainder rows, CLS tail)
-    size_t bytes;
+size_t pad_rows(size_t m) { return tower_pad_rows(m); }
+
+// One pass in flight: where the plan's buffer ids and lanes point
+struct TowerRun {
+    const keds_tower_params* p;
+    int flow, B;
+    char *x, *ws;                   // the caller's fp32 stream; the tower scratch (TowerLayout)
+    TowerLayout L;
+    hipStream_t main;
+    KedsSideLane* lane;             // its stream and its own two events, created once (round 1 made and destroyed a pair on every tower call)
+    const int32_t *rows, *seq_off;  // device: the read-out row of every sample; the packed rows' offsets
+    const KedsTaps* tp;
+    int* guard;                     // x3: the numerics guard of the calling thread's composite call
+    char* at(int buf, int r0 = 0) const {
+        const TowerBuf& b = L.b[buf];
+        return (buf == TB_X ? x : ws + b.off) + (size_t)r0 * b.cols * b.esize;
+    }
+    char* at_or_null(int buf, int r0 = 0) const { return buf == TB_NONE ? nullptr : at(buf, r0); }
+    long long ld(int buf, int step) const { return (long long)step * L.b[buf].cols; }
 };
 
-TowerWs carve_tower(void* ws, int width, int seq, int B) {
-    const size_t Mp = pad_rows((size_t)B * seq);
-    TowerWs t;
-    char* p = (char*)ws;
-    size_t off = 0;
-    auto take = [&](size_t n) {
-        char* r = p ? p + off : nullptr;
-        off += keds_align_up(n, 256);
-        return r;
-    };
-    t.h = (bf16_t*)take(Mp * width * 2);
-    t.qkv = (bf16_t*)take(Mp * (size_t)width * 3 * 2);
-    t.att = (bf16_t*)take(Mp * (size_t)width * 2);
-    t.hid = (bf16_t*)take(Mp * (size_t)width * 4 * 2);
-    t.st1 = (keds_stat_t*)take(Mp * 2 * sizeof(keds_stat_t));
-    t.st2 = (keds_stat_t*)take(Mp * 2 * sizeof(keds_stat_t));
-    const size_t Mm = (size_t)B * seq / 256 * 256;
-    const size_t q1 = Mm * width, s1 = Mm * (size_t)(width / 32);   // 1 scale byte / 32
-    t.xq = (unsigned char*)take(q1);
-    t.xs = (unsigned char*)take(s1);
-    t.aq = (unsigned char*)take(q1);
-    t.as = (unsigned char*)take(s1);
-    t.hq = (unsigned char*)take(4 * q1);
-    t.hs = (unsigned char*)take(4 * s1);
-    t.splitk = take(KEDS_SPLITK_BYTES);
-    t.bytes = off;
-    return t;
+struct TowerWeight {
+    const void *w, *scales;         // (scales: MXFP8)
+    const float* bias;
+    int N, K, x3_exp;
+};
+TowerWeight tower_weight(const keds_block_params& k, const TowerStep& s, int w) {
+    const bool mx = s.op == KEDS_TOWER_OP_GEMM_MX;
+    switch (s.weight) {
+        case TW_QKV: return mx ? TowerWeight{k.qkv_q8, k.qkv_s8, k.qkv_bc8, 3 * w, w, 0} : TowerWeight{k.qkv_w, nullptr, k.qkv_b, 3 * w, w, k.x3_exp[0]};
+        case TW_OUT: return mx ? TowerWeight{k.out_q8, k.out_s8, k.out_b, w, w, 0} : TowerWeight{k.out_w, nullptr, k.out_b, w, w, k.x3_exp[1]};
+        case TW_FC: return mx ? TowerWeight{k.fc_q8, k.fc_s8, k.fc_bc8, 4 * w, w, 0} : TowerWeight{k.fc_w, nullptr, k.fc_b, 4 * w, w, k.x3_exp[2]};
+        case TW_PROJ: return mx ? TowerWeight{k.proj_q8, k.proj_s8, k.proj_b, w, 4 * w, 0} : TowerWeight{k.proj_w, nullptr, k.proj_b, w, 4 * w, k.x3_exp[3]};
+        case TW_QKV_FOLDED: return TowerWeight{k.qkv_wf, nullptr, k.qkv_bc, 3 * w, w, 0};
+        case TW_FC_FOLDED: return TowerWeight{k.fc_wf, nullptr, k.fc_bc, 4 * w, w, 0};
+    }
+    return TowerWeight{};
 }
 
-// Two lanes for one tower pass.  At B = 128 a ViT-L/14 tower has 32,896 rows = 128 full 256-row tiles + 128 remainder
-// rows; every GEMM of the remainder is a handful of workgroups whose time is pure latency (13-14 us each, 61 us per block,
-// 5.6 % of the step when it runs between the full-tile launches).  Rows only meet in the attention, so per block the
-// remainder chain (out-proj, fc, proj, next qkv) runs on the side lane while the caller's stream runs the same four GEMMs
-// on the full tiles: fork after the attention, join before the next one.
-// Measured in round 2 (bench step, 128 images): 21.85 ms with the side lane, 22.85 ms with the remainder launches between
-// the full-tile ones, 21.46 ms with the remainder rows not computed at all (timing only) -- the lane recovers 0.6 of the
-// 1.0 ms these 0.39 % of the rows cost.  A side workgroup cannot share a CU with a 256 x 256 tile (registers), so each one
-// displaces a tile of the kernel running beside it; forking the chain behind the out-proj launch instead of in front of it
-// (so that it runs under c_fc's eight rounds of tiles rather than out-proj's two) changes nothing measurable.
-struct RowLanes {
-    hipStream_t main = nullptr, side = nullptr;
-    hipEvent_t fork = nullptr, join = nullptr;
-    bool split = false;
-    int init(hipStream_t st, bool want) {
-        main = side = st;
-        KedsSideLane* lane = want ? keds_side_lane() : nullptr;
-        if (!lane) return KEDS_OK;
-        side = lane->s;
-        fork = lane->fork;                                    // the lane's own two events, created once (round 1 made and
-        join = lane->join;                                    // destroyed a pair on every tower call)
-        split = true;
-        return KEDS_OK;
+// the attention of a step: bf16 or fp16, rectangular or packed rows, and for the fp8 tower rows < q8_rows as MXFP8 into aq / as (the
+// 16-bit flows); fp32; split fp16 with its output as fp32 rows or as the out-projection's operand planes.  stop / taken: AttnArgs
+int tower_attention(const TowerRun& r, const TowerStep& s, hipEvent_t stop, bool* taken) {
+    const keds_tower_params* p = r.p;
+    const int32_t* off = s.packed ? r.seq_off : nullptr;
+    const float* qkv = (const float*)r.at(s.in);
+    if (r.flow == KEDS_TOWER_FLOW_F32) return attention_f32_impl(qkv, (float*)r.at(s.out), r.B, p->seq, p->heads, p->causal, s.q_limit, off, r.main);
+    if (r.flow == KEDS_TOWER_FLOW_X3) {
+        const bool planes = s.out == TB_LN;
+        return keds_attention_x3_impl(qkv, planes ? nullptr : (float*)r.at(s.out), planes ? r.at(s.out) : nullptr, r.ld(s.out, planes ? s.plane_rows : 0),
+                                      r.B, p->seq, p->heads, p->causal, s.q_limit, r.guard, off, r.main);
     }
-    int to_side() { return split ? keds_stream_order(main, fork, side) : KEDS_OK; }
-    // the fork behind an attention launch: the launch records the event itself (its stop event: no marker packet between it and
-    // the next GEMM on the main stream); kernel forms that do not take it get the recorded event.
-    template <typename F>
-    int attention_then_side(F launch) {      // launch(stop event or null, &taken)
-        bool taken = false;
-        if (!split) {
-            const int rc = launch(nullptr, &taken);
-            return rc ? rc : to_side();
+    const AttnArgs a{qkv, r.at(s.out), r.B, p->seq, p->heads, r.at_or_null(s.out2), s.out2 ? r.at(s.out2 + 1) : nullptr, s.q8_rows, off, r.main, stop};
+    return keds_attention16(a, p->f16, p->causal, s.q_limit, taken);
+}
+
+int tower_hip_error(const char* what) {
+    keds_set_error("keds_tower_forward: %s: %s", what, hipGetErrorString(hipGetLastError()));
+    return KEDS_E_LAUNCH;
+}
+
+// One step of a pass.  Every kernel entry a tower pass uses has its one call site here.
+int tower_step(const TowerRun& r, const TowerStep& s) {
+    const keds_tower_params* p = r.p;
+    const int w = p->width;
+    hipStream_t st = s.lane ? r.lane->s : r.main;
+    const keds_block_params* k = s.layer >= 0 ? &p->blocks[s.layer] : nullptr;
+    const void* in = r.at_or_null(s.in, s.in_r0);
+    void* out = r.at_or_null(s.out, s.out_r0);
+    // the statistics a LayerNorm-folded GEMM reads or a residual GEMM adds into, and the buffer the former clears for the next producer
+    float* stats = (float*)r.at_or_null(s.st_read ? s.st_read : s.st_add, s.st_r0);
+    void* stats_clear = r.at_or_null(s.st_clear, s.st_r0);
+    const size_t out_row_bytes = s.out ? (size_t)r.L.b[s.out].cols * r.L.b[s.out].esize : 0;
+    switch (s.op) {
+        case KEDS_TOWER_OP_ZERO:
+            return hipMemsetAsync(out, 0, (size_t)s.n * out_row_bytes, st) == hipSuccess ? KEDS_OK : tower_hip_error("packed rows");
+        case KEDS_TOWER_OP_STATS_CAST: return keds_rowstats_cast_ex((const float*)in, out, s.epi, stats, s.n, w, st);
+        case KEDS_TOWER_OP_QUANT: return keds_quantize_mxfp8(in, 0, s.n, w, s.n, out, r.at(s.out + 1), st);
+        case KEDS_TOWER_OP_CAST: return keds_cast_rows_f16_f32_impl(in, (float*)out, s.n, w, r.ld(s.in, s.in_step), st);
+        case KEDS_TOWER_OP_COPY: {
+            const hipError_t e = s.epi ? hipMemcpy2DAsync(out, s.out_step * out_row_bytes, in, s.in_step * out_row_bytes, out_row_bytes, s.n,
+                                                          hipMemcpyDeviceToDevice, st)
+                                       : hipMemcpyAsync(out, in, s.n * out_row_bytes, hipMemcpyDeviceToDevice, st);
+            return e == hipSuccess ? KEDS_OK : tower_hip_error("read-out rows");
         }
-        keds_order_lock();
-        int rc = launch(fork, &taken);
-        if (!rc && taken) rc = keds_stream_wait_locked(fork, side);
-        keds_order_unlock();
-        if (!rc && !taken) rc = to_side();
-        return rc;
+        case KEDS_TOWER_OP_SPLIT: return keds_split_f16_pair((const float*)in, w, s.n, w, out, r.ld(s.out, s.plane_rows), r.guard, st);
+        case KEDS_TOWER_OP_GATHER: return keds_gather_rows_impl(in, out, r.rows, s.bound, s.n, w, s.epi, st, s.global != 0);
+        case KEDS_TOWER_OP_LN:
+        case KEDS_TOWER_OP_LN_PAIR: {
+            const float *g = s.weight == TW_LN1 ? k->ln1_g : k->ln2_g, *b = s.weight == TW_LN1 ? k->ln1_b : k->ln2_b;
+            if (s.op == KEDS_TOWER_OP_LN) return keds_layernorm_impl((const float*)in, w, nullptr, s.in_step, g, b, out, s.epi, s.n, w, st);
+            return keds_layernorm_pair_impl((const float*)in, w, g, b, out, r.ld(s.out, s.plane_rows), s.n, w, st);
+        }
+        case KEDS_TOWER_OP_ATTN: {
+            bool taken = false;
+            return tower_attention(r, s, nullptr, &taken);
+        }
+        case KEDS_TOWER_OP_ATTN_FORK: {
+            // the launch records the fork event itself (its stop event); kernel forms that do not take it get the recorded event
+            bool taken = false;
+            keds_order_lock();
+            int rc = tower_attention(r, s, r.lane->fork, &taken);
+            if (!rc && taken) rc = keds_stream_wait_locked(r.lane->fork, r.lane->s);
+            keds_order_unlock();
+            if (!rc && !taken) rc = keds_stream_order(r.main, r.lane->fork, r.lane->s);
+            return rc;
+        }
+        case KEDS_TOWER_OP_GEMM16: {
+            const TowerWeight wt = tower_weight(*k, s, w);
+            return keds_gemm_bt_ex2(in, r.ld(s.in, s.in_step), wt.w, wt.bias, out, r.ld(s.out, s.out_step), s.n, wt.N, wt.K, s.epi, stats, 0,
+                                    stats_clear, st);
+        }
+        case KEDS_TOWER_OP_GEMM_MX: {      // (m_pad and q_pad: the s.n full-tile rows the MXFP8 buffers are carved for)
+            const TowerWeight wt = tower_weight(*k, s, w);
+            const bool mx_out = s.out == TB_HQ;      // c_fc writes the MLP hidden layer as MXFP8 only
+            const int q = mx_out ? s.out : s.out2;
+            return keds_gemm_mxfp8_ex(in, r.at(s.in + 1), s.n, wt.w, wt.scales, wt.N, wt.bias, mx_out ? nullptr : out, s.n, wt.N, wt.K, s.epi,
+                                      stats, (float*)stats_clear, r.at_or_null(q), q ? r.at(q + 1) : nullptr, q ? s.n : 0, st);
+        }
+        case KEDS_TOWER_OP_GEMM_F32: {
+            const TowerWeight wt = tower_weight(*k, s, w);
+            return keds_gemm_f32((const float*)in, r.ld(s.in, s.in_step), (const float*)wt.w, wt.bias, (float*)out, r.ld(s.out, s.out_step), s.n,
+                                 wt.N, wt.K, s.epi, nullptr, 0, st);
+        }
+        case KEDS_TOWER_OP_GEMM_X3: {      // operand planes plane_rows apart; c_fc writes the MLP hidden layer as planes too
+            const TowerWeight wt = tower_weight(*k, s, w);
+            return keds_gemm_x3(in, r.ld(s.in, s.plane_rows), r.ld(s.in, s.in_step), wt.w, (long long)wt.N * wt.K, wt.bias, out,
+                                r.ld(s.out, s.out_step), s.n, wt.N, wt.K, s.epi,
+                                s.epi == KEDS_EPI_X3_QGELU_PAIR ? (int)r.ld(s.out, s.plane_rows) : 0, wt.x3_exp, st);
+        }
+        case KEDS_TOWER_OP_TAP: return keds_tap_rows(r.tp, s.layer, p->layers, r.at(s.in), s.epi, s.in_r0, s.n, w, st);
+        case KEDS_TOWER_OP_FORK: return keds_stream_order(r.main, r.lane->fork, r.lane->s);
+        case KEDS_TOWER_OP_JOIN: return keds_stream_order(r.lane->s, r.lane->join, r.main);
     }
-    int to_main() { return split ? keds_stream_order(side, join, main) : KEDS_OK; }
-};
-
-struct RowSpan {
-    size_t r0;
-    int n;
-    hipStream_t st;
-};
-
-// The four GEMMs of a block on a span of rows, LayerNorm folded (keds_hip.h, KEDS_EPI_LN_*).  The residual stream lives
-// in t.h as fp16 (the reference's own storage type after convert_weights, model.py:531-548): one copy that the residual
-// GEMMs update in place (fp32 sum, rounded once) and the LN-folded GEMMs read as their fp16 operand.
-// h (keds_tower_params.f16, the "fp16" operating point): every operand fp16 -- qkv, the attention output and the MLP hidden layer
-// are fp16 and out_w / proj_w fp16 weights (KEDS_EPI_*_F16_H); otherwise those are bf16.
-int qkv_rows(const TowerWs& t, const keds_block_params& k, int w, RowSpan s, bool h) {
-    return keds_gemm_bt_ex2(t.h + s.r0 * w, w, k.qkv_wf, k.qkv_bc, t.qkv + s.r0 * 3 * w, 3 * w, s.n, 3 * w, w,
-                            h ? KEDS_EPI_LN_BIAS_F16_H : KEDS_EPI_LN_BIAS_BF16_H, (const float*)(t.st1 + 2 * s.r0), 0, t.st2 + 2 * s.r0,
-                            s.st);
-}
-int out_rows(const TowerWs& t, const keds_block_params& k, int w, RowSpan s, bool h) {
-    return keds_gemm_bt_ex2(t.att + s.r0 * w, w, k.out_w, k.out_b, t.h + s.r0 * w, w, s.n, w, w,
-                            h ? KEDS_EPI_RESID_STATS_F16_H : KEDS_EPI_RESID_STATS_F16, (const float*)(t.st2 + 2 * s.r0), 0, nullptr, s.st);
-}
-int fc_rows(const TowerWs& t, const keds_block_params& k, int w, RowSpan s, bool h) {
-    return keds_gemm_bt_ex2(t.h + s.r0 * w, w, k.fc_wf, k.fc_bc, t.hid + s.r0 * 4 * w, 4 * w, s.n, 4 * w, w,
-                            h ? KEDS_EPI_LN_QGELU_F16_H : KEDS_EPI_LN_QGELU_BF16_H, (const float*)(t.st2 + 2 * s.r0), 0, t.st1 + 2 * s.r0,
-                            s.st);
-}
-// (the last block's output feeds no further ln_1: no statistics)
-int proj_rows(const TowerWs& t, const keds_block_params& k, int w, bool last, RowSpan s, bool h) {
-    return keds_gemm_bt_ex2(t.hid + s.r0 * 4 * w, 4 * w, k.proj_w, k.proj_b, t.h + s.r0 * w, w, s.n, w, 4 * w,
-                            h ? KEDS_EPI_RESID_STATS_F16_H : KEDS_EPI_RESID_STATS_F16, last ? nullptr : (const float*)(t.st1 + 2 * s.r0),
-                            0, nullptr, s.st);
-}
-// the attention of the 16-bit flows, t.qkv -> t.att: bf16 or (p->f16) fp16, rectangular or (pk) packed rows, and for the fp8 tower
-// rows < q8_rows as MXFP8 into t.aq / t.as.  stop / taken: RowLanes::attention_then_side
-int tower_attention(const keds_tower_params* p, const TowerWs& t, int B, int q_limit, const PackedRows* pk, int q8_rows, hipStream_t st,
-                    hipEvent_t stop = nullptr, bool* taken = nullptr) {
-    const AttnArgs a{t.qkv, t.att, B, p->seq, p->heads, q8_rows ? t.aq : nullptr, q8_rows ? t.as : nullptr, q8_rows, pk ? pk->off : nullptr, st, stop};
-    return keds_attention16(a, p->f16, p->causal, q_limit, taken);
+    keds_set_error("keds_tower_forward: unknown step %d", s.op);
+    return KEDS_E_ARG;
 }
 
-// After the last block only token 0 of every sample is read (ln_post(x[:,0,:]), model.py:412), so the attention
-// queries, out-proj, ln_2 and the MLP run on those B rows only (row stride S*w in x / attn); fp32 rows, bf16 kernels.
-// x16: the fp16 residual stream whose CLS rows are brought back to fp32 first (folded flow), or nullptr.
-int cls_rows_tail(const keds_tower_params* p, const keds_block_params& k, const TowerWs& t, float* x, const void* x16, int B,
-                  hipStream_t st) {
-    const int w = p->width, S = p->seq;
-    const long long ld = (long long)S * w;
-    const bool h = p->f16;
-    const int resid = h ? KEDS_EPI_BIAS_RESID_F32_H : KEDS_EPI_BIAS_RESID_F32;
-    int rc;
-    if (x16 && (rc = keds_cast_rows_f16_f32_impl(x16, x, B, w, ld, st))) return rc;
-    if ((rc = tower_attention(p, t, B, 1, nullptr, 0, st))) return rc;
-    if ((rc = keds_gemm_bt_ex(t.att, ld, k.out_w, k.out_b, x, ld, B, w, w, resid, nullptr, 0, st))) return rc;
-    if ((rc = keds_layernorm_impl(x, w, nullptr, S, k.ln2_g, k.ln2_b, t.h, h ? 2 : 0, B, w, st))) return rc;
-    if ((rc = keds_gemm_bt(t.h, k.fc_w, k.fc_b, t.hid, B, 4 * w, w, h ? KEDS_EPI_BIAS_QGELU_F16_H : KEDS_EPI_BIAS_QGELU_BF16, nullptr, 0,
-                           st)))
-        return rc;
-    return keds_gemm_bt_ex(t.hid, 4 * w, k.proj_w, k.proj_b, x, ld, B, w, 4 * w, resid, nullptr, 0, st);
+int tower_bad(const char* why) {
+    keds_set_error("%s", why);
+    return KEDS_E_ARG;
 }
 
-// The text tower's form of the same cut: after the last block only ONE row of every sample is read -- the EOT column
-// (+ n_tok - 1 with spliced pseudo tokens; model.py:587-589, 847-849) -- a different row per sample, known on the device only
-// (`rows`, int32 [B]).  The block's in_proj and attention run on all rows (every key is needed; the attention is 1.6 % of a
-// block), then the B read-out rows of the attention output and of the residual stream are gathered into compact [B, w]
-// buffers (in the qkv buffer, which nobody reads any more) and out-proj, ln_2 and the MLP run on those.  On return the first
-// B rows of x hold the block's output for sample b in row b: the caller reads out with S = 1, row 0.
-// pk (packed rows): `rows` are GLOBAL row indices (off[b] + the sample's read-out column).
-int rows_tail(const keds_tower_params* p, const keds_block_params& k, const TowerWs& t, float* x, const void* x16, int B,
-              const int32_t* rows, hipStream_t st, const PackedRows* pk = nullptr) {
-    const int w = p->width, S = p->seq;
-    const bool h = p->f16;
-    const int resid = h ? KEDS_EPI_BIAS_RESID_F32_H : KEDS_EPI_BIAS_RESID_F32;
-    int rc;
-    if ((rc = tower_attention(p, t, B, S, pk, 0, st))) return rc;
-    bf16_t* att_c = t.qkv;                                               // [B, w] 16-bit (2 w bytes per row: a multiple of 256)
-    float* x_c = (float*)((char*)t.qkv + (size_t)B * w * 2);             // [B, w] fp32; 6 B w <= the buffer's 6 w pad256(B S)
-    const int bound = pk ? pk->valid : S;
-    if ((rc = keds_gather_rows_impl(t.att, att_c, rows, bound, B, w, 0, st, pk != nullptr))) return rc;
-    if ((rc = keds_gather_rows_impl(x16 ? x16 : (const void*)x, x_c, rows, bound, B, w, x16 ? 1 : 2, st, pk != nullptr))) return rc;
-    if ((rc = keds_gemm_bt_ex(att_c, w, k.out_w, k.out_b, x_c, w, B, w, w, resid, nullptr, 0, st))) return rc;
-    if ((rc = keds_layernorm_impl(x_c, w, nullptr, 1, k.ln2_g, k.ln2_b, t.h, h ? 2 : 0, B, w, st))) return rc;
-    if ((rc = keds_gemm_bt(t.h, k.fc_w, k.fc_b, t.hid, B, 4 * w, w, h ? KEDS_EPI_BIAS_QGELU_F16_H : KEDS_EPI_BIAS_QGELU_BF16, nullptr, 0,
-                           st)))
-        return rc;
-    if ((rc = keds_gemm_bt_ex(t.hid, 4 * w, k.proj_w, k.proj_b, x_c, w, B, w, 4 * w, resid, nullptr, 0, st))) return rc;
-    if (hipMemcpyAsync(x, x_c, (size_t)B * w * sizeof(float), hipMemcpyDeviceToDevice, st) != hipSuccess) {
-        keds_set_error("keds_tower_forward: read-out rows: %s", hipGetErrorString(hipGetLastError()));
-        return KEDS_E_LAUNCH;
-    }
-    return KEDS_OK;
-}
-
-bool bf16_rows_split(int M, int w) {
-    return keds_gemm_splits_rows(M, 3 * w, w) && keds_gemm_splits_rows(M, w, w) && keds_gemm_splits_rows(M, 4 * w, w) &&
-           keds_gemm_splits_rows(M, w, 4 * w);
-}
-
-// (The ragged last row tile as a full tile on filler rows -- round 3, 4 ms per step slower: docs/findings_r03.md -- and the tail
-// samples' attention on the side lane -- round 4, neutral: profiles/r04_tail_attention_ab.txt -- last existed at 14f64ac.)
-
-// BASELINE config 5: the four GEMMs of every block on MXFP8 operands (gemm_fp8.hip).  The residual stream stays fp32;
-// its MXFP8 copy (xq, xs), the attention output (aq) and the MLP hidden (hq) are e4m3 + one e8m0 scale per 32 columns,
-// produced by the GEMM epilogues themselves (the attention output by the attention kernel).  Rows beyond the last full
-// 256-row tile (128 of 32,896 at B = 128) keep the bf16 path, on the side lane: every producer has a bf16 twin for them.
-int tower_forward_fp8(const keds_tower_params* p, float* x, int B, const TowerWs& t, int Mm, hipStream_t st,
-                      const int32_t* last_rows, const KedsTaps* tp) {
-    const int w = p->width, S = p->seq;
-    const int M = B * S, Mt = M - Mm;
-    RowLanes lanes;
-    int rc;
-    if ((rc = lanes.init(st, Mt > 0))) return rc;
-    const RowSpan rem{(size_t)Mm, Mt, lanes.side};
-    if ((rc = keds_rowstats_cast_ex(x, t.h, 1, (float*)t.st1, M, w, st))) return rc;
-    if ((rc = keds_quantize_mxfp8(x, 0, Mm, w, Mm, t.xq, t.xs, st))) return rc;
-    if ((rc = lanes.to_side())) return rc;
-    for (int l = 0; l < p->layers; ++l) {
-        const keds_block_params& k = p->blocks[l];
-        const bool last = l == p->layers - 1;
-        if ((rc = keds_gemm_mxfp8_ex(t.xq, t.xs, Mm, k.qkv_q8, k.qkv_s8, 3 * w, k.qkv_bc8, t.qkv, Mm, 3 * w, w,
-                                     KEDS_FP8_EPI_LN_BIAS_BF16, (float*)t.st1, (float*)t.st2, nullptr, nullptr, 0, st)))
-            return rc;
-        if (Mt && (rc = qkv_rows(t, k, w, rem, false))) return rc;
-        if ((rc = lanes.to_main())) return rc;
-        if (last && last_rows) return rows_tail(p, k, t, x, t.h, B, last_rows, st);
-        if (last && p->last_cls_only) return cls_rows_tail(p, k, t, x, t.h, B, st);
-        // attention writes its output as MXFP8 for the full-tile rows and as bf16 for the remainder rows
-        if ((rc = lanes.attention_then_side([&](hipEvent_t stop, bool* taken) { return tower_attention(p, t, B, S, nullptr, Mm, st, stop, taken); })))
-            return rc;
-        if ((rc = keds_gemm_mxfp8_ex(t.aq, t.as, Mm, k.out_q8, k.out_s8, w, k.out_b, t.h, Mm, w, w,
-                                     KEDS_FP8_EPI_RESID_STATS_MX_H, (float*)t.st2, nullptr, t.xq, t.xs, Mm, st)))
-            return rc;
-        if (Mt && (rc = out_rows(t, k, w, rem, false))) return rc;
-        if ((rc = keds_gemm_mxfp8_ex(t.xq, t.xs, Mm, k.fc_q8, k.fc_s8, 4 * w, k.fc_bc8, nullptr, Mm, 4 * w, w,
-                                     KEDS_FP8_EPI_LN_QGELU_MX, (float*)t.st2, (float*)t.st1, t.hq, t.hs, Mm, st)))
-            return rc;
-        if (Mt && (rc = fc_rows(t, k, w, rem, false))) return rc;
-        if ((rc = keds_gemm_mxfp8_ex(t.hq, t.hs, Mm, k.proj_q8, k.proj_s8, w, k.proj_b, t.h, Mm, w, 4 * w,
-                                     KEDS_FP8_EPI_RESID_STATS_MX_H, (float*)t.st1, nullptr, t.xq, t.xs, Mm, st)))
-            return rc;
-        if ((rc = keds_tap_rows(tp, l, p->layers, t.h, 2, 0, Mm, w, st))) return rc;
-        if (Mt && (rc = proj_rows(t, k, w, last, rem, false))) return rc;
-        if (Mt && (rc = keds_tap_rows(tp, l, p->layers, t.h, 2, rem.r0, rem.n, w, rem.st))) return rc;
-    }
-    if ((rc = lanes.to_main())) return rc;
-    return keds_cast_rows_f16_f32_impl(t.h, x, M, w, w, st);       // the caller reads x in fp32
-}
-
-// last_rows (device int32 [B], nullable): the one row of every sample that is read after the last block (rows_tail): on
-// return x[b] (row b of the first B rows) holds that row of sample b; without it x holds every row as before
-// pk (nullable): packed rows -- M = pk->rows <= B * seq, the workspace is carved for B * seq
+// last_rows (device int32 [B], nullable): the one row of every sample that is read after the last block: on return x[b] (row b of
+// the first B rows) holds that row of sample b; without it x holds every row (p->last_cls_only: the CLS rows)
+// pk (nullable): packed rows -- M = pk->rows <= B * seq, the workspace is carved for B * seq; last_rows are global rows
 // tp (nullable): per-block taps (KedsTaps, keds_vit_run_tokens); the caller clears last_cls_only for such a pass
-int tower_forward(const keds_tower_params* p, float* x, int B, void* ws, hipStream_t st,
-                  const int32_t* last_rows = nullptr, const PackedRows* pk = nullptr, const KedsTaps* tp = nullptr) {
-    const int w = p->width, S = p->seq;
-    const int M = pk ? pk->rows : B * S;
-    TowerWs t = carve_tower(ws, w, S, B);
-    KedsSplitKScope splitk(t.splitk, KEDS_SPLITK_BYTES);   // this call's GEMMs split K into this call's scratch only
-    int rc;
-    // LayerNorm folded into the GEMMs (keds_hip.h, KEDS_EPI_LN_*): t.h holds the bf16 copy of the residual stream,
-    // st1 / st2 the {sum, sum sq} of its rows as seen by ln_1 / ln_2.  Each LN-consuming GEMM also clears the
-    // statistics buffer the next producer accumulates into, so no memset sits between the launches.
-    bool folded = true, have8 = true;
-    for (int l = 0; l < p->layers; ++l) {
-        const keds_block_params& k = p->blocks[l];
-        folded = folded && k.qkv_wf && k.fc_wf && k.qkv_bc && k.fc_bc;
-        have8 = have8 && k.qkv_q8 && k.out_q8 && k.fc_q8 && k.proj_q8 && k.qkv_s8 && k.out_s8 && k.fc_s8 && k.proj_s8 &&
-                k.qkv_bc8 && k.fc_bc8;
-    }
-    const int Mm = M / 256 * 256;                  // rows in full 256-row tiles: MXFP8 GEMMs; the rest stays on the bf16 kernels
-    if (p->fp8 && !(folded && have8 && w % 256 == 0)) {
-        keds_set_error("keds_tower_forward: fp8 needs the folded and MXFP8 weights and width %% 256 == 0");
-        return KEDS_E_ARG;
-    }
-    const bool fp8 = p->fp8 && Mm > 0;             // fewer than 256 rows: everything is "remainder rows" (bf16 kernels)
-    const bool h = p->f16;                         // the fp16 operating point: every 16-bit operand fp16 (folded flow only)
-    if (h && (p->fp8 || p->f32 || !folded)) {
-        keds_set_error("keds_tower_forward: f16 needs the folded weights and excludes fp8 / f32");
-        return KEDS_E_ARG;
-    }
-    if (pk && (p->fp8 || !p->causal || !last_rows)) {
-        keds_set_error("keds_tower_forward: packed rows need a causal 16-bit (bf16 / fp16) tower with a read-out row per sample");
-        return KEDS_E_ARG;
-    }
-    if (pk && pk->rows > pk->valid &&
-        hipMemsetAsync(t.att + (size_t)pk->valid * w, 0, (size_t)(pk->rows - pk->valid) * w * sizeof(bf16_t), st) != hipSuccess) {
-        keds_set_error("keds_tower_forward: packed rows: %s", hipGetErrorString(hipGetLastError()));
-        return KEDS_E_LAUNCH;
-    }
-    auto attention = [&](hipEvent_t stop, bool* taken) {           // the block's attention on all samples
-        return tower_attention(p, t, B, S, pk, 0, st, stop, taken);
-    };
-    if (fp8) return tower_forward_fp8(p, x, B, t, Mm, st, last_rows, tp);
-    if (folded) {
-        // When every GEMM of the block would split into full 256-row tiles + a remainder launch anyway, the remainder
-        // rows become their own chain on the side lane; otherwise one span covers all rows.
-        RowLanes lanes;
-        if ((rc = lanes.init(st, bf16_rows_split(M, w)))) return rc;
-        const RowSpan body{0, lanes.split ? Mm : M, st};
-        const RowSpan rem{(size_t)Mm, lanes.split ? M - Mm : 0, lanes.side};
-        if ((rc = keds_rowstats_cast_ex(x, t.h, 1, (float*)t.st1, M, w, st))) return rc;
-        if ((rc = lanes.to_side())) return rc;
-        for (int l = 0; l < p->layers; ++l) {
-            const keds_block_params& k = p->blocks[l];
-            const bool last = l == p->layers - 1;
-            if ((rc = qkv_rows(t, k, w, body, h))) return rc;
-            if (rem.n && (rc = qkv_rows(t, k, w, rem, h))) return rc;
-            if (last && (p->last_cls_only || last_rows)) {
-                if ((rc = lanes.to_main())) return rc;
-                return last_rows ? rows_tail(p, k, t, x, t.h, B, last_rows, st, pk) : cls_rows_tail(p, k, t, x, t.h, B, st);
-            }
-            if ((rc = lanes.to_main())) return rc;
-            if ((rc = lanes.attention_then_side(attention))) return rc;
-            if ((rc = out_rows(t, k, w, body, h))) return rc;
-            if (rem.n && (rc = out_rows(t, k, w, rem, h))) return rc;
-            if ((rc = fc_rows(t, k, w, body, h))) return rc;
-            if (rem.n && (rc = fc_rows(t, k, w, rem, h))) return rc;
-            if ((rc = proj_rows(t, k, w, last, body, h))) return rc;
-            if ((rc = keds_tap_rows(tp, l, p->layers, t.h, 2, body.r0, body.n, w, body.st))) return rc;
-            if (rem.n && (rc = proj_rows(t, k, w, last, rem, h))) return rc;
-            if (rem.n && (rc = keds_tap_rows(tp, l, p->layers, t.h, 2, rem.r0, rem.n, w, rem.st))) return rc;
+// front: what the pass entry enqueues behind the clearing of the packed zero rows of x and in front of everything else (the embedding)
+template <typename Front>
+int run_tower(const keds_tower_params* p, float* x, int B, void* ws, hipStream_t st, const int32_t* last_rows, const PackedRows* pk,
+              const KedsTaps* tp, Front&& front) {
+    const char* why = nullptr;
+    const int flow = tower_flow(p, &why);
+    if (flow < 0) return tower_bad(why);
+    TowerPlanArgs a{flow, p->width, p->heads, p->seq, p->causal != 0, p->layers, B,
+                    last_rows ? TAIL_READOUT : p->last_cls_only ? TAIL_CLS : TAIL_ALL, pk ? pk->rows : 0, pk ? pk->valid : 0, tp != nullptr,
+                    false, false};
+    if ((why = tower_plan_check(a))) return tower_bad(why);
+    const int M = pk ? pk->rows : B * p->seq;
+    a.split = tower_splits_rows(flow == KEDS_TOWER_FLOW_FP8 && M < 256 ? KEDS_TOWER_FLOW_BF16 : flow, M, p->width);
+    KedsSideLane* lane = a.split ? keds_side_lane() : nullptr;      // (created on first use; null: disabled, everything on `st`)
+    a.lane = lane != nullptr;
+    const TowerRun r{p, flow, B, (char*)x, (char*)ws, tower_layout(flow, p->width, p->seq, B), st, lane, last_rows, pk ? pk->off : nullptr, tp,
+                     flow == KEDS_TOWER_FLOW_X3 ? keds_numerics_guard() : nullptr};
+    std::optional<KedsSplitKScope> splitk;      // this call's GEMMs split K into this call's scratch only
+    if (r.L.b[TB_SPLITK].bytes) splitk.emplace(r.at(TB_SPLITK), KEDS_SPLITK_BYTES);
+    int rc = KEDS_OK;
+    bool fronted = false;
+    tower_plan(a, [&](const TowerStep& s) {
+        if (!fronted && !(s.op == KEDS_TOWER_OP_ZERO && s.out == TB_X)) {
+            fronted = true;
+            if ((rc = front())) return false;
         }
-        if ((rc = lanes.to_main())) return rc;
-        return keds_cast_rows_f16_f32_impl(t.h, x, M, w, w, st);   // the caller reads x in fp32
-    }
-    // KEDS_DETERMINISTIC / unfolded weights: stand-alone LayerNorm launches, plain bias epilogues
-    for (int l = 0; l < p->layers; ++l) {
-        const keds_block_params& k = p->blocks[l];
-        const bool last = l == p->layers - 1;
-        if ((rc = keds_layernorm_impl(x, w, nullptr, 1, k.ln1_g, k.ln1_b, t.h, 0, M, w, st))) return rc;
-        if ((rc = keds_gemm_bt(t.h, k.qkv_w, k.qkv_b, t.qkv, M, 3 * w, w, KEDS_EPI_BIAS_BF16, nullptr, 0, st))) return rc;
-        if (last && last_rows) return rows_tail(p, k, t, x, nullptr, B, last_rows, st, pk);
-        if (last && p->last_cls_only) return cls_rows_tail(p, k, t, x, nullptr, B, st);
-        if ((rc = attention(nullptr, nullptr))) return rc;
-        if ((rc = keds_gemm_bt(t.att, k.out_w, k.out_b, x, M, w, w, KEDS_EPI_BIAS_RESID_F32, nullptr, 0, st))) return rc;
-        if ((rc = keds_layernorm_impl(x, w, nullptr, 1, k.ln2_g, k.ln2_b, t.h, 0, M, w, st))) return rc;
-        if ((rc = keds_gemm_bt(t.h, k.fc_w, k.fc_b, t.hid, M, 4 * w, w, KEDS_EPI_BIAS_QGELU_BF16, nullptr, 0, st))) return rc;
-        if ((rc = keds_gemm_bt(t.hid, k.proj_w, k.proj_b, x, M, w, 4 * w, KEDS_EPI_BIAS_RESID_F32, nullptr, 0, st))) return rc;
-        if ((rc = keds_tap_rows(tp, l, p->layers, x, 1, 0, M, w, st))) return rc;
-    }
-    return KEDS_OK;
+        rc = tower_step(r, s);
+        return rc == KEDS_OK;
+    });
+    return rc;
+}
+int run_tower(const keds_tower_params* p, float* x, int B, void* ws, hipStream_t st, const int32_t* last_rows = nullptr,
+              const PackedRows* pk = nullptr, const KedsTaps* tp = nullptr) {
+    return run_tower(p, x, B, ws, st, last_rows, pk, tp, [] { return KEDS_OK; });
+}
+
+// ln_post / ln_final of the read-out rows + projection (+ L2 normalisation), in the tower's arithmetic
+size_t readout_bytes(const keds_tower_params& t, int B) {
+    return t.f32 ? keds_readout_f32_workspace_bytes(B, t.width) : keds_readout_workspace_bytes(B, t.width);
+}
+int run_readout(const keds_tower_params& t, const float* x, int S, const int32_t* row, const float* gamma, const float* beta,
+                const void* proj_t, float* out, int B, int E, int normalize, void* ro, void* stream) {
+    if (t.f32) return keds_readout_f32(x, S, row, gamma, beta, (const float*)proj_t, out, B, t.width, E, normalize, ro, (hipStream_t)stream);
+    return keds_readout_impl(x, S, row, gamma, beta, proj_t, out, B, t.width, E, normalize, ro, keds_readout_workspace_bytes(B, t.width), stream,
+                             t.f16);
 }
 
 int check_tower(const keds_tower_params* p, const char* who) {
@@ -384,14 +257,44 @@ int check_tower(const keds_tower_params* p, const char* who) {
 }  // namespace
 
 extern "C" size_t keds_tower_workspace_bytes(int width, int seq, int B) {
-    return carve_tower(nullptr, width, seq, B).bytes;
+    return tower_layout(KEDS_TOWER_FLOW_BF16, width, seq, B).total;
+}
+
+extern "C" size_t keds_tower_workspace_bytes_ex(const keds_tower_params* p, int B) {
+    if (!p || B <= 0) return 0;
+    return tower_layout(p->f32 ? KEDS_TOWER_FLOW_F32 : KEDS_TOWER_FLOW_BF16, p->width, p->seq, B).total;
 }
 
 extern "C" int keds_tower_side_rows(int width, int seq, int B, int fp8) {
     if (width <= 0 || seq <= 0 || B <= 0) return 0;
-    const int M = B * seq, Mt = M % 256;
-    const bool split = fp8 ? (M >= 256 && Mt > 0) : bf16_rows_split(M, width);
-    return split && keds_side_lane_enabled() ? Mt : 0;    // only a query: no stream is created here (no GPU needed)
+    const int M = B * seq;
+    const bool split = tower_splits_rows(fp8 ? KEDS_TOWER_FLOW_FP8 : KEDS_TOWER_FLOW_BF16, M, width);
+    return split && keds_side_lane_enabled() ? M % 256 : 0;    // only a query: no stream is created here (no GPU needed)
+}
+
+extern "C" int keds_tower_plan_query(int flow, int width, int heads, int seq, int causal, int layers, int B, int tail, int packed_rows,
+                                     int packed_valid, int taps, int split, int lane, int32_t* steps, int max_steps, int* n_steps,
+                                     int64_t* buffers, size_t* workspace_bytes) {
+    TowerPlanArgs a{flow, width, heads, seq, causal != 0, layers, B, tail, packed_rows, packed_valid, taps != 0, split > 0, lane > 0};
+    if (const char* why = tower_plan_check(a)) return tower_bad(why);
+    KEDS_REQUIRE(n_steps && (steps || max_steps <= 0), "keds_tower_plan_query: null pointer");
+    const int M = packed_rows ? packed_rows : B * seq;
+    if (split < 0) a.split = tower_splits_rows(flow == KEDS_TOWER_FLOW_FP8 && M < 256 ? KEDS_TOWER_FLOW_BF16 : flow, M, width);
+    if (lane < 0) a.lane = keds_side_lane_enabled();
+    int n = 0;
+    tower_plan(a, [&](const TowerStep& s) {
+        if (n < max_steps) memcpy(steps + (size_t)n * KEDS_TOWER_STEP_INTS, &s, sizeof s);
+        ++n;
+        return true;
+    });
+    *n_steps = n;
+    const TowerLayout L = tower_layout(flow, width, seq, B);
+    for (int id = 0; buffers && id < TB_N; ++id) {
+        const int64_t row[4] = {id, id == TB_X ? -1 : (int64_t)L.b[id].off, (int64_t)L.b[id].bytes, L.b[id].alias_of};
+        memcpy(buffers + 4 * id, row, sizeof row);
+    }
+    if (workspace_bytes) *workspace_bytes = L.total;
+    return KEDS_OK;
 }
 
 extern "C" int keds_tower_forward(const keds_tower_params* p, float* x, int B, void* workspace, size_t workspace_bytes,
@@ -403,13 +306,7 @@ extern "C" int keds_tower_forward(const keds_tower_params* p, float* x, int B, v
         keds_set_error("keds_tower_forward: workspace too small");
         return KEDS_E_WORKSPACE;
     }
-    if (p->f32) return keds_tower_forward_f32(p, x, B, workspace, (hipStream_t)stream);
-    return tower_forward(p, x, B, workspace, (hipStream_t)stream);
-}
-
-extern "C" size_t keds_tower_workspace_bytes_ex(const keds_tower_params* p, int B) {
-    if (!p || B <= 0) return 0;
-    return p->f32 ? keds_tower_f32_workspace_bytes(p->width, p->seq, B) : keds_tower_workspace_bytes(p->width, p->seq, B);
+    return run_tower(p, x, B, workspace, (hipStream_t)stream);
 }
 
 // ---- ViT -------------------------------------------------------------------------------------
@@ -429,7 +326,7 @@ VitWs carve_vit(const keds_vit_params* p, int B, void* ws) {
     size_t tb = keds_tower_workspace_bytes_ex(&p->tower, B);
     const size_t colb = keds_align_up(pad_rows((size_t)B * (S - 1)) * p->kpad * (p->tower.f32 ? 4 : 2), 256);
     if (colb > tb) tb = colb;
-    const size_t rb = keds_align_up(p->tower.f32 ? keds_readout_f32_workspace_bytes(B, w) : keds_readout_workspace_bytes(B, w), 256);
+    const size_t rb = keds_align_up(readout_bytes(p->tower, B), 256);
     v.x = (float*)base;
     v.tower = base ? base + xb : nullptr;
     v.ro = base ? base + xb + tb : nullptr;
@@ -474,27 +371,21 @@ int vit_run(const keds_vit_params* p, const float* image, int B, float* out, int
         // the fp32-accurate flow (f32path.hip): every weight pointer of the structs is an fp32 array
         if ((rc = keds_im2col_f32(image, (float*)col, B, p->resolution, p->patch, p->kpad, stream))) return rc;
         if ((rc = keds_gemm_f32((const float*)col, p->kpad, (const float*)p->conv_w, nullptr, v.x, w, B * G, w, p->kpad,
-                                4 /* patch rows + positional embedding */, p->pos_emb, G, stream)))
+                                KEDS_F32_EPI_PATCH /* patch rows + positional embedding */, p->pos_emb, G, stream)))
             return rc;
-        if ((rc = keds_cls_rows_impl(v.x, p->class_emb, p->pos_emb, B, S, w, st))) return rc;
-        if ((rc = keds_layernorm_impl(v.x, w, nullptr, 1, p->ln_pre_g, p->ln_pre_b, v.x, 1, B * S, w, st))) return rc;
-        if ((rc = keds_tower_forward_f32(tw, v.x, B, v.tower, st, nullptr, nullptr, tp))) return rc;
-        if (!out) return KEDS_OK;
-        return keds_readout_f32(v.x, S, nullptr, p->ln_post_g, p->ln_post_b, (const float*)p->proj_t, out, B, w, p->embed_dim,
-                                normalize, v.ro, st);
+    } else {
+        const bool h = p->tower.f16;              // (conv_w / proj_t fp16 too)
+        if ((rc = keds_im2col_ex(image, col, h ? 1 : 0, B, p->resolution, p->patch, p->kpad, stream))) return rc;
+        if ((rc = keds_gemm_bt(col, p->conv_w, nullptr, v.x, B * G, w, p->kpad, h ? KEDS_EPI_PATCH_F32_H : KEDS_EPI_PATCH_F32, p->pos_emb, G,
+                               stream)))
+            return rc;
     }
-    const bool h = p->tower.f16;                  // (conv_w / proj_t fp16 too)
-    if ((rc = keds_im2col_ex(image, col, h ? 1 : 0, B, p->resolution, p->patch, p->kpad, stream))) return rc;
-    if ((rc = keds_gemm_bt(col, p->conv_w, nullptr, v.x, B * G, w, p->kpad, h ? KEDS_EPI_PATCH_F32_H : KEDS_EPI_PATCH_F32, p->pos_emb, G,
-                           stream)))
-        return rc;
     if ((rc = keds_cls_rows_impl(v.x, p->class_emb, p->pos_emb, B, S, w, st))) return rc;
     // ln_pre in place (each wave holds its whole row in registers before it stores)
     if ((rc = keds_layernorm_impl(v.x, w, nullptr, 1, p->ln_pre_g, p->ln_pre_b, v.x, 1, B * S, w, st))) return rc;
-    if ((rc = tower_forward(tw, v.x, B, v.tower, st, nullptr, nullptr, tp))) return rc;
+    if ((rc = run_tower(tw, v.x, B, v.tower, st, nullptr, nullptr, tp))) return rc;
     if (!out) return KEDS_OK;
-    return keds_readout_impl(v.x, S, nullptr, p->ln_post_g, p->ln_post_b, p->proj_t, out, B, w, p->embed_dim, normalize, v.ro,
-                             keds_readout_workspace_bytes(B, w), stream, h);
+    return run_readout(p->tower, v.x, S, nullptr, p->ln_post_g, p->ln_post_b, p->proj_t, out, B, p->embed_dim, normalize, v.ro, stream);
 }
 }  // namespace
 
@@ -535,7 +426,7 @@ TextWs carve_text_cols(const keds_text_params* p, int B, int S, void* ws) {     
     keds_tower_params tp = p->tower;
     tp.seq = S;
     const size_t tb = keds_tower_workspace_bytes_ex(&tp, B);
-    const size_t rb = keds_align_up(p->tower.f32 ? keds_readout_f32_workspace_bytes(B, w) : keds_readout_workspace_bytes(B, w), 256);
+    const size_t rb = keds_align_up(readout_bytes(p->tower, B), 256);
     v.x = (float*)base;
     v.tower = base ? base + xb : nullptr;
     v.ro = base ? base + xb + tb : nullptr;
@@ -543,6 +434,35 @@ TextWs carve_text_cols(const keds_text_params* p, int B, int S, void* ws) {     
     return v;
 }
 TextWs carve_text(const keds_text_params* p, int B, void* ws) { return carve_text_cols(p, B, p->tower.seq, ws); }
+
+// the prologue the text entries share: the tower's shape (and the projection's), then the workspace for all L columns
+int text_check(const keds_text_params* p, bool projects, const char* who) {
+    int rc = check_tower(&p->tower, who);
+    if (rc) return rc;
+    KEDS_REQUIRE(!projects || p->embed_dim % 128 == 0, "%s: embed_dim must be a multiple of 128", who);
+    return KEDS_OK;
+}
+int text_workspace(const keds_text_params* p, int B, size_t workspace_bytes, const char* who) {
+    const size_t need = carve_text(p, B, nullptr).bytes;
+    if (workspace_bytes < need) {
+        keds_set_error("%s: workspace %zu < %zu", who, workspace_bytes, need);
+        return KEDS_E_WORKSPACE;
+    }
+    return KEDS_OK;
+}
+// the tower on `cols` columns per sequence (never larger than the full layout text_workspace covers), then ln_final of the read-out
+// rows + projection.  last_rows: the read-out-row tail (the read-out then takes row b of the compact x); front: run_tower
+template <typename Front>
+int text_tower_readout(const keds_text_params* p, int cols, const int32_t* readout_row, const int32_t* last_rows, const PackedRows* pk,
+                       int B, float* out, int normalize, void* workspace, void* stream, Front&& front) {
+    keds_tower_params tp = p->tower;              // the tower on the columns that are computed
+    tp.seq = cols;
+    const TextWs v = carve_text_cols(p, B, cols, workspace);
+    int rc = run_tower(&tp, v.x, B, v.tower, (hipStream_t)stream, last_rows, pk, nullptr, front);
+    if (rc) return rc;
+    return run_readout(tp, v.x, last_rows ? 1 : cols, last_rows ? nullptr : readout_row, p->ln_final_g, p->ln_final_b, p->proj_t, out, B,
+                       p->embed_dim, normalize, v.ro, stream);
+}
 }  // namespace
 
 extern "C" size_t keds_text_workspace_bytes(const keds_text_params* p, int B) {
@@ -572,42 +492,27 @@ extern "C" int keds_text_trim_mode(void) {       // the flow in force: 1 = cut +
 //  * the mask is causal (model.py:543-549), so columns to the right of the last read-out column change no row that is read:
 //    `seq_used` (host-known: max(readout_row) + 1; 0 = unknown, all L columns) cuts the sequence there for the embedding, all
 //    blocks and the workspace layout ([B, columns, w]);
-//  * the last block's out-proj, ln_2 and MLP run on the B read-out rows only (rows_tail), as the ViT's do on the CLS rows.
+//  * the last block's out-proj, ln_2 and MLP run on the B read-out rows only (tower_plan.h, the READOUT tail), as the ViT's do on the CLS rows.
 extern "C" int keds_text_run_ex(const keds_text_params* p, const int32_t* tokens, const int32_t* readout_row,
                                 const float* img_tokens, int n_tok, int insert_col, int B, int seq_used, float* out,
                                 int normalize, void* workspace, size_t workspace_bytes, void* stream) {
-    KEDS_REQUIRE(p && tokens && readout_row && out && workspace && B > 0, "keds_text_run: bad argument");
-    int rc = check_tower(&p->tower, "keds_text_run");
+    const char* who = "keds_text_run";
+    KEDS_REQUIRE(p && tokens && readout_row && out && workspace && B > 0, "%s: bad argument", who);
+    int rc = text_check(p, true, who);
     if (rc) return rc;
-    KEDS_REQUIRE(p->embed_dim % 128 == 0, "keds_text_run: embed_dim must be a multiple of 128");
-    KEDS_REQUIRE(seq_used >= 0 && seq_used <= p->tower.seq, "keds_text_run: seq_used %d outside [0, %d]", seq_used, p->tower.seq);
-    TextWs v = carve_text(p, B, workspace);
-    if (workspace_bytes < v.bytes) {
-        keds_set_error("keds_text_run: workspace %zu < %zu", workspace_bytes, v.bytes);
-        return KEDS_E_WORKSPACE;
-    }
+    KEDS_REQUIRE(seq_used >= 0 && seq_used <= p->tower.seq, "%s: seq_used %d outside [0, %d]", who, seq_used, p->tower.seq);
+    if ((rc = text_workspace(p, B, workspace_bytes, who))) return rc;
     const int w = p->tower.width, L = p->tower.seq;
-    const int mode = g_text_trim < 0 ? (text_trim_on() ? 1 : 0) : g_text_trim;
+    const int mode = keds_text_trim_mode();
     const bool cut = mode == 1 || mode == 2, trim = mode == 1 || mode == 3;
     int Lx = L;
     // (no rounding of the cut to whole row tiles: measured at B = 128 -- tools/text_shapes.py, profiles/r05_text_shapes.txt --
     // the four GEMMs of a block take 161 us at 43 columns, 170 at 44, 172-174 at 46-48: at these sizes the 128 x 128 kernel's
     // rounds of 512 workgroups decide, and fewer rows are never slower)
     if (cut && seq_used > 0 && seq_used < L && p->tower.causal) Lx = seq_used;
-    keds_tower_params tp = p->tower;              // the tower on the columns that are computed
-    tp.seq = Lx;
-    v = carve_text_cols(p, B, Lx, workspace);     // (never larger than the full layout the size check above covers)
-    if ((rc = keds_embed_tokens_impl(tokens, p->token_emb, p->pos_emb, img_tokens, n_tok, insert_col, v.x, B, L, Lx, w, stream)))
-        return rc;
-    const int32_t* last_rows = trim ? readout_row : nullptr;
-    if (tp.f32) {
-        if ((rc = keds_tower_forward_f32(&tp, v.x, B, v.tower, (hipStream_t)stream, last_rows))) return rc;
-        return keds_readout_f32(v.x, last_rows ? 1 : Lx, last_rows ? nullptr : readout_row, p->ln_final_g, p->ln_final_b,
-                                (const float*)p->proj_t, out, B, w, p->embed_dim, normalize, v.ro, (hipStream_t)stream);
-    }
-    if ((rc = tower_forward(&tp, v.x, B, v.tower, (hipStream_t)stream, last_rows))) return rc;
-    return keds_readout_impl(v.x, last_rows ? 1 : Lx, last_rows ? nullptr : readout_row, p->ln_final_g, p->ln_final_b, p->proj_t, out,
-                             B, w, p->embed_dim, normalize, v.ro, keds_readout_workspace_bytes(B, w), stream, tp.f16);
+    return text_tower_readout(p, Lx, readout_row, trim ? readout_row : nullptr, nullptr, B, out, normalize, workspace, stream, [&] {
+        return keds_embed_tokens_impl(tokens, p->token_emb, p->pos_emb, img_tokens, n_tok, insert_col, (float*)workspace, B, L, Lx, w, stream);
+    });
 }
 
 // The same on PACKED rows (round 6).  Captions end at different columns and under the causal mask (model.py:543-549) a column to
@@ -623,44 +528,27 @@ extern "C" int keds_text_run_packed(const keds_text_params* p, const int32_t* to
                                     const int32_t* readout_global, int rows_total, int seq_max, const float* img_tokens, int n_tok,
                                     int insert_col, int B, float* out, int normalize, void* workspace, size_t workspace_bytes,
                                     void* stream) {
-    KEDS_REQUIRE(p && tokens && seq_off && readout_global && out && workspace && B > 0, "keds_text_run_packed: bad argument");
-    int rc = check_tower(&p->tower, "keds_text_run_packed");
+    const char* who = "keds_text_run_packed";
+    KEDS_REQUIRE(p && tokens && seq_off && readout_global && out && workspace && B > 0, "%s: bad argument", who);
+    int rc = text_check(p, true, who);
     if (rc) return rc;
-    KEDS_REQUIRE(p->embed_dim % 128 == 0, "keds_text_run_packed: embed_dim must be a multiple of 128");
     const int w = p->tower.width, L = p->tower.seq;
-    KEDS_REQUIRE(p->tower.causal && !p->tower.fp8, "keds_text_run_packed: a causal bf16 / fp32 / fp32x3 tower (the MXFP8 tower keeps the rectangular layout)");
-    KEDS_REQUIRE(keds_text_trim_mode() == 1, "keds_text_run_packed: the A/B flows of keds_text_trim_enable / KEDS_TEXT_TRIM=0 go through keds_text_run_ex");
+    KEDS_REQUIRE(p->tower.causal && !p->tower.fp8, "%s: a causal bf16 / fp32 / fp32x3 tower (the MXFP8 tower keeps the rectangular layout)", who);
+    KEDS_REQUIRE(keds_text_trim_mode() == 1, "%s: the A/B flows of keds_text_trim_enable / KEDS_TEXT_TRIM=0 go through keds_text_run_ex", who);
     KEDS_REQUIRE(seq_max >= 1 && seq_max <= L && rows_total >= B && (long long)rows_total <= (long long)B * seq_max,
-                 "keds_text_run_packed: rows_total %d / seq_max %d do not fit B = %d sequences of <= %d columns", rows_total, seq_max, B, L);
-    TextWs v = carve_text(p, B, workspace);
-    if (workspace_bytes < v.bytes) {
-        keds_set_error("keds_text_run_packed: workspace %zu < %zu", workspace_bytes, v.bytes);
-        return KEDS_E_WORKSPACE;
-    }
-    keds_tower_params tp = p->tower;
-    tp.seq = seq_max;
-    v = carve_text_cols(p, B, seq_max, workspace);
+                 "%s: rows_total %d / seq_max %d do not fit B = %d sequences of <= %d columns", who, rows_total, seq_max, B, L);
+    if ((rc = text_workspace(p, B, workspace_bytes, who))) return rc;
     // the tower runs WHOLE 256-row tiles: the rows between rows_total and the next multiple of 256 are zero rows that belong to no
-    // sample (no attention reads them, nothing gathers them).  A ragged last tile would send every GEMM of every block through the
-    // remainder-row launches and the stricter fill rule of the 256 x 256 kernels (gemm_plan.h, gemm_big_tiles_fill).
+    // sample (no attention reads them, nothing gathers them; the pass clears them in front of the embedding).  A ragged last tile
+    // would send every GEMM of every block through the remainder-row launches and the stricter fill rule of the 256 x 256 kernels
+    // (gemm_plan.h, gemm_big_tiles_fill).
     int rows_run = (rows_total + 255) / 256 * 256;
     if ((size_t)rows_run > pad_rows((size_t)B * seq_max)) rows_run = rows_total;
-    if (rows_run > rows_total &&
-        hipMemsetAsync(v.x + (size_t)rows_total * w, 0, (size_t)(rows_run - rows_total) * w * sizeof(float), (hipStream_t)stream) != hipSuccess) {
-        keds_set_error("keds_text_run_packed: %s", hipGetErrorString(hipGetLastError()));
-        return KEDS_E_LAUNCH;
-    }
-    if ((rc = keds_embed_tokens_impl(tokens, p->token_emb, p->pos_emb, img_tokens, n_tok, insert_col, v.x, B, L, seq_max, w, stream, seq_off)))
-        return rc;
     const PackedRows pk{seq_off, rows_run, rows_total};
-    if (tp.f32) {
-        if ((rc = keds_tower_forward_f32(&tp, v.x, B, v.tower, (hipStream_t)stream, readout_global, &pk))) return rc;
-        return keds_readout_f32(v.x, 1, nullptr, p->ln_final_g, p->ln_final_b, (const float*)p->proj_t, out, B, w, p->embed_dim, normalize,
-                                v.ro, (hipStream_t)stream);
-    }
-    if ((rc = tower_forward(&tp, v.x, B, v.tower, (hipStream_t)stream, readout_global, &pk))) return rc;
-    return keds_readout_impl(v.x, 1, nullptr, p->ln_final_g, p->ln_final_b, p->proj_t, out, B, w, p->embed_dim, normalize, v.ro,
-                             keds_readout_workspace_bytes(B, w), stream, tp.f16);
+    return text_tower_readout(p, seq_max, nullptr, readout_global, &pk, B, out, normalize, workspace, stream, [&] {
+        return keds_embed_tokens_impl(tokens, p->token_emb, p->pos_emb, img_tokens, n_tok, insert_col, (float*)workspace, B, L, seq_max, w, stream,
+                                      seq_off);
+    });
 }
 
 // CLIP.get_text_tokens (model.py:592-605): ln_final over the residual stream of ALL L columns of every sample after the last block,
@@ -673,21 +561,16 @@ extern "C" int keds_text_run_tokens(const keds_text_params* p, const int32_t* to
     KEDS_REQUIRE(out, "%s: no output requested (out is null)", who);
     KEDS_REQUIRE(out_type >= 0 && out_type <= 2, "%s: out_type %d (0 bf16, 1 fp32, 2 fp16)", who, out_type);
     KEDS_REQUIRE(p && tokens && workspace, "%s: bad argument (null params, tokens or workspace)", who);
-    int rc = check_tower(&p->tower, who);
+    int rc = text_check(p, false, who);
     if (rc) return rc;
-    TextWs v = carve_text(p, B, workspace);
-    if (workspace_bytes < v.bytes) {
-        keds_set_error("%s: workspace %zu < %zu", who, workspace_bytes, v.bytes);
-        return KEDS_E_WORKSPACE;
-    }
+    if ((rc = text_workspace(p, B, workspace_bytes, who))) return rc;
+    const TextWs v = carve_text(p, B, workspace);
     const int w = p->tower.width, L = p->tower.seq;
     hipStream_t st = (hipStream_t)stream;
     keds_tower_params tp = p->tower;
     tp.last_cls_only = 0;
     if ((rc = keds_embed_tokens_impl(tokens, p->token_emb, p->pos_emb, nullptr, 0, 0, v.x, B, L, L, w, stream))) return rc;
-    if (tp.f32) rc = keds_tower_forward_f32(&tp, v.x, B, v.tower, st);
-    else rc = tower_forward(&tp, v.x, B, v.tower, st);
-    if (rc) return rc;
+    if ((rc = run_tower(&tp, v.x, B, v.tower, st))) return rc;
     return keds_layernorm_impl(v.x, w, nullptr, 1, p->ln_final_g, p->ln_final_b, out, out_type, B * L, w, st);
 }
 

@@ -185,7 +185,7 @@ def test_vitl14_full_size_against_reference_golden():
 @pytest.mark.parametrize("precision", ["bf16", "fp8"])
 def test_side_lane_for_remainder_rows_changes_no_bit(precision):
     """At B = 128 the ViT-L/14 tower has 128 full 256-row tiles + 128 remainder rows; the remainder chain runs on a second
-    stream beside the full tiles (towers.hip, RowLanes).  Same kernels on the same rows: the embeddings must be the very
+    stream beside the full tiles (tower_plan.h, the fork / join steps).  Same kernels on the same rows: the embeddings must be the very
     same bits with the lane on and off, run after run (a missing fork / join would show up here as a race)."""
     from keds_amd import _lib
     lib = _lib.load()

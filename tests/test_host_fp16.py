@@ -53,14 +53,14 @@ def test_tower_params_carry_the_f16_field_and_header_and_library_agree_on_abi_9(
     p = _lib.TowerParams(768, 12, 12, 77, 1, None, 0, 0, 0, 1)
     assert p.f16 == 1 and p.f32 == 0
     hdr = open(os.path.join(ROOT, "include", "keds_hip.h")).read()
-    assert int(re.search(r"#define KEDS_ABI_VERSION (\d+)", hdr).group(1)) == _lib.ABI_VERSION == 14
+    assert int(re.search(r"#define KEDS_ABI_VERSION (\d+)", hdr).group(1)) == _lib.ABI_VERSION == 15
     assert re.search(r"int f16;", hdr)
     for name, val in (("KEDS_EPI_LN_BIAS_F16_H", 16), ("KEDS_EPI_LN_QGELU_F16_H", 17), ("KEDS_EPI_RESID_STATS_F16_H", 18),
                       ("KEDS_EPI_BIAS_RESID_F32_H", 19), ("KEDS_EPI_BIAS_QGELU_F16_H", 20), ("KEDS_EPI_PATCH_F32_H", 21),
                       ("KEDS_EPI_BIAS_F32_H", 22)):
         assert int(re.search(rf"#define {name} (\d+)", hdr).group(1)) == val == getattr(_lib, name[5:])
     lib = _lib.load()
-    assert lib.keds_abi_version() == 14
+    assert lib.keds_abi_version() == 15
     for sym in ("keds_attention_h", "keds_attention_packed_h", "keds_im2col_ex", "keds_layernorm_ex", "keds_cast_f16"):
         assert hasattr(lib, sym)
 

@@ -319,7 +319,7 @@ def test_x3_row_remainder_launch_behind_big_tiles(lib):
              persistent=int(224 > T and code != 14), flags=0)
 
 
-# ---- keds_gemm_splits_rows: whether a tower runs two lanes (towers.hip, bf16_rows_split) -----------------------------------------
+# ---- keds_gemm_splits_rows: whether a tower runs two lanes (tower_plan.h, tower_splits_rows) -----------------------------------------
 def test_splits_rows_is_the_models_remainder_launch(lib):
     splits_rows = getattr(lib, "_Z21keds_gemm_splits_rowsiii")      # bool keds_gemm_splits_rows(int, int, int): library-internal, C++
     splits_rows.restype, splits_rows.argtypes = ctypes.c_bool, [ctypes.c_int] * 3

@@ -32,7 +32,7 @@ def test_token_entry_points_are_declared_exported_and_bound():
         assert re.search(rf"\b{name}\s*\(", text), f"{name} not declared in include/*.h"
         assert name in _lib.SIGNATURES, f"{name} missing from keds_amd._lib.SIGNATURES"
         assert hasattr(lib, name), f"{name} not exported"
-    assert lib.keds_abi_version() == 14 == _lib.ABI_VERSION
+    assert lib.keds_abi_version() == 15 == _lib.ABI_VERSION
 
 
 def test_token_entry_points_reject_bad_arguments_without_a_gpu():

@@ -1,4 +1,4 @@
-"""A tower pass as DATA: the ordered chain of kernel launches a pass of keds_amd/csrc/towers.hip / f32path.hip has to make, written
+"""A tower pass as DATA: the ordered chain of kernel launches a pass of keds_amd/csrc/towers.hip (planned in tower_plan.h) has to make, written
 from the model's arithmetic (a pre-LN residual block, a CLS or read-out row after the last block, a causal mask) and the documented
 properties of the epilogues (include/keds_hip.h) -- and a float64 executor of such a chain that models the BUFFERS as state.
 
