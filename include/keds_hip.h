@@ -32,6 +32,8 @@ extern "C" {
 
 #define KEDS_ABI_VERSION 15       /* 15: keds_tower_plan_query (every tower pass is planned by one pure host function and run from its steps, as the
                                      GEMM and attention launches are);
+                                     (still 15: keds_cross_attn_seq, keds_cross_seq_plan_query, keds_cross_seq_last_launch,
+                                     keds_crossformer_seq_workspace_bytes and keds_crossformer_forward_seq were added; no earlier entry changed)
                                      14: keds_attention_f32_packed, keds_attention_x3_packed (the fp32 and split-fp16 attention on packed rows, one call at a
                                      time; the tower passes launch through the same helpers);
                                      13: keds_cross_attn_core, keds_cross_core_f32, keds_knowledge_pack_rows, keds_place_token (the knowledge stream's
@@ -794,6 +796,37 @@ int keds_cross_attn_core(const void* Q, const void* Kp, const void* Vp, void* ou
 int keds_knowledge_pack_rows(const float* q, const float* nbr_img, const float* nbr_txt, void* rows, int B, int K, int dim,
                              void* stream);
 int keds_place_token(const float* src, float* tokens, int B, int dim, int slot, int nslots, void* stream);
+
+/* Multi-query cross-attention core (CrossAttention.forward, model.py:56-79, for any number of queries and keys), dim_head 64, no mask:
+ *   out[b, i, h] = softmax(Q[b, i, h] . K[b, :, h]^T / 8) . V[b, :, h]
+ * Q bf16 rows [B Lq] of stride q_ld elements, head h at columns 64 h .. 64 h + 63; Kp / Vp bf16 rows [B Lk] of stride kv_ld (two
+ * pointers: K and V may be two column ranges of one wide buffer, and only the 64 heads columns behind each pointer are ever read);
+ * out bf16 rows [B Lq] of stride o_ld, of which only the 64 heads leading columns are written.  1 <= Lk <= KEDS_CROSS_SEQ_MAX_KEYS;
+ * Lq >= 1 has no limit of its own.  KEDS_E_ARG before any launch for a null pointer, B, Lq or heads < 1, Lk outside the range, a
+ * stride below 64 heads or not a multiple of 8, or a pointer that is not 16-byte aligned.  The arithmetic is keds_attention's
+ * (bf16 operands and probabilities on the matrix instruction, fp32 statistics).  keds_cross_attn_core keeps its own limits. */
+#define KEDS_CROSS_SEQ_MAX_KEYS 288
+int keds_cross_attn_seq(const void* Q, const void* Kp, const void* Vp, void* out, int B, int Lq, int Lk, int heads, int q_ld, int kv_ld,
+                        int o_ld, void* stream);
+/* Which launch the call above gets is decided in one host function (csrc/cross_seq_plan.h: the rules; docs/kernels.md: the table).
+ * info[8] (host ints, written): [0] KEDS_CROSS_SEQ_FORM_*, [1] 16-key tiles held in LDS (2, 6, 18), [2] leading key tiles left
+ * unmasked (0 or 16), [3] query rows per workgroup, [4] grid, [5] block, [6] LDS bytes, [7] workgroups per (sample, head). */
+#define KEDS_CROSS_SEQ_FORM_NONE 0
+#define KEDS_CROSS_SEQ_FORM_TILE 1  /* cross_attn_seq_kernel<nkt, nfull>: 4 waves, keys padded to whole tiles, K and V^T in LDS */
+/* the plan of a call; touches no device; B, Lq, heads >= 1 and 1 <= Lk <= 288, else KEDS_E_ARG with info untouched */
+int keds_cross_seq_plan_query(int B, int Lq, int Lk, int heads, int* info);
+/* test hook: what the calling thread's last keds_cross_attn_seq call launched -- written where the kernel is launched, not copied
+ * from the plan; a call whose launch differs from its plan fails with KEDS_E_LAUNCH */
+int keds_cross_seq_last_launch(int* info);
+
+/* CrossFormer.forward (model.py:98-101) on sequences: q fp32 [B,Lq,dim], k, v fp32 [B,Lk,dim] (Lk <= KEDS_CROSS_SEQ_MAX_KEYS; v may
+ * alias k, which skips its cast) -> out fp32 [B,Lq,dim].  The per-layer chain of keds_crossformer_forward on B Lq query rows, made
+ * of public pieces: keds_cast_bf16 of the inputs; per layer the q / k / v projections (keds_gemm_bt, KEDS_EPI_BIAS_BF16),
+ * keds_cross_attn_seq, and the output projection (bf16 between layers, KEDS_EPI_BIAS_F32 for the last).  p->fused is not used.
+ * KEDS_E_ARG before any launch; a workspace below keds_crossformer_seq_workspace_bytes is KEDS_E_WORKSPACE with nothing written. */
+size_t keds_crossformer_seq_workspace_bytes(const keds_crossformer_params* p, int B, int Lq, int Lk);
+int keds_crossformer_forward_seq(const keds_crossformer_params* p, const float* q, const float* k, const float* v, int B, int Lq, int Lk,
+                                 float* out, void* workspace, size_t workspace_bytes, void* stream);
 
 size_t keds_knowledge_workspace_bytes(const keds_knowledge_params* p, int B, int K);
 /* one stream of eval_utils.py:661-672: q [B,dim] fp32, nbr_img / nbr_txt [B,K,dim] fp32 ->

@@ -278,6 +278,12 @@ SIGNATURES = {
     "keds_cross_attn_core": (i32, [vp, vp, vp, vp, i32, i32, i32, i32, vp]),
     "keds_cross_core_f32": (i32, [vp, vp, vp, vp, i32, i32, i32, vp]),
     "keds_knowledge_pack_rows": (i32, [vp, vp, vp, vp, i32, i32, i32, vp]),
+    # the multi-query cross-attention core (Lk <= 288), its plan, and the CrossFormer on sequences (csrc/cross_seq.hip)
+    "keds_cross_attn_seq": (i32, [vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, vp]),
+    "keds_cross_seq_plan_query": (i32, [i32, i32, i32, i32, vp]),
+    "keds_cross_seq_last_launch": (i32, [vp]),
+    "keds_crossformer_seq_workspace_bytes": (sz, [C.POINTER(CrossFormerParams), i32, i32, i32]),
+    "keds_crossformer_forward_seq": (i32, [C.POINTER(CrossFormerParams), vp, vp, vp, i32, i32, i32, vp, vp, sz, vp]),
     "keds_place_token": (i32, [vp, vp, i32, i32, i32, i32, vp]),
     "keds_knowledge_workspace_bytes": (sz, [C.POINTER(KnowledgeParams), i32, i32]),
     "keds_knowledge_run": (i32, [C.POINTER(KnowledgeParams), vp, vp, vp, i32, i32, vp, vp, sz, vp]),

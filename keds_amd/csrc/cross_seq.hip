@@ -1,0 +1,398 @@
+// Multi-query cross-attention core and the CrossFormer on sequences:
+//   out[b, i, h] = softmax(Q[b, i, h] . K[b, :, h]^T / 8) . V[b, :, h]        (no mask, dim_head = 64, bf16 operands)
+// with Lq queries and Lk <= 288 keys per sample, Q / K / V / out in four buffers with their own row counts and strides.
+// Reference: CrossAttention.forward (src/model/model.py:56-79), written for any number of queries and keys, as Transformer.forward
+// (model.py:343-371) and the late-fusion call of eval_utils.py:249 (one query over the 77 text tokens) use it.
+//
+// The arithmetic and the LDS image are attention_kernel's (attention.hip; that file's kernels are pinned bit for bit and stay as they
+// are, so the tile routine is written out again here without the causal / tail / MXFP8 branches): all of a (sample, head)'s K rows
+// (swizzled 128-byte rows) and V^T (permuted key order) resident in LDS, scores computed swapped, S^T = K . Q^T on
+// v_mfma_f32_16x16x32_bf16, so a lane holds one query column and four keys per 16-key tile: row maximum and sum are in-lane plus two
+// shuffles, exp2 with the folded 1 / sqrt(64) . log2 e, the probabilities rounded to bf16 in registers are the B operand of
+// O^T = V^T . P^T, and the sum is taken over the unrounded probabilities.
+// What differs from the self-attention kernel: a sample's query rows start at b Lq and its key rows at b Lk (two offsets, three
+// strides, all products in size_t); only columns [64 h, 64 h + 64) of the rows the call owns are ever read (K and V may be column
+// ranges of one wide buffer whose other columns hold anything); the query rows of a partly filled last tile are clamped on load and
+// never stored; pad keys >= Lk are zero in LDS (K and V^T: a NaN there would survive a zero probability) and -inf before the row
+// maximum.  Which template arguments, grid and LDS a call gets is decided in cross_seq_plan.h and nowhere else.
+#include "keds_common.h"
+#include "cross_seq_plan.h"      // DH, AttnCfg (attention_plan.h) and cross_seq_plan()
+#include <math.h>
+
+namespace {
+
+typedef float f32x2 __attribute__((ext_vector_type(2)));
+__device__ __forceinline__ f32x2 pk_fma(f32x2 a, f32x2 b, f32x2 c) {
+    f32x2 d;
+    asm("v_pk_fma_f32 %0, %1, %2, %3" : "=v"(d) : "v"(a), "v"(b), "v"(c));
+    return d;
+}
+
+struct SeqCtx {
+    const bf16_t* q;     // Q of (b, h): row stride q_ld
+    bf16_t* out;         // out of (b, h): row stride o_ld
+    const char* k_lds;
+    const char* vt_lds;
+    size_t q_ld, o_ld;
+    int Lq, Lk, q_end;   // rows [.., q_end) of the sample are this workgroup's to store
+    int g, c;
+};
+
+// NQ consecutive 16-query tiles whose first query row (inside the sample) is q0, for one wave
+template <int NKT, int NFULL, int NQ>
+__device__ __forceinline__ void seq_tiles(const SeqCtx& cx, int q0) {
+    using C = AttnCfg<NKT>;
+    const int g = cx.g, c = cx.c;
+    const float sl2 = 0.125f * 1.4426950408889634f;  // 1/sqrt(64) * log2(e)
+    int qidx[NQ];
+    bf16x8 qf[NQ][2];
+#pragma unroll
+    for (int t = 0; t < NQ; ++t) {
+        qidx[t] = q0 + t * 16 + c;
+        const int qrow = qidx[t] < cx.Lq ? qidx[t] : cx.Lq - 1;      // a partly filled tile: a row of this sample, never stored
+        const bf16_t* qp = cx.q + (size_t)qrow * cx.q_ld + 8 * g;
+        qf[t][0] = *reinterpret_cast<const bf16x8*>(qp);
+        qf[t][1] = *reinterpret_cast<const bf16x8*>(qp + 32);
+    }
+    // ---- S^T tiles
+    f32x4 sc[NQ][NKT];
+#pragma unroll
+    for (int kt = 0; kt < NKT; ++kt) {
+        const int key = kt * 16 + c;
+        const char* kr = cx.k_lds + key * 128;
+        const int f = (key >> 1) & 7;
+        const bf16x8 a0 = *reinterpret_cast<const bf16x8*>(kr + ((g ^ f) << 4));
+        const bf16x8 a1 = *reinterpret_cast<const bf16x8*>(kr + (((4 + g) ^ f) << 4));
+#pragma unroll
+        for (int t = 0; t < NQ; ++t) {
+            f32x4 acc = f32x4{0.f, 0.f, 0.f, 0.f};
+            acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a0, qf[t][0], acc, 0, 0, 0);
+            acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a1, qf[t][1], acc, 0, 0, 0);
+            sc[t][kt] = acc;
+        }
+        if (kt % 3 == 2) __builtin_amdgcn_sched_barrier(0);   // bound how far LDS reads are hoisted (VGPR pressure)
+    }
+    // ---- pad keys, row max, exp, row sum (lane holds query qidx[t], keys kt*16 + 4g + r)
+    float inv[NQ];
+#pragma unroll
+    for (int t = 0; t < NQ; ++t) {
+        float mx = -INFINITY;
+#pragma unroll
+        for (int kt = 0; kt < NKT; ++kt)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                float v = sc[t][kt][r];
+                if (kt >= NFULL) {                // resolved at compile time once the kt loop is unrolled
+                    v = kt * 16 + 4 * g + r < cx.Lk ? v : -INFINITY;
+                    sc[t][kt][r] = v;
+                }
+                mx = fmaxf(mx, v);
+            }
+        mx = rows_max(mx);                        // key 0 is always below Lk: finite
+        const float nmx = -mx * sl2;
+        // packed fp32 math (v_pk_fma_f32 / v_pk_add_f32: two elements per VALU issue); v_exp_f32 stays per element
+        const f32x2 vs = f32x2{sl2, sl2}, vn = f32x2{nmx, nmx};
+        f32x2 vsum = f32x2{0.f, 0.f};
+#pragma unroll
+        for (int kt = 0; kt < NKT; ++kt) {
+#pragma unroll
+            for (int hh = 0; hh < 2; ++hh) {
+                f32x2 e = f32x2{sc[t][kt][2 * hh], sc[t][kt][2 * hh + 1]};
+                e = pk_fma(e, vs, vn);
+                e[0] = __builtin_amdgcn_exp2f(e[0]);   // exp2(-inf) = 0
+                e[1] = __builtin_amdgcn_exp2f(e[1]);
+                sc[t][kt][2 * hh] = e[0];
+                sc[t][kt][2 * hh + 1] = e[1];
+                vsum += e;
+            }
+        }
+        inv[t] = 1.0f / rows_sum(vsum[0] + vsum[1]);
+    }
+    // ---- O^T = V^T . P^T
+    f32x4 o[NQ][4];
+#pragma unroll
+    for (int t = 0; t < NQ; ++t)
+#pragma unroll
+        for (int dt = 0; dt < 4; ++dt) o[t][dt] = f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int u = 0; u < NKT / 2; ++u) {
+        bf16x8 pf[NQ];
+#pragma unroll
+        for (int t = 0; t < NQ; ++t) {
+            const f32x4 p0 = sc[t][2 * u], p1 = sc[t][2 * u + 1];
+            pf[t] = bf16x8{(bf16_t)p0[0], (bf16_t)p0[1], (bf16_t)p0[2], (bf16_t)p0[3],
+                           (bf16_t)p1[0], (bf16_t)p1[1], (bf16_t)p1[2], (bf16_t)p1[3]};
+        }
+#pragma unroll
+        for (int dt = 0; dt < 4; ++dt) {
+            const bf16x8 a = *reinterpret_cast<const bf16x8*>(cx.vt_lds + (dt * 16 + c) * C::VT_ROW + (4 * u + g) * 16);
+#pragma unroll
+            for (int t = 0; t < NQ; ++t) o[t][dt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, pf[t], o[t][dt], 0, 0, 0);
+        }
+        if (u % 3 == 2) __builtin_amdgcn_sched_barrier(0);
+    }
+#pragma unroll
+    for (int t = 0; t < NQ; ++t) {
+        if (qidx[t] < cx.q_end) {
+            bf16_t* op = cx.out + (size_t)qidx[t] * cx.o_ld + 4 * g;
+#pragma unroll
+            for (int dt = 0; dt < 4; ++dt) {
+                const f32x4 v = o[t][dt] * inv[t];
+                *reinterpret_cast<bf16x4*>(op + dt * 16) = bf16x4{(bf16_t)v[0], (bf16_t)v[1], (bf16_t)v[2], (bf16_t)v[3]};
+            }
+        }
+    }
+}
+
+// One workgroup per (sample, head, chunk of q_per_wg queries); chunks = workgroups per (sample, head), the chunk fastest.
+// NFULL: key tiles [0, NFULL) are known at compile time to lie entirely below Lk and need no mask.
+template <int NKT, int NFULL>
+__global__ __launch_bounds__(256, 2) void cross_attn_seq_kernel(const bf16_t* __restrict__ Q, const bf16_t* __restrict__ Kp,
+                                                                const bf16_t* __restrict__ Vp, bf16_t* __restrict__ out, int Lq,
+                                                                int Lk, int heads, int q_ld, int kv_ld, int o_ld, int q_per_wg,
+                                                                int chunks) {
+    using C = AttnCfg<NKT>;
+    constexpr bool NQ2 = NKT == 18;     // two query tiles per step share every K / V^T fragment read (attention_kernel's rule)
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    char* k_lds = smem;
+    char* vt_lds = smem + C::K_BYTES;
+    const int bh = blockIdx.x / chunks, chunk = blockIdx.x - bh * chunks;
+    const int b = bh / heads, h = bh - b * heads;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int g = lane >> 4, c = lane & 15;
+    const bf16_t* kbase = Kp + (size_t)b * Lk * (size_t)kv_ld + h * DH;
+    const bf16_t* vbase = Vp + (size_t)b * Lk * (size_t)kv_ld + h * DH;
+
+    // ---- stage K (swizzled rows) and V^T (permuted key order); keys >= Lk are zero.  Work item = (4 consecutive keys, one 8-wide
+    // dh chunk): every global load of a thread is issued before the first LDS write, and the four keys of an item are adjacent in
+    // the permuted V^T row.
+    {
+        constexpr int ITEMS = (C::KEYS / 4) * 8;
+        constexpr int PER = (ITEMS + 255) / 256;
+        bf16x8 kreg[PER][4], vreg[PER][4];
+#pragma unroll
+        for (int it = 0; it < PER; ++it) {
+            const int id = tid + it * 256;
+            const int quad = id >> 3, ch = id & 7;
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                const int key = quad * 4 + e;
+                kreg[it][e] = bf16x8{0, 0, 0, 0, 0, 0, 0, 0};
+                vreg[it][e] = kreg[it][e];
+                if (id < ITEMS && key < Lk) {
+                    const size_t off = (size_t)key * (size_t)kv_ld + ch * 8;
+                    kreg[it][e] = *reinterpret_cast<const bf16x8*>(kbase + off);
+                    vreg[it][e] = *reinterpret_cast<const bf16x8*>(vbase + off);
+                }
+            }
+        }
+#pragma unroll
+        for (int it = 0; it < PER; ++it) {
+            const int id = tid + it * 256;
+            if (id >= ITEMS) continue;
+            const int quad = id >> 3, ch = id & 7;
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                const int key = quad * 4 + e;
+                *reinterpret_cast<bf16x8*>(k_lds + key * 128 + ((ch ^ ((key >> 1) & 7)) << 4)) = kreg[it][e];
+            }
+            // keys 4*quad .. 4*quad+3: u = key>>5, w = key&31, chunk (4u + ((w&15)>>2)), element 4*(w>>4) + (w&3)
+            const int k0 = quad * 4;
+            const int u = k0 >> 5, w = k0 & 31;
+            const int pos = (4 * u + ((w & 15) >> 2)) * 16 + ((w >> 4) << 2) * 2;
+#pragma unroll
+            for (int j = 0; j < 8; ++j)
+                *reinterpret_cast<bf16x4*>(vt_lds + (ch * 8 + j) * C::VT_ROW + pos) =
+                    bf16x4{vreg[it][0][j], vreg[it][1][j], vreg[it][2][j], vreg[it][3][j]};
+        }
+    }
+    __syncthreads();
+
+    // ---- this workgroup's queries: rows [q0, q_end) of the sample, in 16-query tiles dealt over the four waves
+    const int q0 = chunk * q_per_wg;
+    const int q_end = q0 + q_per_wg < Lq ? q0 + q_per_wg : Lq;
+    const int nqt = (q_end - q0 + 15) >> 4;
+    const SeqCtx cx{Q + (size_t)b * Lq * (size_t)q_ld + h * DH, out + (size_t)b * Lq * (size_t)o_ld + h * DH, k_lds, vt_lds,
+                    (size_t)q_ld, (size_t)o_ld, Lq, Lk, q_end, g, c};
+    if constexpr (NQ2) {
+        const int npair = nqt >> 1;
+        for (int qp = wave; qp < npair; qp += 4) seq_tiles<NKT, NFULL, 2>(cx, q0 + 32 * qp);
+        if ((nqt & 1) && wave == ((blockIdx.x + npair) & 3)) seq_tiles<NKT, NFULL, 1>(cx, q0 + 16 * (nqt - 1));
+    } else {
+        for (int qt = wave; qt < nqt; qt += 4) seq_tiles<NKT, NFULL, 1>(cx, q0 + 16 * qt);
+    }
+}
+
+// ---- host: the launch is planned by cross_seq_plan() (cross_seq_plan.h); launch_plan() runs the plan -----------------------------
+
+// What the last keds_cross_attn_seq call of this thread launched (keds_cross_seq_last_launch): written at the launch site with the
+// literal template arguments of the kernel launched there, and compared with the plan afterwards
+thread_local CrossSeqPlan tl_seq_rec = {};
+
+struct SeqArgs {
+    const bf16_t *Q, *Kp, *Vp;
+    bf16_t* out;
+    int B, Lq, Lk, heads, q_ld, kv_ld, o_ld;
+    hipStream_t stream;
+};
+
+template <int NKT, int NFULL>
+int launch_seq(const SeqArgs& a, const CrossSeqPlan& p) {
+    const auto kernel = cross_attn_seq_kernel<NKT, NFULL>;
+    const CrossSeqPlan rec{KEDS_CROSS_SEQ_FORM_TILE, NKT, NFULL, p.q_per_wg, a.B * a.heads * p.chunks, 256, AttnCfg<NKT>::LDS, p.chunks};
+    if (int rc = keds_func_lds_once((const void*)kernel, rec.lds, "cross_attn_seq_kernel")) return rc;
+    KedsProfScope prof(KEDS_PROF_ATTN, a.stream);
+    tl_seq_rec = rec;
+    kernel<<<rec.grid, rec.block, rec.lds, a.stream>>>(a.Q, a.Kp, a.Vp, a.out, a.Lq, a.Lk, a.heads, a.q_ld, a.kv_ld, a.o_ld, rec.q_per_wg,
+                                                     rec.chunks);
+    return keds_check_launch("cross_attn_seq_kernel");
+}
+
+// (nkt, nfull) -> the template instantiation: the only place that names them
+int launch_plan(const SeqArgs& a, const CrossSeqPlan& p) {
+    if (p.form == KEDS_CROSS_SEQ_FORM_TILE && p.nkt == 2 && !p.nfull) return launch_seq<2, 0>(a, p);
+    if (p.form == KEDS_CROSS_SEQ_FORM_TILE && p.nkt == 6 && !p.nfull) return launch_seq<6, 0>(a, p);
+    if (p.form == KEDS_CROSS_SEQ_FORM_TILE && p.nkt == 18 && p.nfull == 16) return launch_seq<18, 16>(a, p);
+    if (p.form == KEDS_CROSS_SEQ_FORM_TILE && p.nkt == 18 && !p.nfull) return launch_seq<18, 0>(a, p);
+    keds_set_error("keds_cross_attn_seq: no kernel of form %d with %d key tiles, %d unmasked", p.form, p.nkt, p.nfull);
+    return KEDS_E_LAUNCH;
+}
+
+int cross_seq(const SeqArgs& a) {
+    const CrossSeqPlan p = cross_seq_plan(a.B, a.Lq, a.Lk, a.heads);
+    tl_seq_rec = CrossSeqPlan{};
+    if (int rc = launch_plan(a, p)) return rc;
+    // keds_cross_seq_last_launch reports what the launch site recorded, not the plan: the two must agree
+    int want[8], got[8];
+    p.info(want);
+    tl_seq_rec.info(got);
+    for (int i = 0; i < 8; ++i) {
+        if (got[i] != want[i]) {
+            keds_set_error("keds_cross_attn_seq: the launch differs from the plan at [%d]: %d, planned %d (B %d, Lq %d, Lk %d, heads %d)", i,
+                           got[i], want[i], a.B, a.Lq, a.Lk, a.heads);
+            return KEDS_E_LAUNCH;
+        }
+    }
+    return KEDS_OK;
+}
+
+bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
+
+// every argument rule of keds_cross_attn_seq (keds_hip.h), before any launch
+int check_seq(const void* Q, const void* Kp, const void* Vp, const void* out, int B, int Lq, int Lk, int heads, int q_ld, int kv_ld, int o_ld) {
+    KEDS_REQUIRE(Q && Kp && Vp && out, "keds_cross_attn_seq: null pointer");
+    KEDS_REQUIRE(B >= 1 && Lq >= 1 && heads >= 1, "keds_cross_attn_seq: B=%d, Lq=%d, heads=%d must be at least 1", B, Lq, heads);
+    KEDS_REQUIRE(Lk >= 1 && Lk <= KEDS_CROSS_SEQ_MAX_KEYS, "keds_cross_attn_seq: Lk=%d must be in [1,%d]", Lk, KEDS_CROSS_SEQ_MAX_KEYS);
+    KEDS_REQUIRE(heads <= (1 << 20) && cross_seq_grid_fits(B, Lq, heads), "keds_cross_attn_seq: B=%d x heads=%d x Lq=%d is too large for one launch", B, heads, Lq);
+    const int inner = DH * heads;
+    KEDS_REQUIRE(q_ld >= inner && kv_ld >= inner && o_ld >= inner, "keds_cross_attn_seq: q_ld=%d, kv_ld=%d, o_ld=%d must be at least 64 heads = %d",
+                 q_ld, kv_ld, o_ld, inner);
+    KEDS_REQUIRE(q_ld % 8 == 0 && kv_ld % 8 == 0 && o_ld % 8 == 0, "keds_cross_attn_seq: q_ld=%d, kv_ld=%d, o_ld=%d must be multiples of 8", q_ld,
+                 kv_ld, o_ld);
+    KEDS_REQUIRE(aligned16(Q) && aligned16(Kp) && aligned16(Vp) && aligned16(out), "keds_cross_attn_seq: Q, Kp, Vp and out must be 16-byte aligned");
+    return KEDS_OK;
+}
+
+size_t rpad(size_t r) { return keds_align_up(r, 128); }
+
+// ---- CrossFormer on sequences: the per-layer chain of knowledge.hip's xf_run on B Lq query rows ---------------------------------
+struct XfSeqWs {
+    char *q_bf, *k_bf, *v_bf, *qcur, *Qp, *Kp, *Vp, *att;
+    size_t bytes;
+};
+// every GEMM operand addressable up to the next multiple of 128 rows, as carve_xf does
+XfSeqWs carve_xf_seq(const keds_crossformer_params* p, int B, int Lq, int Lk, char* base) {
+    XfSeqWs s;
+    size_t off = 0;
+    auto take = [&](size_t b) {
+        char* r = base ? base + off : nullptr;
+        off += keds_align_up(b, 256);
+        return r;
+    };
+    const size_t Rq = rpad((size_t)B * Lq), Rk = rpad((size_t)B * Lk);
+    const size_t dim = (size_t)p->dim, inner = (size_t)p->heads * DH;
+    s.q_bf = take(Rq * dim * 2);
+    s.k_bf = take(Rk * dim * 2);
+    s.v_bf = take(Rk * dim * 2);
+    s.qcur = take(Rq * dim * 2);
+    s.Qp = take(Rq * inner * 2);
+    s.Kp = take(Rk * inner * 2);
+    s.Vp = take(Rk * inner * 2);
+    s.att = take(Rq * inner * 2);
+    s.bytes = off;
+    return s;
+}
+
+int check_xf_seq(const keds_crossformer_params* p, int B, int Lq, int Lk, const char* who) {
+    KEDS_REQUIRE(p && p->layer && p->layers >= 1 && p->heads >= 1 && (p->heads * DH) % 128 == 0 && p->dim >= 128 && p->dim % 128 == 0,
+                 "%s: bad CrossFormer parameters (dim and 64 heads must be multiples of 128)", who);
+    KEDS_REQUIRE(B >= 1 && Lq >= 1, "%s: B=%d and Lq=%d must be at least 1", who, B, Lq);
+    KEDS_REQUIRE(Lk >= 1 && Lk <= KEDS_CROSS_SEQ_MAX_KEYS, "%s: Lk=%d must be in [1,%d]", who, Lk, KEDS_CROSS_SEQ_MAX_KEYS);
+    KEDS_REQUIRE((long long)B * Lq <= 0x7FFFFFFFLL && (long long)B * Lk <= 0x7FFFFFFFLL && cross_seq_grid_fits(B, Lq, p->heads),
+                 "%s: B=%d x Lq=%d (Lk=%d) rows are too many for one call", who, B, Lq, Lk);
+    return KEDS_OK;
+}
+
+}  // namespace
+
+extern "C" int keds_cross_seq_plan_query(int B, int Lq, int Lk, int heads, int* info) {
+    KEDS_REQUIRE(info && B >= 1 && Lq >= 1 && heads >= 1 && heads <= (1 << 20) && cross_seq_grid_fits(B, Lq, heads),
+                 "keds_cross_seq_plan_query: bad argument (B, Lq, heads >= 1, one launch's grid)");
+    KEDS_REQUIRE(Lk >= 1 && Lk <= KEDS_CROSS_SEQ_MAX_KEYS, "keds_cross_seq_plan_query: Lk=%d must be in [1,%d]", Lk, KEDS_CROSS_SEQ_MAX_KEYS);
+    cross_seq_plan(B, Lq, Lk, heads).info(info);
+    return KEDS_OK;
+}
+
+extern "C" int keds_cross_seq_last_launch(int* info) {
+    KEDS_REQUIRE(info, "keds_cross_seq_last_launch: null pointer");
+    tl_seq_rec.info(info);
+    return KEDS_OK;
+}
+
+extern "C" int keds_cross_attn_seq(const void* Q, const void* Kp, const void* Vp, void* out, int B, int Lq, int Lk, int heads, int q_ld,
+                                   int kv_ld, int o_ld, void* stream) {
+    if (int rc = check_seq(Q, Kp, Vp, out, B, Lq, Lk, heads, q_ld, kv_ld, o_ld)) return rc;
+    return cross_seq(SeqArgs{(const bf16_t*)Q, (const bf16_t*)Kp, (const bf16_t*)Vp, (bf16_t*)out, B, Lq, Lk, heads, q_ld, kv_ld, o_ld,
+                             (hipStream_t)stream});
+}
+
+extern "C" size_t keds_crossformer_seq_workspace_bytes(const keds_crossformer_params* p, int B, int Lq, int Lk) {
+    if (!p || B <= 0 || Lq <= 0 || Lk <= 0 || p->dim <= 0 || p->heads <= 0) return 0;
+    return carve_xf_seq(p, B, Lq, Lk, nullptr).bytes;
+}
+
+extern "C" int keds_crossformer_forward_seq(const keds_crossformer_params* p, const float* q, const float* k, const float* v, int B, int Lq,
+                                            int Lk, float* out, void* workspace, size_t workspace_bytes, void* stream) {
+    if (int rc = check_xf_seq(p, B, Lq, Lk, "keds_crossformer_forward_seq")) return rc;
+    KEDS_REQUIRE(q && k && v && out && workspace, "keds_crossformer_forward_seq: null pointer");
+    const XfSeqWs s = carve_xf_seq(p, B, Lq, Lk, (char*)workspace);
+    if (workspace_bytes < s.bytes) {
+        keds_set_error("keds_crossformer_forward_seq: workspace %zu < %zu", workspace_bytes, s.bytes);
+        return KEDS_E_WORKSPACE;
+    }
+    // (the fused weight form, p->fused, is not used here: with B Lq query rows the GEMMs carry the work)
+    const int dim = p->dim, inner = p->heads * DH, Rq = B * Lq, Rk = B * Lk;
+    int rc;
+    if ((rc = keds_cast_bf16(q, s.q_bf, (int64_t)Rq * dim, stream))) return rc;
+    if ((rc = keds_cast_bf16(k, s.k_bf, (int64_t)Rk * dim, stream))) return rc;
+    const char* v_bf = s.k_bf;
+    if (v != k) {
+        if ((rc = keds_cast_bf16(v, s.v_bf, (int64_t)Rk * dim, stream))) return rc;
+        v_bf = s.v_bf;
+    }
+    const void* qin = s.q_bf;
+    for (int l = 0; l < p->layers; ++l) {
+        const keds_cross_layer_params& c = p->layer[l];
+        if ((rc = keds_gemm_bt(qin, c.wq, c.bq, s.Qp, Rq, inner, dim, KEDS_EPI_BIAS_BF16, nullptr, 0, stream))) return rc;
+        if ((rc = keds_gemm_bt(s.k_bf, c.wk, c.bk, s.Kp, Rk, inner, dim, KEDS_EPI_BIAS_BF16, nullptr, 0, stream))) return rc;
+        if ((rc = keds_gemm_bt(v_bf, c.wv, c.bv, s.Vp, Rk, inner, dim, KEDS_EPI_BIAS_BF16, nullptr, 0, stream))) return rc;
+        if ((rc = keds_cross_attn_seq(s.Qp, s.Kp, s.Vp, s.att, B, Lq, Lk, p->heads, inner, inner, inner, stream))) return rc;
+        if (l == p->layers - 1) {
+            if ((rc = keds_gemm_bt(s.att, c.wo, c.bo, out, Rq, dim, inner, KEDS_EPI_BIAS_F32, nullptr, 0, stream))) return rc;
+        } else {
+            if ((rc = keds_gemm_bt(s.att, c.wo, c.bo, s.qcur, Rq, dim, inner, KEDS_EPI_BIAS_BF16, nullptr, 0, stream))) return rc;
+            qin = s.qcur;
+        }
+    }
+    return KEDS_OK;
+}

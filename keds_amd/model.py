@@ -749,7 +749,10 @@ class CrossAttention(nn.Module):
 
 
 class CrossFormer(nn.Module):
-    """model.py:81-101: q chained through `num_layers` CrossAttention layers, k and v fixed."""
+    """model.py:81-101: q chained through `num_layers` CrossAttention layers, k and v fixed.  q may hold any number of query rows per
+    sample and k, v up to MAX_KEYS = 288 rows (KEDS_CROSS_SEQ_MAX_KEYS); dim_head = 64 and q_dim == k_dim == v_dim."""
+
+    MAX_KEYS = 288
 
     def __init__(self, q_dim, k_dim, v_dim, num_layers=1, heads=8, dim_head=64, dropout=0.):
         super().__init__()
@@ -814,23 +817,36 @@ class CrossFormer(nn.Module):
         return self._packed[0]
 
     def forward(self, q, k, v):
-        """q [B,1,D], k [B,K,D], v [B,K,D] -> [B,1,D]"""
+        """q [B,Lq,D], k [B,Lk,D], v [B,Lk,D] -> [B,Lq,D] in q's dtype; 1 <= Lk <= 288 (MAX_KEYS), dim_head = 64.
+
+        One query over at most 32 keys (the neighbour streams of eval_utils.py:661-672) is the single-query call,
+        keds_crossformer_forward; every other shape -- one query over the 77 text tokens (the late fusion of eval_utils.py:249), a
+        token sequence as queries (model.py:343-371) -- is keds_crossformer_forward_seq, whose attention runs on the matrix
+        instruction.  There is no CPU path."""
         p = self.params()
-        if q.dim() != 3 or q.shape[1] != 1:
-            raise RuntimeError("the HIP CrossFormer handles single-query attention: q must be [B,1,D]")
-        if k.shape != v.shape or k.shape[0] != q.shape[0] or k.shape[2] != self.dim:
-            raise RuntimeError("k and v must both be [B,K,D]")
-        B, K = k.shape[0], k.shape[1]
+        if q.dim() != 3 or q.shape[1] < 1 or q.shape[2] != self.dim:
+            raise RuntimeError("q must be [B,Lq,D] with Lq >= 1")
+        if k.dim() != 3 or k.shape != v.shape or k.shape[0] != q.shape[0] or k.shape[2] != self.dim or k.shape[1] < 1:
+            raise RuntimeError("k and v must both be [B,Lk,D] with Lk >= 1")
+        B, Lq, K = q.shape[0], q.shape[1], k.shape[1]
+        if K > self.MAX_KEYS:
+            raise ValueError(f"the HIP CrossFormer attends over at most {self.MAX_KEYS} keys per sample, got {K}")
         lib = load()
-        qf = q.reshape(B, self.dim).to(dtype=torch.float32).contiguous()
+        qf = q.to(dtype=torch.float32).contiguous()
         kf = k.to(dtype=torch.float32).contiguous()
         vf = kf if v is k else v.to(dtype=torch.float32).contiguous()
-        nbytes = lib.keds_crossformer_workspace_bytes(C.byref(p), B, K)
-        ws = self._ws.get(nbytes, qf.device)
-        out = torch.empty((B, self.dim), dtype=torch.float32, device=qf.device)
-        check(lib.keds_crossformer_forward(C.byref(p), ptr(qf), ptr(kf), ptr(vf), B, K, ptr(out), ptr(ws), ws.numel(),
-                                           stream()), "keds_crossformer_forward")
-        return out.reshape(B, 1, self.dim).to(q.dtype)
+        out = torch.empty((B, Lq, self.dim), dtype=torch.float32, device=qf.device)
+        if Lq == 1 and K <= 32:
+            nbytes = lib.keds_crossformer_workspace_bytes(C.byref(p), B, K)
+            ws = self._ws.get(nbytes, qf.device)
+            check(lib.keds_crossformer_forward(C.byref(p), ptr(qf), ptr(kf), ptr(vf), B, K, ptr(out), ptr(ws), ws.numel(),
+                                               stream()), "keds_crossformer_forward")
+        else:
+            nbytes = lib.keds_crossformer_seq_workspace_bytes(C.byref(p), B, Lq, K)
+            ws = self._ws.get(nbytes, qf.device)
+            check(lib.keds_crossformer_forward_seq(C.byref(p), ptr(qf), ptr(kf), ptr(vf), B, Lq, K, ptr(out), ptr(ws), ws.numel(),
+                                                   stream()), "keds_crossformer_forward_seq")
+        return out.to(q.dtype)
 
 
 class KnowledgeStream:

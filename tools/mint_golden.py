@@ -133,6 +133,38 @@ def mint_knowledge(dim, middle, batch=5, k=16):
     print("knowledge: ok")
 
 
+def mint_crossseq(dim=128):
+    """CrossFormer.forward on sequences (model.py:56-101 is written for any number of queries and keys): one query over 77 keys,
+    five queries over 77 keys with v != k, 17 queries over 257 keys, and the late fusion of eval_utils.py:244-254 on the tiny CLIP
+    (its image feature as the one query, its 77 text tokens as keys and values; two samples of clip_tiny.npz's batch)."""
+    sd = O.synth_crossformer_state_dict(dim, 3, seed=5)
+    xf = CrossFormer(q_dim=dim, k_dim=dim, v_dim=dim, num_layers=3).eval()
+    xf.load_state_dict(sd, strict=True)
+    rs = np.random.RandomState(77)
+    rnd = lambda *s: rs.standard_normal(s).astype(np.float32)   # noqa: E731
+    out = {"weights_checksum": np.float64(checksum(sd))}
+    out["q1"], out["q5"], out["k77"], out["v77"] = rnd(2, 1, dim), rnd(2, 5, dim), rnd(2, 77, dim), rnd(2, 77, dim)
+    out["q17"], out["k257"] = rnd(1, 17, dim), rnd(1, 257, dim)
+    t = {k: torch.from_numpy(v) for k, v in out.items() if k[0] in "qkv"}
+    out["out_1_77"] = xf(t["q1"], t["k77"], t["k77"]).numpy()
+    out["out_5_77"] = xf(t["q5"], t["k77"], t["v77"]).numpy()
+    out["out_17_257"] = xf(t["q17"], t["k257"], t["k257"]).numpy()
+    g = np.load(os.path.join(OUT, "clip_tiny.npz"))
+    sd_clip = O.synth_clip_state_dict(**TINY, seed=7)
+    assert TINY["embed_dim"] == TINY["transformer_width"] == dim
+    clip = CLIP(TINY["embed_dim"], TINY["image_resolution"], TINY["vision_layers"], TINY["vision_width"], TINY["vision_patch_size"],
+                TINY["context_length"], TINY["vocab_size"], TINY["transformer_width"], TINY["transformer_width"] // 64,
+                TINY["transformer_layers"]).eval().float()
+    clip.load_state_dict(sd_clip, strict=True)
+    feat = clip.encode_image(torch.from_numpy(g["image"][:2]))
+    tokens, _ = clip.get_text_tokens(torch.from_numpy(g["text"][:2]))
+    out["late_q"], out["late_k"] = feat.numpy(), tokens.numpy()
+    out["late_out"] = xf(feat.unsqueeze(1), tokens, tokens).numpy()
+    out["clip_checksum"] = np.float64(checksum(sd_clip))
+    np.savez_compressed(os.path.join(OUT, "crossformer_seq.npz"), **out)
+    print("crossseq: ok", {k: v.shape for k, v in out.items() if hasattr(v, "shape")})
+
+
 def mint_cirr_batch(model, sd_clip, timg, ttxt, star, dim, middle):
     """Per-batch body of evaluate_cirr (eval_utils.py:652-714) driven through the
     reference's own modules and its own get_retrieved_features."""
@@ -550,6 +582,8 @@ if __name__ == "__main__":
     if "knowledge" in which:
         mint_knowledge(128, 128)
         mint_knowledge(768, 512, batch=3)
+    if "crossseq" in which:
+        mint_crossseq()
     if "cirr" in which:
         mint_cirr_batch(model, sd, timg, ttxt, 265, 128, 128)
     if "search" in which:
