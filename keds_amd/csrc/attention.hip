@@ -15,213 +15,17 @@
 // nowhere else; the host section at the end of this file launches the plan.
 #include "keds_common.h"
 #include "attention_plan.h"      // DH, AttnCfg, TAIL_LDS, s257::* (the LDS layouts) and attention_plan()
+#include "attn_tile.h"           // attn_stage_kv, attn_tiles: the LDS image of AttnCfg, shared with cross_seq.hip; Ev, mfma16, pk_fma
 #include <math.h>
 #include <hip/hip_ext.h>
 
 namespace {
 
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ f32x2 pk_fma(f32x2 a, f32x2 b, f32x2 c) {
-    f32x2 d;
-    asm("v_pk_fma_f32 %0, %1, %2, %3" : "=v"(d) : "v"(a), "v"(b), "v"(c));
-    return d;
-}
-
-// element type of the kernels below: bf16 (default flow) or fp16 (the "fp16" operating point, keds_attention_h) -- the
-// same code; only the matrix instructions, the dot products and the roundings of P / the output follow the type
-template <typename T> struct Ev;
-template <> struct Ev<bf16_t> { using v8 = bf16x8; using v4 = bf16x4; };
-template <> struct Ev<f16_t> { using v8 = f16x8; using v4 = __attribute__((ext_vector_type(4))) _Float16; };
-__device__ __forceinline__ f32x4 mfma16(bf16x8 a, bf16x8 b, f32x4 c, int, int, int) {
-    return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0);
-}
-__device__ __forceinline__ f32x4 mfma16(f16x8 a, f16x8 b, f32x4 c, int, int, int) {
-    return __builtin_amdgcn_mfma_f32_16x16x32_f16(a, b, c, 0, 0, 0);
-}
 __device__ __forceinline__ f32x16 mfma32(bf16x8 a, bf16x8 b, f32x16 c, int, int, int) {
     return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, c, 0, 0, 0);
 }
 __device__ __forceinline__ f32x16 mfma32(f16x8 a, f16x8 b, f32x16 c, int, int, int) {
     return __builtin_amdgcn_mfma_f32_32x32x16_f16(a, b, c, 0, 0, 0);
-}
-
-template <typename T>
-struct AttnCtx {
-    const T* base;   // qkv of (b, h): row stride ld
-    T* out;          // out of (b, h): row stride d
-    const char* k_lds;
-    const char* vt_lds;
-    int S, q_limit, ld, d, g, c;
-    // fp8 towers: rows < q8_rows of the [B*S, d] output go out as MXFP8 (e4m3 + e8m0 per 32 columns) INSTEAD of bf16
-    unsigned char* q8;    // element (row, col) at q8[row*d + col]; nullptr = bf16 everywhere
-    unsigned char* s8;    // scale dwords [d/128][q8_rows]
-    int q8_rows, row0, col0;   // first global row of this sample, first column of this head
-    const char* tail;          // TAIL kernels: [K row of the last key: 64 bf16, unswizzled][its V row: 64 bf16]
-};
-
-// NQ consecutive 16-query tiles starting at tile qt0, for one wave.
-// TAIL: the sequence is 16*NKT + 1 keys; the MFMA tiles cover the first 16*NKT and the last key is a rank-1 VALU update
-// (its score from the lane's 16 query dims + a reduction over the four lanes of the query, its P.V term 16 FMAs per tile)
-// instead of two more key tiles of which 31 of 32 columns would be padding.
-template <typename T, int NKT, bool CAUSAL, int NFULL, int NQ, bool TAIL = false>
-__device__ __forceinline__ void attn_tiles(const AttnCtx<T>& cx, int qt0) {
-    using C = AttnCfg<NKT>;
-    using V8 = typename Ev<T>::v8;
-    using V4 = typename Ev<T>::v4;
-    const int g = cx.g, c = cx.c, S = cx.S;
-    const float sl2 = 0.125f * 1.4426950408889634f;  // 1/sqrt(64) * log2(e)
-    int qidx[NQ];
-    V8 qf[NQ][2];
-#pragma unroll
-    for (int t = 0; t < NQ; ++t) {
-        qidx[t] = (qt0 + t) * 16 + c;
-        const int qrow = qidx[t] < S ? qidx[t] : S - 1;
-        const T* qp = cx.base + (size_t)qrow * cx.ld + 8 * g;
-        qf[t][0] = *reinterpret_cast<const V8*>(qp);
-        qf[t][1] = *reinterpret_cast<const V8*>(qp + 32);
-    }
-    // ---- S^T tiles
-    f32x4 sc[NQ][NKT];
-#pragma unroll
-    for (int kt = 0; kt < NKT; ++kt) {
-        const int key = kt * 16 + c;
-        const char* kr = cx.k_lds + key * 128;
-        const int f = (key >> 1) & 7;
-        const V8 a0 = *reinterpret_cast<const V8*>(kr + ((g ^ f) << 4));
-        const V8 a1 = *reinterpret_cast<const V8*>(kr + (((4 + g) ^ f) << 4));
-#pragma unroll
-        for (int t = 0; t < NQ; ++t) {
-            f32x4 acc = f32x4{0.f, 0.f, 0.f, 0.f};
-            acc = mfma16(a0, qf[t][0], acc, 0, 0, 0);
-            acc = mfma16(a1, qf[t][1], acc, 0, 0, 0);
-            sc[t][kt] = acc;
-        }
-        if (kt % 3 == 2) __builtin_amdgcn_sched_barrier(0);   // bound how far LDS reads are hoisted (VGPR pressure)
-    }
-    // ---- TAIL: score of the last key for the lane's query (replicated over the four g lanes after the reduction)
-    [[maybe_unused]] float tsc[NQ];
-    if constexpr (TAIL) {
-        const V8 k0 = *reinterpret_cast<const V8*>(cx.tail + g * 16);
-        const V8 k1 = *reinterpret_cast<const V8*>(cx.tail + (4 + g) * 16);
-#pragma unroll
-        for (int t = 0; t < NQ; ++t) {
-            float a = 0.f;
-#pragma unroll
-            for (int j = 0; j < 8; ++j) a += (float)qf[t][0][j] * (float)k0[j] + (float)qf[t][1][j] * (float)k1[j];
-            tsc[t] = rows_sum(a);
-        }
-    }
-    // ---- mask, row max, exp, row sum (lane holds query qidx[t], keys kt*16 + 4g + r)
-    float inv[NQ];
-    [[maybe_unused]] float tp[NQ];
-#pragma unroll
-    for (int t = 0; t < NQ; ++t) {
-        float mx = -INFINITY;
-#pragma unroll
-        for (int kt = 0; kt < NKT; ++kt)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                float v = sc[t][kt][r];
-                if (CAUSAL || kt >= NFULL) {      // resolved at compile time once the kt loop is unrolled
-                    const int kidx = kt * 16 + 4 * g + r;
-                    const bool ok = kidx < S && (!CAUSAL || kidx <= qidx[t]);
-                    v = ok ? v : -INFINITY;
-                    sc[t][kt][r] = v;
-                }
-                mx = fmaxf(mx, v);
-            }
-        mx = rows_max(mx);
-        if constexpr (TAIL) mx = fmaxf(mx, tsc[t]);
-        const float nmx = -mx * sl2;
-        // packed fp32 math (v_pk_fma_f32 / v_pk_add_f32: two elements per VALU issue); v_exp_f32 stays per element
-        const f32x2 vs = f32x2{sl2, sl2}, vn = f32x2{nmx, nmx};
-        f32x2 vsum = f32x2{0.f, 0.f};
-#pragma unroll
-        for (int kt = 0; kt < NKT; ++kt) {
-#pragma unroll
-            for (int hh = 0; hh < 2; ++hh) {
-                f32x2 e = f32x2{sc[t][kt][2 * hh], sc[t][kt][2 * hh + 1]};
-                e = pk_fma(e, vs, vn);
-                e[0] = __builtin_amdgcn_exp2f(e[0]);   // exp2(-inf) = 0
-                e[1] = __builtin_amdgcn_exp2f(e[1]);
-                sc[t][kt][2 * hh] = e[0];
-                sc[t][kt][2 * hh + 1] = e[1];
-                vsum += e;
-            }
-        }
-        float sum = vsum[0] + vsum[1];
-        sum = rows_sum(sum);
-        if constexpr (TAIL) {
-            const float e = __builtin_amdgcn_exp2f(tsc[t] * sl2 + nmx);
-            sum += e;
-            tp[t] = (float)(T)e;             // rounded to T like the probabilities the MFMA path multiplies
-        }
-        inv[t] = 1.0f / sum;
-    }
-    // ---- O^T = V^T . P^T
-    f32x4 o[NQ][4];
-#pragma unroll
-    for (int t = 0; t < NQ; ++t)
-#pragma unroll
-        for (int dt = 0; dt < 4; ++dt) o[t][dt] = f32x4{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-    for (int u = 0; u < NKT / 2; ++u) {
-        V8 pf[NQ];
-#pragma unroll
-        for (int t = 0; t < NQ; ++t) {
-            const f32x4 p0 = sc[t][2 * u], p1 = sc[t][2 * u + 1];
-            pf[t] = V8{(T)p0[0], (T)p0[1], (T)p0[2], (T)p0[3],
-                           (T)p1[0], (T)p1[1], (T)p1[2], (T)p1[3]};
-        }
-#pragma unroll
-        for (int dt = 0; dt < 4; ++dt) {
-            const V8 a = *reinterpret_cast<const V8*>(cx.vt_lds + (dt * 16 + c) * C::VT_ROW + (4 * u + g) * 16);
-#pragma unroll
-            for (int t = 0; t < NQ; ++t) o[t][dt] = mfma16(a, pf[t], o[t][dt], 0, 0, 0);
-        }
-        if (u % 3 == 2) __builtin_amdgcn_sched_barrier(0);
-    }
-    if constexpr (TAIL) {      // + p_last * V[last key][16 dt + 4 g + r]
-#pragma unroll
-        for (int dt = 0; dt < 4; ++dt) {
-            const V4 v = *reinterpret_cast<const V4*>(cx.tail + 128 + (16 * dt + 4 * g) * 2);
-#pragma unroll
-            for (int t = 0; t < NQ; ++t)
-#pragma unroll
-                for (int r = 0; r < 4; ++r) o[t][dt][r] += tp[t] * (float)v[r];
-        }
-    }
-#pragma unroll
-    for (int t = 0; t < NQ; ++t) {
-        if (qidx[t] < cx.q_limit) {
-            const int row = cx.row0 + qidx[t];
-            if (cx.q8 && row < cx.q8_rows) {
-                // lane (g, c): head columns 16*dt + 4g + r; a 32-column MX block = dt in {2b, 2b+1} over the four g lanes
-#pragma unroll
-                for (int b2 = 0; b2 < 2; ++b2) {
-                    const f32x4 v0 = o[t][2 * b2] * inv[t], v1 = o[t][2 * b2 + 1] * inv[t];
-                    const float v[8] = {v0[0], v0[1], v0[2], v0[3], v1[0], v1[1], v1[2], v1[3]};
-                    float amax = 0.f;
-#pragma unroll
-                    for (int j = 0; j < 8; ++j) amax = fmaxf(amax, fabsf(v[j]));
-                    amax = rows_max(amax);
-                    const int e = mx_block_exp(amax);
-                    const uint2 pk = mx_pack8(v, e);
-                    unsigned char* qp = cx.q8 + (size_t)row * cx.d + cx.col0 + 32 * b2 + 4 * g;
-                    *reinterpret_cast<unsigned*>(qp) = pk.x;
-                    *reinterpret_cast<unsigned*>(qp + 16) = pk.y;
-                    if (g == 0) cx.s8[mx_scale_index((cx.col0 >> 5) + b2, row, cx.q8_rows)] = (unsigned char)(e + 127);
-                }
-            } else {
-                T* op = cx.out + (size_t)qidx[t] * cx.d + 4 * g;
-#pragma unroll
-                for (int dt = 0; dt < 4; ++dt) {
-                    const f32x4 v = o[t][dt] * inv[t];
-                    *reinterpret_cast<V4*>(op + dt * 16) = V4{(T)v[0], (T)v[1], (T)v[2], (T)v[3]};
-                }
-            }
-        }
-    }
 }
 
 // CAUSAL: text tower mask.  NFULL: key tiles [0, NFULL) are known at compile time to lie entirely below S and
@@ -232,8 +36,6 @@ __global__ __launch_bounds__(256, 2) void attention_kernel(const T* __restrict__
                                                         unsigned char* __restrict__ s8, int q8_rows,
                                                         const int* __restrict__ seq_off) {
     using C = AttnCfg<NKT>;
-    using V8 = typename Ev<T>::v8;
-    using V4 = typename Ev<T>::v4;
     extern __shared__ __attribute__((aligned(16))) char smem[];
     char* k_lds = smem;
     char* vt_lds = smem + C::K_BYTES;
@@ -252,62 +54,19 @@ __global__ __launch_bounds__(256, 2) void attention_kernel(const T* __restrict__
     }
     const T* base = qkv + (size_t)row0 * ld + h * DH;
 
-    // ---- stage K (swizzled rows) and V^T (permuted key order); keys >= S are zero.
-    // Work item = (4 consecutive keys, one 8-wide dh chunk): all global loads of a thread are issued before the
-    // first LDS write (one HBM round trip instead of one per item), K goes in with ds_write_b128, and the four
-    // keys of an item are adjacent in the permuted V^T row, so V^T goes in with 8-byte stores.
-    {
-        constexpr int ITEMS = (C::KEYS / 4) * 8;
-        constexpr int PER = (ITEMS + 255) / 256;
-        V8 kreg[PER][4], vreg[PER][4];
-#pragma unroll
-        for (int it = 0; it < PER; ++it) {
-            const int id = tid + it * 256;
-            const int quad = id >> 3, ch = id & 7;
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                const int key = quad * 4 + e;
-                kreg[it][e] = V8{0, 0, 0, 0, 0, 0, 0, 0};
-                vreg[it][e] = kreg[it][e];
-                if (id < ITEMS && key < S) {
-                    const T* row = base + (size_t)key * ld + ch * 8;
-                    kreg[it][e] = *reinterpret_cast<const V8*>(row + d);
-                    vreg[it][e] = *reinterpret_cast<const V8*>(row + 2 * d);
-                }
-            }
-        }
-#pragma unroll
-        for (int it = 0; it < PER; ++it) {
-            const int id = tid + it * 256;
-            if (id >= ITEMS) continue;
-            const int quad = id >> 3, ch = id & 7;
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                const int key = quad * 4 + e;
-                *reinterpret_cast<V8*>(k_lds + key * 128 + ((ch ^ ((key >> 1) & 7)) << 4)) = kreg[it][e];
-            }
-            // keys 4*quad .. 4*quad+3: u = key>>5, w = key&31, chunk (4u + ((w&15)>>2)), element 4*(w>>4) + (w&3)
-            const int k0 = quad * 4;
-            const int u = k0 >> 5, w = k0 & 31;
-            const int pos = (4 * u + ((w & 15) >> 2)) * 16 + ((w >> 4) << 2) * 2;
-#pragma unroll
-            for (int j = 0; j < 8; ++j)
-                *reinterpret_cast<V4*>(vt_lds + (ch * 8 + j) * C::VT_ROW + pos) =
-                    V4{vreg[it][0][j], vreg[it][1][j], vreg[it][2][j], vreg[it][3][j]};
-        }
-    }
+    attn_stage_kv<T, NKT, false>(base + d, base + 2 * d, ld, S, k_lds, vt_lds, tid);     // keys >= S are zero
     __syncthreads();
 
     // ---- queries: NQ = 2 tiles (32 queries) per step share every K / V^T fragment read from LDS (the loop is
     // LDS-bandwidth bound: 72 ds_read_b128 per 16-query tile); an odd last tile runs alone on a rotating wave.
     const int nqt = (q_limit + 15) >> 4;      // only the first q_limit query rows are computed and stored
-    AttnCtx<T> cx{base, out + (size_t)row0 * d + h * DH, k_lds, vt_lds, S, q_limit, ld, d, g, c, q8, s8, q8_rows, row0, h * DH};
+    const AttnCtx<T> cx{base, out + (size_t)row0 * d + h * DH, k_lds, vt_lds, (size_t)ld, (size_t)d, S, S, q_limit, g, c, q8, s8, q8_rows, row0, h * DH};
     if constexpr (NQ2) {
         const int npair = nqt >> 1;
-        for (int qp = wave; qp < npair; qp += 4) attn_tiles<T, NKT, CAUSAL, NFULL, 2>(cx, 2 * qp);
-        if ((nqt & 1) && wave == ((blockIdx.x + npair) & 3)) attn_tiles<T, NKT, CAUSAL, NFULL, 1>(cx, nqt - 1);
+        for (int qp = wave; qp < npair; qp += 4) attn_tiles<T, NKT, CAUSAL, NFULL, 2, false, true>(cx, 32 * qp);
+        if ((nqt & 1) && wave == ((blockIdx.x + npair) & 3)) attn_tiles<T, NKT, CAUSAL, NFULL, 1, false, true>(cx, 16 * (nqt - 1));
     } else {
-        for (int qt = wave; qt < nqt; qt += 4) attn_tiles<T, NKT, CAUSAL, NFULL, 1>(cx, qt);
+        for (int qt = wave; qt < nqt; qt += 4) attn_tiles<T, NKT, CAUSAL, NFULL, 1, false, true>(cx, 16 * qt);
     }
 }
 
@@ -323,7 +82,6 @@ __global__ __launch_bounds__(256, 2) void attention_tail1_kernel(const T* __rest
                                                                  int heads, int q_limit) {
     using C = AttnCfg<NKT>;
     using V8 = typename Ev<T>::v8;
-    using V4 = typename Ev<T>::v4;
     constexpr int S = 16 * NKT + 1, LAST = 16 * NKT;
     extern __shared__ __attribute__((aligned(16))) char smem[];
     char* k_lds = smem;
@@ -338,52 +96,19 @@ __global__ __launch_bounds__(256, 2) void attention_tail1_kernel(const T* __rest
     const int g = lane >> 4, c = lane & 15;
     const T* base = qkv + (size_t)b * S * ld + h * DH;
 
-    // ---- stage K (swizzled rows), V^T (permuted key order) of the 16 * NKT leading keys, and the last key's two rows
-    {
-        constexpr int ITEMS = (C::KEYS / 4) * 8;
-        constexpr int PER = ITEMS / 256;
-        static_assert(ITEMS % 256 == 0, "staging items must divide over the workgroup");
-        V8 kreg[PER][4], vreg[PER][4];
-        V8 treg = V8{0, 0, 0, 0, 0, 0, 0, 0};
-#pragma unroll
-        for (int it = 0; it < PER; ++it) {
-            const int id = tid + it * 256;
-            const int quad = id >> 3, ch = id & 7;
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                const T* row = base + (size_t)(quad * 4 + e) * ld + ch * 8;
-                kreg[it][e] = *reinterpret_cast<const V8*>(row + d);
-                vreg[it][e] = *reinterpret_cast<const V8*>(row + 2 * d);
-            }
-        }
-        if (tid < 16) treg = *reinterpret_cast<const V8*>(base + (size_t)LAST * ld + (tid < 8 ? d : 2 * d) + (tid & 7) * 8);
-#pragma unroll
-        for (int it = 0; it < PER; ++it) {
-            const int id = tid + it * 256;
-            const int quad = id >> 3, ch = id & 7;
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                const int key = quad * 4 + e;
-                *reinterpret_cast<V8*>(k_lds + key * 128 + ((ch ^ ((key >> 1) & 7)) << 4)) = kreg[it][e];
-            }
-            const int k0 = quad * 4;
-            const int u = k0 >> 5, w = k0 & 31;
-            const int pos = (4 * u + ((w & 15) >> 2)) * 16 + ((w >> 4) << 2) * 2;
-#pragma unroll
-            for (int j = 0; j < 8; ++j)
-                *reinterpret_cast<V4*>(vt_lds + (ch * 8 + j) * C::VT_ROW + pos) =
-                    V4{vreg[it][0][j], vreg[it][1][j], vreg[it][2][j], vreg[it][3][j]};
-        }
-        if (tid < 16) *reinterpret_cast<V8*>(tail + tid * 16) = treg;
-    }
+    // ---- stage K and V^T of the 16 * NKT leading keys (all valid), and the last key's two rows around them
+    V8 treg = V8{0, 0, 0, 0, 0, 0, 0, 0};
+    if (tid < 16) treg = *reinterpret_cast<const V8*>(base + (size_t)LAST * ld + (tid < 8 ? d : 2 * d) + (tid & 7) * 8);
+    attn_stage_kv<T, NKT, true>(base + d, base + 2 * d, ld, LAST, k_lds, vt_lds, tid);
+    if (tid < 16) *reinterpret_cast<V8*>(tail + tid * 16) = treg;
     __syncthreads();
 
     const int ql = q_limit < LAST ? q_limit : LAST;               // query rows covered by the MFMA tiles
     const int nqt = (ql + 15) >> 4;
-    AttnCtx<T> cx{base, out + (size_t)b * S * d + h * DH, k_lds, vt_lds, S, q_limit, ld, d, g, c, nullptr, nullptr, 0, b * S, h * DH, tail};
+    const AttnCtx<T> cx{base, out + (size_t)b * S * d + h * DH, k_lds, vt_lds, (size_t)ld, (size_t)d, S, S, q_limit, g, c, nullptr, nullptr, 0, 0, 0, tail};
     const int npair = nqt >> 1;
-    for (int qp = wave; qp < npair; qp += 4) attn_tiles<T, NKT, false, NKT, 2, true>(cx, 2 * qp);
-    if ((nqt & 1) && wave == ((blockIdx.x + npair) & 3)) attn_tiles<T, NKT, false, NKT, 1, true>(cx, nqt - 1);
+    for (int qp = wave; qp < npair; qp += 4) attn_tiles<T, NKT, false, NKT, 2, true, false>(cx, 32 * qp);
+    if ((nqt & 1) && wave == ((blockIdx.x + npair) & 3)) attn_tiles<T, NKT, false, NKT, 1, true, false>(cx, 16 * (nqt - 1));
     if (q_limit <= LAST) return;                                   // kernel-uniform: nobody waits at the barriers below
 
     // ---- the last query row: scores of this wave's 64 keys (lane = key)
@@ -965,14 +690,7 @@ int attention16(const AttnArgs& a, const AttnPlan& p, bool* stop_taken) {
     int want[8], got[8];
     p.info(want);
     tl_attn_rec.info(got);
-    for (int i = 0; i < 8; ++i) {
-        if (got[i] != want[i]) {
-            keds_set_error("keds_attention: launched form differs from the plan at [%d]: %d, planned %d (B %d, S %d, heads %d)", i, got[i], want[i],
-                           a.B, a.S, a.heads);
-            return KEDS_E_LAUNCH;
-        }
-    }
-    return KEDS_OK;
+    return keds_launch_is_planned(want, got, "keds_attention", "B %d, S %d, heads %d", a.B, a.S, a.heads);
 }
 
 }  // namespace

@@ -4,8 +4,9 @@
 // Reference: CrossAttention.forward (src/model/model.py:56-79), written for any number of queries and keys, as Transformer.forward
 // (model.py:343-371) and the late-fusion call of eval_utils.py:249 (one query over the 77 text tokens) use it.
 //
-// The arithmetic and the LDS image are attention_kernel's (attention.hip; that file's kernels are pinned bit for bit and stay as they
-// are, so the tile routine is written out again here without the causal / tail / MXFP8 branches): all of a (sample, head)'s K rows
+// The arithmetic and the LDS image are attention_kernel's (attention.hip), as one piece of code: attn_tile.h holds the K / V^T staging
+// (attn_stage_kv) and the tile routine (attn_tiles), and this kernel instantiates them for bf16 with the causal, tail and MXFP8
+// branches switched off at compile time (attn_tiles<bf16_t, NKT, false, NFULL, NQ, false, false>): all of a (sample, head)'s K rows
 // (swizzled 128-byte rows) and V^T (permuted key order) resident in LDS, scores computed swapped, S^T = K . Q^T on
 // v_mfma_f32_16x16x32_bf16, so a lane holds one query column and four keys per 16-key tile: row maximum and sum are in-lane plus two
 // shuffles, exp2 with the folded 1 / sqrt(64) . log2 e, the probabilities rounded to bf16 in registers are the B operand of
@@ -17,132 +18,9 @@
 // maximum.  Which template arguments, grid and LDS a call gets is decided in cross_seq_plan.h and nowhere else.
 #include "keds_common.h"
 #include "cross_seq_plan.h"      // DH, AttnCfg (attention_plan.h) and cross_seq_plan()
-#include <math.h>
+#include "attn_tile.h"           // attn_stage_kv, attn_tiles
 
 namespace {
-
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ f32x2 pk_fma(f32x2 a, f32x2 b, f32x2 c) {
-    f32x2 d;
-    asm("v_pk_fma_f32 %0, %1, %2, %3" : "=v"(d) : "v"(a), "v"(b), "v"(c));
-    return d;
-}
-
-struct SeqCtx {
-    const bf16_t* q;     // Q of (b, h): row stride q_ld
-    bf16_t* out;         // out of (b, h): row stride o_ld
-    const char* k_lds;
-    const char* vt_lds;
-    size_t q_ld, o_ld;
-    int Lq, Lk, q_end;   // rows [.., q_end) of the sample are this workgroup's to store
-    int g, c;
-};
-
-// NQ consecutive 16-query tiles whose first query row (inside the sample) is q0, for one wave
-template <int NKT, int NFULL, int NQ>
-__device__ __forceinline__ void seq_tiles(const SeqCtx& cx, int q0) {
-    using C = AttnCfg<NKT>;
-    const int g = cx.g, c = cx.c;
-    const float sl2 = 0.125f * 1.4426950408889634f;  // 1/sqrt(64) * log2(e)
-    int qidx[NQ];
-    bf16x8 qf[NQ][2];
-#pragma unroll
-    for (int t = 0; t < NQ; ++t) {
-        qidx[t] = q0 + t * 16 + c;
-        const int qrow = qidx[t] < cx.Lq ? qidx[t] : cx.Lq - 1;      // a partly filled tile: a row of this sample, never stored
-        const bf16_t* qp = cx.q + (size_t)qrow * cx.q_ld + 8 * g;
-        qf[t][0] = *reinterpret_cast<const bf16x8*>(qp);
-        qf[t][1] = *reinterpret_cast<const bf16x8*>(qp + 32);
-    }
-    // ---- S^T tiles
-    f32x4 sc[NQ][NKT];
-#pragma unroll
-    for (int kt = 0; kt < NKT; ++kt) {
-        const int key = kt * 16 + c;
-        const char* kr = cx.k_lds + key * 128;
-        const int f = (key >> 1) & 7;
-        const bf16x8 a0 = *reinterpret_cast<const bf16x8*>(kr + ((g ^ f) << 4));
-        const bf16x8 a1 = *reinterpret_cast<const bf16x8*>(kr + (((4 + g) ^ f) << 4));
-#pragma unroll
-        for (int t = 0; t < NQ; ++t) {
-            f32x4 acc = f32x4{0.f, 0.f, 0.f, 0.f};
-            acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a0, qf[t][0], acc, 0, 0, 0);
-            acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a1, qf[t][1], acc, 0, 0, 0);
-            sc[t][kt] = acc;
-        }
-        if (kt % 3 == 2) __builtin_amdgcn_sched_barrier(0);   // bound how far LDS reads are hoisted (VGPR pressure)
-    }
-    // ---- pad keys, row max, exp, row sum (lane holds query qidx[t], keys kt*16 + 4g + r)
-    float inv[NQ];
-#pragma unroll
-    for (int t = 0; t < NQ; ++t) {
-        float mx = -INFINITY;
-#pragma unroll
-        for (int kt = 0; kt < NKT; ++kt)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                float v = sc[t][kt][r];
-                if (kt >= NFULL) {                // resolved at compile time once the kt loop is unrolled
-                    v = kt * 16 + 4 * g + r < cx.Lk ? v : -INFINITY;
-                    sc[t][kt][r] = v;
-                }
-                mx = fmaxf(mx, v);
-            }
-        mx = rows_max(mx);                        // key 0 is always below Lk: finite
-        const float nmx = -mx * sl2;
-        // packed fp32 math (v_pk_fma_f32 / v_pk_add_f32: two elements per VALU issue); v_exp_f32 stays per element
-        const f32x2 vs = f32x2{sl2, sl2}, vn = f32x2{nmx, nmx};
-        f32x2 vsum = f32x2{0.f, 0.f};
-#pragma unroll
-        for (int kt = 0; kt < NKT; ++kt) {
-#pragma unroll
-            for (int hh = 0; hh < 2; ++hh) {
-                f32x2 e = f32x2{sc[t][kt][2 * hh], sc[t][kt][2 * hh + 1]};
-                e = pk_fma(e, vs, vn);
-                e[0] = __builtin_amdgcn_exp2f(e[0]);   // exp2(-inf) = 0
-                e[1] = __builtin_amdgcn_exp2f(e[1]);
-                sc[t][kt][2 * hh] = e[0];
-                sc[t][kt][2 * hh + 1] = e[1];
-                vsum += e;
-            }
-        }
-        inv[t] = 1.0f / rows_sum(vsum[0] + vsum[1]);
-    }
-    // ---- O^T = V^T . P^T
-    f32x4 o[NQ][4];
-#pragma unroll
-    for (int t = 0; t < NQ; ++t)
-#pragma unroll
-        for (int dt = 0; dt < 4; ++dt) o[t][dt] = f32x4{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-    for (int u = 0; u < NKT / 2; ++u) {
-        bf16x8 pf[NQ];
-#pragma unroll
-        for (int t = 0; t < NQ; ++t) {
-            const f32x4 p0 = sc[t][2 * u], p1 = sc[t][2 * u + 1];
-            pf[t] = bf16x8{(bf16_t)p0[0], (bf16_t)p0[1], (bf16_t)p0[2], (bf16_t)p0[3],
-                           (bf16_t)p1[0], (bf16_t)p1[1], (bf16_t)p1[2], (bf16_t)p1[3]};
-        }
-#pragma unroll
-        for (int dt = 0; dt < 4; ++dt) {
-            const bf16x8 a = *reinterpret_cast<const bf16x8*>(cx.vt_lds + (dt * 16 + c) * C::VT_ROW + (4 * u + g) * 16);
-#pragma unroll
-            for (int t = 0; t < NQ; ++t) o[t][dt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, pf[t], o[t][dt], 0, 0, 0);
-        }
-        if (u % 3 == 2) __builtin_amdgcn_sched_barrier(0);
-    }
-#pragma unroll
-    for (int t = 0; t < NQ; ++t) {
-        if (qidx[t] < cx.q_end) {
-            bf16_t* op = cx.out + (size_t)qidx[t] * cx.o_ld + 4 * g;
-#pragma unroll
-            for (int dt = 0; dt < 4; ++dt) {
-                const f32x4 v = o[t][dt] * inv[t];
-                *reinterpret_cast<bf16x4*>(op + dt * 16) = bf16x4{(bf16_t)v[0], (bf16_t)v[1], (bf16_t)v[2], (bf16_t)v[3]};
-            }
-        }
-    }
-}
 
 // One workgroup per (sample, head, chunk of q_per_wg queries); chunks = workgroups per (sample, head), the chunk fastest.
 // NFULL: key tiles [0, NFULL) are known at compile time to lie entirely below Lk and need no mask.
@@ -163,63 +41,21 @@ __global__ __launch_bounds__(256, 2) void cross_attn_seq_kernel(const bf16_t* __
     const bf16_t* kbase = Kp + (size_t)b * Lk * (size_t)kv_ld + h * DH;
     const bf16_t* vbase = Vp + (size_t)b * Lk * (size_t)kv_ld + h * DH;
 
-    // ---- stage K (swizzled rows) and V^T (permuted key order); keys >= Lk are zero.  Work item = (4 consecutive keys, one 8-wide
-    // dh chunk): every global load of a thread is issued before the first LDS write, and the four keys of an item are adjacent in
-    // the permuted V^T row.
-    {
-        constexpr int ITEMS = (C::KEYS / 4) * 8;
-        constexpr int PER = (ITEMS + 255) / 256;
-        bf16x8 kreg[PER][4], vreg[PER][4];
-#pragma unroll
-        for (int it = 0; it < PER; ++it) {
-            const int id = tid + it * 256;
-            const int quad = id >> 3, ch = id & 7;
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                const int key = quad * 4 + e;
-                kreg[it][e] = bf16x8{0, 0, 0, 0, 0, 0, 0, 0};
-                vreg[it][e] = kreg[it][e];
-                if (id < ITEMS && key < Lk) {
-                    const size_t off = (size_t)key * (size_t)kv_ld + ch * 8;
-                    kreg[it][e] = *reinterpret_cast<const bf16x8*>(kbase + off);
-                    vreg[it][e] = *reinterpret_cast<const bf16x8*>(vbase + off);
-                }
-            }
-        }
-#pragma unroll
-        for (int it = 0; it < PER; ++it) {
-            const int id = tid + it * 256;
-            if (id >= ITEMS) continue;
-            const int quad = id >> 3, ch = id & 7;
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                const int key = quad * 4 + e;
-                *reinterpret_cast<bf16x8*>(k_lds + key * 128 + ((ch ^ ((key >> 1) & 7)) << 4)) = kreg[it][e];
-            }
-            // keys 4*quad .. 4*quad+3: u = key>>5, w = key&31, chunk (4u + ((w&15)>>2)), element 4*(w>>4) + (w&3)
-            const int k0 = quad * 4;
-            const int u = k0 >> 5, w = k0 & 31;
-            const int pos = (4 * u + ((w & 15) >> 2)) * 16 + ((w >> 4) << 2) * 2;
-#pragma unroll
-            for (int j = 0; j < 8; ++j)
-                *reinterpret_cast<bf16x4*>(vt_lds + (ch * 8 + j) * C::VT_ROW + pos) =
-                    bf16x4{vreg[it][0][j], vreg[it][1][j], vreg[it][2][j], vreg[it][3][j]};
-        }
-    }
+    attn_stage_kv<bf16_t, NKT, false>(kbase, vbase, kv_ld, Lk, k_lds, vt_lds, tid);     // keys >= Lk are zero
     __syncthreads();
 
     // ---- this workgroup's queries: rows [q0, q_end) of the sample, in 16-query tiles dealt over the four waves
     const int q0 = chunk * q_per_wg;
     const int q_end = q0 + q_per_wg < Lq ? q0 + q_per_wg : Lq;
     const int nqt = (q_end - q0 + 15) >> 4;
-    const SeqCtx cx{Q + (size_t)b * Lq * (size_t)q_ld + h * DH, out + (size_t)b * Lq * (size_t)o_ld + h * DH, k_lds, vt_lds,
-                    (size_t)q_ld, (size_t)o_ld, Lq, Lk, q_end, g, c};
+    const AttnCtx<bf16_t> cx{Q + (size_t)b * Lq * (size_t)q_ld + h * DH, out + (size_t)b * Lq * (size_t)o_ld + h * DH, k_lds, vt_lds,
+                             (size_t)q_ld, (size_t)o_ld, Lq, Lk, q_end, g, c};
     if constexpr (NQ2) {
         const int npair = nqt >> 1;
-        for (int qp = wave; qp < npair; qp += 4) seq_tiles<NKT, NFULL, 2>(cx, q0 + 32 * qp);
-        if ((nqt & 1) && wave == ((blockIdx.x + npair) & 3)) seq_tiles<NKT, NFULL, 1>(cx, q0 + 16 * (nqt - 1));
+        for (int qp = wave; qp < npair; qp += 4) attn_tiles<bf16_t, NKT, false, NFULL, 2, false, false>(cx, q0 + 32 * qp);
+        if ((nqt & 1) && wave == ((blockIdx.x + npair) & 3)) attn_tiles<bf16_t, NKT, false, NFULL, 1, false, false>(cx, q0 + 16 * (nqt - 1));
     } else {
-        for (int qt = wave; qt < nqt; qt += 4) seq_tiles<NKT, NFULL, 1>(cx, q0 + 16 * qt);
+        for (int qt = wave; qt < nqt; qt += 4) attn_tiles<bf16_t, NKT, false, NFULL, 1, false, false>(cx, q0 + 16 * qt);
     }
 }
 
@@ -266,14 +102,7 @@ int cross_seq(const SeqArgs& a) {
     int want[8], got[8];
     p.info(want);
     tl_seq_rec.info(got);
-    for (int i = 0; i < 8; ++i) {
-        if (got[i] != want[i]) {
-            keds_set_error("keds_cross_attn_seq: the launch differs from the plan at [%d]: %d, planned %d (B %d, Lq %d, Lk %d, heads %d)", i,
-                           got[i], want[i], a.B, a.Lq, a.Lk, a.heads);
-            return KEDS_E_LAUNCH;
-        }
-    }
-    return KEDS_OK;
+    return keds_launch_is_planned(want, got, "keds_cross_attn_seq", "B %d, Lq %d, Lk %d, heads %d", a.B, a.Lq, a.Lk, a.heads);
 }
 
 bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
@@ -292,8 +121,6 @@ int check_seq(const void* Q, const void* Kp, const void* Vp, const void* out, in
     KEDS_REQUIRE(aligned16(Q) && aligned16(Kp) && aligned16(Vp) && aligned16(out), "keds_cross_attn_seq: Q, Kp, Vp and out must be 16-byte aligned");
     return KEDS_OK;
 }
-
-size_t rpad(size_t r) { return keds_align_up(r, 128); }
 
 // ---- CrossFormer on sequences: the per-layer chain of knowledge.hip's xf_run on B Lq query rows ---------------------------------
 struct XfSeqWs {

@@ -1753,14 +1753,7 @@ int launch_gemm(GemmArgs a) {
     int want[8], got[8];
     plan.info(want);
     tl_rec.info(got);
-    for (int i = 0; i < 8; ++i) {
-        if (got[i] != want[i]) {
-            keds_set_error("keds_gemm_bt: launched form differs from the plan at [%d]: %d, planned %d (epilogue %d, %d x %d x %d)", i, got[i],
-                           want[i], EPI, M, N, K);
-            return KEDS_E_LAUNCH;
-        }
-    }
-    return KEDS_OK;
+    return keds_launch_is_planned(want, got, "keds_gemm_bt", "epilogue %d, %d x %d x %d", EPI, M, N, K);
 }
 
 }  // namespace

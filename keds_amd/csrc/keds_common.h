@@ -4,6 +4,8 @@
 #include <hip/hip_ext.h>
 #include <stdint.h>
 #include <stddef.h>
+#include <stdarg.h>
+#include <stdio.h>
 #include "../../include/keds_hip.h"
 
 typedef __bf16 bf16_t;
@@ -115,6 +117,25 @@ struct AttnArgs {
 int keds_attention16(const AttnArgs& a, bool f16, int causal, int q_limit, bool* stop_taken = nullptr);
 
 static inline size_t keds_align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
+// rows of a GEMM operand of the knowledge streams: addressable up to the next multiple of 128
+static inline size_t rpad(size_t r) { return keds_align_up(r, 128); }
+
+// The *_last_launch entries report what the launch sites recorded, not the plan: the two info[8] must agree.  `entry`: the public
+// entry's name; the trailing format and its arguments describe the call.  KEDS_OK, or KEDS_E_LAUNCH with the first difference.
+__attribute__((format(printf, 4, 5))) static inline int keds_launch_is_planned(const int (&want)[8], const int (&got)[8], const char* entry,
+                                                                               const char* call_fmt, ...) {
+    for (int i = 0; i < 8; ++i) {
+        if (got[i] == want[i]) continue;
+        char call[160];
+        va_list ap;
+        va_start(ap, call_fmt);
+        vsnprintf(call, sizeof call, call_fmt, ap);
+        va_end(ap);
+        keds_set_error("%s: launched form differs from the plan at [%d]: %d, planned %d (%s)", entry, i, got[i], want[i], call);
+        return KEDS_E_LAUNCH;
+    }
+    return KEDS_OK;
+}
 
 // ---- per-device launch state (host) --------------------------------------------------------------------------------
 // hipFuncAttributeMaxDynamicSharedMemorySize is a per-device attribute and the session API creates contexts on any

@@ -95,8 +95,6 @@ __global__ __launch_bounds__(256) void fold_qo_kernel(const bf16_t* __restrict__
     }
 }
 
-size_t rpad(size_t r) { return keds_align_up(r, 128); }
-
 // the launches of the three kernels above: the module paths and the stand-alone entries share them
 int launch_core(const bf16_t* Q, const bf16_t* Kp, const bf16_t* Vp, bf16_t* out, int B, int K, int heads, int kv_ld,
                 hipStream_t st) {

@@ -207,3 +207,62 @@ def test_crossformer_forward_seq_equals_its_chain(layers, dim, heads, B, Lq, Lk)
     assert _same(_twice(run(k), nbytes, B * Lq, dim), want["v_is_k"]), "v is k"
     assert _same(_twice(run(v), nbytes, B * Lq, dim), want["v_separate"]), "v separate"
     assert lib.keds_crossformer_forward_seq(C.byref(p), P(q), P(k), P(k), B, Lq, Lk, P(want["v_is_k"]), P(q_bf), nbytes - 1, _lib.stream()) == E_WORKSPACE
+
+
+# ---- the shared tile routine: cross-attention on a packed qkv buffer is self-attention, to the bit ----------------------------------
+def test_cross_attn_seq_equals_self_attention_bit_for_bit():
+    """keds_attention (full mask) on a packed bf16 qkv [B S, 3 x 64 H] against keds_cross_attn_seq with Q, Kp, Vp pointing at the three
+    column ranges of the same buffer (q_ld = kv_ld = 3 x 64 H, o_ld = 64 H, Lq = Lk = S): both kernels instantiate one tile routine and
+    one K / V^T staging (attn_tile.h), so every output bit is equal.  S over every tile count, both nfull values, a lone odd tile and
+    the pair loop; S = 257 through the generic form (keds_attention_debug 16).  Before each comparison the two launch records name the
+    generic / tile form with equal nkt and nfull.  Then q_limit rows of S = 273 against Lq = q_limit queries over Lk = 273 keys."""
+    from tests import attention_check as ac
+    lib = _lib.load()
+    st = _lib.stream()
+    GENERIC, TILE = 1, 1                         # KEDS_ATTN_FORM_GENERIC, KEDS_CROSS_SEQ_FORM_TILE
+    H = 2
+    d = 64 * H
+
+    def both(qkv, B, S, q_limit, hook):
+        """(self-attention rows [B S, d] over sentinels, cross rows [B q_limit, d]); q_limit < S only with B = 1"""
+        out_s = torch.full((B * S, d), SENT, dtype=BF, device=DEV)
+        out_c = torch.full((B * q_limit, d), SENT, dtype=BF, device=DEV)
+        a, c = (C.c_int * 8)(), (C.c_int * 8)()
+        try:
+            assert lib.keds_attention_debug(hook) == 0
+            if q_limit == S:
+                _done(lib.keds_attention(P(qkv), P(out_s), B, S, H, 0, st), f"keds_attention S{S}")
+            else:
+                _done(lib.keds_attention_ex(P(qkv), P(out_s), B, S, H, 0, q_limit, st), f"keds_attention_ex S{S}.q{q_limit}")
+            assert lib.keds_attention_last_launch(a) == 0
+        finally:
+            lib.keds_attention_debug(0)
+        _done(lib.keds_cross_attn_seq(P(qkv), P(qkv) + 2 * d, P(qkv) + 4 * d, P(out_c), B, q_limit, S, H, 3 * d, 3 * d, d, st),
+              f"keds_cross_attn_seq Lq{q_limit}.Lk{S}")
+        assert lib.keds_cross_seq_last_launch(c) == 0
+        a, c = list(a), list(c)
+        assert a[0] == GENERIC and c[0] == TILE and a[1:3] == c[1:3], f"S{S}.q{q_limit}: attention launched {a}, cross {c}"
+        return out_s, out_c
+
+    msgs, launches = [], 0
+    B = 2
+    for S, hook in [(S, 0) for S in (1, 16, 17, 32, 33, 96, 97, 255, 256, 258, 272, 273, 288)] + [(257, 16)]:
+        for regime in ("random", "ramp"):
+            qkv = ac.make_qkv(B, S, H, regime, BF, seed=S, device=DEV)
+            assert qkv.shape == (B * S, 3 * d) and qkv.dtype == BF
+            out_s, out_c = both(qkv, B, S, S, hook)
+            launches += 2
+            if not torch.equal(out_s, out_c):
+                bad = (out_s != out_c).any(1).nonzero().flatten().tolist()
+                msgs.append(f"S{S}.{regime}: {len(bad)} rows differ, first {bad[:8]}")
+    S = 273
+    qkv = ac.make_qkv(1, S, H, "random", BF, seed=S, device=DEV)
+    for q_limit in (1, 17, 257):
+        out_s, out_c = both(qkv, 1, S, q_limit, 0)
+        launches += 2
+        if not torch.equal(out_s[:q_limit], out_c):
+            msgs.append(f"S{S}.q_limit{q_limit}: stored rows differ")
+        if not bool((out_s[q_limit:] == SENT).all()):
+            msgs.append(f"S{S}.q_limit{q_limit}: self-attention wrote rows >= q_limit")
+    assert launches == 2 * (14 * 2 + 3)
+    assert not msgs, f"{len(msgs)} failures:\n" + "\n".join(msgs)
