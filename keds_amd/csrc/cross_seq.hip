@@ -1,4 +1,4 @@
-// Multi-query cross-attention core and the CrossFormer on sequences:
+// Multi-query cross-attention core (the CrossFormer on sequences that runs on it: keds_crossformer_forward_seq, knowledge.hip):
 //   out[b, i, h] = softmax(Q[b, i, h] . K[b, :, h]^T / 8) . V[b, :, h]        (no mask, dim_head = 64, bf16 operands)
 // with Lq queries and Lk <= 288 keys per sample, Q / K / V / out in four buffers with their own row counts and strides.
 // Reference: CrossAttention.forward (src/model/model.py:56-79), written for any number of queries and keys, as Transformer.forward
@@ -122,44 +122,6 @@ int check_seq(const void* Q, const void* Kp, const void* Vp, const void* out, in
     return KEDS_OK;
 }
 
-// ---- CrossFormer on sequences: the per-layer chain of knowledge.hip's xf_run on B Lq query rows ---------------------------------
-struct XfSeqWs {
-    char *q_bf, *k_bf, *v_bf, *qcur, *Qp, *Kp, *Vp, *att;
-    size_t bytes;
-};
-// every GEMM operand addressable up to the next multiple of 128 rows, as carve_xf does
-XfSeqWs carve_xf_seq(const keds_crossformer_params* p, int B, int Lq, int Lk, char* base) {
-    XfSeqWs s;
-    size_t off = 0;
-    auto take = [&](size_t b) {
-        char* r = base ? base + off : nullptr;
-        off += keds_align_up(b, 256);
-        return r;
-    };
-    const size_t Rq = rpad((size_t)B * Lq), Rk = rpad((size_t)B * Lk);
-    const size_t dim = (size_t)p->dim, inner = (size_t)p->heads * DH;
-    s.q_bf = take(Rq * dim * 2);
-    s.k_bf = take(Rk * dim * 2);
-    s.v_bf = take(Rk * dim * 2);
-    s.qcur = take(Rq * dim * 2);
-    s.Qp = take(Rq * inner * 2);
-    s.Kp = take(Rk * inner * 2);
-    s.Vp = take(Rk * inner * 2);
-    s.att = take(Rq * inner * 2);
-    s.bytes = off;
-    return s;
-}
-
-int check_xf_seq(const keds_crossformer_params* p, int B, int Lq, int Lk, const char* who) {
-    KEDS_REQUIRE(p && p->layer && p->layers >= 1 && p->heads >= 1 && (p->heads * DH) % 128 == 0 && p->dim >= 128 && p->dim % 128 == 0,
-                 "%s: bad CrossFormer parameters (dim and 64 heads must be multiples of 128)", who);
-    KEDS_REQUIRE(B >= 1 && Lq >= 1, "%s: B=%d and Lq=%d must be at least 1", who, B, Lq);
-    KEDS_REQUIRE(Lk >= 1 && Lk <= KEDS_CROSS_SEQ_MAX_KEYS, "%s: Lk=%d must be in [1,%d]", who, Lk, KEDS_CROSS_SEQ_MAX_KEYS);
-    KEDS_REQUIRE((long long)B * Lq <= 0x7FFFFFFFLL && (long long)B * Lk <= 0x7FFFFFFFLL && cross_seq_grid_fits(B, Lq, p->heads),
-                 "%s: B=%d x Lq=%d (Lk=%d) rows are too many for one call", who, B, Lq, Lk);
-    return KEDS_OK;
-}
-
 }  // namespace
 
 extern "C" int keds_cross_seq_plan_query(int B, int Lq, int Lk, int heads, int* info) {
@@ -181,45 +143,4 @@ extern "C" int keds_cross_attn_seq(const void* Q, const void* Kp, const void* Vp
     if (int rc = check_seq(Q, Kp, Vp, out, B, Lq, Lk, heads, q_ld, kv_ld, o_ld)) return rc;
     return cross_seq(SeqArgs{(const bf16_t*)Q, (const bf16_t*)Kp, (const bf16_t*)Vp, (bf16_t*)out, B, Lq, Lk, heads, q_ld, kv_ld, o_ld,
                              (hipStream_t)stream});
-}
-
-extern "C" size_t keds_crossformer_seq_workspace_bytes(const keds_crossformer_params* p, int B, int Lq, int Lk) {
-    if (!p || B <= 0 || Lq <= 0 || Lk <= 0 || p->dim <= 0 || p->heads <= 0) return 0;
-    return carve_xf_seq(p, B, Lq, Lk, nullptr).bytes;
-}
-
-extern "C" int keds_crossformer_forward_seq(const keds_crossformer_params* p, const float* q, const float* k, const float* v, int B, int Lq,
-                                            int Lk, float* out, void* workspace, size_t workspace_bytes, void* stream) {
-    if (int rc = check_xf_seq(p, B, Lq, Lk, "keds_crossformer_forward_seq")) return rc;
-    KEDS_REQUIRE(q && k && v && out && workspace, "keds_crossformer_forward_seq: null pointer");
-    const XfSeqWs s = carve_xf_seq(p, B, Lq, Lk, (char*)workspace);
-    if (workspace_bytes < s.bytes) {
-        keds_set_error("keds_crossformer_forward_seq: workspace %zu < %zu", workspace_bytes, s.bytes);
-        return KEDS_E_WORKSPACE;
-    }
-    // (the fused weight form, p->fused, is not used here: with B Lq query rows the GEMMs carry the work)
-    const int dim = p->dim, inner = p->heads * DH, Rq = B * Lq, Rk = B * Lk;
-    int rc;
-    if ((rc = keds_cast_bf16(q, s.q_bf, (int64_t)Rq * dim, stream))) return rc;
-    if ((rc = keds_cast_bf16(k, s.k_bf, (int64_t)Rk * dim, stream))) return rc;
-    const char* v_bf = s.k_bf;
-    if (v != k) {
-        if ((rc = keds_cast_bf16(v, s.v_bf, (int64_t)Rk * dim, stream))) return rc;
-        v_bf = s.v_bf;
-    }
-    const void* qin = s.q_bf;
-    for (int l = 0; l < p->layers; ++l) {
-        const keds_cross_layer_params& c = p->layer[l];
-        if ((rc = keds_gemm_bt(qin, c.wq, c.bq, s.Qp, Rq, inner, dim, KEDS_EPI_BIAS_BF16, nullptr, 0, stream))) return rc;
-        if ((rc = keds_gemm_bt(s.k_bf, c.wk, c.bk, s.Kp, Rk, inner, dim, KEDS_EPI_BIAS_BF16, nullptr, 0, stream))) return rc;
-        if ((rc = keds_gemm_bt(v_bf, c.wv, c.bv, s.Vp, Rk, inner, dim, KEDS_EPI_BIAS_BF16, nullptr, 0, stream))) return rc;
-        if ((rc = keds_cross_attn_seq(s.Qp, s.Kp, s.Vp, s.att, B, Lq, Lk, p->heads, inner, inner, inner, stream))) return rc;
-        if (l == p->layers - 1) {
-            if ((rc = keds_gemm_bt(s.att, c.wo, c.bo, out, Rq, dim, inner, KEDS_EPI_BIAS_F32, nullptr, 0, stream))) return rc;
-        } else {
-            if ((rc = keds_gemm_bt(s.att, c.wo, c.bo, s.qcur, Rq, dim, inner, KEDS_EPI_BIAS_BF16, nullptr, 0, stream))) return rc;
-            qin = s.qcur;
-        }
-    }
-    return KEDS_OK;
 }

@@ -600,7 +600,7 @@ static thread_local int tl_ln_pair_form = -1;
 // LayerNorm whose output is a pair of fp16 planes (hi = out, lo = out + plane elements; dense rows of `dim`)
 // form: 0 the library's choice, 1 the one-row-per-wave form at any row count (keds_layernorm_pair)
 int keds_layernorm_pair_impl(const float* x, long long x_stride, const float* gamma, const float* beta, void* out, long long plane,
-                             int rows, int dim, hipStream_t st, int form = 0) {
+                             int rows, int dim, hipStream_t st, int form) {
     KedsProfScope prof(KEDS_PROF_LN, st);
     if (form != 1 && (dim == 1024 || dim == 512) && rows >= 2048 && x_stride % 4 == 0 && plane % 8 == 0) {
         // every wave resident at once (82 VGPRs: five per SIMD, five blocks per CU); at 32,768 rows a wave walks six or seven
@@ -774,9 +774,6 @@ int keds_cls_rows_impl(float* x, const float* cls, const float* pos, int B, int 
     return keds_check_launch("cls_rows_kernel");
 }
 
-int keds_embed_tokens_impl(const int32_t* tokens, const float* table, const float* pos, const float* img_tokens,
-                           int n_tok, int insert_col, float* x, int B, int L, int Lx, int d, void* stream,
-                           const int32_t* seq_off = nullptr);
 
 extern "C" int keds_cls_rows(float* x, const float* cls, const float* pos, int B, int S, int d, void* stream) {
     KEDS_REQUIRE(x && cls && pos && B > 0 && S > 0 && d > 0, "keds_cls_rows: bad argument");

@@ -16,9 +16,6 @@
 #include "keds_common.h"
 #include <math.h>
 
-int keds_layernorm_impl(const float* x, long long x_stride, const int* row_map, int row_mul, const float* gamma,
-                        const float* beta, void* out, int out_f32, int rows, int dim, hipStream_t st);
-
 namespace {
 
 namespace g32 {
@@ -308,7 +305,6 @@ extern "C" int keds_gemm_f32(const float* A, int64_t lda, const float* W, const 
 }
 
 // (seq_off: packed rows or null; what the tower passes launch, towers.hip)
-int attention_f32_impl(const float* qkv, float* out, int B, int S, int heads, int causal, int q_limit, const int32_t* seq_off, void* stream);
 extern "C" int keds_attention_f32(const float* qkv, float* out, int B, int S, int heads, int causal, int q_limit, void* stream) {
     return attention_f32_impl(qkv, out, B, S, heads, causal, q_limit, nullptr, stream);
 }
@@ -357,7 +353,8 @@ int keds_readout_f32(const float* x, int S, const int32_t* row, const float* gam
     return rc;
 }
 
-// ---- knowledge injection in fp32 (IM2TEXT + 2 x CrossFormer, model.py:37-123, eval_utils.py:661-672) ------------------
+// ---- knowledge injection in fp32 (IM2TEXT + 2 x CrossFormer, model.py:37-123, eval_utils.py:661-672): the core; the host chain
+// that runs it and keds_gemm_f32 is keds_knowledge_run_f32 (knowledge.hip) ----------------------------------------------------
 namespace {
 // single-query cross-attention core (model.py:56-79) on projected fp32 rows: one wave per (sample, head), lane = dim of the
 // 64-wide head; Q [B, inner], Kp / Vp [B*K, inner] -> out [B, inner]; K <= 64
@@ -385,113 +382,15 @@ __global__ __launch_bounds__(256) void cross_core_f32_kernel(const float* __rest
     out[(size_t)b * inner + h * 64 + lane] = o / sum;
 }
 
-int launch_core_f32(const float* Q, const float* Kp, const float* Vp, float* out, int B, int K, int heads, hipStream_t st) {
+}  // namespace
+
+int keds_cross_core_f32_impl(const float* Q, const float* Kp, const float* Vp, float* out, int B, int K, int heads, hipStream_t st) {
     cross_core_f32_kernel<<<(B * heads + 3) / 4, 256, 0, st>>>(Q, Kp, Vp, out, B, K, heads);
     return keds_check_launch("cross_core_f32_kernel");
 }
 
-struct KnowF32Ws {
-    float *x, *h1, *h2, *y, *qp, *kp, *vp, *core, *qt;
-    size_t bytes;
-};
-KnowF32Ws carve_know_f32(const keds_knowledge_params* p, int B, int K, void* ws) {
-    const size_t R = (size_t)B + 2 * (size_t)B * K;
-    const int inner = p->fuse.heads * 64;
-    KnowF32Ws w;
-    char* base = (char*)ws;
-    size_t off = 0;
-    auto take = [&](size_t n) {
-        float* r = base ? (float*)(base + off) : nullptr;
-        off += keds_align_up(n * sizeof(float), 256);
-        return r;
-    };
-    w.x = take(R * p->i2t.dim_in);
-    w.h1 = take(R * p->i2t.middle);
-    w.h2 = take(R * p->i2t.middle);
-    w.y = take(R * p->i2t.dim_out);
-    w.qp = take((size_t)B * inner);
-    w.kp = take((size_t)B * K * inner);
-    w.vp = take((size_t)B * K * inner);
-    w.core = take((size_t)B * inner);
-    w.qt = take((size_t)B * p->fuse.dim);
-    w.bytes = off;
-    return w;
-}
-
-// q chained through the layers, k and v fixed (model.py:98-101); the last layer's output lands in `out` (row stride ldo)
-int crossformer_f32(const keds_crossformer_params* p, const float* q, long long ldq, const float* kv, int B, int K, float* out,
-                    long long ldo, const KnowF32Ws& w, hipStream_t st) {
-    const int dim = p->dim, inner = p->heads * 64;
-    int rc;
-    for (int l = 0; l < p->layers; ++l) {
-        const keds_cross_layer_params& c = p->layer[l];
-        const bool last = l == p->layers - 1;
-        if ((rc = keds_gemm_f32(q, ldq, (const float*)c.wq, c.bq, w.qp, inner, B, inner, dim, F32_EPI_BIAS, nullptr, 0, st))) return rc;
-        if ((rc = keds_gemm_f32(kv, dim, (const float*)c.wk, c.bk, w.kp, inner, B * K, inner, dim, F32_EPI_BIAS, nullptr, 0, st))) return rc;
-        if ((rc = keds_gemm_f32(kv, dim, (const float*)c.wv, c.bv, w.vp, inner, B * K, inner, dim, F32_EPI_BIAS, nullptr, 0, st))) return rc;
-        if ((rc = launch_core_f32(w.qp, w.kp, w.vp, w.core, B, K, p->heads, st))) return rc;
-        float* dst = last ? out : w.qt;
-        const long long ldd = last ? ldo : dim;
-        if ((rc = keds_gemm_f32(w.core, inner, (const float*)c.wo, c.bo, dst, ldd, B, dim, inner, F32_EPI_BIAS, nullptr, 0, st))) return rc;
-        q = w.qt;
-        ldq = dim;
-    }
-    return KEDS_OK;
-}
-}  // namespace
-
 extern "C" int keds_cross_core_f32(const float* Q, const float* Kp, const float* Vp, float* out, int B, int K, int heads, void* stream) {
     KEDS_REQUIRE(Q && Kp && Vp && out && B > 0 && heads >= 1, "keds_cross_core_f32: bad argument");
     KEDS_REQUIRE(K >= 1 && K <= 64, "keds_cross_core_f32: K=%d must be in [1,64]", K);
-    return launch_core_f32(Q, Kp, Vp, out, B, K, heads, (hipStream_t)stream);
-}
-
-extern "C" size_t keds_knowledge_f32_workspace_bytes(const keds_knowledge_params* p, int B, int K) {
-    if (!p || B <= 0 || K <= 0) return 0;
-    return carve_know_f32(p, B, K, nullptr).bytes;
-}
-
-// One stream of the knowledge injection with EVERY weight pointer of the params an fp32 array (unfused per-layer weights):
-// tokens_out [B,3,dim] = [fuse(m, I, I), cond(m, T, T), m] with m = img2text(q), I / T = img2text(neighbours)
-extern "C" int keds_knowledge_run_f32(const keds_knowledge_params* p, const float* q, const float* nbr_img, const float* nbr_txt,
-                                      int B, int K, float* tokens_out, void* workspace, size_t workspace_bytes, void* stream) {
-    KEDS_REQUIRE(p && q && nbr_img && nbr_txt && tokens_out && workspace && B > 0, "keds_knowledge_run_f32: bad argument");
-    KEDS_REQUIRE(K >= 1 && K <= 64, "keds_knowledge_run_f32: K must be in [1, 64]");
-    const keds_im2text_params& m = p->i2t;
-    const int dim = p->fuse.dim;
-    KEDS_REQUIRE(m.dim_in == dim && m.dim_out == dim && p->cond.dim == dim && p->cond.heads == p->fuse.heads && m.n_layer >= 1 &&
-                     m.n_layer <= 4 && p->fuse.layer && p->cond.layer,
-                 "keds_knowledge_run_f32: inconsistent module shapes");
-    KnowF32Ws w = carve_know_f32(p, B, K, workspace);
-    if (workspace_bytes < w.bytes) {
-        keds_set_error("keds_knowledge_run_f32: workspace %zu < %zu", workspace_bytes, w.bytes);
-        return KEDS_E_WORKSPACE;
-    }
-    hipStream_t st = (hipStream_t)stream;
-    const size_t BK = (size_t)B * K, R = B + 2 * BK;
-    if (hipMemcpyAsync(w.x, q, (size_t)B * dim * 4, hipMemcpyDeviceToDevice, st) != hipSuccess ||
-        hipMemcpyAsync(w.x + (size_t)B * dim, nbr_img, BK * dim * 4, hipMemcpyDeviceToDevice, st) != hipSuccess ||
-        hipMemcpyAsync(w.x + ((size_t)B + BK) * dim, nbr_txt, BK * dim * 4, hipMemcpyDeviceToDevice, st) != hipSuccess) {
-        keds_set_error("keds_knowledge_run_f32: %s", hipGetErrorString(hipGetLastError()));
-        return KEDS_E_LAUNCH;
-    }
-    int rc;
-    const float* cur = w.x;
-    int kdim = m.dim_in;
-    for (int i = 0; i < m.n_layer; ++i) {                                   // (Linear, Dropout = identity, ReLU) x n_layer
-        float* dst = (i & 1) ? w.h2 : w.h1;
-        if ((rc = keds_gemm_f32(cur, kdim, (const float*)m.w[i], m.b[i], dst, m.middle, (int)R, m.middle, kdim, F32_EPI_RELU, nullptr, 0, st)))
-            return rc;
-        cur = dst;
-        kdim = m.middle;
-    }
-    // fc_out: the mapped query rows go straight to token slot 2 (row stride 3 dim), the neighbours to y
-    float* mapped = tokens_out + 2 * (size_t)dim;
-    if ((rc = keds_gemm_f32(cur, m.middle, (const float*)m.out_w, m.out_b, mapped, 3LL * dim, B, dim, m.middle, F32_EPI_BIAS, nullptr, 0, st)))
-        return rc;
-    if ((rc = keds_gemm_f32(cur + (size_t)B * m.middle, m.middle, (const float*)m.out_w, m.out_b, w.y, dim, (int)(2 * BK), dim, m.middle,
-                            F32_EPI_BIAS, nullptr, 0, st)))
-        return rc;
-    if ((rc = crossformer_f32(&p->fuse, mapped, 3LL * dim, w.y, B, K, tokens_out, 3LL * dim, w, st))) return rc;
-    return crossformer_f32(&p->cond, mapped, 3LL * dim, w.y + BK * dim, B, K, tokens_out + dim, 3LL * dim, w, st);
+    return keds_cross_core_f32_impl(Q, Kp, Vp, out, B, K, heads, (hipStream_t)stream);
 }

@@ -117,6 +117,18 @@ struct AttnArgs {
 int keds_attention16(const AttnArgs& a, bool f16, int causal, int q_limit, bool* stop_taken = nullptr);
 
 static inline size_t keds_align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
+// Consecutive 256-byte aligned arrays of a buffer.  With a null base only the size is counted, so ONE function per workspace layout
+// yields both its size and its pointers.
+struct KedsCarver {
+    char* base;
+    size_t used = 0;
+    char* take(size_t bytes) {
+        char* p = base ? base + used : nullptr;
+        used += keds_align_up(bytes, 256);
+        return p;
+    }
+    size_t bytes() const { return used; }
+};
 // rows of a GEMM operand of the knowledge streams: addressable up to the next multiple of 128
 static inline size_t rpad(size_t r) { return keds_align_up(r, 128); }
 
@@ -162,6 +174,32 @@ struct KedsSplitKScope {
     ~KedsSplitKScope();
 };
 void keds_splitk_scratch(float** p, size_t* bytes);   // innermost scope of this thread, else the device registration
+
+// ---- what one file of the library needs from another (host): declared here and nowhere else -------------------------------------
+// elementwise.hip: the row kernels as the tower passes and the read-outs launch them
+int keds_layernorm_impl(const float* x, long long x_stride, const int* row_map, int row_mul, const float* gamma,
+                        const float* beta, void* out, int out_f32, int rows, int dim, hipStream_t st);
+int keds_layernorm_pair_impl(const float* x, long long x_stride, const float* gamma, const float* beta, void* out, long long plane,
+                             int rows, int dim, hipStream_t st, int form = 0);
+int keds_cls_rows_impl(float* x, const float* cls, const float* pos, int B, int S, int d, hipStream_t st);
+int keds_cast_rows_f16_f32_impl(const void* x16, float* x32, int rows, int dim, long long stride, hipStream_t st);
+int keds_gather_rows_impl(const void* src, void* dst, const int32_t* row, int S, int B, int dim, int mode, hipStream_t st,
+                          bool global_rows = false);
+int keds_embed_tokens_impl(const int32_t* tokens, const float* table, const float* pos, const float* img_tokens,
+                           int n_tok, int insert_col, float* x, int B, int L, int Lx, int d, void* stream,
+                           const int32_t* seq_off = nullptr);
+int keds_readout_impl(const float* x, int S, const int32_t* row, const float* gamma, const float* beta, const void* proj_t,
+                      float* out, int B, int d, int E, int normalize, void* workspace, size_t workspace_bytes, void* stream, bool f16);
+// f32path.hip / attention_x3.hip: the attention and the read-out of the fp32-accurate flows (keds_tower_params.f32; seq_off: packed
+// rows or null), and the launch of the fp32 single-query cross-attention core (knowledge.hip's fp32 stream)
+int attention_f32_impl(const float* qkv, float* out, int B, int S, int heads, int causal, int q_limit, const int32_t* seq_off,
+                       void* stream);
+int keds_attention_x3_impl(const float* qkv, float* out, void* pair, int64_t plane, int B, int S, int heads, int causal, int q_limit,
+                           int* overflow, const int32_t* seq_off, void* stream);
+size_t keds_readout_f32_workspace_bytes(int B, int d);
+int keds_readout_f32(const float* x, int S, const int32_t* row, const float* gamma, const float* beta, const float* proj_t,
+                     float* out, int B, int d, int E, int normalize, void* workspace, hipStream_t st);
+int keds_cross_core_f32_impl(const float* Q, const float* Kp, const float* Vp, float* out, int B, int K, int heads, hipStream_t st);
 
 // ---- numerics guard (host): device int32 flag of the calling thread's current composite call, or nullptr -----------
 int* keds_numerics_guard();

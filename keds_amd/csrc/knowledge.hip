@@ -8,7 +8,11 @@
 // (sample, head) with the head dimension (64) on the lanes.  keds_im2text_forward and
 // keds_crossformer_forward expose the two modules on their own (IM2TEXT.forward /
 // CrossFormer.forward of the reference API).
+// Every host chain of the stream lives here, written once over its numeric form (bf16 with one query, bf16 on sequences, fp32):
+// xf_chain is the CrossFormer layer chain (xf_run_fused: the fused weight form) and i2t_hidden the IM2TEXT hidden layers.  The
+// kernels of the other two forms are in cross_seq.hip and f32path.hip.
 #include "keds_common.h"
+#include "cross_seq_plan.h"      // DH, cross_seq_grid_fits: the argument rules of keds_crossformer_forward_seq
 #include <math.h>
 #include <cstring>
 
@@ -133,70 +137,120 @@ int check_xf(const keds_crossformer_params* p, const char* who) {
     return KEDS_OK;
 }
 
-// ---- IM2TEXT on bf16 rows [R, dim_in] -> fp32 [R, dim_out]; scratch: 2 x [Rp, middle] bf16
-size_t i2t_scratch(const keds_im2text_params* p, size_t R) { return 2 * keds_align_up(rpad(R) * p->middle * 2, 256); }
+// ---- the numeric forms of the host chains -----------------------------------------------------------------------------
+// What a chain asks of a GEMM: rows of the form's own element type, the same after ReLU (IM2TEXT's hidden layers), or the fp32
+// rows a CrossFormer's last layer hands back.  A form supplies its element size, the GEMM with row strides and the attention core
+// on projected rows of stride `ld`; the chains below are written once over it.
+enum ChainEpi { CE_ROWS, CE_RELU, CE_OUT_F32 };
 
-int i2t_run(const keds_im2text_params* p, const void* rows_bf, int R, float* out_f, char* scratch, void* stream) {
-    char* hbuf[2] = {scratch, scratch + keds_align_up(rpad(R) * p->middle * 2, 256)};
-    const void* cur = rows_bf;
-    int cur_dim = p->dim_in, rc;
+struct Bf16One {      // bf16 operands on the MFMA GEMM, one query per sample over K <= 32 keys
+    static constexpr size_t esize = 2;
+    static int gemm(const void* A, long long lda, const void* W, const float* bias, void* out, long long ldc, int M, int N, int K,
+                    ChainEpi e, hipStream_t st) {
+        const int epi = e == CE_ROWS ? KEDS_EPI_BIAS_BF16 : e == CE_RELU ? KEDS_EPI_BIAS_RELU_BF16 : KEDS_EPI_BIAS_F32;
+        return keds_gemm_bt_ex(A, lda, W, bias, out, ldc, M, N, K, epi, nullptr, 0, st);
+    }
+    static int core(const void* Q, const void* Kp, const void* Vp, void* out, int B, int, int Lk, int heads, int ld, hipStream_t st) {
+        return launch_core((const bf16_t*)Q, (const bf16_t*)Kp, (const bf16_t*)Vp, (bf16_t*)out, B, Lk, heads, ld, st);
+    }
+};
+struct Bf16Seq : Bf16One {      // ... Lq queries per sample over Lk <= 288 keys (cross_seq.hip: its plan and its record check)
+    static int core(const void* Q, const void* Kp, const void* Vp, void* out, int B, int Lq, int Lk, int heads, int ld, hipStream_t st) {
+        return keds_cross_attn_seq(Q, Kp, Vp, out, B, Lq, Lk, heads, ld, ld, ld, st);
+    }
+};
+struct F32One {       // every weight an fp32 array, every product on the f32-input MFMA (f32path.hip), one query over K <= 64 keys
+    static constexpr size_t esize = 4;
+    static int gemm(const void* A, long long lda, const void* W, const float* bias, void* out, long long ldc, int M, int N, int K,
+                    ChainEpi e, hipStream_t st) {
+        return keds_gemm_f32((const float*)A, lda, (const float*)W, bias, (float*)out, ldc, M, N, K,
+                             e == CE_RELU ? KEDS_F32_EPI_RELU : KEDS_F32_EPI_BIAS, nullptr, 0, st);
+    }
+    static int core(const void* Q, const void* Kp, const void* Vp, void* out, int B, int, int Lk, int heads, int, hipStream_t st) {
+        return keds_cross_core_f32_impl((const float*)Q, (const float*)Kp, (const float*)Vp, (float*)out, B, Lk, heads, st);
+    }
+};
+
+// ---- IM2TEXT: (Linear, Dropout = identity, ReLU) x n_layer on rows [R, dim_in] through the two buffers h in turn; *last: the
+// buffer the last layer wrote, [R, middle].  What follows (fc_out) differs between the flows and stays with the callers.
+template <class P>
+int i2t_hidden(const keds_im2text_params* p, const void* rows, int R, char* const (&h)[2], const void** last, hipStream_t st) {
+    const void* cur = rows;
+    int cur_dim = p->dim_in;
     for (int l = 0; l < p->n_layer; ++l) {
-        if ((rc = keds_gemm_bt(cur, p->w[l], p->b[l], hbuf[l & 1], R, p->middle, cur_dim, KEDS_EPI_BIAS_RELU_BF16, nullptr,
-                               0, stream)))
-            return rc;
-        cur = hbuf[l & 1];
+        if (int rc = P::gemm(cur, cur_dim, p->w[l], p->b[l], h[l & 1], p->middle, R, p->middle, cur_dim, CE_RELU, st)) return rc;
+        cur = h[l & 1];
         cur_dim = p->middle;
     }
-    return keds_gemm_bt(cur, p->out_w, p->out_b, out_f, R, p->dim_out, p->middle, KEDS_EPI_BIAS_F32, nullptr, 0, stream);
+    *last = cur;
+    return KEDS_OK;
 }
 
-// ---- CrossFormer on bf16 inputs: q [B,dim], k rows [B*K,dim], v rows [B*K,dim] -> fp32 [B,dim]
-struct XfScratch {
-    char *qcur, *Qp, *Kp, *Vp, *att;
-    size_t bytes;
+// the two hidden buffers, [R, middle] each (the bf16 flows pad R: every operand of the MFMA GEMM is addressable up to the next
+// multiple of 128 rows; keds_gemm_f32 clamps the rows of a ragged last tile instead)
+template <class P>
+void carve_i2t(KedsCarver& c, const keds_im2text_params* p, size_t R, char* (&h)[2]) {
+    for (char*& b : h) b = c.take(R * p->middle * P::esize);
+}
+
+// IM2TEXT on bf16 rows [R, dim_in] -> fp32 [R, dim_out]
+int i2t_run(const keds_im2text_params* p, const void* rows_bf, int R, float* out_f, char* const (&h)[2], hipStream_t st) {
+    const void* cur;
+    if (int rc = i2t_hidden<Bf16One>(p, rows_bf, R, h, &cur, st)) return rc;
+    return keds_gemm_bt(cur, p->out_w, p->out_b, out_f, R, p->dim_out, p->middle, KEDS_EPI_BIAS_F32, nullptr, 0, st);
+}
+
+// ---- CrossFormer: q chained through the layers, k and v fixed (model.py:98-101).  Per layer the three projections, the core and
+// the output projection; q rows [B Lq, dim] with stride ldq, k / v rows [B Lk, dim] with stride ld_kv, all of the form's element
+// type; the last layer's output lands in `out` as fp32 rows of stride ldo.
+struct XfBufs {
+    char *qcur, *Qp, *Kp, *Vp, *att;      // [Rq, dim], [Rq, inner], [Rk, inner] x 2, [Rq, inner]
 };
-XfScratch carve_xf(const keds_crossformer_params* p, int B, int K, char* base) {
-    XfScratch s;
-    size_t off = 0;
-    auto take = [&](size_t b) {
-        char* r = base ? base + off : nullptr;
-        off += keds_align_up(b, 256);
-        return r;
-    };
-    const size_t Bp = rpad(B), BKp = rpad((size_t)B * K);
-    const int inner = p->heads * 64;
-    s.qcur = take(Bp * p->dim * 2);
-    s.Qp = take(Bp * inner * 2);
-    s.Kp = take(BKp * inner * 2);
-    s.Vp = take(BKp * inner * 2);
-    s.att = take(Bp * inner * 2);
-    s.bytes = off;
-    return s;
-}
 
-int xf_run(const keds_crossformer_params* p, const void* q_bf, const void* k_bf, const void* v_bf, int B, int K,
-           float* out_f, char* scratch, void* stream) {
-    XfScratch s = carve_xf(p, B, K, scratch);
-    hipStream_t st = (hipStream_t)stream;
-    const int dim = p->dim, inner = p->heads * 64, BK = B * K;
-    const void* qin = q_bf;
+template <class P>
+int xf_chain(const keds_crossformer_params* p, const void* q, long long ldq, const void* k, const void* v, long long ld_kv, int B, int Lq,
+             int Lk, float* out, long long ldo, const XfBufs& s, hipStream_t st) {
+    const int dim = p->dim, inner = p->heads * 64, Rq = B * Lq, Rk = B * Lk;
     int rc;
     for (int l = 0; l < p->layers; ++l) {
         const keds_cross_layer_params& c = p->layer[l];
-        if ((rc = keds_gemm_bt(qin, c.wq, c.bq, s.Qp, B, inner, dim, KEDS_EPI_BIAS_BF16, nullptr, 0, stream))) return rc;
-        if ((rc = keds_gemm_bt(k_bf, c.wk, c.bk, s.Kp, BK, inner, dim, KEDS_EPI_BIAS_BF16, nullptr, 0, stream))) return rc;
-        if ((rc = keds_gemm_bt(v_bf, c.wv, c.bv, s.Vp, BK, inner, dim, KEDS_EPI_BIAS_BF16, nullptr, 0, stream))) return rc;
-        if ((rc = launch_core((const bf16_t*)s.Qp, (const bf16_t*)s.Kp, (const bf16_t*)s.Vp, (bf16_t*)s.att, B, K, p->heads, inner, st)))
+        const bool last = l == p->layers - 1;
+        if ((rc = P::gemm(q, ldq, c.wq, c.bq, s.Qp, inner, Rq, inner, dim, CE_ROWS, st))) return rc;
+        if ((rc = P::gemm(k, ld_kv, c.wk, c.bk, s.Kp, inner, Rk, inner, dim, CE_ROWS, st))) return rc;
+        if ((rc = P::gemm(v, ld_kv, c.wv, c.bv, s.Vp, inner, Rk, inner, dim, CE_ROWS, st))) return rc;
+        if ((rc = P::core(s.Qp, s.Kp, s.Vp, s.att, B, Lq, Lk, p->heads, inner, st))) return rc;
+        if ((rc = P::gemm(s.att, inner, c.wo, c.bo, last ? (void*)out : s.qcur, last ? ldo : dim, Rq, dim, inner, last ? CE_OUT_F32 : CE_ROWS, st)))
             return rc;
-        if (l == p->layers - 1) {
-            if ((rc = keds_gemm_bt(s.att, c.wo, c.bo, out_f, B, dim, inner, KEDS_EPI_BIAS_F32, nullptr, 0, stream))) return rc;
-        } else {
-            if ((rc = keds_gemm_bt(s.att, c.wo, c.bo, s.qcur, B, dim, inner, KEDS_EPI_BIAS_BF16, nullptr, 0, stream)))
-                return rc;
-            qin = s.qcur;
-        }
+        q = s.qcur;
+        ldq = dim;
     }
     return KEDS_OK;
+}
+
+// the five buffers for Rq query rows and Rk key rows (padded by the callers of the bf16 forms, as above)
+template <class P>
+XfBufs carve_xf_bufs(KedsCarver& c, const keds_crossformer_params* p, size_t Rq, size_t Rk) {
+    const size_t dim = (size_t)p->dim, inner = (size_t)p->heads * 64;
+    XfBufs s;
+    s.qcur = c.take(Rq * dim * P::esize);
+    s.Qp = c.take(Rq * inner * P::esize);
+    s.Kp = c.take(Rk * inner * P::esize);
+    s.Vp = c.take(Rk * inner * P::esize);
+    s.att = c.take(Rq * inner * P::esize);
+    return s;
+}
+
+// bf16 inputs, one query: q [B,dim], k rows [B*K,dim], v rows [B*K,dim] -> fp32 [B,dim]
+size_t xf_bytes(const keds_crossformer_params* p, int B, int K) {
+    KedsCarver c{nullptr};
+    carve_xf_bufs<Bf16One>(c, p, rpad(B), rpad((size_t)B * K));
+    return c.bytes();
+}
+int xf_run(const keds_crossformer_params* p, const void* q_bf, const void* k_bf, const void* v_bf, int B, int K, float* out_f,
+           char* scratch, hipStream_t st) {
+    KedsCarver c{scratch};
+    const XfBufs s = carve_xf_bufs<Bf16One>(c, p, rpad(B), rpad((size_t)B * K));
+    return xf_chain<Bf16One>(p, q_bf, p->dim, k_bf, v_bf, p->dim, B, 1, K, out_f, p->dim, s, st);
 }
 
 // Fused form (p->fused): ONE GEMM projects the neighbour rows for all layers' k and v, each later layer's query comes
@@ -208,17 +262,12 @@ struct XfFusedScratch {
 };
 XfFusedScratch carve_xf_fused(const keds_crossformer_params* p, int B, int K, char* base) {
     XfFusedScratch s;
-    size_t off = 0;
-    auto take = [&](size_t b) {
-        char* r = base ? base + off : nullptr;
-        off += keds_align_up(b, 256);
-        return r;
-    };
+    KedsCarver c{base};
     const int inner = p->heads * 64;
-    s.KV = take(rpad((size_t)B * K) * (size_t)p->layers * 2 * inner * 2);
-    s.Qp = take(rpad(B) * inner * 2);
-    s.att = take(rpad(B) * inner * 2);
-    s.bytes = off;
+    s.KV = c.take(rpad((size_t)B * K) * (size_t)p->layers * 2 * inner * 2);
+    s.Qp = c.take(rpad(B) * inner * 2);
+    s.att = c.take(rpad(B) * inner * 2);
+    s.bytes = c.bytes();
     return s;
 }
 
@@ -260,15 +309,9 @@ extern "C" int keds_crossformer_fuse(const keds_crossformer_params* p, void* buf
     KEDS_REQUIRE(buffer_bytes >= keds_crossformer_fused_bytes(p), "keds_crossformer_fuse: buffer too small");
     hipStream_t st = (hipStream_t)stream;
     const int inner = p->heads * 64, dim = p->dim;
-    char* base = (char*)buffer;
-    size_t off = 0;
-    auto take = [&](size_t b) {
-        char* r = base + off;
-        off += keds_align_up(b, 256);
-        return r;
-    };
-    bf16_t* wkv = (bf16_t*)take((size_t)p->layers * 2 * inner * dim * 2);
-    float* bkv = (float*)take((size_t)p->layers * 2 * inner * 4);
+    KedsCarver arrays{(char*)buffer};
+    bf16_t* wkv = (bf16_t*)arrays.take((size_t)p->layers * 2 * inner * dim * 2);
+    float* bkv = (float*)arrays.take((size_t)p->layers * 2 * inner * 4);
     memset(out, 0, sizeof(*out));
     out->wkv = wkv;
     out->bkv = bkv;
@@ -280,8 +323,8 @@ extern "C" int keds_crossformer_fuse(const keds_crossformer_params* p, void* buf
         concat_rows_kernel<<<blocks, 256, 0, st>>>((const bf16_t*)c.wv, c.bv, wkv + (size_t)(2 * l + 1) * inner * dim,
                                                    bkv + (2 * l + 1) * inner, inner, dim);
         if (l >= 1) {
-            bf16_t* w = (bf16_t*)take((size_t)inner * inner * 2);
-            float* b = (float*)take((size_t)inner * 4);
+            bf16_t* w = (bf16_t*)arrays.take((size_t)inner * inner * 2);
+            float* b = (float*)arrays.take((size_t)inner * 4);
             const keds_cross_layer_params& prev = p->layer[l - 1];
             fold_qo_kernel<<<inner, 256, 0, st>>>((const bf16_t*)c.wq, c.bq, (const bf16_t*)prev.wo, prev.bo, inner, dim, w, b);
             out->wqn[l] = w;
@@ -313,9 +356,25 @@ extern "C" int keds_place_token(const float* src, float* tokens, int B, int dim,
 }
 
 // ---- standalone IM2TEXT ------------------------------------------------------------------------
+namespace {
+struct I2tWs {
+    char* x_bf;      // [Rp, dim_in] bf16
+    char* h[2];
+    size_t bytes;
+};
+I2tWs carve_i2t_ws(const keds_im2text_params* p, int rows, void* ws) {
+    I2tWs w;
+    KedsCarver c{(char*)ws};
+    w.x_bf = c.take(rpad(rows) * p->dim_in * 2);
+    carve_i2t<Bf16One>(c, p, rpad(rows), w.h);
+    w.bytes = c.bytes();
+    return w;
+}
+}  // namespace
+
 extern "C" size_t keds_im2text_workspace_bytes(const keds_im2text_params* p, int rows) {
     if (!p || rows <= 0) return 0;
-    return keds_align_up(rpad(rows) * p->dim_in * 2, 256) + i2t_scratch(p, rows);
+    return carve_i2t_ws(p, rows, nullptr).bytes;
 }
 
 extern "C" int keds_im2text_forward(const keds_im2text_params* p, const float* x, int rows, float* out, void* workspace,
@@ -323,24 +382,87 @@ extern "C" int keds_im2text_forward(const keds_im2text_params* p, const float* x
     int rc = check_i2t(p, "keds_im2text_forward");
     if (rc) return rc;
     KEDS_REQUIRE(x && out && workspace && rows > 0, "keds_im2text_forward: bad argument");
-    if (workspace_bytes < keds_im2text_workspace_bytes(p, rows)) {
+    const I2tWs w = carve_i2t_ws(p, rows, workspace);
+    if (workspace_bytes < w.bytes) {
         keds_set_error("keds_im2text_forward: workspace too small");
         return KEDS_E_WORKSPACE;
     }
-    char* xb = (char*)workspace;
-    char* scratch = xb + keds_align_up(rpad(rows) * p->dim_in * 2, 256);
-    if ((rc = keds_cast_bf16(x, xb, (int64_t)rows * p->dim_in, stream))) return rc;
-    return i2t_run(p, xb, rows, out, scratch, stream);
+    if ((rc = keds_cast_bf16(x, w.x_bf, (int64_t)rows * p->dim_in, stream))) return rc;
+    return i2t_run(p, w.x_bf, rows, out, w.h, (hipStream_t)stream);
 }
 
-// ---- standalone CrossFormer --------------------------------------------------------------------
+// ---- standalone CrossFormer: one query per sample, and sequences ---------------------------------------------------
+namespace {
+// scratch of xf_run, or of xf_run_fused where the parameters carry the fused weights and it is larger
+size_t xf_scratch_bytes(const keds_crossformer_params* p, int B, int K) {
+    const size_t sc = xf_bytes(p, B, K), fb = p->fused ? carve_xf_fused(p, B, K, nullptr).bytes : 0;
+    return fb > sc ? fb : sc;
+}
+
+// the head of both entries' workspace: the fp32 inputs as bf16 rows
+struct XfIn {
+    char *q, *k, *v;
+};
+XfIn carve_xf_in(KedsCarver& c, const keds_crossformer_params* p, size_t Rq, size_t Rk) {
+    XfIn in;
+    in.q = c.take(Rq * p->dim * 2);
+    in.k = c.take(Rk * p->dim * 2);
+    in.v = c.take(Rk * p->dim * 2);
+    return in;
+}
+// q, k, v -> bf16 (nq and nk elements); v == k is cast once and in.v becomes in.k
+int cast_qkv(const float* q, const float* k, const float* v, int64_t nq, int64_t nk, XfIn& in, void* stream) {
+    int rc;
+    if ((rc = keds_cast_bf16(q, in.q, nq, stream))) return rc;
+    if ((rc = keds_cast_bf16(k, in.k, nk, stream))) return rc;
+    if (v == k) in.v = in.k;
+    else if ((rc = keds_cast_bf16(v, in.v, nk, stream))) return rc;
+    return KEDS_OK;
+}
+
+struct XfWs {
+    XfIn in;
+    char* scratch;
+    size_t bytes;
+};
+XfWs carve_xf_ws(const keds_crossformer_params* p, int B, int K, void* ws) {
+    XfWs w;
+    KedsCarver c{(char*)ws};
+    w.in = carve_xf_in(c, p, rpad(B), rpad((size_t)B * K));
+    w.scratch = c.take(xf_scratch_bytes(p, B, K));
+    w.bytes = c.bytes();
+    return w;
+}
+
+struct XfSeqWs {
+    XfIn in;
+    XfBufs s;
+    size_t bytes;
+};
+XfSeqWs carve_xf_seq(const keds_crossformer_params* p, int B, int Lq, int Lk, void* ws) {
+    XfSeqWs w;
+    KedsCarver c{(char*)ws};
+    const size_t Rq = rpad((size_t)B * Lq), Rk = rpad((size_t)B * Lk);
+    w.in = carve_xf_in(c, p, Rq, Rk);
+    w.s = carve_xf_bufs<Bf16Seq>(c, p, Rq, Rk);
+    w.bytes = c.bytes();
+    return w;
+}
+
+int check_xf_seq(const keds_crossformer_params* p, int B, int Lq, int Lk, const char* who) {
+    KEDS_REQUIRE(p && p->layer && p->layers >= 1 && p->heads >= 1 && (p->heads * DH) % 128 == 0 && p->dim >= 128 && p->dim % 128 == 0,
+                 "%s: bad CrossFormer parameters (dim and 64 heads must be multiples of 128)", who);
+    KEDS_REQUIRE(B >= 1 && Lq >= 1, "%s: B=%d and Lq=%d must be at least 1", who, B, Lq);
+    KEDS_REQUIRE(Lk >= 1 && Lk <= KEDS_CROSS_SEQ_MAX_KEYS, "%s: Lk=%d must be in [1,%d]", who, Lk, KEDS_CROSS_SEQ_MAX_KEYS);
+    KEDS_REQUIRE((long long)B * Lq <= 0x7FFFFFFFLL && (long long)B * Lk <= 0x7FFFFFFFLL && cross_seq_grid_fits(B, Lq, p->heads),
+                 "%s: B=%d x Lq=%d (Lk=%d) rows are too many for one call", who, B, Lq, Lk);
+    return KEDS_OK;
+}
+}  // namespace
+
 extern "C" size_t keds_crossformer_workspace_bytes(const keds_crossformer_params* p, int B, int K) {
     if (!p || B <= 0 || K <= 0) return 0;
-    const size_t qb = keds_align_up(rpad(B) * p->dim * 2, 256);
-    const size_t kb = keds_align_up(rpad((size_t)B * K) * p->dim * 2, 256);
-    size_t sc = carve_xf(p, B, K, nullptr).bytes;
-    if (p->fused && carve_xf_fused(p, B, K, nullptr).bytes > sc) sc = carve_xf_fused(p, B, K, nullptr).bytes;
-    return qb + 2 * kb + sc;
+    return carve_xf_ws(p, B, K, nullptr).bytes;
 }
 
 extern "C" int keds_crossformer_forward(const keds_crossformer_params* p, const float* q, const float* k, const float* v,
@@ -350,23 +472,35 @@ extern "C" int keds_crossformer_forward(const keds_crossformer_params* p, const 
     if (rc) return rc;
     KEDS_REQUIRE(q && k && v && out && workspace && B > 0, "keds_crossformer_forward: bad argument");
     KEDS_REQUIRE(K >= 1 && K <= 32, "keds_crossformer_forward: K=%d must be in [1,32]", K);
-    if (workspace_bytes < keds_crossformer_workspace_bytes(p, B, K)) {
+    XfWs w = carve_xf_ws(p, B, K, workspace);
+    if (workspace_bytes < w.bytes) {
         keds_set_error("keds_crossformer_forward: workspace too small");
         return KEDS_E_WORKSPACE;
     }
-    const size_t qb = keds_align_up(rpad(B) * p->dim * 2, 256);
-    const size_t kb = keds_align_up(rpad((size_t)B * K) * p->dim * 2, 256);
-    char* base = (char*)workspace;
-    char *q_bf = base, *k_bf = base + qb, *v_bf = base + qb + kb, *scratch = base + qb + 2 * kb;
-    if ((rc = keds_cast_bf16(q, q_bf, (int64_t)B * p->dim, stream))) return rc;
-    if ((rc = keds_cast_bf16(k, k_bf, (int64_t)B * K * p->dim, stream))) return rc;
-    if (v != k) {
-        if ((rc = keds_cast_bf16(v, v_bf, (int64_t)B * K * p->dim, stream))) return rc;
-    } else {
-        v_bf = k_bf;
-        if (p->fused) return xf_run_fused(p, q_bf, k_bf, B, K, out, p->dim, scratch, (hipStream_t)stream);
+    if ((rc = cast_qkv(q, k, v, (int64_t)B * p->dim, (int64_t)B * K * p->dim, w.in, stream))) return rc;
+    if (v == k && p->fused) return xf_run_fused(p, w.in.q, w.in.k, B, K, out, p->dim, w.scratch, (hipStream_t)stream);
+    return xf_run(p, w.in.q, w.in.k, w.in.v, B, K, out, w.scratch, (hipStream_t)stream);
+}
+
+extern "C" size_t keds_crossformer_seq_workspace_bytes(const keds_crossformer_params* p, int B, int Lq, int Lk) {
+    if (!p || B <= 0 || Lq <= 0 || Lk <= 0 || p->dim <= 0 || p->heads <= 0) return 0;
+    return carve_xf_seq(p, B, Lq, Lk, nullptr).bytes;
+}
+
+// B Lq query rows over B Lk key rows (keds_hip.h); the core is keds_cross_attn_seq (cross_seq.hip)
+extern "C" int keds_crossformer_forward_seq(const keds_crossformer_params* p, const float* q, const float* k, const float* v, int B, int Lq,
+                                            int Lk, float* out, void* workspace, size_t workspace_bytes, void* stream) {
+    if (int rc = check_xf_seq(p, B, Lq, Lk, "keds_crossformer_forward_seq")) return rc;
+    KEDS_REQUIRE(q && k && v && out && workspace, "keds_crossformer_forward_seq: null pointer");
+    XfSeqWs w = carve_xf_seq(p, B, Lq, Lk, workspace);
+    if (workspace_bytes < w.bytes) {
+        keds_set_error("keds_crossformer_forward_seq: workspace %zu < %zu", workspace_bytes, w.bytes);
+        return KEDS_E_WORKSPACE;
     }
-    return xf_run(p, q_bf, k_bf, v_bf, B, K, out, scratch, stream);
+    // (the fused weight form, p->fused, is not used here: with B Lq query rows the GEMMs carry the work)
+    const int dim = p->dim;
+    if (int rc = cast_qkv(q, k, v, (int64_t)B * Lq * dim, (int64_t)B * Lk * dim, w.in, stream)) return rc;
+    return xf_chain<Bf16Seq>(p, w.in.q, dim, w.in.k, w.in.v, dim, B, Lq, Lk, out, dim, w.s, (hipStream_t)stream);
 }
 
 // ---- one full stream ---------------------------------------------------------------------------
@@ -376,32 +510,44 @@ struct KnWs {
     float* map_f;    // [R, dim] fp32 IM2TEXT output
     char* map_bf;    // [R + 128, dim] bf16
     float* outf;     // [Bp, dim] fp32 CrossFormer output
-    char* i2t;       // IM2TEXT scratch
+    char* h[2];      // IM2TEXT hidden layers
     char* xf;        // CrossFormer scratch (retrieval_fuse)
     char* xf2;       // ... of text_condition: the two chains run side by side on two lanes
     size_t bytes;
 };
 KnWs carve_kn(const keds_knowledge_params* p, int B, int K, void* ws) {
     KnWs w;
-    char* base = (char*)ws;
-    size_t off = 0;
-    auto take = [&](size_t b) {
-        char* r = base ? base + off : nullptr;
-        off += keds_align_up(b, 256);
-        return r;
-    };
+    KedsCarver c{(char*)ws};
     const size_t R = (size_t)B * (1 + 2 * K);
     const int dim = p->i2t.dim_out;
-    w.rows_bf = take(rpad(R) * p->i2t.dim_in * 2);
-    w.map_f = (float*)take(rpad(R) * dim * 4);
-    w.map_bf = take((rpad(R) + 128) * dim * 2);   // GEMMs on sub-ranges may read up to 127 rows past R
-    w.outf = (float*)take(rpad(B) * dim * 4);
-    w.i2t = take(i2t_scratch(&p->i2t, R));
-    size_t xb = carve_xf(&p->fuse, B, K, nullptr).bytes;
-    if (p->fuse.fused && carve_xf_fused(&p->fuse, B, K, nullptr).bytes > xb) xb = carve_xf_fused(&p->fuse, B, K, nullptr).bytes;
-    w.xf = take(xb);
-    w.xf2 = take(xb);
-    w.bytes = off;
+    w.rows_bf = c.take(rpad(R) * p->i2t.dim_in * 2);
+    w.map_f = (float*)c.take(rpad(R) * dim * 4);
+    w.map_bf = c.take((rpad(R) + 128) * dim * 2);   // GEMMs on sub-ranges may read up to 127 rows past R
+    w.outf = (float*)c.take(rpad(B) * dim * 4);
+    carve_i2t<Bf16One>(c, &p->i2t, rpad(R), w.h);
+    const size_t xb = xf_scratch_bytes(&p->fuse, B, K);
+    w.xf = c.take(xb);
+    w.xf2 = c.take(xb);
+    w.bytes = c.bytes();
+    return w;
+}
+
+// the fp32 stream: unpadded rows (keds_gemm_f32 clamps the rows of a ragged last tile), one CrossFormer at a time
+struct KnowF32Ws {
+    float *x, *y;    // [R, dim_in] stacked inputs; [2 B K, dim] mapped neighbours
+    char* h[2];      // IM2TEXT hidden layers [R, middle]
+    XfBufs s;
+    size_t bytes;
+};
+KnowF32Ws carve_know_f32(const keds_knowledge_params* p, int B, int K, void* ws) {
+    const size_t R = (size_t)B + 2 * (size_t)B * K;
+    KnowF32Ws w;
+    KedsCarver c{(char*)ws};
+    w.x = (float*)c.take(R * p->i2t.dim_in * 4);
+    carve_i2t<F32One>(c, &p->i2t, R, w.h);
+    w.y = (float*)c.take(R * p->i2t.dim_out * 4);
+    w.s = carve_xf_bufs<F32One>(c, &p->fuse, B, (size_t)B * K);
+    w.bytes = c.bytes();
     return w;
 }
 }  // namespace
@@ -439,16 +585,8 @@ extern "C" int keds_knowledge_run(const keds_knowledge_params* p, const float* q
         // GEMM for all layers + (query GEMM, attention core) per layer + the output GEMM straight into its token slot.
         // The two CrossFormer chains are independent: text_condition runs on the side lane beside retrieval_fuse.
         if ((rc = launch_pack(q, nbr_img, nbr_txt, rows, B, K, dim, st))) return rc;
-        char* hbuf[2] = {w.i2t, w.i2t + keds_align_up(rpad(R) * p->i2t.middle * 2, 256)};
-        const void* cur = rows;
-        int cur_dim = p->i2t.dim_in;
-        for (int l = 0; l < p->i2t.n_layer; ++l) {
-            if ((rc = keds_gemm_bt(cur, p->i2t.w[l], p->i2t.b[l], hbuf[l & 1], R, p->i2t.middle, cur_dim, KEDS_EPI_BIAS_RELU_BF16,
-                                   nullptr, 0, stream)))
-                return rc;
-            cur = hbuf[l & 1];
-            cur_dim = p->i2t.middle;
-        }
+        const void* cur;
+        if ((rc = i2t_hidden<Bf16One>(&p->i2t, rows, R, w.h, &cur, st))) return rc;
         if ((rc = keds_gemm_bt(cur, p->i2t.out_w, p->i2t.out_b, w.map_bf, R, dim, p->i2t.middle, KEDS_EPI_BIAS_BF16_HEADF32,
                                tokens_out + 2 * dim, B, stream)))
             return rc;
@@ -467,15 +605,60 @@ extern "C" int keds_knowledge_run(const keds_knowledge_params* p, const float* q
     if ((rc = keds_cast_bf16(q, rows, (int64_t)B * dim, stream))) return rc;
     if ((rc = keds_cast_bf16(nbr_img, rows + (size_t)B * dim, (int64_t)BK * dim, stream))) return rc;
     if ((rc = keds_cast_bf16(nbr_txt, rows + (size_t)(B + BK) * dim, (int64_t)BK * dim, stream))) return rc;
-    if ((rc = i2t_run(&p->i2t, rows, R, w.map_f, w.i2t, stream))) return rc;
+    if ((rc = i2t_run(&p->i2t, rows, R, w.map_f, w.h, st))) return rc;
     if ((rc = keds_cast_bf16(w.map_f, w.map_bf, (int64_t)R * dim, stream))) return rc;
     if ((rc = launch_place(w.map_f, tokens_out, B, dim, 2, 3, st))) return rc;
     const bf16_t* map_bf = (const bf16_t*)w.map_bf;
     for (int which = 0; which < 2; ++which) {
         const keds_crossformer_params* xf = which == 0 ? &p->fuse : &p->cond;
         const bf16_t* nb = map_bf + (size_t)(B + which * BK) * dim;
-        if ((rc = xf_run(xf, map_bf, nb, nb, B, K, w.outf, w.xf, stream))) return rc;
+        if ((rc = xf_run(xf, map_bf, nb, nb, B, K, w.outf, w.xf, st))) return rc;
         if ((rc = launch_place(w.outf, tokens_out, B, dim, which, 3, st))) return rc;
     }
     return KEDS_OK;
+}
+
+// ---- one full stream in fp32 (f32path.hip: the kernels) -------------------------------------------------------------
+extern "C" size_t keds_knowledge_f32_workspace_bytes(const keds_knowledge_params* p, int B, int K) {
+    if (!p || B <= 0 || K <= 0) return 0;
+    return carve_know_f32(p, B, K, nullptr).bytes;
+}
+
+// One stream of the knowledge injection with EVERY weight pointer of the params an fp32 array (unfused per-layer weights):
+// tokens_out [B,3,dim] = [fuse(m, I, I), cond(m, T, T), m] with m = img2text(q), I / T = img2text(neighbours)
+extern "C" int keds_knowledge_run_f32(const keds_knowledge_params* p, const float* q, const float* nbr_img, const float* nbr_txt,
+                                      int B, int K, float* tokens_out, void* workspace, size_t workspace_bytes, void* stream) {
+    KEDS_REQUIRE(p && q && nbr_img && nbr_txt && tokens_out && workspace && B > 0, "keds_knowledge_run_f32: bad argument");
+    KEDS_REQUIRE(K >= 1 && K <= 64, "keds_knowledge_run_f32: K must be in [1, 64]");
+    const keds_im2text_params& m = p->i2t;
+    const int dim = p->fuse.dim;
+    KEDS_REQUIRE(m.dim_in == dim && m.dim_out == dim && p->cond.dim == dim && p->cond.heads == p->fuse.heads && m.n_layer >= 1 &&
+                     m.n_layer <= 4 && p->fuse.layer && p->cond.layer,
+                 "keds_knowledge_run_f32: inconsistent module shapes");
+    KnowF32Ws w = carve_know_f32(p, B, K, workspace);
+    if (workspace_bytes < w.bytes) {
+        keds_set_error("keds_knowledge_run_f32: workspace %zu < %zu", workspace_bytes, w.bytes);
+        return KEDS_E_WORKSPACE;
+    }
+    hipStream_t st = (hipStream_t)stream;
+    const size_t BK = (size_t)B * K, R = B + 2 * BK;
+    if (hipMemcpyAsync(w.x, q, (size_t)B * dim * 4, hipMemcpyDeviceToDevice, st) != hipSuccess ||
+        hipMemcpyAsync(w.x + (size_t)B * dim, nbr_img, BK * dim * 4, hipMemcpyDeviceToDevice, st) != hipSuccess ||
+        hipMemcpyAsync(w.x + ((size_t)B + BK) * dim, nbr_txt, BK * dim * 4, hipMemcpyDeviceToDevice, st) != hipSuccess) {
+        keds_set_error("keds_knowledge_run_f32: %s", hipGetErrorString(hipGetLastError()));
+        return KEDS_E_LAUNCH;
+    }
+    int rc;
+    const void* last;
+    if ((rc = i2t_hidden<F32One>(&m, w.x, (int)R, w.h, &last, st))) return rc;
+    const float* cur = (const float*)last;
+    // fc_out: the mapped query rows go straight to token slot 2 (row stride 3 dim), the neighbours to y
+    float* mapped = tokens_out + 2 * (size_t)dim;
+    if ((rc = keds_gemm_f32(cur, m.middle, (const float*)m.out_w, m.out_b, mapped, 3LL * dim, B, dim, m.middle, KEDS_F32_EPI_BIAS, nullptr, 0, st)))
+        return rc;
+    if ((rc = keds_gemm_f32(cur + (size_t)B * m.middle, m.middle, (const float*)m.out_w, m.out_b, w.y, dim, (int)(2 * BK), dim, m.middle,
+                            KEDS_F32_EPI_BIAS, nullptr, 0, st)))
+        return rc;
+    if ((rc = xf_chain<F32One>(&p->fuse, mapped, 3LL * dim, w.y, w.y, dim, B, 1, K, tokens_out, 3LL * dim, w.s, st))) return rc;
+    return xf_chain<F32One>(&p->cond, mapped, 3LL * dim, w.y + BK * dim, w.y + BK * dim, dim, B, 1, K, tokens_out + dim, 3LL * dim, w.s, st);
 }

@@ -17,24 +17,13 @@ const char* mode_error(int width, int fp8, int f32, int f16, int folded) {
     return nullptr;
 }
 
-// consecutive 256-byte aligned arrays of a buffer; with a null base only the size is counted
-struct Carver {
-    char* base;
-    size_t used = 0;
-    void* take(size_t bytes) {
-        void* p = base ? base + used : nullptr;
-        used += keds_align_up(bytes, 256);
-        return p;
-    }
-};
-
 struct Gemm {
     int n, k;
 };
 
 // The arrays of a VALID mode, in buffer order (documented at keds_block_pack in keds_hip.h).  Fills every field of `out`;
 // returns the scratch {bias, column sums} vector of the out-proj / c_proj MXFP8 calls (fp8 only), which no kernel reads.
-float* layout(Carver& c, int d, int fp8, int f32, int folded, keds_block_params* out) {
+float* layout(KedsCarver& c, int d, int fp8, int f32, int folded, keds_block_params* out) {
     const Gemm g[4] = {{3 * d, d}, {d, d}, {4 * d, d}, {d, 4 * d}};                  // qkv, out, fc, proj
     const size_t wsize = f32 ? 4 : 2;                                              // (f32 == 2: two fp16 planes)
     *out = keds_block_params{};
@@ -66,10 +55,10 @@ extern "C" size_t keds_block_pack_bytes(int width, int fp8, int f32, int f16, in
         keds_set_error("keds_block_pack_bytes: %s", why);
         return 0;
     }
-    Carver c{nullptr};
+    KedsCarver c{nullptr};
     keds_block_params p;
     layout(c, width, fp8, f32, folded, &p);
-    return c.used;
+    return c.bytes();
 }
 
 extern "C" int keds_block_pack(const keds_block_source* src, int width, int fp8, int f32, int f16, int folded, void* buf,
@@ -86,7 +75,7 @@ extern "C" int keds_block_pack(const keds_block_source* src, int width, int fp8,
     hipStream_t st = (hipStream_t)stream;
     const int d = width;
     const Gemm g[4] = {{3 * d, d}, {d, d}, {4 * d, d}, {d, 4 * d}};
-    Carver c{(char*)buf};
+    KedsCarver c{(char*)buf};
     keds_block_params p;
     float* scratch_bc8 = layout(c, d, fp8, f32, folded, &p);
     auto copy = [&](const void* dst, const float* from, size_t count) {

@@ -999,39 +999,33 @@ struct SearchWs {
 
 SearchWs carve(void* ws, int nq, int dim, int64_t n, int k) {
     SearchWs w;
-    char* p = (char*)ws;
+    KedsCarver c{(char*)ws};
     const int nwg = 256;  // upper bound used for sizing
-    size_t off = 0;
-    auto take = [&](size_t b) {
-        char* r = p ? p + off : nullptr;
-        off += keds_align_up(b, 256);
-        return r;
-    };
     const int ncand = k > LISTK ? NCAND_WIDE : NCAND;
     const size_t nq_pad = keds_align_up((size_t)nq, QBLOCK);
     const size_t set = MAXQB * QBLOCK;
-    w.qn = (float*)take(nq_pad * dim * sizeof(float));
-    w.qb = (bf16_t*)take(set * dim * 2);
-    w.lpairs = (unsigned long long*)take((size_t)QBLOCK * nwg * 4 * LISTK * sizeof(unsigned long long));
-    w.lmeta = (uint2*)take((size_t)QBLOCK * nwg * sizeof(uint2));
-    w.cidx = (int*)take(set * ncand * sizeof(int));
-    w.cval = (float*)take(set * ncand * sizeof(float));
-    w.cdist = (float*)take(set * ncand * sizeof(float));
-    w.aidx = (int*)take(set * ncand * sizeof(int));
-    w.aval = (float*)take(set * ncand * sizeof(float));
-    w.thr = (float*)take(set * sizeof(float));
-    w.sbound = (float*)take(set * sizeof(float));
-    w.qstat = (f32x4*)take(set * sizeof(f32x4));
-    w.dk = (float*)take(set * sizeof(float));
-    w.fail_ids = (int*)take(set * sizeof(int));
-    w.fslot = (int*)take(set * sizeof(int));
-    w.counters = (int*)take((8 + set) * sizeof(int));   // [0] failed certificates | [8 + f] finished chunks of fail slot f
+    w.qn = (float*)c.take(nq_pad * dim * sizeof(float));
+    w.qb = (bf16_t*)c.take(set * dim * 2);
+    w.lpairs = (unsigned long long*)c.take((size_t)QBLOCK * nwg * 4 * LISTK * sizeof(unsigned long long));
+    w.lmeta = (uint2*)c.take((size_t)QBLOCK * nwg * sizeof(uint2));
+    w.cidx = (int*)c.take(set * ncand * sizeof(int));
+    w.cval = (float*)c.take(set * ncand * sizeof(float));
+    w.cdist = (float*)c.take(set * ncand * sizeof(float));
+    w.aidx = (int*)c.take(set * ncand * sizeof(int));
+    w.aval = (float*)c.take(set * ncand * sizeof(float));
+    w.thr = (float*)c.take(set * sizeof(float));
+    w.sbound = (float*)c.take(set * sizeof(float));
+    w.qstat = (f32x4*)c.take(set * sizeof(f32x4));
+    w.dk = (float*)c.take(set * sizeof(float));
+    w.fail_ids = (int*)c.take(set * sizeof(int));
+    w.fslot = (int*)c.take(set * sizeof(int));
+    w.counters = (int*)c.take((8 + set) * sizeof(int));   // [0] failed certificates | [8 + f] finished chunks of fail slot f
     const int nq_set = nq < (int)set ? nq : (int)set;
     w.chunk_rows = exact_chunk_rows(n, nq_set, k);
     w.nchunks = w.chunk_rows ? (int)((n + w.chunk_rows - 1) / w.chunk_rows) : 0;
-    w.plist = (unsigned long long*)take((size_t)nq_set * w.nchunks * k * 8);
-    w.pcnt = (int*)take((size_t)nq_set * w.nchunks * sizeof(int));
-    w.bytes = off;
+    w.plist = (unsigned long long*)c.take((size_t)nq_set * w.nchunks * k * 8);
+    w.pcnt = (int*)c.take((size_t)nq_set * w.nchunks * sizeof(int));
+    w.bytes = c.bytes();
     return w;
 }
 

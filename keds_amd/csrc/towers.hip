@@ -14,29 +14,6 @@
 #include <cstring>
 #include <optional>
 
-int keds_layernorm_impl(const float* x, long long x_stride, const int* row_map, int row_mul, const float* gamma,
-                        const float* beta, void* out, int out_f32, int rows, int dim, hipStream_t st);
-int keds_layernorm_pair_impl(const float* x, long long x_stride, const float* gamma, const float* beta, void* out, long long plane,
-                             int rows, int dim, hipStream_t st, int form = 0);
-int keds_cls_rows_impl(float* x, const float* cls, const float* pos, int B, int S, int d, hipStream_t st);
-int keds_cast_rows_f16_f32_impl(const void* x16, float* x32, int rows, int dim, long long stride, hipStream_t st);
-int keds_gather_rows_impl(const void* src, void* dst, const int32_t* row, int S, int B, int dim, int mode, hipStream_t st,
-                          bool global_rows = false);
-int keds_embed_tokens_impl(const int32_t* tokens, const float* table, const float* pos, const float* img_tokens,
-                           int n_tok, int insert_col, float* x, int B, int L, int Lx, int d, void* stream,
-                           const int32_t* seq_off = nullptr);
-
-// f32path.hip / attention_x3.hip: the attention and the read-out of the fp32-accurate flows (keds_tower_params.f32)
-int attention_f32_impl(const float* qkv, float* out, int B, int S, int heads, int causal, int q_limit, const int32_t* seq_off,
-                       void* stream);
-int keds_attention_x3_impl(const float* qkv, float* out, void* pair, int64_t plane, int B, int S, int heads, int causal, int q_limit,
-                           int* overflow, const int32_t* seq_off, void* stream);
-size_t keds_readout_f32_workspace_bytes(int B, int d);
-int keds_readout_f32(const float* x, int S, const int32_t* row, const float* gamma, const float* beta, const float* proj_t,
-                     float* out, int B, int d, int E, int normalize, void* workspace, hipStream_t st);
-int keds_readout_impl(const float* x, int S, const int32_t* row, const float* gamma, const float* beta, const void* proj_t,
-                      float* out, int B, int d, int E, int normalize, void* workspace, size_t workspace_bytes, void* stream, bool f16);
-
 namespace {
 
 static_assert(TOWER_SPLITK_BYTES == KEDS_SPLITK_BYTES, "tower_plan.h carves the split-K scratch");

@@ -777,33 +777,21 @@ class CrossFormer(nn.Module):
         _lib.require_gpu()
         if not self.cross_layers[0].to_q.weight.is_cuda:
             raise RuntimeError("keds_amd.CrossFormer: move the module to the GPU first; no CPU path exists")
-        if f32:
-            if getattr(self, "_packed32", None) is None:
-                keep = []
-                arr = (_lib.CrossLayerParams * self._num_layers)()
-                for i, l in enumerate(self.cross_layers):
-                    t = dict(wq=_f32(l.to_q.weight), wk=_f32(l.to_k.weight), wv=_f32(l.to_v.weight), wo=_f32(l.to_out[0].weight),
-                             bq=_f32(l.to_q.bias), bk=_f32(l.to_k.bias), bv=_f32(l.to_v.bias), bo=_f32(l.to_out[0].bias))
-                    for k, v in t.items():
-                        setattr(arr[i], k, ptr(v))
-                    keep.append(t)
-                self._packed32 = (_lib.CrossFormerParams(self.dim, self.heads, self._num_layers, arr, None), keep, arr)
-            return self._packed32[0]
-        if self._packed is None:
+        slot, cast = ("_packed32", _f32) if f32 else ("_packed", _bf16)
+        if getattr(self, slot, None) is None:
             keep = []
             arr = (_lib.CrossLayerParams * self._num_layers)()
             for i, l in enumerate(self.cross_layers):
-                t = dict(wq=_bf16(l.to_q.weight), wk=_bf16(l.to_k.weight), wv=_bf16(l.to_v.weight),
-                         wo=_bf16(l.to_out[0].weight), bq=_f32(l.to_q.bias), bk=_f32(l.to_k.bias),
-                         bv=_f32(l.to_v.bias), bo=_f32(l.to_out[0].bias))
+                t = dict(wq=cast(l.to_q.weight), wk=cast(l.to_k.weight), wv=cast(l.to_v.weight), wo=cast(l.to_out[0].weight),
+                         bq=_f32(l.to_q.bias), bk=_f32(l.to_k.bias), bv=_f32(l.to_v.bias), bo=_f32(l.to_out[0].bias))
                 for k, v in t.items():
                     setattr(arr[i], k, ptr(v))
                 keep.append(t)
             p = _lib.CrossFormerParams(self.dim, self.heads, self._num_layers, arr, None)
-            # launch-saving re-arrangement (keds_hip.h, keds_crossformer_fused): one k/v GEMM for all layers, and every
-            # later layer's query projection folded with the previous output projection
-            lib = load()
-            if self._num_layers <= 8:
+            # launch-saving re-arrangement of the bf16 weights (keds_hip.h, keds_crossformer_fused): one k/v GEMM for all layers,
+            # and every later layer's query projection folded with the previous output projection
+            if not f32 and self._num_layers <= 8:
+                lib = load()
                 dev = self.cross_layers[0].to_q.weight.device
                 buf = torch.empty(int(lib.keds_crossformer_fused_bytes(C.byref(p))), dtype=torch.uint8, device=dev)
                 fused = _lib.CrossFormerFused()
@@ -812,9 +800,10 @@ class CrossFormer(nn.Module):
                 torch.cuda.current_stream().synchronize()
                 p.fused = C.pointer(fused)
                 keep += [buf, fused]
-            self._packed = (p, keep, arr)
-        _lib.ensure_gemm_workspace(self.cross_layers[0].to_q.weight.device)
-        return self._packed[0]
+            setattr(self, slot, (p, keep, arr))
+        if not f32:
+            _lib.ensure_gemm_workspace(self.cross_layers[0].to_q.weight.device)
+        return getattr(self, slot)[0]
 
     def forward(self, q, k, v):
         """q [B,Lq,D], k [B,Lk,D], v [B,Lk,D] -> [B,Lq,D] in q's dtype; 1 <= Lk <= 288 (MAX_KEYS), dim_head = 64.
@@ -867,18 +856,11 @@ class KnowledgeStream:
         qf = q.to(dtype=torch.float32).contiguous()
         ni = nbr_img.to(dtype=torch.float32).contiguous()
         nt = nbr_txt.to(dtype=torch.float32).contiguous()
-        if f32:
-            nbytes = lib.keds_knowledge_f32_workspace_bytes(C.byref(kp), B, K)
-            ws = self._ws.get(nbytes, qf.device)
-            out = torch.empty((B, 3, dim), dtype=torch.float32, device=qf.device)
-            check(lib.keds_knowledge_run_f32(C.byref(kp), ptr(qf), ptr(ni), ptr(nt), B, K, ptr(out), ptr(ws), ws.numel(), stream()),
-                  "keds_knowledge_run_f32")
-            return out
-        nbytes = lib.keds_knowledge_workspace_bytes(C.byref(kp), B, K)
-        ws = self._ws.get(nbytes, qf.device)
+        size, run = (("keds_knowledge_f32_workspace_bytes", "keds_knowledge_run_f32") if f32 else
+                     ("keds_knowledge_workspace_bytes", "keds_knowledge_run"))
+        ws = self._ws.get(getattr(lib, size)(C.byref(kp), B, K), qf.device)
         out = torch.empty((B, 3, dim), dtype=torch.float32, device=qf.device)
-        check(lib.keds_knowledge_run(C.byref(kp), ptr(qf), ptr(ni), ptr(nt), B, K, ptr(out), ptr(ws), ws.numel(),
-                                         stream()), "keds_knowledge_run")
+        check(getattr(lib, run)(C.byref(kp), ptr(qf), ptr(ni), ptr(nt), B, K, ptr(out), ptr(ws), ws.numel(), stream()), run)
         return out
 
 

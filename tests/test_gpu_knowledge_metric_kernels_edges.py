@@ -583,11 +583,49 @@ def test_knowledge_run_equals_its_chain(no_splitk, dim, heads, layers, middle, B
     report(f"knowledge_edges.compose.knowledge_run.d{dim}.B{B}.K{K}", **{"fused_vs_unfused_" + k: v for k, v in d.items()})
 
 
+I2T = [(128, middle, n_layer) for middle in (128, 256) for n_layer in (1, 2, 3)]
+
+
+@pytest.mark.parametrize("dim,middle,n_layer", I2T)
+def test_im2text_forward_equals_its_chain(dim, middle, n_layer):
+    """the cast, n_layer x (Linear, ReLU) through two buffers in turn (at n_layer = 3 the third layer writes the buffer the second one
+    read), the output Linear; rows on both sides of the 128-row padding"""
+    lib = _lib.load()
+    g = kc._gen(7, dim, middle, n_layer)
+    rnd = lambda *s: torch.randn(*s, generator=g)   # noqa: E731
+    dims = [dim] + [middle] * n_layer
+    W = [(rnd(middle, k) / k ** 0.5).to(BF).to(DEV) for k in dims[:-1]] + [(rnd(dim, middle) / middle ** 0.5).to(BF).to(DEV)]
+    bias = [(0.1 * rnd(middle)).to(DEV) for _ in range(n_layer)] + [(0.1 * rnd(dim)).to(DEV)]
+    p = _lib.Im2TextParams()
+    p.dim_in, p.middle, p.dim_out, p.n_layer = dim, middle, dim, n_layer
+    for i in range(n_layer):
+        p.w[i], p.b[i] = W[i].data_ptr(), bias[i].data_ptr()
+    p.out_w, p.out_b = W[-1].data_ptr(), bias[-1].data_ptr()
+    for rows in (1, 129):
+        x = rnd(rows, dim).to(DEV)
+        cur, h = _cast(lib, x, rows, dim), [_pad_rows(rows, middle, BF), _pad_rows(rows, middle, BF)]
+        for i in range(n_layer):
+            _gemm(lib, P(cur), P(W[i]), P(bias[i]), P(h[i & 1]), rows, middle, dims[i], _lib.EPI_BIAS_RELU_BF16)
+            cur = h[i & 1]
+        want = _pad_rows(rows, dim, F32)[:rows]
+        _gemm(lib, P(cur), P(W[-1]), P(bias[-1]), P(want), rows, dim, middle, _lib.EPI_BIAS_F32)
+        torch.cuda.synchronize()
+        assert bool(torch.isfinite(want).all())
+        nbytes = lib.keds_im2text_workspace_bytes(C.byref(p), rows)
+        run = lambda ws, n, out: _done(lib.keds_im2text_forward(C.byref(p), P(x), rows, out, ws, n, _lib.stream()), "keds_im2text_forward")   # noqa: E731
+        assert _same(_twice(run, nbytes, rows, dim), want), f"rows={rows}"
+        assert lib.keds_im2text_forward(C.byref(p), P(x), rows, P(want), P(cur), nbytes - 1, _lib.stream()) == -3
+
+
 def _gemm32(lib, A, lda, W, bias, out, ldc, M, N, K, epi):
     _done(lib.keds_gemm_f32(A, lda, W, bias, out, ldc, M, N, K, epi, None, 0, _lib.stream()), "keds_gemm_f32")
 
 
-@pytest.mark.parametrize("dim,heads,layers,middle,B,K", COMPOSE)
+# keds_knowledge_run_f32 takes up to 64 neighbours (keds_cross_core_f32's own limit), twice what the bf16 entries take
+COMPOSE_F32 = COMPOSE + [(128, 2, 3, 128, 2, 64)]
+
+
+@pytest.mark.parametrize("dim,heads,layers,middle,B,K", COMPOSE_F32)
 def test_knowledge_run_f32_equals_its_chain(dim, heads, layers, middle, B, K):
     lib = _lib.load()
     S = Stream(dim, heads, layers, middle, seed=B * 100 + K)
