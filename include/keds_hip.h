@@ -34,6 +34,8 @@ extern "C" {
                                      GEMM and attention launches are);
                                      (still 15: keds_cross_attn_seq, keds_cross_seq_plan_query, keds_cross_seq_last_launch,
                                      keds_crossformer_seq_workspace_bytes and keds_crossformer_forward_seq were added; no earlier entry changed)
+                                     (still 15: keds_pass_plan_query and keds_text_runs_packed were added; the step record keeps its 24 ints -- [23], always
+                                     0 before, is now the read-out LayerNorm's flag -- and keds_tower_plan_query its 18 buffer rows)
                                      14: keds_attention_f32_packed, keds_attention_x3_packed (the fp32 and split-fp16 attention on packed rows, one call at a
                                      time; the tower passes launch through the same helpers);
                                      13: keds_cross_attn_core, keds_cross_core_f32, keds_knowledge_pack_rows, keds_place_token (the knowledge stream's
@@ -625,7 +627,12 @@ int keds_side_lane_enable(int on);            /* run-time override of KEDS_SIDE_
  * [7] out  [8] first row  [9] row step  [10] rows  [11] out2: the MXFP8 copy written beside out (its scale buffer: the next id)
  * [12] fp32x3: rows of one fp16 plane of in / out  [13] statistics buffer read  [14] added into (statistics cast: written)
  * [15] cleared  [16] their first row  [17] attention: q_limit  [18] rows written as MXFP8  [19] packed rows  [20] gather: rows
- * outside [0, bound) give NaN  [21] global (packed) row indices  [22] lane (0 the caller's stream, 1 the side lane)  [23] 0.
+ * outside [0, bound) give NaN  [21] global (packed) row indices  [22] lane (0 the caller's stream, 1 the side lane)  [23] a LayerNorm
+ * of the read-out rows: 1 when sample b's row is row b * [6] + its read-out column (the device array of keds_text_run_ex).
+ * A whole pass (keds_pass_plan_query) adds the weights 9 conv1 (the patch embedding; its GEMM spreads row i of col to row
+ * i / G * (G + 1) + 1 + i % G of x and adds the positional embedding), 10 ln_pre, 11 ln_post / ln_final, 12 the projection; the ops
+ * KEDS_TOWER_OP_IM2COL ([3]: the output type), _CLS (B rows [9] apart), _EMBED ([10] = B x the columns that run; [19] packed rows)
+ * and _L2NORM ([3] 1: the fp32 flows' kernel); and the buffers KEDS_PASS_BUF_*.
  * KEDS_E_ARG for an unknown flow, bad geometry, or packed rows on an MXFP8 / non-causal tower or without a read-out row. */
 #define KEDS_TOWER_FLOW_UNFOLDED 0   /* stand-alone LayerNorm launches (no folded weights) */
 #define KEDS_TOWER_FLOW_BF16 1
@@ -654,14 +661,54 @@ int keds_side_lane_enable(int on);            /* run-time override of KEDS_SIDE_
 #define KEDS_TOWER_OP_TAP 16         /* a span of the stream written out (keds_vit_run_tokens) */
 #define KEDS_TOWER_OP_FORK 17        /* the side lane waits for the caller's stream */
 #define KEDS_TOWER_OP_JOIN 18        /* the caller's stream waits for the side lane */
+#define KEDS_TOWER_OP_IM2COL 19      /* keds_im2col_ex / keds_im2col_f32 */
+#define KEDS_TOWER_OP_CLS 20         /* keds_cls_rows */
+#define KEDS_TOWER_OP_EMBED 21       /* keds_embed_tokens_ex */
+#define KEDS_TOWER_OP_L2NORM 22      /* keds_l2_normalize in place; the fp32 flows' own rows kernel */
 enum { KEDS_TOWER_BUF_NONE = 0, KEDS_TOWER_BUF_X, KEDS_TOWER_BUF_H, KEDS_TOWER_BUF_QKV, KEDS_TOWER_BUF_ATT, KEDS_TOWER_BUF_HID,
        KEDS_TOWER_BUF_ST1, KEDS_TOWER_BUF_ST2, KEDS_TOWER_BUF_XQ, KEDS_TOWER_BUF_XS, KEDS_TOWER_BUF_AQ, KEDS_TOWER_BUF_AS,
        KEDS_TOWER_BUF_HQ, KEDS_TOWER_BUF_HS, KEDS_TOWER_BUF_SPLITK, KEDS_TOWER_BUF_LN, KEDS_TOWER_BUF_ATT_C, KEDS_TOWER_BUF_X_C,
-       KEDS_TOWER_BUF_COUNT };
+       KEDS_TOWER_BUF_COUNT,
+       /* a whole pass: col, the im2col matrix (an alias: it starts where the tower scratch starts); ro, the LayerNorm of the read-out
+          rows; and the caller's: out [B, embed_dim], the token output of keds_text_run_tokens, the images / token ids */
+       KEDS_PASS_BUF_COL = KEDS_TOWER_BUF_COUNT, KEDS_PASS_BUF_RO, KEDS_PASS_BUF_OUT, KEDS_PASS_BUF_TOK, KEDS_PASS_BUF_SRC,
+       KEDS_PASS_BUF_COUNT };
 #define KEDS_TOWER_STEP_INTS 24
 int keds_tower_plan_query(int flow, int width, int heads, int seq, int causal, int layers, int B, int tail, int packed_rows,
                           int packed_valid, int taps, int split, int lane, int32_t* steps, int max_steps, int* n_steps,
                           int64_t* buffers, size_t* workspace_bytes);
+
+
+/* The same for a WHOLE pass -- front end, blocks, read-out -- of keds_vit_run (KEDS_PASS_VIT), keds_vit_run_tokens with taps or
+ * tokens (_VIT_TOKENS), keds_text_run_ex (_TEXT), keds_text_run_packed (_TEXT_PACKED) and keds_text_run_tokens (_TEXT_TOKENS);
+ * KEDS_PASS_TOWER is keds_tower_plan_query.  The entries themselves run from these steps.  The steps are the record above; buffers:
+ * int64 [KEDS_PASS_BUF_COUNT][4], byte offsets in the PASS workspace (-1: the caller's own buffer); *workspace_bytes:
+ * keds_vit_workspace_bytes / keds_text_workspace_bytes for the shape (for a text kind: of the columns that run). */
+#define KEDS_PASS_TOWER 0
+#define KEDS_PASS_VIT 1
+#define KEDS_PASS_VIT_TOKENS 2
+#define KEDS_PASS_TEXT 3
+#define KEDS_PASS_TEXT_PACKED 4
+#define KEDS_PASS_TEXT_TOKENS 5
+typedef struct {
+    int kind, flow, width, heads, layers, B, causal;
+    int seq;                                   /* tower and ViT kinds: rows per sample; text kinds: derived (the columns that run) */
+    int resolution, patch, kpad, embed_dim;    /* ViT kinds; embed_dim: every kind with a read-out */
+    int context;                               /* text kinds: L */
+    int seq_used;                              /* _TEXT: the host's cut (0: unknown); _TEXT_PACKED: seq_max */
+    int trim;                                  /* keds_text_trim_mode: 0 - 3 */
+    int rows_total;                            /* _TEXT_PACKED */
+    int n_tok, insert_col;                     /* the splice of pseudo tokens (n_tok 0: none) */
+    int cls_only;                              /* keds_tower_params.last_cls_only */
+    int readout;                               /* _VIT_TOKENS: 0 without `out` */
+    int normalize, out_type;
+    int split, lane;                           /* as keds_tower_plan_query's */
+} keds_pass_shape;
+int keds_pass_plan_query(const keds_pass_shape* shape, int32_t* steps, int max_steps, int* n_steps, int64_t* buffers,
+                         size_t* workspace_bytes);
+/* 1 when keds_text_forward_packed runs a batch of B captions with rows_total = sum of (read-out column + 1) and seq_used = the longest
+ * on packed rows: a causal tower that is not the MXFP8 one, trim mode 1, and rows_total * 8 <= B * seq_used * 7.  No GPU needed. */
+int keds_text_runs_packed(int causal, int fp8, int trim, int64_t rows_total, int B, int seq_used);
 
 /* x fp32 [B*seq (padded to 128), width] in place through all residual blocks (model.py:372-373); workspace: rows padded to 256 */
 int keds_tower_forward(const keds_tower_params* p, float* x, int B,

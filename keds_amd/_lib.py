@@ -65,6 +65,13 @@ class TextParams(C.Structure):
                 ("ln_final_g", vp), ("ln_final_b", vp), ("proj_t", vp)]
 
 
+class PassShape(C.Structure):
+    """keds_pass_shape: one whole pass (front end, blocks, read-out) as keds_pass_plan_query takes it."""
+    _fields_ = [(n, i32) for n in ("kind", "flow", "width", "heads", "layers", "B", "causal", "seq", "resolution", "patch", "kpad",
+                                   "embed_dim", "context", "seq_used", "trim", "rows_total", "n_tok", "insert_col", "cls_only",
+                                   "readout", "normalize", "out_type", "split", "lane")]
+
+
 class CrossLayerParams(C.Structure):
     _fields_ = [(n, vp) for n in ("wq", "wk", "wv", "wo", "bq", "bk", "bv", "bo")]
 
@@ -237,6 +244,8 @@ SIGNATURES = {
     "keds_tower_side_rows": (i32, [i32, i32, i32, i32]),
     "keds_side_lane_enable": (i32, [i32]),
     "keds_tower_plan_query": (i32, [i32] * 13 + [vp, i32, C.POINTER(i32), vp, C.POINTER(sz)]),
+    "keds_pass_plan_query": (i32, [C.POINTER(PassShape), vp, i32, C.POINTER(i32), vp, C.POINTER(sz)]),
+    "keds_text_runs_packed": (i32, [i32, i32, i32, i64, i32, i32]),
     "keds_tower_forward": (i32, [C.POINTER(TowerParams), vp, i32, vp, sz, vp]),
     "keds_vit_workspace_bytes": (sz, [C.POINTER(VitParams), i32]),
     "keds_vit_run": (i32, [C.POINTER(VitParams), vp, i32, vp, i32, vp, sz, vp]),

@@ -809,32 +809,17 @@ extern "C" size_t keds_readout_workspace_bytes(int B, int d) {
     return keds_align_up((size_t)B, 128) * d * 2;
 }
 
-// f16: the "fp16" operating point -- LayerNorm output and proj_t fp16
-int keds_readout_impl(const float* x, int S, const int32_t* row, const float* gamma, const float* beta,
-                      const void* proj_t, float* out, int B, int d, int E, int normalize, void* workspace,
-                      size_t workspace_bytes, void* stream, bool f16) {
+// the read-out steps themselves: tower_plan.h (readout_plan) says what they are, towers.hip runs them
+extern "C" int keds_readout(const float* x, int S, const int32_t* row, const float* gamma, const float* beta,
+                            const void* proj_t, float* out, int B, int d, int E, int normalize, void* workspace,
+                            size_t workspace_bytes, void* stream) {
     KEDS_REQUIRE(x && gamma && beta && proj_t && out && workspace && B > 0, "keds_readout: bad argument");
     KEDS_REQUIRE(ln_dim_ok(d), "keds_readout: d %d unsupported", d);
     if (workspace_bytes < keds_readout_workspace_bytes(B, d)) {
         keds_set_error("keds_readout: workspace too small");
         return KEDS_E_WORKSPACE;
     }
-    hipStream_t st = (hipStream_t)stream;
-    int rc = keds_layernorm_impl(x, d, row, S, gamma, beta, workspace, f16 ? 2 : 0, B, d, st);
-    if (rc) return rc;
-    rc = keds_gemm_bt(workspace, proj_t, nullptr, out, B, E, d, f16 ? KEDS_EPI_BIAS_F32_H : KEDS_EPI_BIAS_F32, nullptr, 0, stream);
-    if (rc) return rc;
-    if (normalize) {
-        l2norm_kernel<<<(B + 3) / 4, 256, 0, st>>>(out, out, B, E);
-        rc = keds_check_launch("l2norm_kernel");
-    }
-    return rc;
-}
-
-extern "C" int keds_readout(const float* x, int S, const int32_t* row, const float* gamma, const float* beta,
-                            const void* proj_t, float* out, int B, int d, int E, int normalize, void* workspace,
-                            size_t workspace_bytes, void* stream) {
-    return keds_readout_impl(x, S, row, gamma, beta, proj_t, out, B, d, E, normalize, workspace, workspace_bytes, stream, false);
+    return keds_run_readout(x, S, row, gamma, beta, proj_t, out, B, d, E, normalize, workspace, (hipStream_t)stream);
 }
 
 extern "C" int keds_l2_normalize(const float* x, float* out, int rows, int dim, void* stream) {

@@ -337,20 +337,10 @@ extern "C" int keds_im2col_f32(const float* image, float* out, int B, int R, int
     return keds_check_launch("im2col_f32_kernel");
 }
 
-// ---- read-out (the tower passes themselves: tower_plan.h says what they launch, towers.hip runs it) -----------------------------
-// ln_post / ln_final on the read-out rows + projection (+ L2 normalisation), fp32 (model.py:412-414, 586-589, 841-849)
-size_t keds_readout_f32_workspace_bytes(int B, int d) { return keds_align_up((size_t)B, 128) * d * 4; }
-
-int keds_readout_f32(const float* x, int S, const int32_t* row, const float* gamma, const float* beta, const float* proj_t,
-                     float* out, int B, int d, int E, int normalize, void* workspace, hipStream_t st) {
-    int rc = keds_layernorm_impl(x, d, row, S, gamma, beta, workspace, 1, B, d, st);
-    if (rc) return rc;
-    if ((rc = keds_gemm_f32((const float*)workspace, d, proj_t, nullptr, out, E, B, E, d, F32_EPI_BIAS, nullptr, 0, st))) return rc;
-    if (normalize) {
-        l2norm_rows_f32_kernel<<<(B + 3) / 4, 256, 0, st>>>(out, B, E);
-        rc = keds_check_launch("l2norm_rows_f32_kernel");
-    }
-    return rc;
+// ---- read-out (tower_plan.h says what the passes launch, towers.hip runs it): the L2 normalisation of the fp32 flows, in place
+int keds_l2norm_rows_f32_impl(float* x, int rows, int dim, hipStream_t st) {
+    l2norm_rows_f32_kernel<<<(rows + 3) / 4, 256, 0, st>>>(x, rows, dim);
+    return keds_check_launch("l2norm_rows_f32_kernel");
 }
 
 // ---- knowledge injection in fp32 (IM2TEXT + 2 x CrossFormer, model.py:37-123, eval_utils.py:661-672): the core; the host chain

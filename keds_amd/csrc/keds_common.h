@@ -188,17 +188,16 @@ int keds_gather_rows_impl(const void* src, void* dst, const int32_t* row, int S,
 int keds_embed_tokens_impl(const int32_t* tokens, const float* table, const float* pos, const float* img_tokens,
                            int n_tok, int insert_col, float* x, int B, int L, int Lx, int d, void* stream,
                            const int32_t* seq_off = nullptr);
-int keds_readout_impl(const float* x, int S, const int32_t* row, const float* gamma, const float* beta, const void* proj_t,
-                      float* out, int B, int d, int E, int normalize, void* workspace, size_t workspace_bytes, void* stream, bool f16);
-// f32path.hip / attention_x3.hip: the attention and the read-out of the fp32-accurate flows (keds_tower_params.f32; seq_off: packed
-// rows or null), and the launch of the fp32 single-query cross-attention core (knowledge.hip's fp32 stream)
+// towers.hip: keds_readout's steps, run by the executor of the passes
+int keds_run_readout(const float* x, int S, const int32_t* row, const float* gamma, const float* beta, const void* proj_t, float* out,
+                     int B, int d, int E, int normalize, void* workspace, hipStream_t st);
+// f32path.hip / attention_x3.hip: the attention and the read-out's L2 normalisation of the fp32-accurate flows (keds_tower_params.f32;
+// seq_off: packed rows or null), and the launch of the fp32 single-query cross-attention core (knowledge.hip's fp32 stream)
 int attention_f32_impl(const float* qkv, float* out, int B, int S, int heads, int causal, int q_limit, const int32_t* seq_off,
                        void* stream);
 int keds_attention_x3_impl(const float* qkv, float* out, void* pair, int64_t plane, int B, int S, int heads, int causal, int q_limit,
                            int* overflow, const int32_t* seq_off, void* stream);
-size_t keds_readout_f32_workspace_bytes(int B, int d);
-int keds_readout_f32(const float* x, int S, const int32_t* row, const float* gamma, const float* beta, const float* proj_t,
-                     float* out, int B, int d, int E, int normalize, void* workspace, hipStream_t st);
+int keds_l2norm_rows_f32_impl(float* x, int rows, int dim, hipStream_t st);
 int keds_cross_core_f32_impl(const float* Q, const float* Kp, const float* Vp, float* out, int B, int K, int heads, hipStream_t st);
 
 // ---- numerics guard (host): device int32 flag of the calling thread's current composite call, or nullptr -----------

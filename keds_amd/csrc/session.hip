@@ -3,6 +3,7 @@
 // keds_hip.h, so results are bit-identical to the torch-hosted path.  Architecture inference
 // follows build_model (src/model/model.py:951-991): everything is read off the tensor shapes.
 #include "keds_common.h"
+#include "tower_plan.h"      // text_runs_packed
 #include "../../include/keds_session.h"
 #include <dlfcn.h>
 #include <cmath>
@@ -613,8 +614,7 @@ extern "C" int keds_text_forward_packed(keds_text* txt, const int32_t* tokens, c
     // (pageable source: the copy has left `host` when the call returns)
     HIP_TRY(hipMemcpyAsync(txt->tok.p, host.data(), host.size() * sizeof(int32_t), hipMemcpyHostToDevice, st), what);
     const int32_t* dev = (const int32_t*)txt->tok.p;
-    const bool packed = txt->p.tower.causal && !txt->p.tower.fp8 && keds_text_trim_mode() == 1 &&
-                        rows * 8 <= (long long)B * seq_used * 7;
+    const bool packed = text_runs_packed(txt->p.tower.causal != 0, txt->p.tower.fp8 != 0, keds_text_trim_mode(), rows, B, seq_used);
     KEDS_REQUIRE((img_tokens == nullptr) == (n_img_tok == 0), "%s: img_tokens and n_img_tok disagree", what);
     KEDS_REQUIRE(n_img_tok == 0 || n_img_tok == 2 || n_img_tok == 3, "%s: 2 or 3 pseudo tokens (model.py:831-834)", what);
     KEDS_REQUIRE(n_img_tok == 0 || (insert_idx >= 0 && insert_idx + n_img_tok <= L), "%s: insert_idx out of range", what);

@@ -1,8 +1,11 @@
-// What a tower pass launches (keds_tower_forward, keds_vit_run*, keds_text_run*): the one place that says.  Host C++ without a HIP
-// header, a device call or a getenv, exactly as gemm_plan.h and attention_plan.h are.  tower_layout() names the buffers of one tower's
-// scratch, tower_plan() emits the ordered steps of a pass, the executor of towers.hip runs them one by one, keds_tower_plan_query
-// (keds_hip.h) answers from both without a GPU, and tests/test_host_tower_plan.py holds the steps to tests/tower_check.py's plan(),
-// pins the enqueue order and checks that no two steps that share rows of a buffer are left unordered.
+// What a tower pass launches (keds_tower_forward, keds_vit_run*, keds_text_run*, keds_readout): the one place that says.  Host C++
+// without a HIP header, a device call or a getenv, exactly as gemm_plan.h and attention_plan.h are.  tower_layout() names the buffers
+// of one tower's scratch and tower_plan() emits the ordered steps of its blocks; pass_layout() and pass_plan() do the same for a WHOLE
+// pass: the front end (ViT: im2col, patch GEMM, CLS rows, ln_pre; text: the embedding) in front of the blocks and the read-out
+// (LayerNorm of the read-out rows, projection, L2 normalisation) behind them.  The executor of towers.hip runs the steps one by one,
+// keds_pass_plan_query / keds_tower_plan_query (keds_hip.h) answer from the same functions without a GPU, and
+// tests/test_host_tower_plan.py holds the steps to tests/tower_check.py's plan() / plan_pass(), pins the enqueue order and checks that
+// no two steps that share rows (or, through an alias, bytes) of a buffer are left unordered.
 //
 // The per-flow table of a pass -- which kernel, on which rows, reading and writing what, on which lane -- is read off tower_plan():
 //   unfolded  stand-alone LayerNorm launches and plain bias epilogues, fp32 residual stream in x (KEDS_DETERMINISTIC / no folded weights)
@@ -70,7 +73,10 @@ enum {
     TB_ATT = KEDS_TOWER_BUF_ATT, TB_HID = KEDS_TOWER_BUF_HID, TB_ST1 = KEDS_TOWER_BUF_ST1, TB_ST2 = KEDS_TOWER_BUF_ST2,
     TB_XQ = KEDS_TOWER_BUF_XQ, TB_XS = KEDS_TOWER_BUF_XS, TB_AQ = KEDS_TOWER_BUF_AQ, TB_AS = KEDS_TOWER_BUF_AS,
     TB_HQ = KEDS_TOWER_BUF_HQ, TB_HS = KEDS_TOWER_BUF_HS, TB_SPLITK = KEDS_TOWER_BUF_SPLITK, TB_LN = KEDS_TOWER_BUF_LN,
-    TB_ATT_C = KEDS_TOWER_BUF_ATT_C, TB_X_C = KEDS_TOWER_BUF_X_C, TB_N = KEDS_TOWER_BUF_COUNT
+    TB_ATT_C = KEDS_TOWER_BUF_ATT_C, TB_X_C = KEDS_TOWER_BUF_X_C, TB_N = KEDS_TOWER_BUF_COUNT,
+    // a whole pass: the im2col matrix, the read-out rows, and the caller's embeddings / token output / images or token ids
+    TB_COL = KEDS_PASS_BUF_COL, TB_RO = KEDS_PASS_BUF_RO, TB_OUT = KEDS_PASS_BUF_OUT, TB_TOK = KEDS_PASS_BUF_TOK, TB_SRC = KEDS_PASS_BUF_SRC,
+    PB_N = KEDS_PASS_BUF_COUNT
 };
 constexpr size_t TOWER_SPLITK_BYTES = (size_t)8 << 20;      // (keds_common.h, KEDS_SPLITK_BYTES)
 
@@ -89,9 +95,10 @@ struct TowerBuf {
     size_t off = 0, bytes = 0;      // bytes 0: the flow has no such buffer
     int cols = 0, esize = 0;        // a row is cols elements of esize bytes (planes: of ONE plane)
     int alias_of = TB_NONE;
+    bool caller = false;            // the caller's own buffer, outside the workspace (off means nothing)
 };
 struct TowerLayout {
-    TowerBuf b[TB_N];
+    TowerBuf b[PB_N];               // (ids >= TB_N: a whole pass, pass_layout())
     size_t total = 0;
 };
 
@@ -110,6 +117,7 @@ inline TowerLayout tower_layout(int flow, int width, int seq, int B) {
     L.b[TB_X].bytes = Mp * w * 4;
     L.b[TB_X].cols = width;
     L.b[TB_X].esize = 4;
+    L.b[TB_X].caller = true;
     const bool f32 = tower_flow_f32(flow), pair = flow == KEDS_TOWER_FLOW_X3;
     if (f32) {
         take(TB_LN, Mp, w, pair ? 2 : 4, w * 4);
@@ -132,8 +140,8 @@ inline TowerLayout tower_layout(int flow, int width, int seq, int B) {
         take(TB_SPLITK, 1, TOWER_SPLITK_BYTES, 1, TOWER_SPLITK_BYTES);
     }
     const int ea = f32 ? 4 : 2;                                      // [B, w] of the attention output's type (2 w bytes per row: a multiple of 256)
-    L.b[TB_ATT_C] = TowerBuf{L.b[TB_QKV].off, (size_t)B * w * ea, width, ea, TB_QKV};
-    L.b[TB_X_C] = TowerBuf{L.b[TB_QKV].off + (size_t)B * w * ea, (size_t)B * w * 4, width, 4, TB_QKV};
+    L.b[TB_ATT_C] = TowerBuf{L.b[TB_QKV].off, (size_t)B * w * ea, width, ea, TB_QKV, false};
+    L.b[TB_X_C] = TowerBuf{L.b[TB_QKV].off + (size_t)B * w * ea, (size_t)B * w * 4, width, 4, TB_QKV, false};
     return L;
 }
 
@@ -178,10 +186,12 @@ inline bool tower_splits_rows(int flow, int M, int w) {
 }
 
 // ---- the steps -----------------------------------------------------------------------------------------------------------------
-enum { TW_NONE = 0, TW_QKV, TW_OUT, TW_FC, TW_PROJ, TW_QKV_FOLDED, TW_FC_FOLDED, TW_LN1, TW_LN2 };
+enum { TW_NONE = 0, TW_QKV, TW_OUT, TW_FC, TW_PROJ, TW_QKV_FOLDED, TW_FC_FOLDED, TW_LN1, TW_LN2,
+       TW_CONV, TW_LN_PRE, TW_LN_OUT, TW_PROJ_T };      // a whole pass: patch embedding, ln_pre, ln_post / ln_final, the projection
 enum { TAIL_ALL = KEDS_TOWER_TAIL_ALL, TAIL_CLS = KEDS_TOWER_TAIL_CLS, TAIL_READOUT = KEDS_TOWER_TAIL_READOUT };
 
-// One launch (or stream operation) of a pass; the int32 record of keds_tower_plan_query in this order (keds_hip.h documents it)
+// One launch (or stream operation) of a pass; the int32 record of keds_pass_plan_query / keds_tower_plan_query in this order (keds_hip.h
+// documents it)
 struct TowerStep {
     int op = 0, layer = -1, weight = TW_NONE, epi = 0;
     int in = TB_NONE, in_r0 = 0, in_step = 1;
@@ -193,7 +203,7 @@ struct TowerStep {
     int q_limit = 0, q8_rows = 0, packed = 0;
     int bound = 0, global = 0;      // gather: rows outside [0, bound) come out as NaN; global (packed) or per-sample row indices
     int lane = 0;                   // 0: the caller's stream, 1: the side lane
-    int reserved = 0;
+    int rows = 0;                   // LayerNorm of the read-out: sample b's row is in_r0 + b * in_step + its read-out column (device)
 };
 static_assert(sizeof(TowerStep) == KEDS_TOWER_STEP_INTS * sizeof(int), "the record of keds_tower_plan_query");
 
@@ -219,9 +229,9 @@ inline const char* tower_plan_check(const TowerPlanArgs& a) {
 }
 
 // emit(const TowerStep&) -> bool (false: stop).  Returns false when emit stopped the plan.  The order of the steps is the enqueue
-// order of the pass.
-template <typename Emit>
-inline bool tower_plan(const TowerPlanArgs& a, Emit&& emit) {
+// order of the pass.  front(): pass_plan()'s steps that fill x, behind the clearing of the packed zero rows of x.
+template <typename Emit, typename Front>
+inline bool tower_plan(const TowerPlanArgs& a, Emit&& emit, Front&& front) {
     const int S = a.seq, B = a.B;
     const int M = a.packed_rows ? a.packed_rows : B * S, Mm = M / 256 * 256;
     const int Mp = (int)tower_pad_rows((size_t)B * S), Bp = (int)tower_pad_rows((size_t)B);
@@ -341,18 +351,18 @@ inline bool tower_plan(const TowerPlanArgs& a, Emit&& emit) {
         put(s);
     };
 
-    // packed rows: the zero rows up to the next 256-row tile belong to no sample.  Their x rows are cleared (the pass entry embeds
+    // packed rows: the zero rows up to the next 256-row tile belong to no sample.  Their x rows are cleared (the embedding goes
     // behind that), and they are nobody's queries -- their attention output is cleared once so that they stay finite through the blocks
     // (x3: the out-projection reads ln_1's output there, which is finite)
-    if (packed && M > a.packed_valid) {
-        for (const int buf : {TB_X, TB_ATT}) {
-            if (buf == TB_ATT && x3) continue;
-            TowerStep s;
-            s.op = KEDS_TOWER_OP_ZERO;
-            s.out = buf, s.out_r0 = a.packed_valid, s.n = M - a.packed_valid;
-            put(s);
-        }
-    }
+    auto zero_rows = [&](int buf) {
+        TowerStep s;
+        s.op = KEDS_TOWER_OP_ZERO;
+        s.out = buf, s.out_r0 = a.packed_valid, s.n = M - a.packed_valid;
+        put(s);
+    };
+    if (packed && M > a.packed_valid) zero_rows(TB_X);
+    front();
+    if (packed && M > a.packed_valid && !x3) zero_rows(TB_ATT);
     if (folded) {      // h = the fp16 copy of the stream, st1 = its row statistics; fp8: the MXFP8 copy of the full-tile rows
         TowerStep s;
         s.op = KEDS_TOWER_OP_STATS_CAST, s.epi = 1;
@@ -434,6 +444,202 @@ inline bool tower_plan(const TowerPlanArgs& a, Emit&& emit) {
     gemm(l, TW_PROJ, TB_HID, 0, 1, xa, 0, xs, B, 0, Bp);
     // the caller reads row b of a compact x (read-out rows) or row b * S (x3: CLS rows back in place)
     if (compact) rows_op(KEDS_TOWER_OP_COPY, x3 ? 1 : 0, TB_X_C, 1, TB_X, a.tail == TAIL_READOUT ? 1 : S, B);
+    return go;
+}
+template <typename Emit>
+inline bool tower_plan(const TowerPlanArgs& a, Emit&& emit) {
+    return tower_plan(a, emit, [] {});
+}
+
+// ---- a whole pass --------------------------------------------------------------------------------------------------------------
+// When a text batch whose captions end at different columns runs on packed rows (keds_text_run_packed: rows_total = the sum of the
+// captions' lengths) instead of B x seq_used rectangular ones: a causal tower that is not the MXFP8 one, on the default trim mode,
+// and at least an eighth of the rows saved.
+inline bool text_runs_packed(bool causal, bool fp8, int trim, long long rows_total, int B, int seq_used) {
+    return causal && !fp8 && trim == 1 && rows_total * 8 <= (long long)B * seq_used * 7;
+}
+
+// ln_post / ln_final of one row per sample (row b * in_step, + the sample's read-out column with `rows`) into ro, the projection into
+// out, L2 normalisation in place.  type: keds_layernorm_ex's output type of the flow (0 bf16, 1 fp32, 2 fp16).  The fp32 flows
+// normalise with the fp32 rows kernel, the 16-bit flows with keds_l2_normalize's.
+template <typename Put>
+inline void readout_plan(int type, int B, int in_step, bool rows, bool normalize, Put&& put) {
+    TowerStep ln;
+    ln.op = KEDS_TOWER_OP_LN, ln.weight = TW_LN_OUT, ln.epi = type;
+    ln.in = TB_X, ln.in_step = in_step, ln.rows = rows, ln.out = TB_RO, ln.n = B;
+    put(ln);
+    TowerStep g;
+    g.op = type == 1 ? KEDS_TOWER_OP_GEMM_F32 : KEDS_TOWER_OP_GEMM16, g.weight = TW_PROJ_T;
+    g.epi = type == 1 ? KEDS_F32_EPI_BIAS : type == 2 ? KEDS_EPI_BIAS_F32_H : KEDS_EPI_BIAS_F32;
+    g.in = TB_RO, g.out = TB_OUT, g.n = B;
+    put(g);
+    if (!normalize) return;
+    TowerStep l2;
+    l2.op = KEDS_TOWER_OP_L2NORM, l2.epi = type == 1;
+    l2.in = l2.out = TB_OUT, l2.n = B;
+    put(l2);
+}
+
+struct PassArgs {
+    int kind;                       // KEDS_PASS_*
+    TowerPlanArgs t;                // the blocks: seq = the columns that run (text), tail and packed rows as the kind and trim mode say
+    int resolution, patch, kpad, embed_dim;
+    int context;                    // text: L, the columns of a token row (t.seq <= L run)
+    int n_tok, insert_col;          // text: the splice of pseudo tokens (n_tok 0: none)
+    int trim;                       // text: keds_text_trim_enable's mode 0 - 3
+    int normalize, out_type;        // out_type: the token output of text_tokens (keds_layernorm_ex)
+    bool readout;                   // vit_tokens without `out`: no read-out
+};
+
+// keds_pass_shape (keds_hip.h) -> PassArgs: which columns run, what the tail is, how many packed rows.  t.split / t.lane as given
+// (> 0); the caller resolves -1.
+inline PassArgs pass_args(const keds_pass_shape& q) {
+    PassArgs a{};
+    a.kind = q.kind;
+    a.resolution = q.resolution, a.patch = q.patch, a.kpad = q.kpad, a.embed_dim = q.embed_dim;
+    a.context = q.context, a.n_tok = q.n_tok, a.insert_col = q.insert_col, a.trim = q.trim;
+    a.normalize = q.normalize, a.out_type = q.out_type, a.readout = q.readout != 0;
+    TowerPlanArgs& t = a.t;
+    t = TowerPlanArgs{q.flow, q.width, q.heads, q.seq, q.causal != 0, q.layers, q.B, q.cls_only ? TAIL_CLS : TAIL_ALL, 0, 0, false,
+                      q.split > 0, q.lane > 0};
+    const int L = q.context;
+    switch (q.kind) {
+        case KEDS_PASS_VIT_TOKENS:      // the last block on every row; the CLS read-out comes from the full stream
+            t.tail = TAIL_ALL, t.taps = true;
+            break;
+        case KEDS_PASS_TEXT: {
+            // (no rounding of the cut to whole row tiles: measured at B = 128 -- tools/text_shapes.py, profiles/r05_text_shapes.txt --
+            // the four GEMMs of a block take 161 us at 43 columns, 170 at 44, 172-174 at 46-48: at these sizes the 128 x 128 kernel's
+            // rounds of 512 workgroups decide, and fewer rows are never slower)
+            const bool cut = q.trim == 1 || q.trim == 2, trim = q.trim == 1 || q.trim == 3;
+            t.seq = cut && q.seq_used > 0 && q.seq_used < L && q.causal ? q.seq_used : L;
+            if (trim) t.tail = TAIL_READOUT;
+            a.readout = true;
+            break;
+        }
+        case KEDS_PASS_TEXT_PACKED:
+            // the tower runs WHOLE 256-row tiles: the rows between rows_total and the next multiple of 256 are zero rows that belong to
+            // no sample (no attention reads them, nothing gathers them; the pass clears them in front of the embedding).  A ragged
+            // last tile would send every GEMM of every block through the remainder-row launches and the stricter fill rule of the
+            // 256 x 256 kernels (gemm_plan.h, gemm_big_tiles_fill).
+            t.seq = q.seq_used, t.tail = TAIL_READOUT;
+            t.packed_valid = q.rows_total, t.packed_rows = (q.rows_total + 255) / 256 * 256;
+            if ((size_t)t.packed_rows > tower_pad_rows((size_t)q.B * t.seq)) t.packed_rows = q.rows_total;
+            a.readout = true;
+            break;
+        case KEDS_PASS_TEXT_TOKENS:     // every column is an output: no cut, no read-out-row tail
+            t.seq = L, t.tail = TAIL_ALL;
+            break;
+    }
+    return a;
+}
+inline bool pass_is_vit(int kind) { return kind == KEDS_PASS_VIT || kind == KEDS_PASS_VIT_TOKENS; }
+inline bool pass_is_text(int kind) { return kind >= KEDS_PASS_TEXT && kind <= KEDS_PASS_TEXT_TOKENS; }
+// the rows of a pass's blocks; whether the library's own rule gives them a remainder span (keds_tower_side_rows)
+inline int pass_rows(const TowerPlanArgs& t) { return t.packed_rows ? t.packed_rows : t.B * t.seq; }
+inline bool pass_splits_rows(const TowerPlanArgs& t) {
+    const int M = pass_rows(t);
+    return tower_splits_rows(t.flow == KEDS_TOWER_FLOW_FP8 && M < 256 ? KEDS_TOWER_FLOW_BF16 : t.flow, M, t.width);
+}
+
+inline const char* pass_plan_check(const PassArgs& a) {
+    if (a.kind < KEDS_PASS_TOWER || a.kind > KEDS_PASS_TEXT_TOKENS) return "keds_pass_plan_query: unknown kind";
+    if (pass_is_vit(a.kind)) {
+        const int g = a.patch > 0 ? a.resolution / a.patch : 0;
+        if (a.patch <= 0 || a.resolution % a.patch != 0 || g * g + 1 != a.t.seq) return "keds_pass_plan_query: seq must be (res/patch)^2 + 1";
+        if (a.kpad % 64 != 0 || a.kpad < 3 * a.patch * a.patch) return "keds_pass_plan_query: bad kpad";
+    }
+    if (pass_is_text(a.kind)) {
+        if (a.t.seq < 1 || a.t.seq > a.context || a.trim < 0 || a.trim > 3) return "keds_pass_plan_query: columns outside the context, or a trim mode outside 0 - 3";
+        if (a.n_tok && (a.insert_col < 0 || a.insert_col + a.n_tok > a.context)) return "keds_pass_plan_query: splice outside the context";
+        if (a.kind == KEDS_PASS_TEXT_PACKED &&
+            (a.t.packed_valid < a.t.B || (long long)a.t.packed_valid > (long long)a.t.B * a.t.seq || a.trim != 1))
+            return "keds_pass_plan_query: packed rows do not fit B sequences, or a trim mode other than 1";
+    }
+    if (a.readout && a.kind != KEDS_PASS_TOWER && a.embed_dim % 128 != 0) return "keds_pass_plan_query: embed_dim must be a multiple of 128";
+    if (a.out_type < 0 || a.out_type > 2) return "keds_pass_plan_query: out_type outside 0 - 2";
+    return tower_plan_check(a.t);
+}
+
+// The workspace of a pass, every buffer on a 256-byte boundary:
+//   x [Mp, w] fp32 | the tower scratch (tower_layout) | ro: the LayerNorm of the read-out rows, [B up to 128, w] of the flow's type
+// ViT: col, the im2col matrix [B (S - 1) up to 256, kpad] of the flow's type, is a declared alias: it starts where the tower scratch
+// starts and runs over as many of its buffers as it needs -- it is dead behind the patch GEMM, in front of the first step of the
+// blocks -- and the scratch is at least as large as col.  out / the token output / the images or token ids are the caller's, as x is
+// for the kind "tower", whose layout is tower_layout().
+inline TowerLayout pass_layout(const PassArgs& a) {
+    const TowerPlanArgs& t = a.t;
+    TowerLayout L = tower_layout(t.flow, t.width, t.seq, t.B);
+    if (a.kind == KEDS_PASS_TOWER) return L;
+    const bool f32 = tower_flow_f32(t.flow);
+    const int e = f32 ? 4 : 2;
+    const size_t w = (size_t)t.width, xb = tower_align(L.b[TB_X].bytes, 256);
+    for (int id = TB_H; id < TB_N; ++id) L.b[id].off += xb;
+    L.b[TB_X].caller = false;
+    size_t tb = L.total;
+    if (pass_is_vit(a.kind)) {
+        L.b[TB_COL] = TowerBuf{xb, tower_pad_rows((size_t)t.B * (t.seq - 1)) * a.kpad * e, a.kpad, e, f32 ? TB_LN : TB_H, false};
+        if (tower_align(L.b[TB_COL].bytes, 256) > tb) tb = tower_align(L.b[TB_COL].bytes, 256);
+        L.b[TB_SRC] = TowerBuf{0, (size_t)t.B * 3 * a.resolution * a.resolution * 4, 3 * a.resolution * a.resolution, 4, TB_NONE, true};
+    } else {
+        L.b[TB_SRC] = TowerBuf{0, (size_t)t.B * a.context * 4, a.context, 4, TB_NONE, true};
+    }
+    L.b[TB_RO] = TowerBuf{xb + tb, tower_align((size_t)t.B, 128) * w * e, t.width, e, TB_NONE, false};
+    L.total = xb + tb + tower_align(L.b[TB_RO].bytes, 256);
+    if (a.kind == KEDS_PASS_TEXT_TOKENS) {
+        const int eo = a.out_type == 1 ? 4 : 2;
+        L.b[TB_TOK] = TowerBuf{0, (size_t)t.B * t.seq * w * eo, t.width, eo, TB_NONE, true};
+    } else if (a.readout) {
+        L.b[TB_OUT] = TowerBuf{0, (size_t)t.B * a.embed_dim * 4, a.embed_dim, 4, TB_NONE, true};
+    }
+    return L;
+}
+
+// The steps of a whole pass in enqueue order: the front end, exactly tower_plan()'s steps, the read-out.
+template <typename Emit>
+inline bool pass_plan(const PassArgs& a, Emit&& emit) {
+    const TowerPlanArgs& t = a.t;
+    const int S = t.seq, B = t.B;
+    const bool f32 = tower_flow_f32(t.flow);
+    const int type = f32 ? 1 : t.flow == KEDS_TOWER_FLOW_FP16 ? 2 : 0;      // keds_layernorm_ex's output type of the flow's operands
+    bool go = true;
+    auto put = [&](const TowerStep& s) { go = go && emit(s); };
+    if (pass_is_vit(a.kind)) {
+        TowerStep c;
+        c.op = KEDS_TOWER_OP_IM2COL, c.epi = type;
+        c.in = TB_SRC, c.out = TB_COL, c.n = B * (S - 1);
+        put(c);
+        TowerStep g;                    // patch rows + positional embedding: row i of col is row i / (S - 1) * S + 1 + i % (S - 1) of x
+        g.op = f32 ? KEDS_TOWER_OP_GEMM_F32 : KEDS_TOWER_OP_GEMM16, g.weight = TW_CONV;
+        g.epi = f32 ? KEDS_F32_EPI_PATCH : type == 2 ? KEDS_EPI_PATCH_F32_H : KEDS_EPI_PATCH_F32;
+        g.in = TB_COL, g.out = TB_X, g.n = B * (S - 1);
+        put(g);
+        TowerStep k;
+        k.op = KEDS_TOWER_OP_CLS;
+        k.out = TB_X, k.out_step = S, k.n = B;
+        put(k);
+        TowerStep ln;                   // ln_pre in place (each wave holds its whole row in registers before it stores)
+        ln.op = KEDS_TOWER_OP_LN, ln.weight = TW_LN_PRE, ln.epi = 1;
+        ln.in = ln.out = TB_X, ln.n = B * S;
+        put(ln);
+    }
+    go = go && tower_plan(t, [&](const TowerStep& s) { put(s); return go; }, [&] {
+        if (!pass_is_text(a.kind)) return;
+        TowerStep e;                    // the first S columns of every token row (packed: of sample b, its own rows' worth)
+        e.op = KEDS_TOWER_OP_EMBED;
+        e.in = TB_SRC, e.out = TB_X, e.n = B * S, e.packed = t.packed_rows != 0;
+        put(e);
+    });
+    if (a.kind == KEDS_PASS_TEXT_TOKENS) {
+        TowerStep ln;                   // ln_final over all rows, as out_type
+        ln.op = KEDS_TOWER_OP_LN, ln.weight = TW_LN_OUT, ln.epi = a.out_type;
+        ln.in = TB_X, ln.out = TB_TOK, ln.n = B * S;
+        put(ln);
+    } else if (a.readout && a.kind != KEDS_PASS_TOWER) {
+        // behind a read-out-row tail row b of x is sample b's; else the CLS row, or the read-out column of the sample's S rows
+        const bool compact = t.tail == TAIL_READOUT;
+        readout_plan(type, B, compact ? 1 : S, pass_is_text(a.kind) && !compact, a.normalize != 0, put);
+    }
     return go;
 }
 

@@ -186,6 +186,12 @@ TEXT_PACKED = True          # the text tower on packed rows when captions end at
 GUARD_EAGER_PASSES = 8      # numerics = "auto": tower passes whose guard flag is read back at once (see CLIP.__init__)
 
 
+def x3_chunk(width, rows_per_sample):
+    """samples per call of an "fp32x3" tower pass: the split-operand GEMMs address their planes with 32-bit byte offsets
+    (keds_gemm_x3), so the MLP hidden planes of one call -- rows * 4 * width * 2 bytes -- stay below 2 GiB, less a margin of 512 rows"""
+    return max(1, ((1 << 31) // (8 * width) - 512) // rows_per_sample)
+
+
 class CLIP(nn.Module):
     def __init__(self, embed_dim: int, image_resolution: int, vision_layers: Union[Tuple[int, int, int, int], int],
                  vision_width: int, vision_patch_size: int, context_length: int, vocab_size: int,
@@ -463,8 +469,7 @@ class CLIP(nn.Module):
         if self.precision == "fp32x3":
             # the split-operand GEMMs address their planes with 32-bit byte offsets (keds_gemm_x3): the MLP hidden planes of one call
             # must stay below 2 GiB -- rows * 4 * width * 2 bytes.  Larger batches run in chunks (rows are independent between samples).
-            rows_max = (1 << 31) // (8 * self.visual.transformer.width) - 512
-            chunk = max(1, rows_max // ((self.visual.input_resolution // self.visual.conv1.kernel_size[0]) ** 2 + 1))
+            chunk = x3_chunk(self.visual.transformer.width, (self.visual.input_resolution // self.visual.conv1.kernel_size[0]) ** 2 + 1)
             if B > chunk:
                 parts = [self._image_pass(img[i:i + chunk], normalize, mode) for i in range(0, B, chunk)]
                 if mode == "mid":
@@ -532,14 +537,14 @@ class CLIP(nn.Module):
         # (keds_text_run_packed, round 6) -- sum(len_b) rows instead of B * max(len_b).  Worth it from an eighth fewer rows; the
         # MXFP8 tower and KEDS_TEXT_TRIM=0 keep the rectangular layout.
         if self.precision == "fp32x3":                       # (see encode_image: the planes of one call stay below 2 GiB)
-            chunk = max(1, ((1 << 31) // (8 * self.transformer.width) - 512) // self.context_length)
+            chunk = x3_chunk(self.transformer.width, self.context_length)
             if B > chunk:
                 return torch.cat([self._run_text(text[i:i + chunk], readout[i:i + chunk], None if img_tokens is None else img_tokens[i:i + chunk],
                                                  insert_col, normalize) for i in range(0, B, chunk)])
         lens = readout.to(torch.int64).cpu() + 1
         rows_total = int(lens.sum())
         packed = None
-        if self.precision != "fp8" and TEXT_PACKED and lib.keds_text_trim_mode() == 1 and rows_total * 8 <= B * seq_used * 7:
+        if TEXT_PACKED and lib.keds_text_runs_packed(1, int(self.precision == "fp8"), lib.keds_text_trim_mode(), rows_total, B, seq_used):
             off = torch.zeros(B + 1, dtype=torch.int64)
             off[1:] = torch.cumsum(lens, 0)
             both = torch.cat([off, off[:-1] + readout.to(torch.int64).cpu()]).to(torch.int32)
@@ -640,7 +645,7 @@ class CLIP(nn.Module):
     def _text_tokens(self, text, eng):
         B, L, W = text.shape[0], self.context_length, self.transformer_width
         if self.precision == "fp32x3":                       # (see encode_image: the planes of one call stay below 2 GiB)
-            chunk = max(1, ((1 << 31) // (8 * W) - 512) // L)
+            chunk = x3_chunk(W, L)
             if B > chunk:
                 return torch.cat([self._text_tokens(text[i:i + chunk], eng) for i in range(0, B, chunk)])
         lib = load()

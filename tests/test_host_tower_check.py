@@ -368,3 +368,34 @@ def test_pass_workspaces_are_the_sums_of_the_plan_buffers(lane, flow, f32, B):
         else:
             xp = _lib.TextParams(tp, VOCAB, E)
             assert lib.keds_text_workspace_bytes(C.byref(xp), B) == x + tower + al(ro)
+
+
+# ---- mutations of a whole pass (tower_check.PASS_MUTATIONS) -------------------------------------------------------------------------
+def _pass_mutation_cases():
+    out = []
+    for flow in tc.FLOWS:
+        out += [("cls_dropped", flow, "vit", {}), ("no_ln_pre", flow, "vit", {}), ("readout_stride_plus1", flow, "vit", {}),
+                ("no_l2norm", flow, "vit", dict(normalize=1)), ("readout_stride_plus1", flow, "text", dict(trim=0)),
+                ("readout_stride_plus1", flow, "text", dict(trim=1, seq_used=21)), ("no_l2norm", flow, "text", dict(trim=1, normalize=1))]
+    return out
+
+
+@pytest.mark.parametrize("name,flow,kind,kw", _pass_mutation_cases(), ids=lambda v: v if isinstance(v, str) else "")
+def test_mutations_of_a_pass_are_caught(full, name, flow, kind, kw):
+    """a dropped CLS row, a missing ln_pre, a read-out stride wrong by one and a missing L2 normalisation change the embeddings by
+    NaN or >= 1e-3 relative.  (embed_before_zero changes the enqueue order only -- the two steps write disjoint rows --, so this executor
+    computes the same; tests/test_host_tower_plan.py holds it to the order)"""
+    B, cols = 3, [3, 20, 9]
+    g = torch.Generator().manual_seed(12)
+    inputs = {"img": torch.randn(B, 3, 56, 56, generator=g, dtype=torch.float64), "tokens": torch.randint(0, VOCAB, (B, L), generator=g)}
+    p = tc.plan_pass(flow, kind, LAYERS, B, rows=cols, **kw) if kind == "text" else tc.plan_pass(flow, kind, LAYERS, B, **kw)
+    clean = tc.run64(p, full, None, rows=cols, inputs=inputs)["bufs"]["out"]
+    bad = tc.run64(tc.mutate_pass(p, name), full, None, rows=cols, inputs=inputs)["bufs"]["out"]
+    assert torch.isfinite(clean).all()
+    worst = _rel(bad, clean)
+    print(f"[pass mutation] {name} {flow} {kind}: worst element {worst:.3g}")
+    assert worst >= 1e-3
+
+
+def test_every_pass_mutation_has_a_case():
+    assert {c[0] for c in _pass_mutation_cases()} | {"embed_before_zero"} == set(tc.PASS_MUTATIONS)

@@ -465,9 +465,47 @@ def plan_pass(flow, kind, layers, B, width=256, heads=4, embed_dim=128, res=56, 
         p.readout = dict(op="readout", S=1, rows=None, g="ln_final", normalize=normalize)
         p.steps.append(p.readout)
     p.pass_kind, p.E, p.L = kind, embed_dim, L
-    p.buffers["ro"] = (pad256(B), w, "fp32" if flow in ("f32", "x3") else "fp16" if flow == "fp16" else "bf16")
+    # the LayerNorm of the read-out rows is a GEMM operand: addressable up to the next multiple of 128 rows
+    p.buffers["ro"] = ((B + 127) // 128 * 128, w, "fp32" if flow in ("f32", "x3") else "fp16" if flow == "fp16" else "bf16")
     p.buffers["out"] = (B, embed_dim, "fp32")
     return p
+
+
+# ---- mutations of a whole pass ---------------------------------------------------------------------------------------------------
+# (embed_before_zero changes the order only: the embedding writes the samples' own rows, the zero steps the rows behind them, so the
+# float64 executor, which runs the steps one after the other, computes the same; it shows in the comparison of the plans)
+PASS_MUTATIONS = ("cls_dropped", "embed_before_zero", "no_ln_pre", "readout_stride_plus1", "no_l2norm")
+
+
+def mutate_pass(p, name):
+    """-> a copy of a plan_pass() plan with the defect; LookupError when the plan has no step the defect applies to"""
+    q = p.clone()
+    if name == "cls_dropped":
+        hit = q.find(op="cls")
+        q.steps = [s for s in q.steps if s["op"] != "cls"]
+    elif name == "embed_before_zero":
+        hit = [s for s in q.find(op="zero") if q.steps.index(s) < q.steps.index(q.find(op="embed")[0])] if q.find(op="embed") else []
+        if hit:
+            e = q.find(op="embed")[0]
+            q.steps.remove(e)
+            q.steps.insert(0, e)
+    elif name == "no_ln_pre":
+        hit = q.find(op="ln", g="ln_pre")
+        q.steps = [s for s in q.steps if not (s["op"] == "ln" and s.get("g") == "ln_pre")]
+    elif name == "readout_stride_plus1":
+        hit = q.find(op="readout")
+        for s in hit:
+            s["S"] += 1
+    elif name == "no_l2norm":
+        hit = [s for s in q.find(op="readout") if s["normalize"]]
+        for s in hit:
+            s["normalize"] = 0
+    else:
+        raise ValueError(name)
+    if not hit:
+        raise LookupError(f"{name}: no such step in this plan")
+    q.readout = (q.find(op="readout") or [None])[0]
+    return q
 
 
 def synth_front(w, E, kreal, kpad, S, L, vocab, seed=0):
