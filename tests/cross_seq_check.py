@@ -24,6 +24,7 @@ layer 1: K at column 2 inner, V at 3 inner) whose other columns are NaN; Q sits 
 of stride inner + 8 (so q_ld != o_ld != 64 heads), the columns beyond inner NaN (Q) / sentinel (out)."""
 import torch
 
+from keds_amd import _lib
 from tests import attention_check as ac
 
 DH = 64
@@ -172,7 +173,7 @@ def model(lay, mutation=None):
 
 
 # ---- the plan (cross_seq_plan.h) as a Python model: tests/test_host_cross_seq_plan.py holds the library against it ----------------
-FORM_TILE = 1
+FORM_TILE = _lib.CROSS_SEQ_FORM_TILE
 ONE_WG_MAX, CHUNK = 288, 256
 
 

@@ -53,6 +53,7 @@ CPU model: emulate_mx() accumulates per 128-wide K-tile in fp32, forwards or bac
 the kernels' order, and packs MX outputs as mx_block_exp / mx_pack8 do.  MUTATIONS are deliberate defects of it."""
 import torch
 
+from keds_amd import _lib
 from tests import gemm_check as gc
 from tests.gemm_check import BF, F32, HF, STAT_SCALE, Failures, _collect, check_stats      # noqa: F401  (re-exported)
 
@@ -62,7 +63,8 @@ PAD_SCALE = 127 + 20
 C_ACC_MX = 8.0                                 # see above: the measured single-instruction error of the block-scaled MFMA, 5.7, rounded up
 NAN_BYTE = 0x7F                                # e4m3 NaN: the sentinel of MX copy buffers
 REGIMES = ("integer", "integer_pow2", "random", "blockramp_up", "blockramp_down", "blockjump", "offset")
-EPI_BIAS, EPI_LN, EPI_LN_QGELU_MX, EPI_RESID_MX, EPI_RESID_MX_H = range(5)     # KEDS_FP8_EPI_*
+EPI_BIAS, EPI_LN, EPI_LN_QGELU_MX, EPI_RESID_MX, EPI_RESID_MX_H = (
+    _lib.FP8_EPI_BIAS_BF16, _lib.FP8_EPI_LN_BIAS_BF16, _lib.FP8_EPI_LN_QGELU_MX, _lib.FP8_EPI_RESID_STATS_MX, _lib.FP8_EPI_RESID_STATS_MX_H)
 NAMES = {0: "BIAS_BF16", 1: "LN_BIAS_BF16", 2: "LN_QGELU_MX", 3: "RESID_STATS_MX", 4: "RESID_STATS_MX_H"}
 CODE_OF = {0: 0, 1: 6, 2: 7, 3: 8, 4: 9}       # the gemm_check epilogue with the same fp32 operations (7: before its bf16 rounding)
 LN_EPIS = (EPI_LN, EPI_LN_QGELU_MX)

@@ -19,10 +19,12 @@ Everything else (lists, cuts, ties, ranks, fillers, counters) is integer work an
 """
 import numpy as np
 
+from keds_amd import _lib
+
 U = 2.0 ** -24
 STAGE_KEYS, QBLOCK, LISTK = 32, 128, 16
 DIMS = (128, 256, 512, 768, 1024)
-L2, IP = 0, 1
+L2, IP = _lib.METRIC_L2, _lib.METRIC_IP
 NEG_INF_KEY = 0x007FFFFF                    # ord_key(-inf)
 PLAN_FIELDS = ("two_phase", "stagesA", "nqb", "nwgA", "nwgB", "depthA", "ncand", "chunk_rows", "nchunks", "total_stages")
 EXACT_BUDGET = 256 << 20

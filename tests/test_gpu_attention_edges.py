@@ -23,8 +23,9 @@ DTYPE = {"bf16": torch.bfloat16, "fp16": torch.float16, "f32": torch.float32, "x
 ENTRIES = ("bf16", "fp16", "f32", "x3")      # keds_attention_ex, keds_attention_h, keds_attention_f32, keds_attention_x3
 MASKS = pytest.mark.parametrize("causal", [False, True], ids=["full", "causal"])
 X3_OUT_FLOOR, X3_PLANE_FLOOR = 2.0 ** -25, 2.0 ** -24     # attention_check.check_f32: what the split-fp16 format itself implies
-GENERIC, TAIL1, S257 = 1, 2, 3               # KEDS_ATTN_FORM_*
-F_CAUSAL, F_F16, F_Q8, F_PACKED, F_STOP = 1, 2, 4, 8, 16                       # KEDS_ATTN_FLAG_*
+GENERIC, TAIL1, S257 = _lib.ATTN_FORM_GENERIC, _lib.ATTN_FORM_TAIL1, _lib.ATTN_FORM_S257
+F_CAUSAL, F_F16, F_Q8, F_PACKED, F_STOP = (_lib.ATTN_FLAG_CAUSAL, _lib.ATTN_FLAG_F16, _lib.ATTN_FLAG_Q8, _lib.ATTN_FLAG_PACKED,
+                                            _lib.ATTN_FLAG_STOP_EVENT)
 
 
 @functools.lru_cache(maxsize=None)

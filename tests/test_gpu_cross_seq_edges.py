@@ -219,7 +219,7 @@ def test_cross_attn_seq_equals_self_attention_bit_for_bit():
     from tests import attention_check as ac
     lib = _lib.load()
     st = _lib.stream()
-    GENERIC, TILE = 1, 1                         # KEDS_ATTN_FORM_GENERIC, KEDS_CROSS_SEQ_FORM_TILE
+    GENERIC, TILE = _lib.ATTN_FORM_GENERIC, _lib.CROSS_SEQ_FORM_TILE
     H = 2
     d = 64 * H
 

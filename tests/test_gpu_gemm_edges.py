@@ -22,8 +22,8 @@ GUARD = 256                                   # rows behind M that no launch may
 SENT = gc.SENTINEL
 STAT_BASE = (3 << 28, 11 << 28)               # what the statistics a launch ADDS INTO hold before it
 STAT_GUARD = 7
-SMALL, PAIR, QUAD, QUAD3 = 1, 2, 3, 4         # KEDS_GEMM_FORM_*
-DEFER, PROLOGUE = 1, 2                        # KEDS_GEMM_FLAG_*
+SMALL, PAIR, QUAD, QUAD3 = _lib.GEMM_FORM_SMALL, _lib.GEMM_FORM_PAIR, _lib.GEMM_FORM_QUAD, _lib.GEMM_FORM_QUAD3
+DEFER, PROLOGUE = _lib.GEMM_FLAG_DEFER, _lib.GEMM_FLAG_RESID_PROLOGUE
 F_SMALL, F_NOSPLIT, F_PROLOGUE, F_QUAD, F_PERSIST, F_PAIR, F_NOQUAD3, F_NODEFER = 1, 1 << 9, 1 << 10, 1 << 11, 2 << 11, 3 << 11, 1 << 16, 1 << 17
 WS_BYTES = 32 << 20
 ALL_CODES = tuple(gc.EPILOGUES)

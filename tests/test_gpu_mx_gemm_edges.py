@@ -25,7 +25,7 @@ GUARD = 256
 SENT = gc.SENTINEL
 STAT_BASE = (3 << 28, 11 << 28)               # what the statistics a launch ADDS INTO hold before it
 STAT_GUARD = 7
-PAIR, QUAD = 1, 2                             # KEDS_FP8_FORM_*
+PAIR, QUAD = _lib.FP8_FORM_PAIR, _lib.FP8_FORM_QUAD
 QUAD_EPIS = (mc.EPI_BIAS, mc.EPI_LN, mc.EPI_LN_QGELU_MX, mc.EPI_RESID_MX_H)      # the fp32-residual epilogue stays on 8 waves
 ALL_EPIS = tuple(mc.NAMES)
 SHAPES = [(256, 256), (768, 256), (256, 768), (2304, 256), (512, 1024)]          # 1, 3, 3, 9 (no multiple of 8: the XCD remap) and 8 tiles

@@ -695,7 +695,7 @@ def test_split_k_tower_equals_its_chain(flow):
 
 
 # ---- big cases: the smallest shapes at which the 16-bit flows put remainder rows on the side lane; bits only ------------------------
-ATTN_FORM_GENERIC, ATTN_FORM_S257, ATTN_FLAG_STOP_EVENT = 1, 3, 16
+ATTN_FORM_GENERIC, ATTN_FORM_S257, ATTN_FLAG_STOP_EVENT = _lib.ATTN_FORM_GENERIC, _lib.ATTN_FORM_S257, _lib.ATTN_FLAG_STOP_EVENT
 
 
 @pytest.mark.parametrize("tail", ("cls", "all"))

@@ -24,7 +24,7 @@ pytestmark = pytest.mark.gpu
 
 GUARD, GAP = 256, 256
 SENT = gc.SENTINEL
-SMALL, PAIR, QUAD = 1, 2, 3                   # KEDS_GEMM_FORM_*
+SMALL, PAIR, QUAD = _lib.GEMM_FORM_SMALL, _lib.GEMM_FORM_PAIR, _lib.GEMM_FORM_QUAD
 F_SMALL, F_PAIR = 1, 3 << 11                  # keds_gemm_force_small: bit 0, bits 11-12 = 3
 CODES = tuple(gc.X3_EPILOGUES)
 IDS = [gc.X3_NAMES[c] for c in CODES]

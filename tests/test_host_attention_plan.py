@@ -12,8 +12,9 @@ import pytest
 from keds_amd import _lib
 from tests.conftest import ROOT
 
-NONE, GENERIC, TAIL1, S257 = range(4)                       # KEDS_ATTN_FORM_*
-CAUSAL, F16, Q8, PACKED, STOP = 1, 2, 4, 8, 16              # KEDS_ATTN_FLAG_*
+NONE, GENERIC, TAIL1, S257 = _lib.ATTN_FORM_NONE, _lib.ATTN_FORM_GENERIC, _lib.ATTN_FORM_TAIL1, _lib.ATTN_FORM_S257
+CAUSAL, F16, Q8, PACKED, STOP = (_lib.ATTN_FLAG_CAUSAL, _lib.ATTN_FLAG_F16, _lib.ATTN_FLAG_Q8, _lib.ATTN_FLAG_PACKED,
+                                 _lib.ATTN_FLAG_STOP_EVENT)
 FIELDS = ("form", "nkt", "nfull", "flags", "grid", "block", "lds", "q_limit")      # keds_attention_last_launch's layout
 HOOKS = (0, 16, 32, 48)                                     # keds_attention_debug: bit 4 no S = 257 form at all, bit 5 the 4-wave tail kernel
 REFUSED_BITS = (0, 1, 2, 3, 6)
@@ -207,7 +208,7 @@ def test_query_with_a_bad_argument_returns_e_arg_and_leaves_info_untouched(lib):
 
 
 # ---- the MXFP8 GEMM: keds_gemm_mxfp8_ex's decision at 8ac08b6 (gemm_fp8.hip:951-956, launch_mxfp8_quad :921-928) ------------------------
-FP8_PAIR, FP8_QUAD = 1, 2                                   # KEDS_FP8_FORM_*
+FP8_PAIR, FP8_QUAD = _lib.FP8_FORM_PAIR, _lib.FP8_FORM_QUAD
 
 
 def mxfp8_model(epilogue, M, N, K, cus, debug):

@@ -12,8 +12,9 @@ import pytest
 from keds_amd import _lib
 from tests.conftest import ROOT
 
-NONE, SMALL, PAIR, QUAD, QUAD3 = range(5)     # KEDS_GEMM_FORM_*
-DEFER, PROLOGUE = 1, 2                        # KEDS_GEMM_FLAG_*
+NONE, SMALL, PAIR, QUAD, QUAD3 = (_lib.GEMM_FORM_NONE, _lib.GEMM_FORM_SMALL, _lib.GEMM_FORM_PAIR, _lib.GEMM_FORM_QUAD,
+                                   _lib.GEMM_FORM_QUAD3)
+DEFER, PROLOGUE = _lib.GEMM_FLAG_DEFER, _lib.GEMM_FLAG_RESID_PROLOGUE
 F_SMALL, F_NOSPLIT, F_PROLOGUE, F_QUAD, F_PERSIST, F_PAIR, F_NOQUAD3, F_NODEFER = (
     1, 1 << 9, 1 << 10, 1 << 11, 2 << 11, 3 << 11, 1 << 16, 1 << 17)
 F_REFUSED = (1 << 8, 1 << 13, 1 << 14, 1 << 15)           # timing-only forms the library no longer has: keds_gemm_force_small refuses them

@@ -2,7 +2,6 @@
 before touching a device, and the façade methods raise the library's "no CPU" error instead of NotImplementedError."""
 import ctypes as C
 import os
-import re
 
 import pytest
 import torch
@@ -10,7 +9,6 @@ import torch
 import keds_amd
 from keds_amd import _lib
 from oracle import keds_oracle as O
-from tests.conftest import ROOT
 
 NEW = ("keds_vit_run_tokens", "keds_text_run_tokens", "keds_tap_store_nt", "keds_vit_forward_tokens", "keds_text_forward_tokens")
 TINY = dict(embed_dim=128, image_resolution=56, vision_layers=2, vision_width=128, vision_patch_size=14,
@@ -25,11 +23,8 @@ def _lib_loaded():
 
 def test_token_entry_points_are_declared_exported_and_bound():
     lib = _lib_loaded()
-    text = ""
-    for h in ("keds_hip.h", "keds_session.h"):
-        text += re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", h)).read(), flags=re.S)
     for name in NEW:
-        assert re.search(rf"\b{name}\s*\(", text), f"{name} not declared in include/*.h"
+        assert name in _lib.ABI.functions, f"{name} not declared in include/*.h"
         assert name in _lib.SIGNATURES, f"{name} missing from keds_amd._lib.SIGNATURES"
         assert hasattr(lib, name), f"{name} not exported"
     assert lib.keds_abi_version() == 15 == _lib.ABI_VERSION
