@@ -720,8 +720,10 @@ int keds_tower_forward(const keds_tower_params* p, float* x, int B,
 /* bit-exact form: PIL's integer resampling (22-bit fixed-point weights computed by the host exactly as PIL's Resample.c
  * does, horizontal pass first, uint8 intermediate).  need_h / need_v: the axis is resampled at all (PIL skips a pass that
  * keeps the size); xb/yb [n_px][2] = {first source index, taps} of every output column/row of the crop, xk/yk
- * [n_px][ksx|ksy] their int32 weights; left/top: crop offset when an axis is NOT resampled.  out_u8 (nullable)
- * [B,n_px,n_px,3]: the uint8 image PIL would hand to ToTensor. */
+ * [n_px][ksx|ksy] their int32 weights; left/top: crop offset when an axis is NOT resampled (>= 0, and the window
+ * [left, left + n_px) / [top, top + n_px) must lie inside the image, or the call is refused).  out_u8 (nullable)
+ * [B,n_px,n_px,3]: the uint8 image PIL would hand to ToTensor.
+ * keds_preprocess: the same two passes with fp32 weights computed on the device; one 8-bit step from PIL on rare pixels. */
 int keds_preprocess_pil(const unsigned char* images, int B, int H, int W, int n_px, int need_h, int need_v, int left, int top,
                         const int32_t* xb, const int32_t* xk, int ksx, const int32_t* yb, const int32_t* yk, int ksy,
                         const float* mean3, const float* std3, float* out, unsigned char* out_u8, void* stream);

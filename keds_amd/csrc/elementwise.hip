@@ -968,6 +968,9 @@ extern "C" int keds_preprocess_pil(const unsigned char* images, int B, int H, in
     KEDS_REQUIRE((!need_h || (xb && xk && ksx > 0)) && (!need_v || (yb && yk && ksy > 0)),
                  "keds_preprocess_pil: a resampled axis needs its bounds and weights");
     KEDS_REQUIRE(left >= 0 && top >= 0, "keds_preprocess_pil: negative crop offset");
+    // a skipped pass reads the crop window straight from the image (a resampled one reads what its table names)
+    KEDS_REQUIRE((need_h || (long long)left + n_px <= W) && (need_v || (long long)top + n_px <= H),
+                 "keds_preprocess_pil: the crop window of a skipped pass leaves the image");
     const long long total = (long long)B * n_px * n_px;
     hipStream_t st = (hipStream_t)stream;
     KedsProfScope prof(KEDS_PROF_OTHER, st);
@@ -980,7 +983,8 @@ extern "C" int keds_preprocess_pil(const unsigned char* images, int B, int H, in
 extern "C" int keds_preprocess(const unsigned char* images, int B, int H, int W, int n_px, const float* mean3,
                                const float* std3, float* out, void* stream) {
     KEDS_REQUIRE(images && out && mean3 && std3 && B > 0 && H > 0 && W > 0 && n_px > 0, "keds_preprocess: bad argument");
-    // torchvision Resize(int): shorter side -> n_px, the other int(n_px * long / short); CenterCrop offsets round half up
+    // torchvision Resize(int): shorter side -> n_px, the other int(n_px * long / short); CenterCrop offsets round half to even
+    // (lrintf here, Python's round() in torchvision)
     int RW, RH;
     if (W <= H) {
         RW = n_px;

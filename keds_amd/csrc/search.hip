@@ -901,14 +901,6 @@ __device__ __noinline__ void exact_merge_query(int q, int f, int nchunks, int k,
     }
 }
 
-__global__ void fill_invalid_kernel(float* D, long long* I, long long count, int metric) {
-    const long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x;
-    if (i < count) {
-        D[i] = metric == KEDS_METRIC_L2 ? INFINITY : -INFINITY;
-        I[i] = -1;
-    }
-}
-
 __global__ __launch_bounds__(256) void gather_rows_kernel(const float* __restrict__ db, int dim,
                                                           const long long* __restrict__ idx, long long id_base,
                                                           long long count, float* __restrict__ out) {

@@ -206,18 +206,24 @@ def shard_bounds(n: int, world: int, rank: int) -> Tuple[int, int]:
 
 def merge_partials(D_parts: torch.Tensor, I_parts: torch.Tensor, metric: int = _lib.METRIC_L2):
     """Host-side (torch) merge of [parts, B, k] partial results keyed on (distance, id): the same
-    ordering the device merge uses.  Works on CPU tensors, so the N>1 logic is testable with gloo."""
+    ordering the device merges use, entries with id < 0 behind every valid one and returned as
+    (+inf | -inf, -1).  Works on CPU tensors, so the N>1 logic is testable with gloo."""
     parts, B, k = D_parts.shape
     D = D_parts.permute(1, 0, 2).reshape(B, parts * k)
     I = I_parts.permute(1, 0, 2).reshape(B, parts * k)
     key = D if metric == _lib.METRIC_L2 else -D
-    key = torch.where(I < 0, torch.full_like(key, float("inf")), key)
-    # lexicographic (key, id): sort by id first, then stable sort by key
-    o1 = torch.sort(I, dim=1, stable=True).indices
-    key1 = torch.gather(key, 1, o1)
-    o2 = torch.sort(key1, dim=1, stable=True).indices
-    order = torch.gather(o1, 1, o2)[:, :k]
-    return torch.gather(D, 1, order), torch.gather(I, 1, order)
+    filler = I < 0
+    # lexicographic (filler, key, id): stable sorts by id, then key, then validity -- a VALID entry whose key is +inf (an
+    # L2 distance that overflowed, an IP score of -inf) stays in front of the fillers, as in the device merges
+    order = torch.sort(I, dim=1, stable=True).indices
+    for by in (key, filler.to(torch.int8)):
+        nxt = torch.sort(torch.gather(by, 1, order), dim=1, stable=True).indices
+        order = torch.gather(order, 1, nxt)
+    order = order[:, :k]
+    D, I = torch.gather(D, 1, order), torch.gather(I, 1, order)
+    gone = torch.gather(filler, 1, order)                         # fewer than k valid entries: the fillers of the device merges
+    D = torch.where(gone, torch.full_like(D, float("inf") if metric == _lib.METRIC_L2 else float("-inf")), D)
+    return D, torch.where(gone, torch.full_like(I, -1), I)
 
 
 def exchange_and_merge(D: torch.Tensor, I: torch.Tensor, metric: int = _lib.METRIC_L2, group=None):
@@ -225,7 +231,8 @@ def exchange_and_merge(D: torch.Tensor, I: torch.Tensor, metric: int = _lib.METR
 
     One small collective per search (B*k*12 bytes per rank: latency-bound on xGMI).
     Device tensors are merged by the HIP kernel (keds_topk_merge_parts); CPU tensors -- the gloo
-    tests of the multi-rank logic -- by `merge_partials`, which a GPU test pins to the kernel."""
+    tests of the multi-rank logic -- by `merge_partials`, which tests/test_gpu_exchange_kernels_edges.py
+    pins to the kernels bit for bit (ties, +-0, fillers, ids >= 2^32, valid entries at an infinite distance)."""
     import torch.distributed as dist
     world = dist.get_world_size(group)
     Dp = [torch.empty_like(D) for _ in range(world)]
