@@ -14,7 +14,11 @@ shifted, read-out at EOT + 2.
 Numerics: GEMM operands (activations, weights, the gradients that feed a GEMM) are bf16 with fp32 accumulation; the
 residual stream and its gradient, LayerNorm, softmax, loss and AdamW are fp32.  Parity bar (tests/test_gpu_train.py):
 loss within 2e-3 relative and every parameter gradient within rel-L2 3e-2 / cosine 0.999 of torch autograd on the fp32
-oracle with the same dropout masks (IM2TEXT hidden layers 6e-2 / 0.998: ReLU gates on bf16 pre-activations).
+oracle with the same dropout masks (IM2TEXT hidden layers 6e-2 / 0.998: ReLU gates on bf16 pre-activations).  The WIRING of the
+step is held by bits (docs/kernels.md, "The bar the training step has to pass"): loss_and_grads and apply_gradients equal the chain of
+public calls that tests/step_check.py writes down -- whose float64 execution equals a float64 autograd model of the step
+(tests/test_host_step_check.py) -- and every link of that chain is inside its kernel's per-element bound on the inputs it received
+(tests/test_gpu_train_step_chain.py).  No launch here may depend on the zeros of a pad row: the chain's pad rows are NaN.
 """
 from __future__ import annotations
 
