@@ -13,6 +13,10 @@ import re
 from typing import NamedTuple, Optional
 
 HEADERS = ("keds_hip.h", "keds_session.h")          # in include order: the second includes the first
+# Extension headers: entry points added to the same library between two moves of KEDS_ABI_VERSION.  Each is written in the same C
+# subset, includes "keds_hip.h" only, is parsed by the same parser on top of the core tables and has a lock of its own under
+# tests/golden (keds_select.h: abi_select_v1.json); the next ABI version folds them into the core header.
+EXT_HEADERS = ("keds_select.h",)
 INCLUDE_DIR = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "include")
 SCALARS = {"int": C.c_int, "int32_t": C.c_int, "uint32_t": C.c_uint32, "uint8_t": C.c_uint8, "int64_t": C.c_int64,
            "uint64_t": C.c_uint64, "size_t": C.c_size_t, "float": C.c_float, "double": C.c_double}
@@ -162,6 +166,21 @@ def parse_headers() -> Abi:
         with open(os.path.join(INCLUDE_DIR, h)) as f:
             sources.append((f"include/{h}", f.read()))
     return parse(sources)
+
+
+@functools.lru_cache(maxsize=None)
+def parse_ext_headers() -> Abi:
+    """What EXT_HEADERS add to the core tables: an Abi holding only their constants, structs, functions and handles (their
+    declarations may use every type and constant of the core headers; a name declared twice is a HeaderError)."""
+    core = parse_headers()
+    abi = Abi(dict(core.constants), dict(core.structs), dict(core.functions), list(core.handles))
+    for h in EXT_HEADERS:
+        with open(os.path.join(INCLUDE_DIR, h)) as f:
+            _parse_header(f"include/{h}", f.read(), abi)
+    return Abi({k: v for k, v in abi.constants.items() if k not in core.constants},
+               {k: v for k, v in abi.structs.items() if k not in core.structs},
+               {k: v for k, v in abi.functions.items() if k not in core.functions},
+               [h for h in abi.handles if h not in core.handles])
 
 
 @functools.lru_cache(maxsize=None)

@@ -1,7 +1,8 @@
 """ctypes binding of libkeds_hip.so (the C ABI declared in include/keds_hip.h and include/keds_session.h).
 
 Signatures, parameter structs and constants are not written here: _abi.py parses them out of the two headers at import, so the
-headers are the one place the ABI is edited.
+headers are the one place the ABI is edited.  Extension headers (_abi.EXT_HEADERS: include/keds_select.h) are parsed the same way
+into a second table, EXT_SIGNATURES, and bound into the same CDLL.
 
 There is no CPU fallback anywhere in this package: if the shared library is missing
 or a call fails, a RuntimeError is raised.  Torch is used only for device memory,
@@ -39,6 +40,13 @@ _derived = {cls.__name__: cls for cls in STRUCTS.values()}                      
 _derived.update((name[len("KEDS_"):], value) for name, value in ABI.constants.items())      # _lib.EPI_BIAS_BF16, _lib.ABI_VERSION, ...
 assert not set(_derived) & set(globals()), sorted(set(_derived) & set(globals()))
 globals().update(_derived)
+# the extension headers (_abi.EXT_HEADERS: keds_select.h) in a second table, bound into the same CDLL by load()
+EXT_ABI = _abi.parse_ext_headers()
+EXT_SIGNATURES = _abi.bind(_abi.Abi({**ABI.constants, **EXT_ABI.constants}, {**ABI.structs, **EXT_ABI.structs}, EXT_ABI.functions,
+                                    ABI.handles + EXT_ABI.handles), CLASS_NAMES)[1]
+_derived = {name[len("KEDS_"):]: value for name, value in EXT_ABI.constants.items()}        # _lib.SEL_MAX_EXCLUDE
+assert not set(_derived) & set(globals()), sorted(set(_derived) & set(globals()))
+globals().update(_derived)
 DT_F32, DT_BF16, DT_F16, DT_FP8, DT_F32X3 = (ABI.constants["KEDS_" + k] for k in ("F32", "BF16", "F16", "FP8", "F32X3"))    # keds_dtype
 
 _lib: Optional[C.CDLL] = None
@@ -64,7 +72,7 @@ def load() -> C.CDLL:
         raise RuntimeError(f"{LIB_PATH} not found: run `python -c 'import __graft_entry__ as g; g.build()'` "
                            "(or `make -C keds_amd/csrc`).  keds_amd has no CPU fallback.")
     lib = C.CDLL(LIB_PATH)
-    for name, (res, args) in SIGNATURES.items():
+    for name, (res, args) in list(SIGNATURES.items()) + list(EXT_SIGNATURES.items()):
         fn = getattr(lib, name)          # AttributeError if the .so does not export it
         fn.restype = res
         fn.argtypes = args

@@ -15,6 +15,7 @@
 // Score used by the scan: s = q.x - 0.5*||x||^2 (L2; monotone in -||q-x||^2) or q.x (IP);
 // the per-key bias enters as the MFMA C-in operand, read from the stage's fp32 tail.
 #include "keds_common.h"
+#include "../../include/keds_select.h"
 #include <math.h>
 
 namespace {
@@ -98,10 +99,16 @@ __device__ __forceinline__ float key_float(unsigned k) { return __uint_as_float(
 // out_meta[query * nwg + wg] = {entries written, largest key sitting in the LAST slot of a full list (0: none)}.
 // With insert thresholds almost every list slot stays empty: the merge then reads a handful of pairs per segment instead
 // of all 4L slots of it.
-template <int D, int L = LISTK, int NT = 0>
+// SEL: the filtered form (include/keds_select.h).  sel[t] is the eligibility word of the ABSOLUTE stage t: bit 16 tt + 4 g + r is
+// the key lane (g, r, tt) scores, and a key whose bit is clear scores -inf -- exactly what a row past n scores through its -inf
+// bias -- so it never passes `sc > lmin` in any pass.  The word must not disturb the ring's hand-counted vmcnt: it is a wave-uniform
+// load (sel is const __restrict__, t is uniform: a scalar load into an SGPR, counted on lgkmcnt), issued one stage ahead, BEHIND
+// the stage's last fragment read so that the counted LDS waits of the MFMA chain never see a scalar load in flight.
+template <int D, int L = LISTK, int NT = 0, int SEL = 0>
 __global__ __launch_bounds__(SCAN_THREADS, 2) void scan_topk_kernel(
     const char* __restrict__ packed, int stage_begin, int total_stages, const bf16_t* __restrict__ qb,
-    const float* __restrict__ thr, unsigned long long* __restrict__ out_pairs, uint2* __restrict__ out_meta) {
+    const float* __restrict__ thr, unsigned long long* __restrict__ out_pairs, uint2* __restrict__ out_meta,
+    const unsigned* __restrict__ sel) {
     using C = ScanCfg<D>;
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int tid = threadIdx.x;
@@ -131,6 +138,10 @@ __global__ __launch_bounds__(SCAN_THREADS, 2) void scan_topk_kernel(
     const float thr0 = thr ? thr[qglob] : -INFINITY;
     float lmin = thr0;
     int nocc = 0;                                   // valid entries of this lane's list
+    unsigned selnext = 0;                           // SEL: the word of the stage about to be read
+    // (Measured: touching the workgroup's words with one vector load each before the ring starts, so that the loop's scalar loads
+    // find their lines in L2, changes nothing -- the SEL form's 3-4 % on the scan is not a cache miss.)
+    if constexpr (SEL) selnext = s0 < s1 ? sel[s0] : 0u;
 
     // make sure the query loads are consumed before any LDS-DMA is counted on vmcnt
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -194,11 +205,24 @@ __global__ __launch_bounds__(SCAN_THREADS, 2) void scan_topk_kernel(
         }
         // D layout: lane (g,c) holds query c, keys 4g..4g+3 of each 16-key tile
         const int kbase = t * STAGE_KEYS + g * 4;
+        unsigned mybits = 0;
+        if constexpr (SEL) {
+            mybits = selnext >> (4 * g);
+            // The next word's load is pinned BEHIND the stage's last MFMA (the empty asm makes its index depend on both
+            // accumulators): every fragment read has been waited for by then.  Issued any earlier, the scalar load shares
+            // lgkmcnt with reads still in flight, scalar loads return out of order, and hipcc turns the counted wait in front
+            // of the next MFMA into lgkmcnt(0) right behind the load -- the load's whole latency, once per stage.  From here the
+            // word has the list updates and the barrier to arrive; the first LDS wait of the next stage is lgkmcnt(0) as ever.
+            int tn = t + 1 < s1 ? t + 1 : t;
+            asm volatile("" : "+s"(tn), "+v"(acc0), "+v"(acc1));
+            selnext = sel[tn];
+        }
 #pragma unroll
         for (int tt = 0; tt < 2; ++tt) {
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
-                const float sc = tt == 0 ? acc0[r] : acc1[r];
+                float sc = tt == 0 ? acc0[r] : acc1[r];
+                if constexpr (SEL) sc = (mybits >> (16 * tt + r)) & 1u ? sc : -INFINITY;
                 if (sc > lmin) {
                     // branch-free sorted insert with no serial chain: every slot looks only at the OLD list.
                     // new v[j] = med3(v[j-1], v[j], x); id follows the same three cases (x > v[j] strict, so an
@@ -682,14 +706,23 @@ __global__ __launch_bounds__(256) void certify_select_kernel(const int* __restri
                                                              const DbBounds* __restrict__ bounds, int* __restrict__ counters,
                                                              int* __restrict__ fail_ids, int* __restrict__ fslot,
                                                              float* __restrict__ dk, int* __restrict__ status,
-                                                             int force_fail, int dim) {
+                                                             int force_fail, int dim,
+                                                             const long long* __restrict__ exclude, int n_exclude) {
     __shared__ float s_key[NCAND_WIDE];
     __shared__ int s_id[NCAND_WIDE];
     __shared__ int s_nvalid;
     __shared__ float s_dk;
     const int q = blockIdx.x, t = threadIdx.x;
     const float d = cand_d[q * ncand + t];
-    const int id = cand_idx[q * ncand + t];
+    int id = cand_idx[q * ncand + t];
+    // a candidate on the query's exclude list (global ids; keds_select.h) is an invalid candidate from here on: s_dk is then the
+    // k-th REMAINING candidate, still the distance of a real allowed row and so still a valid pruning bound
+    if (exclude && id >= 0) {
+        const long long gid = (long long)id + id_base;
+        bool ex = false;
+        for (int e = 0; e < n_exclude; ++e) ex |= exclude[(size_t)q * n_exclude + e] == gid;
+        if (ex) id = -1;
+    }
     // (loaded up front by every thread: the certificate at the end then waits for no further memory round trip)
     const f32x4 qs = qstat[q];
     const float sb = sbound[q];
@@ -765,8 +798,10 @@ __global__ __launch_bounds__(256) void exact_chunk_kernel(const float* __restric
                                                           int chunk_rows, int nchunks, int k,
                                                           unsigned long long* __restrict__ plist, int* __restrict__ pcnt,
                                                           int* __restrict__ done, long long id_base, float* __restrict__ Dq,
-                                                          long long* __restrict__ Iq) {
+                                                          long long* __restrict__ Iq, const unsigned* __restrict__ sel,
+                                                          const long long* __restrict__ exclude, int n_exclude) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
+    __shared__ long long s_ex[KEDS_SEL_MAX_EXCLUDE];       // the query's exclude list as LOCAL rows
     const int nfail = counters[0];
     if (nfail == 0) return;
     float* sq = reinterpret_cast<float*>(smem);                                              // [dim]
@@ -780,6 +815,7 @@ __global__ __launch_bounds__(256) void exact_chunk_kernel(const float* __restric
         __syncthreads();                                   // previous item's LDS is no longer read
         for (int i = tid; i < dim; i += 256) sq[i] = qn[(size_t)q * dim + i];
         if (tid == 0) s_cnt = 0;
+        if (exclude && tid < n_exclude) s_ex[tid] = exclude[(size_t)q * n_exclude + tid] - id_base;
         __syncthreads();
         const float bound = dk[q];
         const long long r0 = (long long)c * chunk_rows;
@@ -802,7 +838,11 @@ __global__ __launch_bounds__(256) void exact_chunk_kernel(const float* __restric
                 }
             }
             s = wave_sum(s);                               // same summation order as rerank_kernel: identical bits
-            const bool keep = metric == KEDS_METRIC_L2 ? s <= bound : s >= bound;
+            bool keep = metric == KEDS_METRIC_L2 ? s <= bound : s >= bound;
+            // rows the selector leaves out or the query excludes never survive (keds_select.h)
+            if (sel) keep = keep && ((sel[(r0 + r) >> 5] >> ((r0 + r) & 31)) & 1u);
+            if (exclude)
+                for (int e = 0; e < n_exclude; ++e) keep = keep && s_ex[e] != r0 + r;
             if (lane == 0 && keep) surv[atomicAdd(&s_cnt, 1)] = exact_key(s, (int)(r0 + r), metric);
         }
         __syncthreads();
@@ -1025,9 +1065,10 @@ int g_scan_phases = 0;  // test hook: 1 forces the single-phase scan (no thresho
 int g_force_exact = 0;  // test hook: 1 sends every query through the exact fallback
 int g_scan_nt = 1;      // non-temporal LDS-DMA for the D = 768 candidate pass (A/B hook: keds_scan_debug bit 6 turns it off)
 int g_thr_depth = 0;    // threshold-pass list depth: 0 = by launch shape, 1 / 4 forced (A/B hook: keds_scan_debug bits 7-9)
+// sel == nullptr launches the unfiltered instantiations, the ones every search without a selector has always launched
 template <int D, int L>
 int launch_scan(const void* packed, int stage_begin, int total_stages, const bf16_t* qb, const float* thr,
-                unsigned long long* lval, uint2* lidx, int nwg, int nqb, hipStream_t st) {
+                unsigned long long* lval, uint2* lidx, int nwg, int nqb, const unsigned* sel, hipStream_t st) {
     using C = ScanCfg<D>;
     const size_t lds = (size_t)C::NST * C::LDS_STAGE;
     // the key stream's buffer descriptor starts at the workgroup's first stage and takes signed 32-bit offsets (2 GiB): an
@@ -1035,18 +1076,33 @@ int launch_scan(const void* packed, int stage_begin, int total_stages, const bf1
     KEDS_REQUIRE(nwg > 0 && ((long long)(total_stages + nwg - 1) / nwg + 1) * (long long)C::STAGEB < (1LL << 31),
                  "keds_index_search: %d stages over %d workgroups: a workgroup's key stream would span 2 GiB or more "
                  "(search the index in row ranges)", total_stages, nwg);
-    if (int rc = keds_func_lds_once((const void*)scan_topk_kernel<D, L>, (int)lds, "scan_topk_kernel")) return rc;
+    if (sel) {
+        if (int rc = keds_func_lds_once((const void*)scan_topk_kernel<D, L, 0, 1>, (int)lds, "scan_topk_kernel<sel>")) return rc;
+    } else {
+        if (int rc = keds_func_lds_once((const void*)scan_topk_kernel<D, L>, (int)lds, "scan_topk_kernel")) return rc;
+    }
     KedsProfScope prof(KEDS_PROF_SCAN, st, /*lazy*/ true);
     if constexpr (D == 768 && L == LISTK) {
+        if (g_scan_nt && sel) {
+            if (int rc = keds_func_lds_once((const void*)scan_topk_kernel<D, L, 1, 1>, (int)lds, "scan_topk_kernel<nt,sel>")) return rc;
+            KEDS_LAUNCH((scan_topk_kernel<D, L, 1, 1>), dim3(nwg, nqb), SCAN_THREADS, lds, st, (const char*)packed, stage_begin, total_stages,
+                        qb, thr, lval, lidx, sel);
+            return keds_check_launch("scan_topk_kernel<nt,sel>");
+        }
         if (g_scan_nt) {
             if (int rc = keds_func_lds_once((const void*)scan_topk_kernel<D, L, 1>, (int)lds, "scan_topk_kernel<nt>")) return rc;
             KEDS_LAUNCH((scan_topk_kernel<D, L, 1>), dim3(nwg, nqb), SCAN_THREADS, lds, st, (const char*)packed, stage_begin, total_stages, qb,
-                        thr, lval, lidx);
+                        thr, lval, lidx, sel);
             return keds_check_launch("scan_topk_kernel<nt>");
         }
     }
+    if (sel) {
+        KEDS_LAUNCH((scan_topk_kernel<D, L, 0, 1>), dim3(nwg, nqb), SCAN_THREADS, lds, st, (const char*)packed, stage_begin, total_stages, qb,
+                    thr, lval, lidx, sel);
+        return keds_check_launch("scan_topk_kernel<sel>");
+    }
     KEDS_LAUNCH((scan_topk_kernel<D, L>), dim3(nwg, nqb), SCAN_THREADS, lds, st, (const char*)packed, stage_begin, total_stages, qb, thr, lval,
-                lidx);
+                lidx, sel);
     return keds_check_launch("scan_topk_kernel");
 }
 
@@ -1078,20 +1134,20 @@ size_t stage_bytes(int dim) { return (size_t)STAGE_KEYS * dim * 2 + 128; }
 // one scan launch of list depth `depth` (1 / 4: threshold pass, LISTK: candidate pass) over stages [0, stages)
 template <int D>
 int launch_scan_depth(int depth, const void* packed, int stages, const bf16_t* qb, const float* thr, unsigned long long* lval,
-                      uint2* lidx, int nwg, int nqb, hipStream_t st) {
-    if (depth == 1) return launch_scan<D, 1>(packed, 0, stages, qb, thr, lval, lidx, nwg, nqb, st);
-    if (depth == 4) return launch_scan<D, 4>(packed, 0, stages, qb, thr, lval, lidx, nwg, nqb, st);
-    return launch_scan<D, LISTK>(packed, 0, stages, qb, thr, lval, lidx, nwg, nqb, st);
+                      uint2* lidx, int nwg, int nqb, const unsigned* sel, hipStream_t st) {
+    if (depth == 1) return launch_scan<D, 1>(packed, 0, stages, qb, thr, lval, lidx, nwg, nqb, sel, st);
+    if (depth == 4) return launch_scan<D, 4>(packed, 0, stages, qb, thr, lval, lidx, nwg, nqb, sel, st);
+    return launch_scan<D, LISTK>(packed, 0, stages, qb, thr, lval, lidx, nwg, nqb, sel, st);
 }
 
 int scan_dispatch(int dim, int depth, const void* packed, int stages, const bf16_t* qb, const float* thr, unsigned long long* lval,
-                  uint2* lidx, int nwg, int nqb, hipStream_t st) {
+                  uint2* lidx, int nwg, int nqb, const unsigned* sel, hipStream_t st) {
     switch (dim) {
-        case 128: return launch_scan_depth<128>(depth, packed, stages, qb, thr, lval, lidx, nwg, nqb, st);
-        case 256: return launch_scan_depth<256>(depth, packed, stages, qb, thr, lval, lidx, nwg, nqb, st);
-        case 512: return launch_scan_depth<512>(depth, packed, stages, qb, thr, lval, lidx, nwg, nqb, st);
-        case 768: return launch_scan_depth<768>(depth, packed, stages, qb, thr, lval, lidx, nwg, nqb, st);
-        default: return launch_scan_depth<1024>(depth, packed, stages, qb, thr, lval, lidx, nwg, nqb, st);
+        case 128: return launch_scan_depth<128>(depth, packed, stages, qb, thr, lval, lidx, nwg, nqb, sel, st);
+        case 256: return launch_scan_depth<256>(depth, packed, stages, qb, thr, lval, lidx, nwg, nqb, sel, st);
+        case 512: return launch_scan_depth<512>(depth, packed, stages, qb, thr, lval, lidx, nwg, nqb, sel, st);
+        case 768: return launch_scan_depth<768>(depth, packed, stages, qb, thr, lval, lidx, nwg, nqb, sel, st);
+        default: return launch_scan_depth<1024>(depth, packed, stages, qb, thr, lval, lidx, nwg, nqb, sel, st);
     }
 }
 
@@ -1109,11 +1165,12 @@ int launch_qprep(const float* queries, int nb, int dim, int normalize, float* qn
 
 int launch_exact(const float* db, int64_t n, int dim, int metric, const float* qn, const int* counters, const int* fail_ids,
                  const float* dk, int chunk_rows, int nchunks, int k, unsigned long long* plist, int* pcnt, int* done,
-                 long long id_base, float* Dq, long long* Iq, int cus, hipStream_t st) {
+                 long long id_base, float* Dq, long long* Iq, int cus, const unsigned* sel, const long long* exclude, int n_exclude,
+                 hipStream_t st) {
     const size_t lds = (size_t)dim * 4 + (size_t)chunk_rows * 8;
     if (int rc = keds_func_lds_once((const void*)exact_chunk_kernel, (int)lds, "exact_chunk_kernel")) return rc;
     exact_chunk_kernel<<<4 * cus, 256, lds, st>>>(db, n, dim, metric, qn, counters, fail_ids, dk, chunk_rows, nchunks, k, plist, pcnt,
-                                                 done, id_base, Dq, Iq);
+                                                 done, id_base, Dq, Iq, sel, exclude, n_exclude);
     return keds_check_launch("exact_chunk_kernel");
 }
 
@@ -1222,11 +1279,24 @@ extern "C" size_t keds_index_search_workspace_bytes(int nq, int dim) {
     return keds_index_search_workspace_bytes_ex(nq, dim, (int64_t)1 << 22, LISTK);
 }
 
-extern "C" int keds_index_search_packed_ex(const void* packed, const float* db, int64_t n, int dim, int metric,
-                                           const float* queries, int nq, int normalize_q, int k, int64_t id_base, float* D,
-                                           int64_t* I, float* rows_out, void* workspace, size_t workspace_bytes,
-                                           int32_t* status, void* stream) {
+namespace {
+// the refusals every filtered entry shares (keds_select.h): checked before any launch
+int check_exclude(const char* who, const int64_t* exclude, int n_exclude) {
+    KEDS_REQUIRE(n_exclude >= 0 && n_exclude <= KEDS_SEL_MAX_EXCLUDE, "%s: n_exclude must be in [0,%d] (got %d)", who,
+                 KEDS_SEL_MAX_EXCLUDE, n_exclude);
+    KEDS_REQUIRE(exclude || n_exclude == 0, "%s: exclude is null with n_exclude = %d", who, n_exclude);
+    return KEDS_OK;
+}
+}  // namespace
+
+extern "C" int keds_index_search_packed_sel(const void* packed, const float* db, int64_t n, int dim, int metric,
+                                            const float* queries, int nq, int normalize_q, int k, int64_t id_base, float* D,
+                                            int64_t* I, float* rows_out, void* workspace, size_t workspace_bytes,
+                                            int32_t* status, const uint32_t* sel, const int64_t* exclude, int n_exclude,
+                                            void* stream) {
     KEDS_REQUIRE(packed && db && queries && D && I && workspace, "keds_index_search_packed: null pointer");
+    if (int rc = check_exclude("keds_index_search_packed_sel", exclude, n_exclude)) return rc;
+    if (n_exclude == 0) exclude = nullptr;
     KEDS_REQUIRE(dim_supported(dim), "keds_index_search_packed: dim %d unsupported", dim);
     KEDS_REQUIRE(n > 0 && nq > 0, "keds_index_search_packed: empty database or query set");
     KEDS_REQUIRE(k >= 1 && k <= MAXK, "keds_index_search_packed: k must be in [1,%d] (got %d)", MAXK, k);
@@ -1256,13 +1326,13 @@ extern "C" int keds_index_search_packed_ex(const void* packed, const float* db, 
             // ncand-th best of their union is a score that ncand real rows reach, so the final candidates all beat or
             // equal it.  The candidate pass then rescans everything, inserting only above that threshold, so list
             // inserts are rare for ANY data.
-            if ((rc = scan_dispatch(dim, p.depthA, packed, p.stagesA, w.qb, nullptr, w.lpairs, w.lmeta, p.nwgA, p.nqb, st))) return rc;
+            if ((rc = scan_dispatch(dim, p.depthA, packed, p.stagesA, w.qb, nullptr, w.lpairs, w.lmeta, p.nwgA, p.nqb, sel, st))) return rc;
             KedsProfScope prof(KEDS_PROF_OTHER, st);
             merge_pairs_kernel<<<nb, MERGE_THREADS, 0, st>>>(w.lpairs, w.lmeta, p.nwgA, 4 * p.depthA, w.aidx, w.aval, w.thr, ncand,
                                                              nullptr, nullptr);
             if ((rc = keds_check_launch("merge_pairs_kernel(thr)"))) return rc;
         }
-        if ((rc = scan_dispatch(dim, LISTK, packed, total_stages, w.qb, two_phase ? w.thr : nullptr, w.lpairs, w.lmeta, p.nwgB, p.nqb, st)))
+        if ((rc = scan_dispatch(dim, LISTK, packed, total_stages, w.qb, two_phase ? w.thr : nullptr, w.lpairs, w.lmeta, p.nwgB, p.nqb, sel, st)))
             return rc;
         {
             KedsProfScope prof(KEDS_PROF_OTHER, st);
@@ -1277,12 +1347,15 @@ extern "C" int keds_index_search_packed_ex(const void* packed, const float* db, 
                 if ((rc = keds_check_launch("rerank_kernel"))) return rc;
                 certify_select_kernel<<<nb, ncand, 0, st>>>(w.cidx, w.cdist, ncand, metric, k, (long long)id_base, Dq, Iq, w.qstat,
                                                             w.sbound, bounds, w.counters, w.fail_ids, w.fslot, w.dk, status,
-                                                            g_force_exact, dim);
+                                                            g_force_exact, dim,
+                                                            exclude ? (const long long*)exclude + (size_t)q0 * n_exclude : nullptr,
+                                                            n_exclude);
                 if ((rc = keds_check_launch("certify_select_kernel"))) return rc;
             }
             // exact fallback for the queries whose certificate failed (the kernel returns at once when none did)
             if ((rc = launch_exact(db, n, dim, metric, qn, w.counters, w.fail_ids, w.dk, w.chunk_rows, w.nchunks, k, w.plist, w.pcnt,
-                                   w.counters + 8, (long long)id_base, Dq, Iq, p.cus, st)))
+                                   w.counters + 8, (long long)id_base, Dq, Iq, p.cus, sel,
+                                   exclude ? (const long long*)exclude + (size_t)q0 * n_exclude : nullptr, n_exclude, st)))
                 return rc;
         }
     }
@@ -1293,6 +1366,14 @@ extern "C" int keds_index_search_packed_ex(const void* packed, const float* db, 
         if ((rc = keds_check_launch("gather_rows_kernel"))) return rc;
     }
     return KEDS_OK;
+}
+
+extern "C" int keds_index_search_packed_ex(const void* packed, const float* db, int64_t n, int dim, int metric,
+                                           const float* queries, int nq, int normalize_q, int k, int64_t id_base, float* D,
+                                           int64_t* I, float* rows_out, void* workspace, size_t workspace_bytes,
+                                           int32_t* status, void* stream) {
+    return keds_index_search_packed_sel(packed, db, n, dim, metric, queries, nq, normalize_q, k, id_base, D, I, rows_out, workspace,
+                                        workspace_bytes, status, nullptr, nullptr, 0, stream);
 }
 
 extern "C" int keds_index_search_packed(const void* packed, const float* db, int64_t n, int dim, int metric,
@@ -1329,8 +1410,8 @@ extern "C" int keds_search_qprep(const float* queries, int nq, int dim, int norm
     return launch_qprep(queries, nq, dim, normalize, qn, (bf16_t*)qb, (f32x4*)qstat, counters, (hipStream_t)stream);
 }
 
-extern "C" int keds_search_scan(const void* packed, int64_t n, int dim, int stages, const void* qb, int nqb, const float* thr,
-                                int depth, int nwg, uint64_t* pairs, uint32_t* meta, void* stream) {
+extern "C" int keds_search_scan_sel(const void* packed, int64_t n, int dim, int stages, const void* qb, int nqb, const float* thr,
+                                    int depth, int nwg, uint64_t* pairs, uint32_t* meta, const uint32_t* sel, void* stream) {
     KEDS_REQUIRE(packed && qb && pairs && meta, "keds_search_scan: null pointer");
     KEDS_REQUIRE(dim_supported(dim), "keds_search_scan: dim %d unsupported", dim);
     KEDS_REQUIRE(n > 0 && n <= 2048LL * 16384, "keds_search_scan: n must be in [1, 2048 * 16384]");
@@ -1342,7 +1423,12 @@ extern "C" int keds_search_scan(const void* packed, int64_t n, int dim, int stag
     KEDS_REQUIRE(scan_span_ok(stages, nwg, dim), "keds_search_scan: %d stages over %d workgroups: a workgroup's key stream would "
                  "span 2 GiB or more", stages, nwg);
     return scan_dispatch(dim, depth, packed, stages, (const bf16_t*)qb, thr, (unsigned long long*)pairs, (uint2*)meta, nwg, nqb,
-                         (hipStream_t)stream);
+                         sel, (hipStream_t)stream);
+}
+
+extern "C" int keds_search_scan(const void* packed, int64_t n, int dim, int stages, const void* qb, int nqb, const float* thr,
+                                int depth, int nwg, uint64_t* pairs, uint32_t* meta, void* stream) {
+    return keds_search_scan_sel(packed, n, dim, stages, qb, nqb, thr, depth, nwg, pairs, meta, nullptr, stream);
 }
 
 extern "C" int keds_search_merge(const uint64_t* pairs, const uint32_t* meta, int nq, int nwg, int slots, int ncand,
@@ -1371,10 +1457,12 @@ extern "C" int keds_search_rerank(const float* db, int dim, int metric, const fl
     return keds_check_launch("rerank_kernel");
 }
 
-extern "C" int keds_search_certify(const void* packed, int64_t n, int dim, const int32_t* cand_idx, const float* cand_d, int nq,
-                                   int ncand, int metric, int k, int64_t id_base, const float* qstat, const float* sbound, float* D,
-                                   int64_t* I, int32_t* counters, int32_t* fail_ids, int32_t* fslot, float* dk, int32_t* status,
-                                   int force_fail, void* stream) {
+extern "C" int keds_search_certify_sel(const void* packed, int64_t n, int dim, const int32_t* cand_idx, const float* cand_d, int nq,
+                                       int ncand, int metric, int k, int64_t id_base, const float* qstat, const float* sbound,
+                                       float* D, int64_t* I, int32_t* counters, int32_t* fail_ids, int32_t* fslot, float* dk,
+                                       int32_t* status, int force_fail, const int64_t* exclude, int n_exclude, void* stream) {
+    if (int rc = check_exclude("keds_search_certify_sel", exclude, n_exclude)) return rc;
+    if (n_exclude == 0) exclude = nullptr;
     KEDS_REQUIRE(packed && cand_idx && cand_d && qstat && sbound && D && I && counters && fail_ids && fslot && dk,
                  "keds_search_certify: null pointer");
     KEDS_REQUIRE(dim_supported(dim), "keds_search_certify: dim %d unsupported", dim);
@@ -1387,13 +1475,24 @@ extern "C" int keds_search_certify(const void* packed, int64_t n, int dim, const
     const DbBounds* bounds = (const DbBounds*)((const char*)packed + (size_t)stages * stage_bytes(dim));
     certify_select_kernel<<<nq, ncand, 0, (hipStream_t)stream>>>(cand_idx, cand_d, ncand, metric, k, (long long)id_base, D, (long long*)I,
                                                                  (const f32x4*)qstat, sbound, bounds, counters, fail_ids, fslot, dk,
-                                                                 status, force_fail ? 1 : 0, dim);
+                                                                 status, force_fail ? 1 : 0, dim, (const long long*)exclude, n_exclude);
     return keds_check_launch("certify_select_kernel");
 }
 
-extern "C" int keds_search_exact(const float* db, int64_t n, int dim, int metric, const float* qn, int32_t* counters,
-                                 const int32_t* fail_ids, const float* dk, int chunk_rows, int k, int64_t id_base, uint64_t* plist,
-                                 int32_t* pcnt, float* D, int64_t* I, void* stream) {
+extern "C" int keds_search_certify(const void* packed, int64_t n, int dim, const int32_t* cand_idx, const float* cand_d, int nq,
+                                   int ncand, int metric, int k, int64_t id_base, const float* qstat, const float* sbound, float* D,
+                                   int64_t* I, int32_t* counters, int32_t* fail_ids, int32_t* fslot, float* dk, int32_t* status,
+                                   int force_fail, void* stream) {
+    return keds_search_certify_sel(packed, n, dim, cand_idx, cand_d, nq, ncand, metric, k, id_base, qstat, sbound, D, I, counters,
+                                   fail_ids, fslot, dk, status, force_fail, nullptr, 0, stream);
+}
+
+extern "C" int keds_search_exact_sel(const float* db, int64_t n, int dim, int metric, const float* qn, int32_t* counters,
+                                     const int32_t* fail_ids, const float* dk, int chunk_rows, int k, int64_t id_base, uint64_t* plist,
+                                     int32_t* pcnt, float* D, int64_t* I, const uint32_t* sel, const int64_t* exclude, int n_exclude,
+                                     void* stream) {
+    if (int rc = check_exclude("keds_search_exact_sel", exclude, n_exclude)) return rc;
+    if (n_exclude == 0) exclude = nullptr;
     KEDS_REQUIRE(db && qn && counters && fail_ids && dk && plist && pcnt && D && I, "keds_search_exact: null pointer");
     KEDS_REQUIRE(dim_supported(dim), "keds_search_exact: dim %d unsupported", dim);
     KEDS_REQUIRE(n > 0 && n <= 2048LL * 16384, "keds_search_exact: n must be in [1, 2048 * 16384]");
@@ -1405,7 +1504,50 @@ extern "C" int keds_search_exact(const float* db, int64_t n, int dim, int metric
     int cus = device_cus();
     if (cus > 256) cus = 256;
     return launch_exact(db, n, dim, metric, qn, counters, fail_ids, dk, chunk_rows, (int)nchunks, k, (unsigned long long*)plist, pcnt,
-                        counters + 8, (long long)id_base, D, (long long*)I, cus, (hipStream_t)stream);
+                        counters + 8, (long long)id_base, D, (long long*)I, cus, sel, (const long long*)exclude, n_exclude,
+                        (hipStream_t)stream);
+}
+
+extern "C" int keds_search_exact(const float* db, int64_t n, int dim, int metric, const float* qn, int32_t* counters,
+                                 const int32_t* fail_ids, const float* dk, int chunk_rows, int k, int64_t id_base, uint64_t* plist,
+                                 int32_t* pcnt, float* D, int64_t* I, void* stream) {
+    return keds_search_exact_sel(db, n, dim, metric, qn, counters, fail_ids, dk, chunk_rows, k, id_base, plist, pcnt, D, I, nullptr,
+                                 nullptr, 0, stream);
+}
+
+// ---- selector words from a list of ids: fill, then scatter with vector atomics (duplicate ids are idempotent) ----------------
+namespace {
+__global__ __launch_bounds__(256) void sel_fill_kernel(unsigned* __restrict__ sel, long long words, unsigned v) {
+    const long long i = blockIdx.x * 256LL + threadIdx.x;
+    if (i < words) sel[i] = v;
+}
+__global__ __launch_bounds__(256) void sel_scatter_kernel(unsigned* __restrict__ sel, long long n, const long long* __restrict__ ids,
+                                                          long long count, long long id_base, int drop) {
+    const long long i = blockIdx.x * 256LL + threadIdx.x;
+    if (i >= count) return;
+    const long long id = ids[i];
+    if (id < id_base || id - id_base >= n) return;            // (compared before the subtraction is trusted: no wrap into range)
+    const long long r = id - id_base;
+    const unsigned bit = 1u << (unsigned)(r & 31);
+    if (drop) atomicAnd(sel + (r >> 5), ~bit);
+    else atomicOr(sel + (r >> 5), bit);
+}
+}  // namespace
+
+extern "C" int keds_sel_build(uint32_t* sel, int64_t n, const int64_t* ids, int64_t count, int64_t id_base, int drop, void* stream) {
+    KEDS_REQUIRE(sel, "keds_sel_build: null selector");
+    KEDS_REQUIRE(n > 0 && n <= 2048LL * 16384, "keds_sel_build: n must be in [1, 2048 * 16384]");
+    KEDS_REQUIRE(count >= 0, "keds_sel_build: count must be >= 0 (got %lld)", (long long)count);
+    KEDS_REQUIRE(ids || count == 0, "keds_sel_build: ids is null with count = %lld", (long long)count);
+    KEDS_REQUIRE(count <= (1LL << 31) * 256 - 256, "keds_sel_build: too many ids");
+    hipStream_t st = (hipStream_t)stream;
+    const long long words = (n + 31) / 32;
+    sel_fill_kernel<<<(unsigned)((words + 255) / 256), 256, 0, st>>>(sel, words, drop ? 0xFFFFFFFFu : 0u);
+    if (int rc = keds_check_launch("sel_fill_kernel")) return rc;
+    if (count == 0) return KEDS_OK;
+    sel_scatter_kernel<<<(unsigned)((count + 255) / 256), 256, 0, st>>>(sel, (long long)n, (const long long*)ids, (long long)count,
+                                                                         (long long)id_base, drop ? 1 : 0);
+    return keds_check_launch("sel_scatter_kernel");
 }
 
 extern "C" int keds_topk_merge_parts(const float* D_parts, const int64_t* I_parts, int parts, int nq, int k,

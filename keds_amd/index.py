@@ -29,6 +29,74 @@ from ._lib import check, load, ptr, stream
 ArrayLike = Union[np.ndarray, torch.Tensor]
 
 
+class Selector:
+    """Which rows of an index a search may return: the faiss.SearchParameters(sel=IDSelector...) counterpart (include/keds_select.h).
+
+    One bit per row, bit (r & 31) of word (r >> 5), least significant first, set when row r is eligible: one 32-bit word per 32-key
+    stage of the scan image.  `words` is a device int32 tensor of ceil(n/32) words (the bit patterns of the uint32 words the
+    library reads); bits at or beyond n are ignored."""
+
+    def __init__(self, n: int, words: torch.Tensor):
+        if n < 1 or words.dtype != torch.int32 or words.dim() != 1 or words.shape[0] != (n + 31) // 32:
+            raise ValueError(f"a selector over {n} rows is int32 [{(n + 31) // 32}], got {words.dtype} {tuple(words.shape)}")
+        self.n = int(n)
+        self.words = words
+
+    @staticmethod
+    def pack_mask(mask: np.ndarray) -> np.ndarray:
+        """bool [n] -> uint32 [ceil(n/32)] on the host (the tail bits of the last word are zero)."""
+        mask = np.ascontiguousarray(mask, dtype=bool).reshape(-1)
+        by = np.packbits(mask, bitorder="little")
+        by = np.concatenate([by, np.zeros(-len(by) % 4, dtype=np.uint8)])
+        return by.view("<u4").astype(np.uint32)
+
+    @classmethod
+    def from_mask(cls, mask: ArrayLike, device=None) -> "Selector":
+        """mask: bool [n], True = eligible.  Packed on the host (np.packbits, little bit order) and moved to `device` (default: the
+        device of a device mask; else the words stay on the host until a search moves them to its index's device)."""
+        m = mask.detach().cpu().numpy() if isinstance(mask, torch.Tensor) else np.asarray(mask)
+        if m.ndim != 1 or m.shape[0] < 1:
+            raise ValueError(f"expected a bool [n] mask, got {m.shape}")
+        words = torch.from_numpy(cls.pack_mask(m).view(np.int32).copy())
+        if device is None and isinstance(mask, torch.Tensor) and mask.is_cuda:
+            device = mask.device
+        return cls(m.shape[0], words if device is None else words.to(device))
+
+    @classmethod
+    def from_ids(cls, n: int, ids: ArrayLike, keep: bool = True, id_base: int = 0, device=None) -> "Selector":
+        """keep=True: only `ids` are eligible; keep=False: every row but `ids`.  ids: GLOBAL ids (int64; local row + id_base);
+        ids outside [id_base, id_base + n) are ignored.  Built on the device (keds_sel_build: a fill and a scatter launch)."""
+        t = torch.from_numpy(np.ascontiguousarray(ids, dtype=np.int64)) if not isinstance(ids, torch.Tensor) else ids
+        if device is None:
+            if t.is_cuda:
+                device = t.device
+            else:
+                _lib.require_gpu()
+                device = torch.device("cuda", torch.cuda.current_device())
+        t = t.to(device, dtype=torch.int64).reshape(-1).contiguous()
+        words = torch.empty(((n + 31) // 32,), dtype=torch.int32, device=device)
+        with torch.cuda.device(words.device):
+            check(load().keds_sel_build(ptr(words), n, ptr(t) if t.numel() else None, t.numel(), id_base, 0 if keep else 1,
+                                        stream()), "keds_sel_build")
+        return cls(n, words)
+
+    def to_mask(self) -> np.ndarray:
+        """bool [n] on the host.  Synchronises."""
+        by = self.words.cpu().numpy().view(np.uint8)
+        return np.unpackbits(by, bitorder="little")[:self.n].astype(bool)
+
+    def count(self) -> int:
+        """Eligible rows.  Synchronises."""
+        return int(self.to_mask().sum())
+
+    def shard(self, lo: int, hi: int) -> "Selector":
+        """The selector of rows [lo, hi) as LOCAL rows of a shard: a view of words [lo // 32, ceil(hi / 32)), no copy.  lo must be
+        a multiple of 32, which shard_bounds guarantees."""
+        if lo % 32 or not (0 <= lo < hi <= self.n):
+            raise ValueError(f"shard [{lo}, {hi}) of a selector over {self.n} rows: lo must be a multiple of 32 inside [0, n)")
+        return Selector(hi - lo, self.words[lo // 32:(hi + 31) // 32])
+
+
 class FlatIndex:
     def __init__(self, d: int, metric: str = "l2", device: Optional[Union[str, torch.device]] = None,
                  row0: int = 0):
@@ -128,9 +196,30 @@ class FlatIndex:
         return idx
 
     # ---- search ---------------------------------------------------------------------------------
-    def search_device(self, q: torch.Tensor, k: int, normalize: bool = False,
-                      gather: bool = False) -> Tuple[torch.Tensor, torch.Tensor, Optional[torch.Tensor]]:
-        """Device-resident search.  q fp32 [B, d] on the index's device."""
+    def _filter_args(self, B: int, sel: Optional[Selector], exclude: Optional[ArrayLike]):
+        """(selector words | None, exclude int64 [B, E] on the device | None, E) of one search"""
+        if sel is not None:
+            if not isinstance(sel, Selector):
+                raise TypeError("sel must be a keds_amd.index.Selector")
+            if sel.n != self.ntotal:
+                raise ValueError(f"selector over {sel.n} rows on an index of {self.ntotal}")
+            sel = sel.words.to(self.device)
+        if exclude is None:
+            return sel, None, 0
+        ex = torch.from_numpy(np.ascontiguousarray(exclude, dtype=np.int64)) if not isinstance(exclude, torch.Tensor) else exclude
+        if ex.dim() == 1:
+            ex = ex[:, None]
+        if ex.dim() != 2 or ex.shape[0] != B or ex.shape[1] > _lib.SEL_MAX_EXCLUDE:
+            raise ValueError(f"exclude must be int64 [{B}] or [{B}, E <= {_lib.SEL_MAX_EXCLUDE}], got {tuple(ex.shape)}")
+        if ex.shape[1] == 0:
+            return sel, None, 0
+        return sel, ex.to(self.device, dtype=torch.int64).contiguous(), int(ex.shape[1])
+
+    def search_device(self, q: torch.Tensor, k: int, normalize: bool = False, gather: bool = False,
+                      sel: Optional[Selector] = None,
+                      exclude: Optional[ArrayLike] = None) -> Tuple[torch.Tensor, torch.Tensor, Optional[torch.Tensor]]:
+        """Device-resident search.  q fp32 [B, d] on the index's device.  sel: only its rows can be returned; exclude: int64 [B] or
+        [B, E <= 16] GLOBAL ids (the numbering of I) that query b must not return, -1 = none (include/keds_select.h)."""
         if self.rows is None:
             raise RuntimeError("search on an empty index")
         if not (1 <= k <= _lib.SCAN_MAX_K):
@@ -140,6 +229,7 @@ class FlatIndex:
         q = q.to(self.device, dtype=torch.float32).contiguous()
         B = q.shape[0]
         lib = load()
+        selw, ex, n_ex = self._filter_args(B, sel, exclude)
         nbytes = lib.keds_index_search_workspace_bytes_ex(B, self.d, self.rows.shape[0], k)
         if nbytes == 0:
             raise ValueError(f"search of {B} queries x k={k} over {self.rows.shape[0]} rows is not supported in one call")
@@ -149,9 +239,15 @@ class FlatIndex:
         D = torch.empty((B, k), dtype=torch.float32, device=self.device)
         I = torch.empty((B, k), dtype=torch.int64, device=self.device)
         rows = torch.empty((B, k, self.d), dtype=torch.float32, device=self.device) if gather else None
-        check(lib.keds_index_search_packed_ex(ptr(self.packed), ptr(self.rows), self.rows.shape[0], self.d, self.metric,
-                                              ptr(q), B, 1 if normalize else 0, k, self.row0, ptr(D), ptr(I), ptr(rows),
-                                              ptr(ws), ws.numel(), ptr(self._status), stream()), "keds_index_search_packed")
+        if selw is None and ex is None:
+            check(lib.keds_index_search_packed_ex(ptr(self.packed), ptr(self.rows), self.rows.shape[0], self.d, self.metric,
+                                                  ptr(q), B, 1 if normalize else 0, k, self.row0, ptr(D), ptr(I), ptr(rows),
+                                                  ptr(ws), ws.numel(), ptr(self._status), stream()), "keds_index_search_packed")
+        else:
+            check(lib.keds_index_search_packed_sel(ptr(self.packed), ptr(self.rows), self.rows.shape[0], self.d, self.metric,
+                                                   ptr(q), B, 1 if normalize else 0, k, self.row0, ptr(D), ptr(I), ptr(rows),
+                                                   ptr(ws), ws.numel(), ptr(self._status), ptr(selw), ptr(ex), n_ex, stream()),
+                  "keds_index_search_packed_sel")
         return D, I, rows
 
     def certificate_counts(self, reset: bool = False) -> Tuple[int, int]:
@@ -165,17 +261,18 @@ class FlatIndex:
             self._status.zero_()
         return a, b
 
-    def search(self, q: ArrayLike, k: int):
-        """Faiss call shape: numpy in -> numpy out; device tensor in -> device tensors out."""
+    def search(self, q: ArrayLike, k: int, sel: Optional[Selector] = None, exclude: Optional[ArrayLike] = None):
+        """Faiss call shape: numpy in -> numpy out; device tensor in -> device tensors out.  sel / exclude: search_device."""
         if isinstance(q, np.ndarray):
-            D, I, _ = self.search_device(torch.from_numpy(np.ascontiguousarray(q, dtype=np.float32)), k)
+            D, I, _ = self.search_device(torch.from_numpy(np.ascontiguousarray(q, dtype=np.float32)), k, sel=sel, exclude=exclude)
             return D.cpu().numpy(), I.cpu().numpy()
-        D, I, _ = self.search_device(q, k)
+        D, I, _ = self.search_device(q, k, sel=sel, exclude=exclude)
         return D, I
 
-    def search_gather(self, q: torch.Tensor, k: int, normalize: bool = False):
+    def search_gather(self, q: torch.Tensor, k: int, normalize: bool = False, sel: Optional[Selector] = None,
+                      exclude: Optional[ArrayLike] = None):
         """(D, I, rows [B,k,d]) with the winners' fp32 rows gathered on device."""
-        return self.search_device(q, k, normalize=normalize, gather=True)
+        return self.search_device(q, k, normalize=normalize, gather=True, sel=sel, exclude=exclude)
 
 
 def IndexFlatL2(d: int) -> FlatIndex:
@@ -339,6 +436,16 @@ class PackedExchange:
         self.dist.all_gather_into_tensor(self._q, q, group=self.group)
         return self._q
 
+    def gather_exclude(self, exclude: Optional[torch.Tensor]) -> Optional[torch.Tensor]:
+        """int64 [B, E] exclusion lists of this rank's queries -> [world*B, E] in the order of gather_queries (None -> None: no
+        collective).  One all_gather_into_tensor of B*E*8 bytes per rank."""
+        if exclude is None:
+            return None
+        exclude = exclude.contiguous()
+        out = torch.empty((self.world * exclude.shape[0], exclude.shape[1]), dtype=exclude.dtype, device=exclude.device)
+        self.dist.all_gather_into_tensor(out, exclude, group=self.group)
+        return out
+
     def return_partials(self, D_p: torch.Tensor, I_p: torch.Tensor, metric: int = _lib.METRIC_L2):
         """D_p / I_p [world*B, k]: this shard's partial lists for EVERY rank's queries (global ids)."""
         w = self.world
@@ -447,42 +554,72 @@ class ShardedFlatIndex:
     def ntotal(self) -> int:
         return self.n_global
 
-    def search(self, q: torch.Tensor, k: int, normalize: bool = False):
-        D, I, _ = self.local.search_device(q, k, normalize=normalize)
+    def _local_sel(self, sel: Optional[Selector]) -> Optional[Selector]:
+        """this rank's rows of a GLOBAL selector (over all n_global rows): a view, shard_bounds is 32-row aligned"""
+        if sel is None:
+            return None
+        if sel.n != self.n_global:
+            raise ValueError(f"selector over {sel.n} rows on a sharded index of {self.n_global}")
+        return sel.shard(*shard_bounds(self.n_global, self.world, self.rank))
+
+    @staticmethod
+    def _exclude_2d(exclude: Optional[ArrayLike], device) -> Optional[torch.Tensor]:
+        if exclude is None:
+            return None
+        ex = torch.from_numpy(np.ascontiguousarray(exclude, dtype=np.int64)) if not isinstance(exclude, torch.Tensor) else exclude
+        ex = ex[:, None] if ex.dim() == 1 else ex
+        return ex.to(device, dtype=torch.int64).contiguous()
+
+    def search(self, q: torch.Tensor, k: int, normalize: bool = False, sel: Optional[Selector] = None,
+               exclude: Optional[ArrayLike] = None):
+        """sel: a GLOBAL selector (every rank passes the same one and uses its shard of it); exclude: global ids per query."""
+        D, I, _ = self.local.search_device(q, k, normalize=normalize, sel=self._local_sel(sel), exclude=exclude)
         if self.world == 1:
             return D, I
         return exchange_and_merge(D, I, self.local.metric, self.group)
 
-    def search_own(self, q_local: torch.Tensor, k: int, normalize: bool = False):
+    def search_own(self, q_local: torch.Tensor, k: int, normalize: bool = False, sel: Optional[Selector] = None,
+                   exclude: Optional[ArrayLike] = None):
         """Data-parallel form without the rows: every rank passes ITS OWN B queries (same B everywhere) and gets (D, I)
-        for them -- two packed collectives on preallocated buffers (`PackedExchange`)."""
+        for them -- two packed collectives on preallocated buffers (`PackedExchange`).  `exclude` (this rank's queries' lists, the
+        same width on every rank) is all-gathered with the queries: one more KB-sized collective, only when it is given."""
         if self.world == 1:
-            D, I, _ = self.local.search_device(q_local, k, normalize=normalize)
+            D, I, _ = self.local.search_device(q_local, k, normalize=normalize, sel=self._local_sel(sel), exclude=exclude)
             return D, I
         if self._xchg is None:
             self._xchg = PackedExchange(self.group)
         allq = self._xchg.gather_queries(q_local.to(self.local._dev(), dtype=torch.float32))
-        D_p, I_p, _ = self.local.search_device(allq, k, normalize=normalize)
+        allex = self._xchg.gather_exclude(self._exclude_2d(exclude, self.local._dev()))
+        D_p, I_p, _ = self.local.search_device(allq, k, normalize=normalize, sel=self._local_sel(sel), exclude=allex)
         return self._xchg.return_partials(D_p, I_p, self.local.metric)
 
-    def search_gather(self, q_local: torch.Tensor, k: int, normalize: bool = False):
+    def search_gather(self, q_local: torch.Tensor, k: int, normalize: bool = False, sel: Optional[Selector] = None,
+                      exclude: Optional[ArrayLike] = None):
         """Data-parallel form: every rank passes ITS OWN B queries (same B everywhere) and gets (D, I, rows) for them:
         all-gather of the queries, local scan + gather on the shard, all-to-all of the partials with their rows, merge
         and row selection on the owner (`exchange_merge_gather`)."""
-        return ShardedFlatIndex.search_gather_many([self], q_local, k, normalize=normalize)[0]
+        return ShardedFlatIndex.search_gather_many([self], q_local, k, normalize=normalize, sel=sel, exclude=exclude)[0]
 
     @staticmethod
-    def search_gather_many(indices, q_local: torch.Tensor, k: int, normalize: bool = False):
+    def search_gather_many(indices, q_local: torch.Tensor, k: int, normalize: bool = False, sel=None,
+                           exclude: Optional[ArrayLike] = None):
         """`search_gather` of the SAME queries against several row-sharded databases (the knowledge path searches the image
         and the text database with one query batch, eval_utils.py:169-183): ONE all-gather of the queries, one local
         scan + gather per database, ONE all-to-all carrying every database's partial lists with their rows
-        (`PackedExchange.return_partials_rows`).  Returns [(D, I, rows), ...] in the order of `indices`."""
+        (`PackedExchange.return_partials_rows`).  Returns [(D, I, rows), ...] in the order of `indices`.
+        sel: None, one GLOBAL Selector for every database, or a list of one (or None) per database; exclude: this rank's
+        queries' global ids, applied to every database (all-gathered with the queries when given)."""
         first = indices[0]
+        sels = list(sel) if isinstance(sel, (list, tuple)) else [sel] * len(indices)
+        if len(sels) != len(indices):
+            raise ValueError(f"{len(sels)} selectors for {len(indices)} databases")
+        sels = [ix._local_sel(s) for ix, s in zip(indices, sels)]
         if first.world == 1:
-            return [ix.local.search_gather(q_local, k, normalize=normalize) for ix in indices]
+            return [ix.local.search_gather(q_local, k, normalize=normalize, sel=s, exclude=exclude) for ix, s in zip(indices, sels)]
         if first._xchg is None:
             first._xchg = PackedExchange(first.group)
         x = first._xchg
         allq = x.gather_queries(q_local.to(first.local._dev(), dtype=torch.float32))
-        parts = [ix.local.search_gather(allq, k, normalize=normalize) for ix in indices]
+        allex = x.gather_exclude(ShardedFlatIndex._exclude_2d(exclude, first.local._dev()))
+        parts = [ix.local.search_gather(allq, k, normalize=normalize, sel=s, exclude=allex) for ix, s in zip(indices, sels)]
         return x.return_partials_rows(parts, first.local.metric)

@@ -133,17 +133,25 @@ def load_database_shard(out_dir: str, rank: int = 0, world: int = 1, device=None
     return [ii.rows, ti.rows, None, ii, ti]
 
 
-def get_retrieved_features(feature: torch.Tensor, database, args=None, topk: int = 16, use_faiss: bool = True):
+def get_retrieved_features(feature: torch.Tensor, database, args=None, topk: int = 16, use_faiss: bool = True, exclude=None):
     """eval_utils.py:153-186.  feature [B,D] (any norm) -> (topk_image [B,k,D], topk_text [B,k,D]).
     The reference shuffles the image neighbours along K (a numerical no-op for attention over keys);
-    here they stay in rank order."""
+    here they stay in rank order.
+    exclude (int64 [B] or [B, E <= 16] database row ids, -1 = none; default None changes nothing): rows query b must not
+    retrieve from EITHER database -- the leave-self-out retrieval of a feature whose own image (and caption, same row id) sits
+    in the databases (trainer.py:198-230), where neighbour 0 would otherwise be the feature itself at distance 0."""
     image_index, text_index = database[3], database[4]
     if isinstance(image_index, ShardedFlatIndex) and isinstance(text_index, ShardedFlatIndex):
         # row-sharded databases: one query all-gather and one packed all-to-all for BOTH databases (SURVEY 8e)
-        (_, _, ti), (_, _, tt) = ShardedFlatIndex.search_gather_many([image_index, text_index], feature, topk, normalize=True)
+        (_, _, ti), (_, _, tt) = ShardedFlatIndex.search_gather_many([image_index, text_index], feature, topk, normalize=True,
+                                                                     exclude=exclude)
         return ti, tt
-    _, _, ti = image_index.search_gather(feature, topk, normalize=True)
-    _, _, tt = text_index.search_gather(feature, topk, normalize=True)
+    if exclude is None:
+        _, _, ti = image_index.search_gather(feature, topk, normalize=True)
+        _, _, tt = text_index.search_gather(feature, topk, normalize=True)
+        return ti, tt
+    _, _, ti = image_index.search_gather(feature, topk, normalize=True, exclude=exclude)
+    _, _, tt = text_index.search_gather(feature, topk, normalize=True, exclude=exclude)
     return ti, tt
 
 
