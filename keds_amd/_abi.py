@@ -17,6 +17,9 @@ HEADERS = ("keds_hip.h", "keds_session.h")          # in include order: the seco
 # subset, includes "keds_hip.h" only, is parsed by the same parser on top of the core tables and has a lock of its own under
 # tests/golden (keds_select.h: abi_select_v1.json); the next ABI version folds them into the core header.
 EXT_HEADERS = ("keds_select.h",)
+# ... and the knowledge stream in fp16, in a table and under a lock of its own (abi_knowledge_f16_v1.json): EXT_HEADERS and what
+# parse_ext_headers() returns for it stay what the select lock describes
+KNOWLEDGE_F16_HEADERS = ("keds_knowledge_f16.h",)
 INCLUDE_DIR = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "include")
 SCALARS = {"int": C.c_int, "int32_t": C.c_int, "uint32_t": C.c_uint32, "uint8_t": C.c_uint8, "int64_t": C.c_int64,
            "uint64_t": C.c_uint64, "size_t": C.c_size_t, "float": C.c_float, "double": C.c_double}
@@ -169,12 +172,13 @@ def parse_headers() -> Abi:
 
 
 @functools.lru_cache(maxsize=None)
-def parse_ext_headers() -> Abi:
-    """What EXT_HEADERS add to the core tables: an Abi holding only their constants, structs, functions and handles (their
-    declarations may use every type and constant of the core headers; a name declared twice is a HeaderError)."""
+def parse_ext_headers(headers=EXT_HEADERS) -> Abi:
+    """What the extension headers `headers` (EXT_HEADERS, or another tuple such as KNOWLEDGE_F16_HEADERS) add to the core tables: an
+    Abi holding only their constants, structs, functions and handles (their declarations may use every type and constant of the
+    core headers; a name declared twice is a HeaderError)."""
     core = parse_headers()
     abi = Abi(dict(core.constants), dict(core.structs), dict(core.functions), list(core.handles))
-    for h in EXT_HEADERS:
+    for h in headers:
         with open(os.path.join(INCLUDE_DIR, h)) as f:
             _parse_header(f"include/{h}", f.read(), abi)
     return Abi({k: v for k, v in abi.constants.items() if k not in core.constants},
@@ -206,11 +210,15 @@ def _ctype(t: Type, classes, param=False):
     return ct * t.array if t.array else ct
 
 
-def bind(abi: Abi, class_names=None):
+def bind(abi: Abi, class_names=None, classes=None):
     """-> (classes: typedef name -> ctypes.Structure subclass with the header's members in the header's order,
-           signatures: function name -> (restype, argtypes)).  class_names: typedef name -> Python class name (default: the typedef)."""
-    classes = {}
+           signatures: function name -> (restype, argtypes)).  class_names: typedef name -> Python class name (default: the typedef).
+    classes: Structure classes an earlier bind() made, kept for their typedefs (an extension's functions then take the very structs
+    the core table is bound with)."""
+    classes = dict(classes or {})
     for typedef, members in abi.structs.items():
+        if typedef in classes:
+            continue
         classes[typedef] = type((class_names or {}).get(typedef, typedef), (C.Structure,),
                                 {"_fields_": [(m, _ctype(t, classes)) for m, t in members], "__doc__": f"{typedef} of include/*.h"})
     signatures = {name: (None if ret == Type("void") else _ctype(ret, classes), [_ctype(p, classes, param=True) for p in params])

@@ -2,7 +2,8 @@
 
 Signatures, parameter structs and constants are not written here: _abi.py parses them out of the two headers at import, so the
 headers are the one place the ABI is edited.  Extension headers (_abi.EXT_HEADERS: include/keds_select.h) are parsed the same way
-into a second table, EXT_SIGNATURES, and bound into the same CDLL.
+into a second table, EXT_SIGNATURES, and bound into the same CDLL; include/keds_knowledge_f16.h (_abi.KNOWLEDGE_F16_HEADERS) likewise
+into a third, KF16_SIGNATURES.
 
 There is no CPU fallback anywhere in this package: if the shared library is missing
 or a call fails, a RuntimeError is raised.  Torch is used only for device memory,
@@ -47,6 +48,13 @@ EXT_SIGNATURES = _abi.bind(_abi.Abi({**ABI.constants, **EXT_ABI.constants}, {**A
 _derived = {name[len("KEDS_"):]: value for name, value in EXT_ABI.constants.items()}        # _lib.SEL_MAX_EXCLUDE
 assert not set(_derived) & set(globals()), sorted(set(_derived) & set(globals()))
 globals().update(_derived)
+# the knowledge stream in fp16 (_abi.KNOWLEDGE_F16_HEADERS: keds_knowledge_f16.h) in a third table
+KF16_ABI = _abi.parse_ext_headers(_abi.KNOWLEDGE_F16_HEADERS)
+KF16_SIGNATURES = _abi.bind(_abi.Abi({**ABI.constants, **KF16_ABI.constants}, {**ABI.structs, **KF16_ABI.structs}, KF16_ABI.functions,
+                                     ABI.handles + KF16_ABI.handles), CLASS_NAMES, classes=STRUCTS)[1]    # (its entries take the core's structs)
+_derived = {name[len("KEDS_"):]: value for name, value in KF16_ABI.constants.items()}       # _lib.EPI_BIAS_F16_H, ...
+assert not set(_derived) & set(globals()), sorted(set(_derived) & set(globals()))
+globals().update(_derived)
 DT_F32, DT_BF16, DT_F16, DT_FP8, DT_F32X3 = (ABI.constants["KEDS_" + k] for k in ("F32", "BF16", "F16", "FP8", "F32X3"))    # keds_dtype
 
 _lib: Optional[C.CDLL] = None
@@ -72,7 +80,7 @@ def load() -> C.CDLL:
         raise RuntimeError(f"{LIB_PATH} not found: run `python -c 'import __graft_entry__ as g; g.build()'` "
                            "(or `make -C keds_amd/csrc`).  keds_amd has no CPU fallback.")
     lib = C.CDLL(LIB_PATH)
-    for name, (res, args) in list(SIGNATURES.items()) + list(EXT_SIGNATURES.items()):
+    for name, (res, args) in list(SIGNATURES.items()) + list(EXT_SIGNATURES.items()) + list(KF16_SIGNATURES.items()):
         fn = getattr(lib, name)          # AttributeError if the .so does not export it
         fn.restype = res
         fn.argtypes = args

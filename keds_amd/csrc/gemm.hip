@@ -48,7 +48,7 @@ __device__ __forceinline__ void epilogue_store(f32x4 v0, f32x4 v1, void* __restr
             v1[j] = qgelu(v1[j]);
         }
     }
-    if constexpr (EPI == KEDS_EPI_BIAS_RELU_BF16) {
+    if constexpr (EPI == KEDS_EPI_BIAS_RELU_BF16 || EPI == KEDS_EPI_BIAS_RELU_F16_H) {
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
             v0[j] = fmaxf(v0[j], 0.f);
@@ -67,11 +67,19 @@ __device__ __forceinline__ void epilogue_store(f32x4 v0, f32x4 v1, void* __restr
                 *reinterpret_cast<f32x4*>(t + 4) = v1;
             }
         }
-    } else if constexpr (EPI == EPI_INT_BIAS_F16 || EPI == KEDS_EPI_BIAS_QGELU_F16_H) {
+    } else if constexpr (EPI == EPI_INT_BIAS_F16 || EPI == KEDS_EPI_BIAS_QGELU_F16_H || EPI == KEDS_EPI_BIAS_RELU_F16_H ||
+                         EPI == KEDS_EPI_BIAS_F16_H_HEADF32) {
         // fp16 operating point: fp16 out, and the range guard (|v| > 65504 or non-finite raises the flag instead of passing inf on)
         *reinterpret_cast<f16x8*>(reinterpret_cast<f16_t*>(out) + (size_t)m * ldc + n) =
             f16x8{(f16_t)v0[0], (f16_t)v0[1], (f16_t)v0[2], (f16_t)v0[3], (f16_t)v1[0], (f16_t)v1[1], (f16_t)v1[2], (f16_t)v1[3]};
         f16_range_flag(guard, f16_range_max(0u, v0, v1));
+        if constexpr (EPI == KEDS_EPI_BIAS_F16_H_HEADF32) {
+            if (m < aux_i) {                      // the first aux_i rows also in fp32, row stride 3N (token slot of [B,3,N])
+                float* t = const_cast<float*>(aux) + (size_t)m * 3 * N + n;
+                *reinterpret_cast<f32x4*>(t) = v0;
+                *reinterpret_cast<f32x4*>(t + 4) = v1;
+            }
+        }
     } else if constexpr (EPI == KEDS_EPI_X3_QGELU_PAIR) {
         // QuickGELU in full precision (model.py:300-302; f32path.hip's form), then the value as two fp16 planes: hi = fp16(v),
         // lo = fp16(v - hi) -- the A operand of the next split-operand GEMM (aux_i = elements between the planes)
@@ -1697,16 +1705,19 @@ int launch_quad3(const GemmArgs& a, const GemmPlan::Part&) {
 
 template <int EPI>
 int launch_part(const GemmArgs& a, const GemmPlan::Part& p) {
-    switch (p.form) {
-        case KEDS_GEMM_FORM_SMALL:
-            if (p.splits > 1) return p.ring == 4 ? launch_splitk<EPI, 4>(a, p) : launch_splitk<EPI, 2>(a, p);
-            return p.ring == 4 ? launch_small<EPI, 4>(a, p) : launch_small<EPI, 2>(a, p);
-        case KEDS_GEMM_FORM_PAIR: return launch_pair<EPI>(a, p);
-        case KEDS_GEMM_FORM_QUAD: return p.persistent ? launch_quad_persistent<EPI>(a, p) : launch_quad<EPI>(a, p);
-        case KEDS_GEMM_FORM_QUAD3:
-            if constexpr (epi_resid16(EPI)) return launch_quad3<EPI>(a, p);
-            else break;
-        default: break;
+    if (p.form == KEDS_GEMM_FORM_SMALL) {
+        if (p.splits > 1) return p.ring == 4 ? launch_splitk<EPI, 4>(a, p) : launch_splitk<EPI, 2>(a, p);
+        return p.ring == 4 ? launch_small<EPI, 4>(a, p) : launch_small<EPI, 2>(a, p);
+    }
+    if constexpr (!epi_kf16(EPI)) {      // (ids 32-34 are planned on the 128^2 forms only: no 256^2 kernel is instantiated for them)
+        switch (p.form) {
+            case KEDS_GEMM_FORM_PAIR: return launch_pair<EPI>(a, p);
+            case KEDS_GEMM_FORM_QUAD: return p.persistent ? launch_quad_persistent<EPI>(a, p) : launch_quad<EPI>(a, p);
+            case KEDS_GEMM_FORM_QUAD3:
+                if constexpr (epi_resid16(EPI)) return launch_quad3<EPI>(a, p);
+                else break;
+            default: break;
+        }
     }
     keds_set_error("keds_gemm_bt: no kernel of form %d for epilogue %d", p.form, EPI);
     return KEDS_E_LAUNCH;
@@ -1788,7 +1799,7 @@ static int gemm_check_shape(const char* who, int M, int N, int K, int64_t lda, i
 extern "C" int keds_gemm_plan_query(int epilogue, int M, int N, int K, int64_t lda, int64_t ldc, int cus, size_t splitk_bytes,
                                     int small_lds, int* info) {
     KEDS_REQUIRE(info, "keds_gemm_plan_query: null pointer");
-    KEDS_REQUIRE(epilogue >= 0 && epilogue <= KEDS_EPI_BIAS_F32_H, "keds_gemm_plan_query: unknown epilogue %d", epilogue);
+    KEDS_REQUIRE((epilogue >= 0 && epilogue <= KEDS_EPI_BIAS_F32_H) || epi_kf16(epilogue), "keds_gemm_plan_query: unknown epilogue %d", epilogue);
     if (int rc = gemm_check_shape("keds_gemm_plan_query", M, N, K, lda, ldc, epilogue)) return rc;
     gemm_plan(epilogue, M, N, K, lda, ldc, cus, splitk_bytes, small_lds != 0, gemm_switches()).info(info);
     return KEDS_OK;
@@ -1814,6 +1825,8 @@ extern "C" int keds_gemm_bt_ex2(const void* A, int64_t lda, const void* W, const
     if (epilogue == KEDS_EPI_RESID_STATS_F32) KEDS_REQUIRE(aux && aux2, "keds_gemm_bt: EPI_RESID_STATS needs aux = statistics and aux2 = bf16 copy");
     if (epilogue == KEDS_EPI_BIAS_BF16_HEADF32)
         KEDS_REQUIRE(aux && aux_i >= 0, "keds_gemm_bt: EPI_BIAS_BF16_HEADF32 needs the fp32 head buffer and its row count");
+    if (epilogue == KEDS_EPI_BIAS_F16_H_HEADF32)
+        KEDS_REQUIRE(aux && aux_i >= 0, "keds_gemm_bt: EPI_BIAS_F16_H_HEADF32 needs the fp32 head buffer and its row count");
     if (epi_x3(epilogue)) {
         keds_set_error("keds_gemm_bt: split-operand epilogues go through keds_gemm_x3");
         return KEDS_E_ARG;
@@ -1842,6 +1855,10 @@ extern "C" int keds_gemm_bt_ex2(const void* A, int64_t lda, const void* W, const
         KEDS_GEMM_CASE(KEDS_EPI_BIAS_QGELU_F16_H)
         KEDS_GEMM_CASE(KEDS_EPI_PATCH_F32_H)
         KEDS_GEMM_CASE(KEDS_EPI_BIAS_F32_H)
+        // the knowledge stream in fp16 (keds_knowledge_f16.h)
+        KEDS_GEMM_CASE(KEDS_EPI_BIAS_F16_H)
+        KEDS_GEMM_CASE(KEDS_EPI_BIAS_RELU_F16_H)
+        KEDS_GEMM_CASE(KEDS_EPI_BIAS_F16_H_HEADF32)
         default: keds_set_error("keds_gemm_bt: unknown epilogue %d", epilogue); return KEDS_E_ARG;
     }
 #undef KEDS_GEMM_CASE

@@ -5,6 +5,7 @@
 #pragma once
 #include <stddef.h>
 #include "../../include/keds_hip.h"
+#include "../../include/keds_knowledge_f16.h"      // ids 32-34: the knowledge stream's fp16 epilogues
 
 namespace {
 
@@ -16,20 +17,22 @@ constexpr bool epi_x3(int e) { return e == KEDS_EPI_X3_BIAS_F32 || e == KEDS_EPI
 constexpr bool epi_ln_h(int e) {
     return e == KEDS_EPI_LN_BIAS_BF16_H || e == KEDS_EPI_LN_QGELU_BF16_H || e == KEDS_EPI_LN_BIAS_F16_H || e == KEDS_EPI_LN_QGELU_F16_H;
 }
-constexpr bool epi_h16(int e) {        // the fp16 operating point's own ids (16..22)
+// the knowledge stream's fp16 ids (32..34, keds_knowledge_f16.h): 128^2 kernel forms only
+constexpr bool epi_kf16(int e) { return e == KEDS_EPI_BIAS_F16_H || e == KEDS_EPI_BIAS_RELU_F16_H || e == KEDS_EPI_BIAS_F16_H_HEADF32; }
+constexpr bool epi_h16(int e) {        // the fp16 operating point's own ids (16..22, 32..34)
     return e == KEDS_EPI_LN_BIAS_F16_H || e == KEDS_EPI_LN_QGELU_F16_H || e == KEDS_EPI_RESID_STATS_F16_H || e == KEDS_EPI_BIAS_RESID_F32_H ||
-           e == KEDS_EPI_BIAS_QGELU_F16_H || e == KEDS_EPI_PATCH_F32_H || e == KEDS_EPI_BIAS_F32_H;
+           e == KEDS_EPI_BIAS_QGELU_F16_H || e == KEDS_EPI_PATCH_F32_H || e == KEDS_EPI_BIAS_F32_H || epi_kf16(e);
 }
 constexpr bool epi_f16(int e) { return epi_ln_h(e) || epi_x3(e) || epi_h16(e); }          // fp16 (not bf16) MFMA operands
 constexpr bool epi_is_ln(int e) { return e == KEDS_EPI_LN_BIAS_BF16 || e == KEDS_EPI_LN_QGELU_BF16 || epi_ln_h(e); }
 // the fp16-residual epilogue (residual stream read-modify-written in fp16 + row statistics), bf16 or fp16 A / W
 constexpr bool epi_resid16(int e) { return e == KEDS_EPI_RESID_STATS_F16 || e == KEDS_EPI_RESID_STATS_F16_H; }
-// library-internal: the plain fp16-output store the LN-folded fp16 epilogue ends in (no public id)
+// library-internal: the plain fp16-output store the LN-folded fp16 epilogue ends in (its public name: KEDS_EPI_BIAS_F16_H)
 constexpr int EPI_INT_BIAS_F16 = 100;
 constexpr int epi_base(int e) {
     return (e == KEDS_EPI_LN_BIAS_BF16 || e == KEDS_EPI_LN_BIAS_BF16_H)     ? KEDS_EPI_BIAS_BF16
            : (e == KEDS_EPI_LN_QGELU_BF16 || e == KEDS_EPI_LN_QGELU_BF16_H) ? KEDS_EPI_BIAS_QGELU_BF16
-           : e == KEDS_EPI_LN_BIAS_F16_H                                    ? EPI_INT_BIAS_F16
+           : e == KEDS_EPI_LN_BIAS_F16_H || e == KEDS_EPI_BIAS_F16_H        ? EPI_INT_BIAS_F16
            : e == KEDS_EPI_LN_QGELU_F16_H                                   ? KEDS_EPI_BIAS_QGELU_F16_H
            : e == KEDS_EPI_X3_BIAS_F32 || e == KEDS_EPI_BIAS_F32_H          ? KEDS_EPI_BIAS_F32
            : e == KEDS_EPI_X3_RESID_F32 || e == KEDS_EPI_BIAS_RESID_F32_H   ? KEDS_EPI_BIAS_RESID_F32
@@ -38,7 +41,10 @@ constexpr int epi_base(int e) {
 }
 constexpr bool epi_qgelu(int e) { return epi_base(e) == KEDS_EPI_BIAS_QGELU_BF16 || epi_base(e) == KEDS_EPI_BIAS_QGELU_F16_H; }
 // epilogues that store fp16 values: the range guard applies (|v| > 65504 or non-finite raises the numerics-guard flag)
-constexpr bool epi_out_f16(int e) { return epi_base(e) == EPI_INT_BIAS_F16 || epi_base(e) == KEDS_EPI_BIAS_QGELU_F16_H; }
+constexpr bool epi_out_f16(int e) {
+    return epi_base(e) == EPI_INT_BIAS_F16 || epi_base(e) == KEDS_EPI_BIAS_QGELU_F16_H || e == KEDS_EPI_BIAS_RELU_F16_H ||
+           e == KEDS_EPI_BIAS_F16_H_HEADF32;
+}
 
 // ---- switches ------------------------------------------------------------------------------------------------------------
 // Everything that steers the decision besides the call's own arguments.  The defaults are the product's; keds_gemm_force_small
@@ -113,7 +119,8 @@ inline bool gemm_big_tiles_fill(int M, int N, int K, const GemmSwitches& sw) {
 }
 inline bool gemm_big_tiles(int epi, int M, int N, int K, long long lda, long long ldc, const GemmSwitches& sw) {
     return gemm_big_tiles_fill(M, N, K, sw) && lda == K && ldc == N && (epi_base(epi) != KEDS_EPI_PATCH_F32 || M % 256 == 0) &&
-           epi != KEDS_EPI_BIAS_BF16_HEADF32;      // (its fp32 head rows are numbered from row 0 of the launch)
+           epi != KEDS_EPI_BIAS_BF16_HEADF32 &&    // (its fp32 head rows are numbered from row 0 of the launch)
+           !epi_kf16(epi);                         // (the knowledge stream fills under 85 % of a 256^2 round: no 256^2 kernel is built for them)
 }
 
 // 256^2 tiles on the 4-wave kernel (0: the 8-wave kernel, 1: one tile per workgroup, 2: persistent where the launch allows it).

@@ -202,6 +202,15 @@ int keds_cross_core_f32_impl(const float* Q, const float* Kp, const float* Vp, f
 
 // ---- numerics guard (host): device int32 flag of the calling thread's current composite call, or nullptr -----------
 int* keds_numerics_guard();
+// a call that brings its own flag (keds_knowledge_f16.h, range_flag): the flag stands in for the thread's guard while the call
+// enqueues its launches; the thread's own guard is neither read on the device nor changed for the caller
+struct KedsGuardScope {
+    int* prev;
+    explicit KedsGuardScope(int* flag) : prev(keds_numerics_guard()) { keds_numerics_guard_set(flag); }
+    ~KedsGuardScope() { keds_numerics_guard_set(prev); }
+    KedsGuardScope(const KedsGuardScope&) = delete;
+    KedsGuardScope& operator=(const KedsGuardScope&) = delete;
+};
 
 // ---- GEMM dispatch as the composites see it (gemm.hip; the rules: gemm_plan.h) ------------------------------------------------
 // true when a dense [M,K] x [N,K]^T problem sends its full 256-row tiles to a 256^2 kernel and its M % 256 rows to a second, small

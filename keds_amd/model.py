@@ -674,6 +674,34 @@ class CLIP(nn.Module):
 # ---------------------------------------------------------------------------------------------------
 # knowledge-injection modules
 # ---------------------------------------------------------------------------------------------------
+class _RangeFlag:
+    """The device int32 an fp16 knowledge call raises when a value it stores as fp16 lies beyond +-65504 or is not finite
+    (keds_knowledge_f16.h, range_flag); one per owner, made on first use."""
+
+    def __init__(self):
+        self.flag: Optional[torch.Tensor] = None
+
+    def get(self, device) -> torch.Tensor:
+        if self.flag is None or self.flag.device != torch.device(device):
+            self.flag = torch.zeros(1, dtype=torch.int32, device=device)
+        return self.flag
+
+    def tripped(self) -> bool:
+        """Read and clear (synchronises with the device)."""
+        if self.flag is None:
+            return False
+        hit = bool(self.flag.item())
+        if hit:
+            self.flag.zero_()
+        return hit
+
+
+def _check_module_precision(precision):
+    if precision not in (None, "bf16", "fp16"):
+        raise ValueError("precision must be None, 'bf16' or 'fp16'")
+    return precision == "fp16"
+
+
 class IM2TEXT(nn.Module):
     """model.py:105-123: (Linear, Dropout, ReLU) x n_layer then fc_out; eval-mode forward on HIP."""
 
@@ -690,6 +718,7 @@ class IM2TEXT(nn.Module):
         self.embed_dim, self.middle_dim, self.output_dim, self.n_layer = embed_dim, middle_dim, output_dim, n_layer
         self._packed = None
         self._ws = _lib.Workspace()
+        self._range = _RangeFlag()
 
     def _apply(self, fn, *a, **k):
         self._packed = None
@@ -699,16 +728,19 @@ class IM2TEXT(nn.Module):
         self._packed = None
         return super().load_state_dict(state_dict, strict=strict, **kw)
 
-    def params(self, f32: bool = False) -> _lib.Im2TextParams:
-        """f32: the weights as fp32 arrays (the fp32-accurate flow, keds_knowledge_run_f32); default bf16 GEMM operands."""
+    def params(self, f32: bool = False, f16: bool = False) -> _lib.Im2TextParams:
+        """f32: the weights as fp32 arrays (the fp32-accurate flow, keds_knowledge_run_f32); f16: as fp16 arrays, the fp32 masters
+        rounded as convert_weights rounds them (keds_knowledge_run_f16); default bf16 GEMM operands."""
         _lib.require_gpu()
         if not self.fc_out.weight.is_cuda:
             raise RuntimeError("keds_amd.IM2TEXT: move the module to the GPU first; no CPU path exists")
         if self._packed is None:
             self._packed = {}
+        if f16:
+            f32 = "fp16"                                                      # the third weight set's key
         if f32 not in self._packed:
             keep = []
-            wcast = _f32 if f32 else _bf16
+            wcast = _f16 if f16 else _f32 if f32 else _bf16
             p = _lib.Im2TextParams()
             p.dim_in, p.middle, p.dim_out, p.n_layer = self.embed_dim, self.middle_dim, self.output_dim, self.n_layer
             for i, blk in enumerate(self.layers):
@@ -722,10 +754,17 @@ class IM2TEXT(nn.Module):
         _lib.ensure_gemm_workspace(self.fc_out.weight.device)
         return self._packed[f32][0]
 
-    def forward(self, x: torch.Tensor):
+    def range_tripped(self) -> bool:
+        """True when an fp16 forward since the last call stored a value beyond the fp16 range; reads and clears (synchronises)."""
+        return self._range.tripped()
+
+    def forward(self, x: torch.Tensor, precision: Optional[str] = None):
+        """precision "fp16": every GEMM operand and the hidden rows in fp16 (keds_im2text_forward_f16; range_tripped() tells whether a
+        value left the fp16 range); None or "bf16": the bf16 forward."""
         if self.training:
             raise RuntimeError("keds_amd.IM2TEXT runs the eval-mode forward only (dropout = identity); call .eval()")
-        p = self.params()
+        f16 = _check_module_precision(precision)
+        p = self.params(f16=f16)
         lib = load()
         shape = x.shape
         x2 = x.reshape(-1, shape[-1]).to(dtype=torch.float32).contiguous()
@@ -733,8 +772,12 @@ class IM2TEXT(nn.Module):
         nbytes = lib.keds_im2text_workspace_bytes(C.byref(p), rows)
         ws = self._ws.get(nbytes, x2.device)
         out = torch.empty((rows, self.output_dim), dtype=torch.float32, device=x2.device)
-        check(lib.keds_im2text_forward(C.byref(p), ptr(x2), rows, ptr(out), ptr(ws), ws.numel(), stream()),
-              "keds_im2text_forward")
+        if f16:
+            check(lib.keds_im2text_forward_f16(C.byref(p), ptr(x2), rows, ptr(out), ptr(ws), ws.numel(), ptr(self._range.get(x2.device)),
+                                               stream()), "keds_im2text_forward_f16")
+        else:
+            check(lib.keds_im2text_forward(C.byref(p), ptr(x2), rows, ptr(out), ptr(ws), ws.numel(), stream()),
+                  "keds_im2text_forward")
         return out.reshape(*shape[:-1], self.output_dim).to(x.dtype)
 
 
@@ -766,23 +809,26 @@ class CrossFormer(nn.Module):
         self._num_layers, self.dim, self.heads = num_layers, q_dim, heads
         self.cross_layers = nn.ModuleList([CrossAttention(q_dim, k_dim, v_dim, heads, dim_head, dropout)
                                            for _ in range(num_layers)])
-        self._packed = self._packed32 = None
+        self._packed = self._packed32 = self._packed16 = None
         self._ws = _lib.Workspace()
+        self._range = _RangeFlag()
 
     def _apply(self, fn, *a, **k):
-        self._packed = self._packed32 = None
+        self._packed = self._packed32 = self._packed16 = None
         return super()._apply(fn, *a, **k)
 
     def load_state_dict(self, state_dict, strict: bool = True, **kw):
-        self._packed = self._packed32 = None
+        self._packed = self._packed32 = self._packed16 = None
         return super().load_state_dict(state_dict, strict=strict, **kw)
 
-    def params(self, f32: bool = False) -> _lib.CrossFormerParams:
-        """f32: the per-layer weights as fp32 arrays, nothing fused (keds_knowledge_run_f32); default bf16 GEMM operands."""
+    def params(self, f32: bool = False, f16: bool = False) -> _lib.CrossFormerParams:
+        """f32: the per-layer weights as fp32 arrays, nothing fused (keds_knowledge_run_f32); f16: fp16 arrays, fused by
+        keds_crossformer_fuse_f16 (keds_knowledge_run_f16); default bf16 GEMM operands."""
         _lib.require_gpu()
         if not self.cross_layers[0].to_q.weight.is_cuda:
             raise RuntimeError("keds_amd.CrossFormer: move the module to the GPU first; no CPU path exists")
-        slot, cast = ("_packed32", _f32) if f32 else ("_packed", _bf16)
+        slot, cast = ("_packed16", _f16) if f16 else ("_packed32", _f32) if f32 else ("_packed", _bf16)
+        f32 = f32 and not f16
         if getattr(self, slot, None) is None:
             keep = []
             arr = (_lib.CrossLayerParams * self._num_layers)()
@@ -793,15 +839,15 @@ class CrossFormer(nn.Module):
                     setattr(arr[i], k, ptr(v))
                 keep.append(t)
             p = _lib.CrossFormerParams(self.dim, self.heads, self._num_layers, arr, None)
-            # launch-saving re-arrangement of the bf16 weights (keds_hip.h, keds_crossformer_fused): one k/v GEMM for all layers,
+            # launch-saving re-arrangement of the 16-bit weights (keds_hip.h, keds_crossformer_fused): one k/v GEMM for all layers,
             # and every later layer's query projection folded with the previous output projection
             if not f32 and self._num_layers <= 8:
                 lib = load()
                 dev = self.cross_layers[0].to_q.weight.device
                 buf = torch.empty(int(lib.keds_crossformer_fused_bytes(C.byref(p))), dtype=torch.uint8, device=dev)
                 fused = _lib.CrossFormerFused()
-                check(lib.keds_crossformer_fuse(C.byref(p), ptr(buf), buf.numel(), C.byref(fused), stream()),
-                      "keds_crossformer_fuse")
+                fuse = "keds_crossformer_fuse_f16" if f16 else "keds_crossformer_fuse"
+                check(getattr(lib, fuse)(C.byref(p), ptr(buf), buf.numel(), C.byref(fused), stream()), fuse)
                 torch.cuda.current_stream().synchronize()
                 p.fused = C.pointer(fused)
                 keep += [buf, fused]
@@ -810,14 +856,23 @@ class CrossFormer(nn.Module):
             _lib.ensure_gemm_workspace(self.cross_layers[0].to_q.weight.device)
         return getattr(self, slot)[0]
 
-    def forward(self, q, k, v):
+    def range_tripped(self) -> bool:
+        """True when an fp16 forward since the last call stored a value beyond the fp16 range; reads and clears (synchronises)."""
+        return self._range.tripped()
+
+    def forward(self, q, k, v, precision: Optional[str] = None):
         """q [B,Lq,D], k [B,Lk,D], v [B,Lk,D] -> [B,Lq,D] in q's dtype; 1 <= Lk <= 288 (MAX_KEYS), dim_head = 64.
+        precision "fp16": the single-query shape (Lq == 1, Lk <= 32) with fp16 operands and intermediates
+        (keds_crossformer_forward_f16); the sequence form is built in bf16 only and refuses it.
 
         One query over at most 32 keys (the neighbour streams of eval_utils.py:661-672) is the single-query call,
         keds_crossformer_forward; every other shape -- one query over the 77 text tokens (the late fusion of eval_utils.py:249), a
         token sequence as queries (model.py:343-371) -- is keds_crossformer_forward_seq, whose attention runs on the matrix
         instruction.  There is no CPU path."""
-        p = self.params()
+        f16 = _check_module_precision(precision)
+        if f16 and not (q.dim() == 3 and q.shape[1] == 1 and k.dim() == 3 and k.shape[1] <= 32):
+            raise ValueError("precision 'fp16' is built for one query over at most 32 keys; the sequence form is bf16")
+        p = self.params(f16=f16)
         if q.dim() != 3 or q.shape[1] < 1 or q.shape[2] != self.dim:
             raise RuntimeError("q must be [B,Lq,D] with Lq >= 1")
         if k.dim() != 3 or k.shape != v.shape or k.shape[0] != q.shape[0] or k.shape[2] != self.dim or k.shape[1] < 1:
@@ -830,7 +885,12 @@ class CrossFormer(nn.Module):
         kf = k.to(dtype=torch.float32).contiguous()
         vf = kf if v is k else v.to(dtype=torch.float32).contiguous()
         out = torch.empty((B, Lq, self.dim), dtype=torch.float32, device=qf.device)
-        if Lq == 1 and K <= 32:
+        if f16:
+            nbytes = lib.keds_crossformer_workspace_bytes(C.byref(p), B, K)
+            ws = self._ws.get(nbytes, qf.device)
+            check(lib.keds_crossformer_forward_f16(C.byref(p), ptr(qf), ptr(kf), ptr(vf), B, K, ptr(out), ptr(ws), ws.numel(),
+                                                   ptr(self._range.get(qf.device)), stream()), "keds_crossformer_forward_f16")
+        elif Lq == 1 and K <= 32:
             nbytes = lib.keds_crossformer_workspace_bytes(C.byref(p), B, K)
             ws = self._ws.get(nbytes, qf.device)
             check(lib.keds_crossformer_forward(C.byref(p), ptr(qf), ptr(kf), ptr(vf), B, K, ptr(out), ptr(ws), ws.numel(),
@@ -850,22 +910,32 @@ class KnowledgeStream:
     def __init__(self, img2text: IM2TEXT, retrieval_fuse: CrossFormer, text_condition: CrossFormer):
         self.img2text, self.retrieval_fuse, self.text_condition = img2text, retrieval_fuse, text_condition
         self._ws = _lib.Workspace()
+        self._range = _RangeFlag()
+
+    def range_tripped(self) -> bool:
+        """True when a precision="fp16" call since the last look stored an fp16 value beyond +-65504 or a non-finite one (its tokens
+        then hold inf or NaN: re-run on "fp32").  Reads and clears the stream's device flag; synchronises."""
+        return self._range.tripped()
 
     def __call__(self, q: torch.Tensor, nbr_img: torch.Tensor, nbr_txt: torch.Tensor, precision: str = "bf16") -> torch.Tensor:
         """precision "fp32": the fp32-accurate flow (no operand rounding, keds_knowledge_run_f32) -- what
-        compose_query_features passes when the CLIP model is on set_precision("fp32")."""
-        f32 = precision in ("fp32", "fp32x3")
-        kp = _lib.KnowledgeParams(self.img2text.params(f32), self.retrieval_fuse.params(f32), self.text_condition.params(f32))
+        compose_query_features passes when the CLIP model is on set_precision("fp32").  "fp16": every GEMM operand and 16-bit
+        intermediate in fp16 (keds_knowledge_run_f16), the reference's converted modules; see range_tripped()."""
+        f32, f16 = precision in ("fp32", "fp32x3"), precision == "fp16"
+        kp = _lib.KnowledgeParams(self.img2text.params(f32, f16), self.retrieval_fuse.params(f32, f16),
+                                  self.text_condition.params(f32, f16))
         lib = load()
         B, K, dim = nbr_img.shape
         qf = q.to(dtype=torch.float32).contiguous()
         ni = nbr_img.to(dtype=torch.float32).contiguous()
         nt = nbr_txt.to(dtype=torch.float32).contiguous()
         size, run = (("keds_knowledge_f32_workspace_bytes", "keds_knowledge_run_f32") if f32 else
+                     ("keds_knowledge_f16_workspace_bytes", "keds_knowledge_run_f16") if f16 else
                      ("keds_knowledge_workspace_bytes", "keds_knowledge_run"))
         ws = self._ws.get(getattr(lib, size)(C.byref(kp), B, K), qf.device)
         out = torch.empty((B, 3, dim), dtype=torch.float32, device=qf.device)
-        check(getattr(lib, run)(C.byref(kp), ptr(qf), ptr(ni), ptr(nt), B, K, ptr(out), ptr(ws), ws.numel(), stream()), run)
+        flag = (ptr(self._range.get(qf.device)),) if f16 else ()             # the fp16 entry takes range_flag in front of the stream
+        check(getattr(lib, run)(C.byref(kp), ptr(qf), ptr(ni), ptr(nt), B, K, ptr(out), ptr(ws), ws.numel(), *flag, stream()), run)
         return out
 
 

@@ -158,7 +158,8 @@ def get_retrieved_features(feature: torch.Tensor, database, args=None, topk: int
 def compose_query_features(model: CLIP, stream_image: KnowledgeStream, stream_text: KnowledgeStream,
                            ref_images: torch.Tensor, text_with_blank: torch.Tensor, database,
                            id_split: int = 265, topk: int = 16, repeat: bool = False,
-                           w_text_stream: float = 0.5, verify: bool = True) -> Dict[str, torch.Tensor]:
+                           w_text_stream: float = 0.5, verify: bool = True,
+                           knowledge_precision: Optional[str] = None) -> Dict[str, torch.Tensor]:
     """Per-batch body of evaluate_cirr (eval_utils.py:652-714).  evaluate_coco (:511-548) is the same body with
     mixture weight w = 0.05 j for the text stream, evaluate_imgnet_retrieval (:372-415) passes ONE prompt row with
     repeat=True and w = 0.1 j.
@@ -170,17 +171,51 @@ def compose_query_features(model: CLIP, stream_image: KnowledgeStream, stream_te
     returned, and re-run on the fp32-stream flow if it tripped (`CLIP.numerics_checked`: one host wait per batch, which
     the reference's own `.cpu()` in get_retrieved_features pays too).  A caller that keeps the device busy across
     batches passes verify=False and calls `model.numerics_sync()` itself before it uses the features (bench.py).
+
+    knowledge_precision: None (default) keeps the rule below -- bf16 streams beside bf16 / fp8 towers, fp32 streams beside every
+    other tower precision -- unless the environment says KEDS_KNOWLEDGE_PRECISION=fp16; "fp16" runs both streams with fp16
+    operands and intermediates (KnowledgeStream precision "fp16": the reference's --precision fp16 converts these modules too).
+    A value that leaves the fp16 range raises the streams' flags: with verify they are read before the text passes (one more host
+    wait per batch) and a tripped stream sends both streams through the fp32 path again, with a RuntimeWarning, so the text passes
+    and the result are the fp32 route's; with verify=False the caller asks `range_tripped()` of both streams.
     """
+    if knowledge_precision is None and os.environ.get("KEDS_KNOWLEDGE_PRECISION", "") == "fp16":
+        knowledge_precision = "fp16"
+    if knowledge_precision not in (None, "fp16"):
+        raise ValueError("knowledge_precision must be None or 'fp16'")
+    if verify and knowledge_precision == "fp16":
+        # the streams' flags are settled BEFORE the text passes, so that no token beyond the fp16 range reaches a tower
+        def front():
+            q = model.encode_image(ref_images).float()
+            nbrs = get_retrieved_features(q, database, None, topk=topk)
+            return (q, nbrs) + _knowledge_tokens(stream_image, stream_text, q, nbrs, "fp16")
+        q, nbrs, tok_a, tok_b = model.numerics_checked(front)
+        if stream_image.range_tripped() | stream_text.range_tripped():            # (both flags are read, and cleared)
+            import warnings
+            warnings.warn("keds_amd: an fp16 knowledge stream stored a value beyond the fp16 range; re-running the streams on "
+                          "precision 'fp32'", RuntimeWarning)
+            tok_a, tok_b = _knowledge_tokens(stream_image, stream_text, q, nbrs, "fp32")
+        return model.numerics_checked(lambda: _compose_from_tokens(model, q, tok_a, tok_b, text_with_blank, id_split, repeat, w_text_stream))
     if verify:
         return model.numerics_checked(lambda: compose_query_features(
             model, stream_image, stream_text, ref_images, text_with_blank, database, id_split=id_split, topk=topk,
             repeat=repeat, w_text_stream=w_text_stream, verify=False))
     q = model.encode_image(ref_images).float()
-    topk_image, topk_text = get_retrieved_features(q, database, None, topk=topk)
+    nbrs = get_retrieved_features(q, database, None, topk=topk)
     # fp32: no operand is rounded anywhere (the "fp16" towers take it too: exact, and its GEMMs are a small share of a dual step)
-    prec = "fp32" if getattr(model, "precision", "bf16") in ("fp32", "fp32x3", "fp16") else "bf16"
-    tok_a = stream_image(q, topk_image, topk_text, precision=prec)                   # [B,3,D]
-    tok_b = stream_text(q, topk_image, topk_text, precision=prec)
+    prec = knowledge_precision or ("fp32" if getattr(model, "precision", "bf16") in ("fp32", "fp32x3", "fp16") else "bf16")
+    tok_a, tok_b = _knowledge_tokens(stream_image, stream_text, q, nbrs, prec)
+    return _compose_from_tokens(model, q, tok_a, tok_b, text_with_blank, id_split, repeat, w_text_stream)
+
+
+def _knowledge_tokens(stream_image, stream_text, q, nbrs, prec):
+    """the two streams over the retrieved rows: tokens [B,3,D] each"""
+    topk_image, topk_text = nbrs
+    return stream_image(q, topk_image, topk_text, precision=prec), stream_text(q, topk_image, topk_text, precision=prec)
+
+
+def _compose_from_tokens(model, q, tok_a, tok_b, text_with_blank, id_split, repeat, w_text_stream):
+    """compose_query_features behind the streams: the text passes and the mix"""
     if not repeat and text_with_blank.shape[0] == tok_a.shape[0] == tok_b.shape[0]:
         # the two text-tower passes share the captions and differ in the spliced tokens only: one pass over 2B rows
         # (rows are independent; B = 128 -> 19,712 rows = 77 full 256-row GEMM tiles instead of two ragged 9,856-row passes)
