@@ -56,12 +56,12 @@ const char* keds_build_flags(void);
 const char* keds_last_error(void);
 
 /* ---- numerics guard of the fast tower flow ---------------------------------------------------------------------
- * The default tower flow keeps the residual stream in fp16 and evaluates LayerNorm inside the GEMMs on un-centred rows.
- * That is accurate while |row mean| / row std stays small (CLIP: a few) and the stream stays inside the fp16 range.
- * While a device flag is registered for the calling thread, every LayerNorm-consuming GEMM it enqueues sets *flag = 1 if
- * it meets a row with |mean| / std > 32 or non-finite statistics; the host reads the flag after the pass and re-runs it
- * on the fp32-stream flow (stand-alone LayerNorm: unfolded weights) -- keds_amd.CLIP does so automatically.
- * nullptr unregisters.  The flag is only ever set, never cleared, by the library. */
+ * The default tower flow keeps the residual stream in fp16 and evaluates LayerNorm inside the GEMMs on un-centred rows: accurate while |row mean| /
+ * row std stays small (CLIP: a few) and the stream stays inside the fp16 range.  While a device flag is registered for the calling thread, every
+ * LayerNorm-consuming GEMM it enqueues sets *flag = 1 at a row of the call (not behind M, not a zero row of a packed text pass) with |mean| / std > 32,
+ * and every writer of the fp16 stream (KEDS_EPI_RESID_STATS_F16 / _F16_H in every kernel form, keds_rowstats_cast_ex with out_f16) sets it at a stored
+ * value beyond +-65504 or not finite -- or when a 64-column partial sum of squares reaches 65504^2 (the statistics, fixed-point sums of the fp32
+ * values, cannot show it).  keds_amd.CLIP then re-runs the pass on the fp32-stream flow.  nullptr unregisters.  The library only ever sets the flag. */
 int keds_numerics_guard_set(int32_t* device_flag);
 
 /* ---- profiling of kernel classes with hipEvents on the launch stream -------------
@@ -627,7 +627,7 @@ int keds_side_lane_enable(int on);            /* run-time override of KEDS_SIDE_
  * [7] out  [8] first row  [9] row step  [10] rows  [11] out2: the MXFP8 copy written beside out (its scale buffer: the next id)
  * [12] fp32x3: rows of one fp16 plane of in / out  [13] statistics buffer read  [14] added into (statistics cast: written)
  * [15] cleared  [16] their first row  [17] attention: q_limit  [18] rows written as MXFP8  [19] packed rows  [20] gather: rows
- * outside [0, bound) give NaN  [21] global (packed) row indices  [22] lane (0 the caller's stream, 1 the side lane)  [23] a LayerNorm
+ * outside [0, bound) give NaN; the residual GEMM of a packed folded pass: rows >= bound of out and of [14] are zeroed behind it  [21] global (packed) row indices  [22] lane (0 the caller's stream, 1 the side lane)  [23] a LayerNorm
  * of the read-out rows: 1 when sample b's row is row b * [6] + its read-out column (the device array of keds_text_run_ex).
  * A whole pass (keds_pass_plan_query) adds the weights 9 conv1 (the patch embedding; its GEMM spreads row i of col to row
  * i / G * (G + 1) + 1 + i % G of x and adds the positional embedding), 10 ln_pre, 11 ln_post / ln_final, 12 the projection; the ops

@@ -5,6 +5,7 @@
 // src/eval_utils.py:162,704-710 (normalise / mixture).
 #include "keds_common.h"
 #include <math.h>
+#include <type_traits>
 
 namespace {
 
@@ -93,7 +94,8 @@ __global__ __launch_bounds__(256) void layernorm_kernel(const float* __restrict_
 // emits for every later block; this kernel provides them for the first one)
 template <typename T>   // bf16_t, or f16_t for the fp16 residual stream
 __global__ __launch_bounds__(256) void rowstats_cast_kernel(const float* __restrict__ x, T* __restrict__ xb,
-                                                            float* __restrict__ stats, int rows, int dim) {
+                                                            float* __restrict__ stats, int rows, int dim,
+                                                            int* __restrict__ guard) {
     const int r = blockIdx.x * 4 + (threadIdx.x >> 6);
     const int lane = threadIdx.x & 63;
     if (r >= rows) return;
@@ -114,6 +116,9 @@ __global__ __launch_bounds__(256) void rowstats_cast_kernel(const float* __restr
             typedef __attribute__((ext_vector_type(4))) T tx4;
             *reinterpret_cast<tx4*>(xb + (size_t)r * dim + i) = tx4{(T)v[j][0], (T)v[j][1], (T)v[j][2], (T)v[j][3]};
         }
+    }
+    if constexpr (std::is_same<T, f16_t>::value) {      // the fp16 stream's range check on this lane's values (keds_f16_stream_bad)
+        if (guard && keds_f16_stream_bad(q)) *guard = 1;
     }
     s = wave_sum(s);
     q = wave_sum(q);
@@ -859,9 +864,9 @@ extern "C" int keds_rowstats_cast_ex(const float* x, void* xb, int out_f16, floa
     hipStream_t st = (hipStream_t)stream;
     KedsProfScope prof(KEDS_PROF_LN, st);
     if (out_f16)
-        rowstats_cast_kernel<f16_t><<<(rows + 3) / 4, 256, 0, st>>>(x, (f16_t*)xb, stats, rows, dim);
+        rowstats_cast_kernel<f16_t><<<(rows + 3) / 4, 256, 0, st>>>(x, (f16_t*)xb, stats, rows, dim, keds_numerics_guard());
     else
-        rowstats_cast_kernel<bf16_t><<<(rows + 3) / 4, 256, 0, st>>>(x, (bf16_t*)xb, stats, rows, dim);
+        rowstats_cast_kernel<bf16_t><<<(rows + 3) / 4, 256, 0, st>>>(x, (bf16_t*)xb, stats, rows, dim, nullptr);
     return keds_check_launch("rowstats_cast_kernel");
 }
 

@@ -224,6 +224,7 @@ __device__ __forceinline__ void tile_epilogue(f32x4 (&acc)[4][MI], const float* 
                 b[p][1] = *reinterpret_cast<const f32x4*>(bias + n_lane + 32 * p + 4);
             }
         }
+        bool bad = false;                                                  // a value the fp16 stream cannot hold (keds_f16_stream_bad)
 #pragma unroll
         for (int mi = 0; mi < MI; ++mi) {
             const int m = m_lane + 16 * mi;
@@ -244,8 +245,10 @@ __device__ __forceinline__ void tile_epilogue(f32x4 (&acc)[4][MI], const float* 
             }
             s = rows_sum(s);
             ss = rows_sum(ss);
+            bad |= keds_f16_stream_bad(ss);
             if (valid && zero_lane && stats) keds_stat_add(stats + 2 * (size_t)m, s, ss);
         }
+        if (bad && guard) *guard = 1;
     } else {
 #pragma unroll
         for (int p = 0; p < 2; ++p) {
@@ -378,7 +381,8 @@ __device__ __forceinline__ void quad_flush_pending(const u32x4* __restrict__ pen
 template <bool REDUCE = true>
 __device__ __forceinline__ void pair_resid_epilogue(f32x4 (&acc)[4][8], const char* __restrict__ side, void* __restrict__ out,
                                                     int m0, int n0, int N, int wm, int wn, int g, int c,
-                                                    keds_stat_t* __restrict__ stats, char* __restrict__ red) {
+                                                    keds_stat_t* __restrict__ stats, char* __restrict__ red,
+                                                    int* __restrict__ guard) {
     // `red`: 8 KiB of LDS nobody reads any more (the operand buffer of the last but one K-tile): the four waves that share
     // a row (wn = 0..3) leave their {sum, sum sq} of it there, and after one barrier threads 0-255 add ONE statistics pair
     // per row of the tile -- a quarter of the 64-bit atomics (they cost 5-7 k of this epilogue's ~21 k cycles).
@@ -407,6 +411,7 @@ __device__ __forceinline__ void pair_resid_epilogue(f32x4 (&acc)[4][8], const ch
         b[p][1] = *reinterpret_cast<const f32x4*>(side + 2048 + (nl + 32 * p) * 4 + 16);
     }
     f32x2* rw = reinterpret_cast<f32x2*>(red) + wn * 256 + r0;
+    bool bad = false;                                                      // a value the fp16 stream cannot hold (keds_f16_stream_bad)
 #pragma unroll
     for (int mi = 0; mi < 8; ++mi) {
         // {sum, sum of squares} of the lane's 16 values of the row: four vector partial sums first (packed adds / FMAs, two
@@ -426,8 +431,10 @@ __device__ __forceinline__ void pair_resid_epilogue(f32x4 (&acc)[4][8], const ch
         float s = (sv[0] + sv[1]) + (sv[2] + sv[3]), ss = (qv[0] + qv[1]) + (qv[2] + qv[3]);
         s = rows_sum(s);                 // the four lanes (g = 0..3) that share the row hold this wave's 64 columns of it
         ss = rows_sum(ss);
+        bad |= keds_f16_stream_bad(ss);
         if (stats && g == 0) rw[16 * mi] = f32x2{s, ss};
     }
+    if (bad && guard) *guard = 1;
     if constexpr (REDUCE) {
         if (stats) {                                                    // kernel-uniform
             __syncthreads();
@@ -447,11 +454,12 @@ __device__ __forceinline__ void pair_resid_epilogue(f32x4 (&acc)[4][8], const ch
 // in it (the 16 dependent residual loads per lane were ~9 k of this epilogue's 14.8 k cycles, round-2 stamps).
 __device__ __forceinline__ void pair_resid_epilogue_acc(f32x4 (&acc)[4][8], void* __restrict__ out, int m0, int n0, int N,
                                                         int wm, int wn, int g, int c, keds_stat_t* __restrict__ stats,
-                                                        char* __restrict__ red) {
+                                                        char* __restrict__ red, int* __restrict__ guard) {
     const int r0 = 128 * wm + c;
     char* tile = reinterpret_cast<char*>(out) + ((size_t)m0 * N + n0) * 2;               // wave-uniform
     const int nl = 64 * wn + 8 * g;
     f32x2* rw = reinterpret_cast<f32x2*>(red) + wn * 256 + r0;
+    bool bad = false;
 #pragma unroll
     for (int mi = 0; mi < 8; ++mi) {
         float s = 0.f, ss = 0.f;
@@ -465,8 +473,10 @@ __device__ __forceinline__ void pair_resid_epilogue_acc(f32x4 (&acc)[4][8], void
         }
         s = rows_sum(s);                 // the four lanes (g = 0..3) that share the row hold this wave's 64 columns of it
         ss = rows_sum(ss);
+        bad |= keds_f16_stream_bad(ss);
         if (stats && g == 0) rw[16 * mi] = f32x2{s, ss};
     }
+    if (bad && guard) *guard = 1;
     if (stats) {                                                        // kernel-uniform
         __syncthreads();
         const int t = threadIdx.x;
@@ -719,7 +729,9 @@ __global__ __launch_bounds__(256) void gemm_splitk_reduce_kernel(const float* __
         v1 += f32x4{(float)r[4], (float)r[5], (float)r[6], (float)r[7]} + b1;
         *o = f16x8{(f16_t)v0[0], (f16_t)v0[1], (f16_t)v0[2], (f16_t)v0[3], (f16_t)v1[0], (f16_t)v1[1], (f16_t)v1[2], (f16_t)v1[3]};
         keds_stat_t* stats = reinterpret_cast<keds_stat_t*>(const_cast<float*>(aux));
-        if (stats) row_stats_add(stats + 2 * (size_t)m, sum8(v0, v1), sum8(v0 * v0, v1 * v1), per_row);
+        const float ss = sum8(v0 * v0, v1 * v1);
+        if (guard && keds_f16_stream_bad(ss)) *guard = 1;                      // this thread's 8 values: one beyond the fp16 range
+        if (stats) row_stats_add(stats + 2 * (size_t)m, sum8(v0, v1), ss, per_row);
     } else {
         epilogue_store<epi_base(EPI)>(v0 + b0, v1 + b1, out, m, n, N, aux, aux_i, ldc, guard);
     }
@@ -1005,10 +1017,10 @@ __global__ __launch_bounds__(512, 2) void gemm_bt_pair_kernel(const bf16_t* __re
         pair_ln_epilogue<EPI>(acc, smem + SIDE_OFF, out, m0, n0, N, wm, wn, g, c, aux2, nullptr, false, guard);
     else if constexpr (RESID_IN)
         pair_resid_epilogue_acc(acc, out, m0, n0, N, wm, wn, g, c, reinterpret_cast<keds_stat_t*>(const_cast<float*>(aux)),
-                                smem + (np & 1) * PBUF_BYTES);
+                                smem + (np & 1) * PBUF_BYTES, guard);
     else if constexpr (epi_resid16(EPI))
         pair_resid_epilogue(acc, smem + SIDE_OFF, out, m0, n0, N, wm, wn, g, c,
-                            reinterpret_cast<keds_stat_t*>(const_cast<float*>(aux)), smem + (np & 1) * PBUF_BYTES);
+                            reinterpret_cast<keds_stat_t*>(const_cast<float*>(aux)), smem + (np & 1) * PBUF_BYTES, guard);
     else
         tile_epilogue<EPI, 8>(acc, bias, out, m0 + 128 * wm + c, M, n0 + 64 * wn + 8 * g, N, K, aux, aux_i, aux2, N, zl, guard,
                               epi_x3(EPI) ? x3_wscale(w_plane) : 1.0f);
@@ -1333,7 +1345,7 @@ __global__ __launch_bounds__(256, 1) void gemm_bt_quad_kernel(const bf16_t* __re
     if constexpr (epi_is_ln(EPI))                                                                                      \
         pair_ln_epilogue<EPI>(av, side, out, m0, n0, N, wm, 2 * wn2 + h, g, c, aux2, nullptr, false, guard);        \
     else if constexpr (epi_resid16(EPI))                                                                \
-        pair_resid_epilogue<false>(av, side, out, m0, n0, N, wm, 2 * wn2 + h, g, c, stats, red);                    \
+        pair_resid_epilogue<false>(av, side, out, m0, n0, N, wm, 2 * wn2 + h, g, c, stats, red, guard);             \
     else                                                                                                               \
         tile_epilogue<EPI, 8>(av, bias, out, m0 + 128 * wm + c, M, n0 + 64 * (2 * wn2 + h) + 8 * g, N, K, aux, aux_i, aux2, N, g == 0, guard, \
                               epi_x3(EPI) ? x3_wscale(w_plane) : 1.0f);
@@ -1391,8 +1403,9 @@ __global__ __launch_bounds__(256, 1) void gemm_bt_quad_kernel(const bf16_t* __re
 template <int EPI>
 __global__ __launch_bounds__(256, 1) void gemm_bt_quad3_kernel(const bf16_t* __restrict__ X, const bf16_t* __restrict__ W,
                                                                const float* __restrict__ bias, void* __restrict__ out,
-                                                               int M, int N, int K, int n_tiles,
+                                                               int* __restrict__ guard, int N, int K, int n_tiles,
                                                                const float* __restrict__ aux, int ntiles) {
+    // (guard: the numerics-guard flag, in the place of the row count this kernel never read -- every row of its tiles is valid)
     static_assert(epi_resid16(EPI), "three-deep A ring: residual epilogue only");
     using namespace pr;
     extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -1509,10 +1522,10 @@ __global__ __launch_bounds__(256, 1) void gemm_bt_quad3_kernel(const bf16_t* __r
     f32x4 av[4][8];
     keds_stat_t* stats = reinterpret_cast<keds_stat_t*>(const_cast<float*>(aux));
     KEDS_QUAD_READ_HALF0(av)
-    pair_resid_epilogue<false>(av, side, out, m0, n0, N, wm, 2 * wn2 + 0, g, c, stats, red);
+    pair_resid_epilogue<false>(av, side, out, m0, n0, N, wm, 2 * wn2 + 0, g, c, stats, red, guard);
     __builtin_amdgcn_sched_barrier(0);
     KEDS_QUAD_READ_HALF1(av)
-    pair_resid_epilogue<false>(av, side, out, m0, n0, N, wm, 2 * wn2 + 1, g, c, stats, red);
+    pair_resid_epilogue<false>(av, side, out, m0, n0, N, wm, 2 * wn2 + 1, g, c, stats, red, guard);
     if (stats) {                                                        // kernel-uniform
         __syncthreads();
         const f32x2* rr = reinterpret_cast<const f32x2*>(red) + tid;
@@ -1698,8 +1711,8 @@ int launch_quad3(const GemmArgs& a, const GemmPlan::Part&) {
     const int n_tiles = a.N / pr::TN, ntiles = (a.M / pr::TM) * n_tiles;
     if (int rc = keds_func_lds_once((const void*)gemm_bt_quad3_kernel<EPI>, 5 * pr::OP_BYTES, "gemm_bt_quad3_kernel")) return rc;
     rec_launch(KEDS_GEMM_FORM_QUAD3, 3, 1);
-    KEDS_LAUNCH((gemm_bt_quad3_kernel<EPI>), ntiles, 256, 5 * pr::OP_BYTES, a.st, (const bf16_t*)a.A, (const bf16_t*)a.W, a.bias, a.out, a.M,
-                a.N, a.K, n_tiles, a.aux, ntiles);
+    KEDS_LAUNCH((gemm_bt_quad3_kernel<EPI>), ntiles, 256, 5 * pr::OP_BYTES, a.st, (const bf16_t*)a.A, (const bf16_t*)a.W, a.bias, a.out,
+                keds_numerics_guard(), a.N, a.K, n_tiles, a.aux, ntiles);
     return keds_check_launch("gemm_bt_quad3_kernel");
 }
 

@@ -54,9 +54,12 @@ __device__ __forceinline__ float x3_wscale(long long w_plane) {
 constexpr float LN_EPS = 1e-5f;
 
 // Numerics guard of the folded-LayerNorm flow (keds_hip.h, keds_numerics_guard): the GEMM multiplies UN-centred rows, so
-// operand rounding is amplified by |row mean| / row std = |nmr| (rel-L2 4.8e-3 at 20, 1.8e-2 at 100),
-// and an fp16 residual stream that overflowed shows up as non-finite statistics.  Either raises the caller's flag; the
-// host then re-runs the pass on the fp32-stream flow with stand-alone LayerNorm.
+// operand rounding is amplified by |row mean| / row std = |nmr| (rel-L2 4.8e-3 at 20, 1.8e-2 at 100).
+// An fp16 residual stream that overflowed does NOT show here: the statistics are 64-bit fixed point of the fp32 sums, finite
+// whatever fp16 stored, and a row with one value of 1e5 has a ratio below 0.1.  The kernels that WRITE the fp16 stream raise the
+// same flag themselves (keds_f16_stream_bad, keds_common.h: the fp16-residual epilogues of every GEMM form and the fp16
+// keds_rowstats_cast_ex).  Either way the host re-runs the pass on the fp32-stream flow with stand-alone LayerNorm.
+// (held per row and per element by tests/test_gpu_guard_edges.py, per pass by tests/test_gpu_guard_passes.py)
 constexpr float GUARD_MAX_MEAN_OVER_STD = 32.0f;
 __device__ __forceinline__ void guard_check(int* __restrict__ guard, float nmr) {
     if (guard && !(fabsf(nmr) <= GUARD_MAX_MEAN_OVER_STD)) *guard = 1;       // NaN / inf fail the comparison too

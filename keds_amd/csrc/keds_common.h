@@ -364,6 +364,12 @@ __device__ __forceinline__ void keds_stat_add(keds_stat_t* row, float s, float s
     atomicAdd(reinterpret_cast<unsigned long long*>(row), (unsigned long long)keds_stat_fixed(s));
     atomicAdd(reinterpret_cast<unsigned long long*>(row + 1), (unsigned long long)keds_stat_fixed(ss));
 }
+// The fp16 residual stream's own range check.  The statistics are taken of the fp32 sums and are finite whatever the fp16 store did
+// (the fixed-point conversion turns inf and NaN into small integers), so they cannot show an overflow: the lane that holds a partial
+// sum of squares of the values it is about to store tests it instead.  Any |v| > 65504, inf or NaN among them puts the partial at
+// 65504^2 or beyond (NaN fails the comparison); so does a run of large in-range values (64 values of 8,200), which is as far outside
+// the flow's accuracy range.  One compare per row and wave.
+__device__ __forceinline__ bool keds_f16_stream_bad(float partial_sumsq) { return !(partial_sumsq < 65504.0f * 65504.0f); }
 __device__ __forceinline__ void keds_stat_zero(keds_stat_t* row) {
     row[0] = 0;
     row[1] = 0;

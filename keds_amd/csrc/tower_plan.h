@@ -202,6 +202,7 @@ struct TowerStep {
     int st_read = TB_NONE, st_add = TB_NONE, st_clear = TB_NONE, st_r0 = 0;
     int q_limit = 0, q8_rows = 0, packed = 0;
     int bound = 0, global = 0;      // gather: rows outside [0, bound) come out as NaN; global (packed) or per-sample row indices
+                                    // residual GEMM of a packed folded pass: rows >= bound of out and st_add are zeroed behind it (0: none)
     int lane = 0;                   // 0: the caller's stream, 1: the side lane
     int rows = 0;                   // LayerNorm of the read-out: sample b's row is in_r0 + b * in_step + its read-out column (device)
 };
@@ -319,6 +320,12 @@ inline bool tower_plan(const TowerPlanArgs& a, Emit&& emit, Front&& front) {
                 s.in = sp.mx ? TB_HQ : TB_HID, s.out = TB_H, s.out2 = sp.mx ? TB_XQ : TB_NONE;
                 s.st_add = last && !sp.mx ? TB_NONE : TB_ST1;
         }
+        // packed rows: a residual GEMM leaves its bias (and what the zero rows' hidden values project to) in the zero rows of the
+        // stream, and their statistics with it -- a row of mean 0.2 and deviation 0.001 that no caption owns would trip the numerics
+        // guard of the LayerNorm-folded GEMM that reads them next.  `bound` on such a step: the rows of `out` and of `st_add` from
+        // `bound` on go back to zero behind the launch; the next GEMM sees mean 0, variance 0 there and writes its bias.
+        if (packed && M > a.packed_valid && s.st_add != TB_NONE && !sp.mx && sp.r0 + sp.n > a.packed_valid)
+            s.bound = a.packed_valid > sp.r0 ? a.packed_valid : sp.r0;
         put(s);
     };
     auto pre = [&](int l, const Span& sp) {      // ln_1 + in_proj

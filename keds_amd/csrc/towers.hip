@@ -157,8 +157,16 @@ int tower_step(const TowerRun& r, const TowerStep& s) {
         }
         case KEDS_TOWER_OP_GEMM16: {       // (aux: the row statistics of the folded flows, or the patch embedding's positions)
             const TowerWeight wt = tower_weight(r, s);
-            return keds_gemm_bt_ex2(in, r.ld(s.in, s.in_step), wt.w, wt.bias, out, r.ld(s.out, s.out_step), s.n, wt.N, wt.K, s.epi,
-                                    wt.aux ? wt.aux : stats, wt.aux_i, stats_clear, st);
+            if (int rc = keds_gemm_bt_ex2(in, r.ld(s.in, s.in_step), wt.w, wt.bias, out, r.ld(s.out, s.out_step), s.n, wt.N, wt.K, s.epi,
+                                          wt.aux ? wt.aux : stats, wt.aux_i, stats_clear, st))
+                return rc;
+            if (s.bound > 0) {      // packed rows: the zero rows of the stream and of their statistics stay zero (tower_plan.h, folded_gemm)
+                const size_t n = (size_t)(s.out_r0 + s.n - s.bound);
+                if (hipMemsetAsync(r.at(s.out, s.bound), 0, n * out_row_bytes, st) != hipSuccess ||
+                    hipMemsetAsync(r.at(s.st_add, s.bound), 0, n * 2 * sizeof(keds_stat_t), st) != hipSuccess)
+                    return tower_hip_error("packed rows");
+            }
+            return KEDS_OK;
         }
         case KEDS_TOWER_OP_GEMM_MX: {      // (m_pad and q_pad: the s.n full-tile rows the MXFP8 buffers are carved for)
             const TowerWeight wt = tower_weight(r, s);

@@ -222,7 +222,7 @@ class CLIP(nn.Module):
         self._ws = _lib.Workspace()
         self.precision = os.environ.get("KEDS_PRECISION", "bf16")
         # "auto": the fast tower flow (fp16 residual stream, LayerNorm folded into the GEMMs) guarded by a device flag --
-        # a row with |mean|/std > 32 or non-finite statistics re-runs the pass on the fp32-stream flow with stand-alone
+        # a row with |mean|/std > 32, or a value the fp16 stream cannot hold, re-runs the pass on the fp32-stream flow with stand-alone
         # LayerNorm and keeps the model there (keds_hip.h, keds_numerics_guard_set); "fast": no guard; "safe": always the
         # fp32-stream flow (what KEDS_DETERMINISTIC=1 selected before).
         self.numerics = "safe" if os.environ.get("KEDS_DETERMINISTIC", "0") == "1" else "auto"      # (set_numerics() changes it)
